@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training-step throughput (cells/s) of the 2-group PoE VAE on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -27,7 +27,9 @@ Other workloads, one per BASELINE.json config, selected with --co
     c5  one rank's shard of 2 x 500 000 x 30 000 on 8 GPUs: 62 500 cells x 30 000 genes, paired PoE on a sparse plan, fp32
 Explicit --cells / --genes / ... flags override the preset.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step computed (its LossOutput, the
+inference outputs and the state_dict after the optimiser step) as DIR/<name>.npy; the inputs are seeded, so two builds run with
+the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -36,6 +38,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -88,7 +91,12 @@ def parse(argv=None):
                          "decoder bucket overlapped with the encoder half of the backward pass (auto: overlap when WORLD_SIZE > 1)")
     ap.add_argument("--cpu-batch", type=int, default=None, help="cells per group of the CPU baseline sample (default: the timed batch size)")
     ap.add_argument("--cpu-steps", type=int, default=1, help="timed CPU steps after one untimed one (one step of 2 x 4096 x 10 000 is ~5-10 s of host time)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed, "
+                         "seeded sample of each large array when the whole would not fit)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config is None:
         args.config = "c2" if args.gpus <= 1 else "c3"
     preset = CONFIGS[args.config]
@@ -314,6 +322,61 @@ def elbo_delta_oracle(st, args, plan):
             "what": f"one training-mode step of this workload (B {args.batch_size} x G {args.genes}, {args.poe} PoE, {args.precision}), same parameters / rows / noise, dropout off, kl_weight 1"}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def _host_arrays(prefix, obj, out):
+    """every tensor of a (nested) dict / list / tuple of step outputs, keyed by dotted name, as a float32 / float64 host array
+    (distribution objects and other non-tensors are skipped)"""
+    if isinstance(obj, torch.Tensor):
+        t = obj.detach()
+        exact = t.dtype in (torch.float64, torch.int64, torch.int32)
+        out[prefix] = t.to(torch.float64 if exact else torch.float32).cpu().numpy()
+    elif isinstance(obj, dict):
+        for k, v in dict.items(obj):   # (dict.items: the entries of a lazily materialised dict are left alone)
+            _host_arrays(f"{prefix}.{k}" if prefix else str(k), v, out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _host_arrays(f"{prefix}.{i}" if prefix else str(i), v, out)
+
+
+def step_outputs(last, trainer, module) -> dict:
+    """what a caller of the timed step receives: the step's LossOutput, the inference outputs (latent statistics, library) and
+    the parameters and buffers the optimiser step left behind.  The decoder outputs are materialised only on demand and are
+    not part of the step; the reconstruction-loss vectors carry them."""
+    arrays = {}
+    for f in ("loss", "reconstruction_loss_mean", "reconstruction_loss", "kl_local", "kl_global"):
+        _host_arrays(f, getattr(last, f, None), arrays)
+    _host_arrays("inference", trainer.last_outputs[0], arrays)
+    _host_arrays("state", module.state_dict(), arrays)
+    return arrays
+
+
+def dump_outputs(path: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """DIR/<name>.npy for every array.  When the whole exceeds the budget, arrays of more than 64 Ki elements are cut down to the
+    same fraction of their elements each: a sorted sample of flat indices drawn from a generator seeded by the array's name,
+    so every run with the same arguments writes the same elements."""
+    os.makedirs(path, exist_ok=True)
+    budget -= 128 * len(arrays)   # (.npy headers)
+    small = {k for k, a in arrays.items() if a.size <= 1 << 16}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = 1.0
+    if total > budget:
+        small_bytes = sum(arrays[k].nbytes for k in small)
+        if small_bytes >= budget:
+            raise ValueError(f"--dump-outputs: {len(small)} small arrays alone exceed {budget} bytes")
+        keep = (budget - small_bytes) / (total - small_bytes)
+    written, sampled = 0, []
+    for name, a in arrays.items():
+        if keep < 1.0 and name not in small:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+            sampled.append(name)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": path, "arrays": len(arrays), "bytes": written, "sampled": sampled, "sample_fraction": keep}
+
+
 def launcher_command(n: int, argv) -> list:
     """the one-rank-per-GPU launch of this script (the command the driver uses for N > 1), rendezvous on 127.0.0.1 at a free port"""
     import socket
@@ -380,6 +443,9 @@ def main(argv=None):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
+    n_dev = torch.cuda.device_count()   # (sysfs may list GPUs this process cannot open: the launcher's count is only a first check)
+    if world > n_dev:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but this node exposes {n_dev} GPU(s) to this process")
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     if world > 1:
@@ -482,6 +548,9 @@ def main(argv=None):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t)
+    dumped = None
+    if rank == 0 and args.dump_outputs:   # (before anything else runs a step)
+        dumped = dump_outputs(args.dump_outputs, step_outputs(last, trainer, module))
     loss = float(last.loss)
     # exposed all-reduce time per step (outside the timed region): GPU time between the end of the backward pass and the
     # start of Adam, max over ranks
@@ -597,6 +666,8 @@ def main(argv=None):
                 out["cpu_baseline"] = cpu_baseline(groups, args, plan)
             except Exception as e:  # the baseline is a reported extra; never lose the GPU number over it
                 out["cpu_baseline"] = {"value": None, "unit": "cells/s", "cores": host_cpus()[0], "kind": "port", "sample": f"failed: {e!r}"}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
