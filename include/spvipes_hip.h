@@ -37,6 +37,8 @@ extern "C" {
 #define SPV_NB_CMAX 64      /* rows of the (count, gene) lgamma/digamma table         */
 #define SPV_DEC_KP 16       /* K slots of the private factor regressor (n_p + 1 <= 16) */
 #define SPV_DEC_KS 32       /* K slots of the shared factor regressor  (n_s + 1 <= 32) */
+#define SPV_DEC_KP_WIDE 32  /* the wide operand layout (kslots = 1 in spv_dec_params, spv_zsplit_args, spv_fold_batch): n_p + 1 <= 32 */
+#define SPV_DEC_KS_WIDE 64  /*                                                                                          n_s + 1 <= 64 */
 #define SPV_DEC_CELLS_PER_WG 128
 
 int spv_version(void);
@@ -250,6 +252,8 @@ typedef struct spv_dec_params {
                                                                   followed by a bf16 lo plane, [2][Bp][Gp]: value = hi + lo */
   int32_t nb_splits; int32_t nb_genes_per_split;               /* gene splits of spv_dec_nb_fwd: multiple of 32, <= SPV_NB_GSPL_MAX */
   int32_t nb_cell_tiles;   /* 64-cell tiles one likelihood workgroup walks (0 = 1); dtheta_part then holds ceil(Bp / 64 / nb_cell_tiles) rows */
+  int32_t kslots;          /* operand layout of Wps / Aps: 0 = 16 / 32 K slots, rows of 48; 1 = 32 / 64 K slots, rows of 96 (spv_dec_lse,
+                              spv_dec_nb_fwd, spv_dec_materialize and the in-place spv_dec_softmax_bwd; the fused backward passes take 0 only) */
 } spv_dec_params;
 
 /* theta = exp(px_r) and the per-(count, gene) lgamma / digamma table (module/spVIPESmodule.py:758
@@ -563,6 +567,7 @@ typedef struct spv_zsplit_args {
    *   aps [Bp][48]     <-  [ z_private | 1 | 0 ..(16) | z_shared | 1 | 0 ..(32) ]        (rate-regressor operand)     */
   uint16_t* am_hi[2]; uint16_t* am_lo[2]; int64_t ld_am; int32_t am_col; int32_t am_cols;
   uint16_t* aps_hi[2]; uint16_t* aps_lo[2]; int32_t Bp;
+  int32_t kslots;   /* layout of aps: 0 = [Bp][48] as above; 1 = [Bp][96], slots of 32 (private) and 64 (shared) */
 } spv_zsplit_args;
 int spv_zsplit_fwd(const spv_zsplit_args* a, void* stream);
 int spv_zsplit_bwd(const spv_zsplit_args* a, void* stream);
@@ -585,7 +590,10 @@ typedef struct spv_fold_prob {
    * problems of a group (private block, shared block) together cover every column exactly once. */
   int32_t zcol; float* out_priv; float* out_poe; int32_t n_p, n_s;
 } spv_fold_prob;
-typedef struct spv_fold_batch { spv_fold_prob p[SPV_MAXP]; int32_t nprob, B, training; float eps, momentum; } spv_fold_batch;
+typedef struct spv_fold_batch {
+  spv_fold_prob p[SPV_MAXP]; int32_t nprob, B, training; float eps, momentum;
+  int32_t kslots;   /* 0: K <= 32; 1 (the wide decoder layout): K <= 64 */
+} spv_fold_batch;
 int spv_bn_fold_fwd(const spv_fold_batch* a, void* stream);
 int spv_bn_fold_bwd(const spv_fold_batch* a, void* stream);   /* fold backward + the z-statistics backward */
 

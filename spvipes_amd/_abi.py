@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -17,6 +17,19 @@ LIB_PATH = os.path.join(_HERE, "_lib", "libspvipes_hip.so")
 SPV_COUNT_F32, SPV_COUNT_U16 = 0, 1
 NB_CMAX, DEC_KP, DEC_KS, DEC_CELLS_PER_WG = 64, 16, 32, 128
 DEC_KPS = DEC_KP + DEC_KS
+
+
+class DecSlots(NamedTuple):
+    """K-slot layout of the decoder's regressor operand images (``kslots`` of spv_dec_params / spv_zsplit_args / spv_fold_batch):
+    private slots KP (n_private + 1 <= KP), shared slots KS (n_shared + 1 <= KS), image rows of KPS = KP + KS"""
+    kslots: int
+    KP: int
+    KS: int
+    KPS: int
+
+
+DEC_NARROW = DecSlots(0, DEC_KP, DEC_KS, DEC_KPS)   # SPV_DEC_KP / SPV_DEC_KS
+DEC_WIDE = DecSlots(1, 32, 64, 96)                  # SPV_DEC_KP_WIDE / SPV_DEC_KS_WIDE
 
 
 class SpvCounts(C.Structure):
@@ -36,6 +49,7 @@ class SpvDecParams(C.Structure):
         ("rec_part", C.c_void_p), ("tp_part", C.c_void_p), ("ts_part", C.c_void_p), ("dtheta_part", C.c_void_p),
         ("dL", C.c_void_p), ("tP", C.c_void_p), ("tS", C.c_void_p), ("grads_f32", C.c_int32),
         ("nb_splits", C.c_int32), ("nb_genes_per_split", C.c_int32), ("nb_cell_tiles", C.c_int32),
+        ("kslots", C.c_int32),
     ]
 
 
@@ -161,7 +175,7 @@ class SpvZsplitArgs(C.Structure):
     _fields_ = [("priv", C.c_void_p * 2), ("poe", C.c_void_p * 2), ("zcat", C.c_void_p * 2), ("d_zcat", C.c_void_p * 2),
                 ("d_priv", C.c_void_p * 2), ("d_poe", C.c_void_p * 2), ("B", C.c_int32), ("n_p", C.c_int32), ("n_s", C.c_int32), ("ngroups", C.c_int32),
                 ("am_hi", C.c_void_p * 2), ("am_lo", C.c_void_p * 2), ("ld_am", C.c_int64), ("am_col", C.c_int32), ("am_cols", C.c_int32),
-                ("aps_hi", C.c_void_p * 2), ("aps_lo", C.c_void_p * 2), ("Bp", C.c_int32)]
+                ("aps_hi", C.c_void_p * 2), ("aps_lo", C.c_void_p * 2), ("Bp", C.c_int32), ("kslots", C.c_int32)]
 
 
 class SpvFoldProb(C.Structure):
@@ -175,7 +189,7 @@ class SpvFoldProb(C.Structure):
 
 class SpvFoldBatch(C.Structure):
     _fields_ = [("p", SpvFoldProb * SPV_MAXP), ("nprob", C.c_int32), ("B", C.c_int32), ("training", C.c_int32), ("eps", C.c_float),
-                ("momentum", C.c_float)]
+                ("momentum", C.c_float), ("kslots", C.c_int32)]
 
 
 class SpvGemmFixup(C.Structure):

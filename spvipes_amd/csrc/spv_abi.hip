@@ -551,8 +551,11 @@ static int to_dec(const spv_dec_params* q, DecParams& p) {
   if (p.gene_splits <= 0 || (p.genes_per_split % 32) || (long)p.gene_splits * p.genes_per_split < p.G)
     return fail(SPV_ERR_ARG, "decoder: gene splits must be multiples of 32 covering G%s");
   if (!p.Wps_hi || !p.Wps_lo || !p.Aps_hi || !p.Aps_lo) return fail(SPV_ERR_ARG, "decoder: missing packed regressor operands%s");
+  if (q->kslots != 0 && q->kslots != 1) return fail(SPV_ERR_ARG, "decoder: kslots must be 0 (16 / 32 K slots) or 1 (32 / 64)%s");
   return SPV_OK;
 }
+// KW template argument of the kernels that read the regressor operand images: 1 = narrow layout [.][48], 2 = wide [.][96]
+static inline int dec_kw(const spv_dec_params* q) { return q->kslots ? 2 : 1; }
 
 extern "C" int spv_dec_tables(const float* px_r, int32_t G, int32_t Gp, void* gene_tab, void* cnt_tab, void* stream) {
   if (!px_r || !gene_tab || !cnt_tab || G <= 0 || Gp < G) return fail(SPV_ERR_ARG, "spv_dec_tables: bad arguments%s");
@@ -595,7 +598,8 @@ extern "C" int spv_dec_lse(const spv_dec_params* q, const float* library, void* 
   int rc = lse_prepare(q, library, p);
   if (rc != SPV_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(dec_lse_kernel, dim3(p.Bp / DEC_CELLS_PER_WG, p.gene_splits), dim3(256), 0, s, p);
+  if (dec_kw(q) == 2) hipLaunchKernelGGL(dec_lse_kernel<2>, dim3(p.Bp / DEC_CELLS_PER_WG, p.gene_splits), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(dec_lse_kernel<1>, dim3(p.Bp / DEC_CELLS_PER_WG, p.gene_splits), dim3(256), 0, s, p);
   hipLaunchKernelGGL(dec_lse_combine_kernel, dim3((p.Bp + 63) / 64), dim3(256), 0, s, p.part_max_p, p.part_sum_p,
                      p.part_max_s, p.part_sum_s, p.gene_splits, p.Bp, p.B, library, (float*)p.lse_p, (float*)p.lse_s,
                      (float*)p.a_p, (float*)p.a_s);
@@ -611,8 +615,10 @@ extern "C" int spv_dec_lse_grouped(const spv_dec_group* g, int32_t n, void* stre
     if (rc != SPV_OK) return rc;
     rc = lse_prepare(&g[i + 1].p, g[i + 1].library, p1);
     if (rc != SPV_OK) return rc;
+    if (dec_kw(&g[i].p) != dec_kw(&g[i + 1].p)) break;   // (one grid needs one operand layout)
     const int bp = p0.Bp > p1.Bp ? p0.Bp : p1.Bp, gs = p0.gene_splits > p1.gene_splits ? p0.gene_splits : p1.gene_splits;
-    hipLaunchKernelGGL(dec_lse_pair_kernel, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, s, p0, p1);
+    if (dec_kw(&g[i].p) == 2) hipLaunchKernelGGL(dec_lse_pair_kernel<2>, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, s, p0, p1);
+    else hipLaunchKernelGGL(dec_lse_pair_kernel<1>, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, s, p0, p1);
     const LseCombArgs c0{p0.part_max_p, p0.part_sum_p, p0.part_max_s, p0.part_sum_s, p0.gene_splits, p0.Bp, p0.B, g[i].library, (float*)p0.lse_p, (float*)p0.lse_s, (float*)p0.a_p, (float*)p0.a_s};
     const LseCombArgs c1{p1.part_max_p, p1.part_sum_p, p1.part_max_s, p1.part_sum_s, p1.gene_splits, p1.Bp, p1.B, g[i + 1].library, (float*)p1.lse_p, (float*)p1.lse_s, (float*)p1.a_p, (float*)p1.a_s};
     hipLaunchKernelGGL(dec_lse_combine_pair_kernel, dim3((bp + 63) / 64, 1, 2), dim3(256), 0, s, c0, c1);
@@ -625,19 +631,24 @@ extern "C" int spv_dec_lse_grouped(const spv_dec_group* g, int32_t n, void* stre
   return SPV_OK;
 }
 
-template <bool TRAIN, typename GT, int CM>
+template <bool TRAIN, typename GT, int CM, int KW>
 static void nb_launch_mode(const DecParams& p, hipStream_t s) {
   const int ctiles = (p.Bp + NB_CELLS_PER_WG - 1) / NB_CELLS_PER_WG;
   dim3 grid((ctiles + p.nb_cell_tiles - 1) / p.nb_cell_tiles, p.nb_splits);
-  if (p.logits_f32) hipLaunchKernelGGL((dec_nb_kernel<TRAIN, GT, float, CM>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((dec_nb_kernel<TRAIN, GT, _Float16, CM>), grid, dim3(256), 0, s, p);
+  if (p.logits_f32) hipLaunchKernelGGL((dec_nb_kernel<TRAIN, GT, float, CM, KW>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((dec_nb_kernel<TRAIN, GT, _Float16, CM, KW>), grid, dim3(256), 0, s, p);
+}
+template <bool TRAIN, typename GT, int KW>
+static void nb_launch_kw(const DecParams& p, hipStream_t s) {
+  if (!p.count_is_u16) return nb_launch_mode<TRAIN, GT, CNT_F32, KW>(p, s);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(p.X) & 7) == 0) && (p.ldx % 4 == 0) && (p.col_off % 4 == 0);
+  if (aligned) nb_launch_mode<TRAIN, GT, CNT_U16_ALIGNED, KW>(p, s);
+  else nb_launch_mode<TRAIN, GT, CNT_U16_ANY, KW>(p, s);
 }
 template <bool TRAIN, typename GT>
-static void nb_launch(const DecParams& p, hipStream_t s) {
-  if (!p.count_is_u16) return nb_launch_mode<TRAIN, GT, CNT_F32>(p, s);
-  const bool aligned = ((reinterpret_cast<uintptr_t>(p.X) & 7) == 0) && (p.ldx % 4 == 0) && (p.col_off % 4 == 0);
-  if (aligned) nb_launch_mode<TRAIN, GT, CNT_U16_ALIGNED>(p, s);
-  else nb_launch_mode<TRAIN, GT, CNT_U16_ANY>(p, s);
+static void nb_launch(const DecParams& p, int kw, hipStream_t s) {
+  if (kw == 2) nb_launch_kw<TRAIN, GT, 2>(p, s);
+  else nb_launch_kw<TRAIN, GT, 1>(p, s);
 }
 
 static int nb_prepare(const spv_dec_params* q, int32_t train, DecParams& p) {
@@ -658,11 +669,12 @@ extern "C" int spv_dec_nb_fwd(const spv_dec_params* q, int32_t train, void* stre
   int rc = nb_prepare(q, train, p);
   if (rc != SPV_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
+  const int kw = dec_kw(q);
   if (train) {
-    if (p.grads_f32) nb_launch<true, split_t>(p, s);
-    else nb_launch<true, bf16_t>(p, s);
+    if (p.grads_f32) nb_launch<true, split_t>(p, kw, s);
+    else nb_launch<true, bf16_t>(p, kw, s);
   } else {
-    nb_launch<false, bf16_t>(p, s);
+    nb_launch<false, bf16_t>(p, kw, s);
   }
   return launch_status("spv_dec_nb_fwd");
 }
@@ -671,18 +683,23 @@ static int nb_count_mode(const DecParams& p) {
   const bool aligned = ((reinterpret_cast<uintptr_t>(p.X) & 7) == 0) && (p.ldx % 4 == 0) && (p.col_off % 4 == 0);
   return aligned ? CNT_U16_ALIGNED : CNT_U16_ANY;
 }
-template <bool TRAIN, typename GT, int CM>
+template <bool TRAIN, typename GT, int CM, int KW>
 static void nb_launch_pair_mode(const DecParams& p0, const DecParams& p1, hipStream_t s) {
   auto gx = [](const DecParams& p) { return ((p.Bp + NB_CELLS_PER_WG - 1) / NB_CELLS_PER_WG + p.nb_cell_tiles - 1) / p.nb_cell_tiles; };
   dim3 grid(gx(p0) > gx(p1) ? gx(p0) : gx(p1), p0.nb_splits > p1.nb_splits ? p0.nb_splits : p1.nb_splits, 2);
-  if (p0.logits_f32) hipLaunchKernelGGL((dec_nb_pair_kernel<TRAIN, GT, float, CM>), grid, dim3(256), 0, s, p0, p1);
-  else hipLaunchKernelGGL((dec_nb_pair_kernel<TRAIN, GT, _Float16, CM>), grid, dim3(256), 0, s, p0, p1);
+  if (p0.logits_f32) hipLaunchKernelGGL((dec_nb_pair_kernel<TRAIN, GT, float, CM, KW>), grid, dim3(256), 0, s, p0, p1);
+  else hipLaunchKernelGGL((dec_nb_pair_kernel<TRAIN, GT, _Float16, CM, KW>), grid, dim3(256), 0, s, p0, p1);
+}
+template <bool TRAIN, typename GT, int KW>
+static void nb_launch_pair_kw(const DecParams& p0, const DecParams& p1, int cm, hipStream_t s) {
+  if (cm == CNT_F32) nb_launch_pair_mode<TRAIN, GT, CNT_F32, KW>(p0, p1, s);
+  else if (cm == CNT_U16_ALIGNED) nb_launch_pair_mode<TRAIN, GT, CNT_U16_ALIGNED, KW>(p0, p1, s);
+  else nb_launch_pair_mode<TRAIN, GT, CNT_U16_ANY, KW>(p0, p1, s);
 }
 template <bool TRAIN, typename GT>
-static void nb_launch_pair(const DecParams& p0, const DecParams& p1, int cm, hipStream_t s) {
-  if (cm == CNT_F32) nb_launch_pair_mode<TRAIN, GT, CNT_F32>(p0, p1, s);
-  else if (cm == CNT_U16_ALIGNED) nb_launch_pair_mode<TRAIN, GT, CNT_U16_ALIGNED>(p0, p1, s);
-  else nb_launch_pair_mode<TRAIN, GT, CNT_U16_ANY>(p0, p1, s);
+static void nb_launch_pair(const DecParams& p0, const DecParams& p1, int cm, int kw, hipStream_t s) {
+  if (kw == 2) nb_launch_pair_kw<TRAIN, GT, 2>(p0, p1, cm, s);
+  else nb_launch_pair_kw<TRAIN, GT, 1>(p0, p1, cm, s);
 }
 extern "C" int spv_dec_nb_fwd_grouped(const spv_dec_group* g, int32_t n, int32_t train, void* stream) {
   if (!g || n <= 0) return fail(SPV_ERR_ARG, "spv_dec_nb_fwd_grouped: bad arguments%s");
@@ -695,13 +712,13 @@ extern "C" int spv_dec_nb_fwd_grouped(const spv_dec_group* g, int32_t n, int32_t
     rc = nb_prepare(&g[i + 1].p, train, p1);
     if (rc != SPV_OK) return rc;
     // one grid needs one kernel variant: count storage, logits type and gradient word type of both groups must agree
-    if (nb_count_mode(p0) != nb_count_mode(p1) || p0.logits_f32 != p1.logits_f32 || p0.grads_f32 != p1.grads_f32) break;
-    const int cm = nb_count_mode(p0);
+    if (nb_count_mode(p0) != nb_count_mode(p1) || p0.logits_f32 != p1.logits_f32 || p0.grads_f32 != p1.grads_f32 || dec_kw(&g[i].p) != dec_kw(&g[i + 1].p)) break;
+    const int cm = nb_count_mode(p0), kw = dec_kw(&g[i].p);
     if (train) {
-      if (p0.grads_f32) nb_launch_pair<true, split_t>(p0, p1, cm, s);
-      else nb_launch_pair<true, bf16_t>(p0, p1, cm, s);
+      if (p0.grads_f32) nb_launch_pair<true, split_t>(p0, p1, cm, kw, s);
+      else nb_launch_pair<true, bf16_t>(p0, p1, cm, kw, s);
     } else {
-      nb_launch_pair<false, bf16_t>(p0, p1, cm, s);
+      nb_launch_pair<false, bf16_t>(p0, p1, cm, kw, s);
     }
     if (hipGetLastError() != hipSuccess) return launch_status("spv_dec_nb_fwd_grouped");
   }
@@ -778,7 +795,10 @@ extern "C" int spv_dec_materialize(const spv_dec_params* q, float* scale_p, floa
   if (p.n_gene_tiles != p.Gp / 32) return fail(SPV_ERR_ARG, "spv_dec_materialize: n_gene_tiles must be Gp / 32%s");
   dim3 grid(p.Bp / DEC_CELLS_PER_WG, p.gene_splits);
   hipStream_t s = (hipStream_t)stream;
-  if (p.logits_f32) hipLaunchKernelGGL((dec_materialize_kernel<float>), grid, dim3(256), 0, s, p, scale_p, scale_s, rate_p, rate_s, logits_out, (long)ld);
+  const bool wide = dec_kw(q) == 2;
+  if (p.logits_f32 && wide) hipLaunchKernelGGL((dec_materialize_kernel<float, 2>), grid, dim3(256), 0, s, p, scale_p, scale_s, rate_p, rate_s, logits_out, (long)ld);
+  else if (p.logits_f32) hipLaunchKernelGGL((dec_materialize_kernel<float>), grid, dim3(256), 0, s, p, scale_p, scale_s, rate_p, rate_s, logits_out, (long)ld);
+  else if (wide) hipLaunchKernelGGL((dec_materialize_kernel<_Float16, 2>), grid, dim3(256), 0, s, p, scale_p, scale_s, rate_p, rate_s, logits_out, (long)ld);
   else hipLaunchKernelGGL((dec_materialize_kernel<_Float16>), grid, dim3(256), 0, s, p, scale_p, scale_s, rate_p, rate_s, logits_out, (long)ld);
   return launch_status("spv_dec_materialize");
 }
@@ -790,6 +810,7 @@ extern "C" int spv_dec_dz(const spv_dec_params* q, const float* Tp, const float*
   if (!Tp || !Ts || !p.tP || !p.tS || !p.lse_p || !p.lse_s || !dz_part) return fail(SPV_ERR_ARG, "spv_dec_dz: null pointer%s");
   if (p.n_gene_tiles != p.Gp / 32) return fail(SPV_ERR_ARG, "spv_dec_dz: n_gene_tiles must be Gp / 32%s");
   if (p.grads_f32) return fail(SPV_ERR_UNSUPPORTED, "spv_dec_dz: needs bf16 gradient arrays%s");
+  if (dec_kw(q) != 1) return fail(SPV_ERR_UNSUPPORTED, "spv_dec_dz: narrow operand layout only (kslots = 0)%s");
   hipLaunchKernelGGL((dec_softmax_bwd_kernel<bf16_t, true, false>), dim3(p.Bp / DEC_CELLS_PER_WG, p.gene_splits), dim3(256), 0, (hipStream_t)stream, p, Tp, Ts, dz_part, (float*)nullptr, (float*)nullptr);
   return launch_status("spv_dec_dz");
 }
@@ -803,6 +824,12 @@ extern "C" int spv_dec_softmax_bwd(const spv_dec_params* q, const float* Tp, con
   dim3 grid(p.Bp / DEC_CELLS_PER_WG, p.gene_splits);
   hipStream_t s = (hipStream_t)stream;
   float* const none = nullptr;
+  if (dec_kw(q) == 2) {   // wide layout: the in-place fix only (the latent gradient of the rate heads then comes from split-K GEMMs)
+    if (dz_part) return fail(SPV_ERR_UNSUPPORTED, "spv_dec_softmax_bwd: the wide operand layout (kslots = 1) takes no dz_part%s");
+    if (p.grads_f32) hipLaunchKernelGGL((dec_softmax_bwd_kernel<split_t, false, true, false, 2>), grid, dim3(256), 0, s, p, Tp, Ts, none, none, none);
+    else hipLaunchKernelGGL((dec_softmax_bwd_kernel<bf16_t, false, true, false, 2>), grid, dim3(256), 0, s, p, Tp, Ts, none, none, none);
+    return launch_status("spv_dec_softmax_bwd");
+  }
   if (p.grads_f32 && dz_part) hipLaunchKernelGGL((dec_softmax_bwd_kernel<split_t, true>), grid, dim3(256), 0, s, p, Tp, Ts, dz_part, none, none);
   else if (p.grads_f32) hipLaunchKernelGGL((dec_softmax_bwd_kernel<split_t, false>), grid, dim3(256), 0, s, p, Tp, Ts, none, none, none);
   else if (dz_part) hipLaunchKernelGGL((dec_softmax_bwd_kernel<bf16_t, true>), grid, dim3(256), 0, s, p, Tp, Ts, dz_part, none, none);
@@ -821,6 +848,7 @@ static int heads_bwd_prepare(const spv_dec_params* q, const float* Tp, const flo
   if (p.n_gene_tiles != p.Gp / 32) return fail(SPV_ERR_ARG, "spv_dec_heads_bwd: n_gene_tiles must be Gp / 32%s");
   if (p.Bp % DEC_CELLS_PER_WG) return fail(SPV_ERR_ARG, "spv_dec_heads_bwd: Bp must be a multiple of 128%s");
   if (p.grads_f32 && (!p.Wps_lo || !p.Aps_lo)) return fail(SPV_ERR_ARG, "spv_dec_heads_bwd: split gradient words need the lo planes of the operand images%s");
+  if (dec_kw(q) != 1) return fail(SPV_ERR_UNSUPPORTED, "spv_dec_heads_bwd: narrow operand layout only (kslots = 0)%s");
   return SPV_OK;
 }
 extern "C" int spv_dec_heads_bwd(const spv_dec_params* q, const float* Tp, const float* Ts, float* dz_part, float* dw_part, void* stream) {
@@ -1380,11 +1408,13 @@ extern "C" int spv_zsplit_fwd(const spv_zsplit_args* a, void* stream) {
   // positions itself); otherwise zcat first, then whatever images were asked for
   if (!pack_all) hipLaunchKernelGGL(zsplit_fwd_kernel, dim3((unsigned)((tot + 255) / 256), a->ngroups), dim3(256), 0, (hipStream_t)stream, *a);
   if (pack) {
-    if (a->Bp < a->B || a->n_p + 1 > SPV_DEC_KP || a->n_s + 1 > SPV_DEC_KS || a->am_cols < a->n_p + a->n_s + 1 || a->am_cols < 0 ||
+    const int kp = a->kslots ? SPV_DEC_KP_WIDE : SPV_DEC_KP, ks = a->kslots ? SPV_DEC_KS_WIDE : SPV_DEC_KS;
+    if (a->Bp < a->B || (a->kslots != 0 && a->kslots != 1) || a->n_p + 1 > kp || a->n_s + 1 > ks || a->am_cols < a->n_p + a->n_s + 1 || a->am_cols < 0 ||
         a->ld_am < a->am_col + a->am_cols)
       return fail(SPV_ERR_ARG, "spv_zsplit_fwd: bad operand-image shape%s");
-    const long tp = (long)a->Bp * (SPV_DEC_KP + SPV_DEC_KS + a->am_cols);
-    hipLaunchKernelGGL(zsplit_pack_kernel, dim3((unsigned)((tp + 255) / 256), a->ngroups), dim3(256), 0, (hipStream_t)stream, *a);
+    const long tp = (long)a->Bp * (kp + ks + a->am_cols);
+    if (a->kslots) hipLaunchKernelGGL(zsplit_pack_kernel<2>, dim3((unsigned)((tp + 255) / 256), a->ngroups), dim3(256), 0, (hipStream_t)stream, *a);
+    else hipLaunchKernelGGL(zsplit_pack_kernel<1>, dim3((unsigned)((tp + 255) / 256), a->ngroups), dim3(256), 0, (hipStream_t)stream, *a);
   }
   return launch_status("spv_zsplit_fwd");
 }
@@ -1398,11 +1428,13 @@ extern "C" int spv_zsplit_bwd(const spv_zsplit_args* a, void* stream) {
 
 static int check_fold(const spv_fold_batch* a, const char* who) {
   if (!a || a->nprob <= 0 || a->nprob > SPV_MAXP || a->B <= 0) return fail(SPV_ERR_ARG, "%s: bad batch", who);
+  if (a->kslots != 0 && a->kslots != 1) return fail(SPV_ERR_ARG, "%s: kslots must be 0 or 1", who);
+  const int kmax = a->kslots ? FOLD_KMAX_WIDE : FOLD_KMAX;
   for (int i = 0; i < a->nprob; ++i) {
     const spv_fold_prob& q = a->p[i];
-    if (q.K <= 0 || q.K > FOLD_KMAX || q.G <= 0 || q.Gp < q.G || !q.W || !q.gamma || !q.beta || !q.running_mean || !q.running_var || !q.stat ||
+    if (q.K <= 0 || q.K > kmax || q.G <= 0 || q.Gp < q.G || !q.W || !q.gamma || !q.beta || !q.running_mean || !q.running_var || !q.stat ||
         (a->training && (!q.zsum || !q.zz)))
-      return fail(SPV_ERR_ARG, "%s: bad problem (K <= 32, non-null pointers)", who);
+      return fail(SPV_ERR_ARG, "%s: bad problem (K <= 32, or 64 with kslots = 1; non-null pointers)", who);
   }
   return SPV_OK;
 }
@@ -1417,7 +1449,8 @@ extern "C" int spv_bn_fold_fwd(const spv_fold_batch* a, void* stream) {
       return fail(SPV_ERR_ARG, "spv_bn_fold_fwd: slot, col_off, ld_img must be multiples of 8 elements and the images 16-byte aligned%s");
     gmax = q.Gp > gmax ? q.Gp : gmax;
   }
-  hipLaunchKernelGGL(bn_fold_fwd_kernel, dim3((gmax + FOLD_FWD_GENES - 1) / FOLD_FWD_GENES, a->nprob), dim3(256), 0, (hipStream_t)stream, *a);
+  if (a->kslots) hipLaunchKernelGGL(bn_fold_fwd_kernel<FOLD_KMAX_WIDE>, dim3((gmax + FOLD_FWD_GENES - 1) / FOLD_FWD_GENES, a->nprob), dim3(256), 0, (hipStream_t)stream, *a);
+  else hipLaunchKernelGGL(bn_fold_fwd_kernel<FOLD_KMAX>, dim3((gmax + FOLD_FWD_GENES - 1) / FOLD_FWD_GENES, a->nprob), dim3(256), 0, (hipStream_t)stream, *a);
   return launch_status("spv_bn_fold_fwd");
 }
 extern "C" int spv_bn_fold_bwd(const spv_fold_batch* a, void* stream) {
@@ -1431,14 +1464,16 @@ extern "C" int spv_bn_fold_bwd(const spv_fold_batch* a, void* stream) {
     gmax = q.G > gmax ? q.G : gmax;
   }
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_fold_bwd_kernel, dim3((gmax + 255) / 256, a->nprob), dim3(FOLD_BWD_THREADS), 0, s, *a);
+  if (a->kslots) hipLaunchKernelGGL(bn_fold_bwd_kernel<FOLD_KMAX_WIDE>, dim3((gmax + 255) / 256, a->nprob), dim3(FOLD_BWD_THREADS), 0, s, *a);
+  else hipLaunchKernelGGL(bn_fold_bwd_kernel<FOLD_KMAX>, dim3((gmax + 255) / 256, a->nprob), dim3(FOLD_BWD_THREADS), 0, s, *a);
   if (a->training) {   // (the sum over the gene blocks' partials happens inside zstats_bwd_kernel)
     for (int i = 0; i < a->nprob; ++i) {
       const spv_fold_prob& q = a->p[i];
       if (q.out_priv && (!q.out_poe || q.n_p <= 0 || q.n_s <= 0 || q.zcol < 0 || q.zcol + q.K > q.n_p + q.n_s))
         return fail(SPV_ERR_ARG, "spv_bn_fold_bwd: bad latent-slicing outputs%s");
     }
-    hipLaunchKernelGGL(zstats_bwd_kernel, dim3((a->B + 63) / 64, a->nprob), dim3(256), 0, s, *a);
+    if (a->kslots) hipLaunchKernelGGL(zstats_bwd_kernel<FOLD_KMAX_WIDE>, dim3((a->B + 63) / 64, a->nprob), dim3(256), 0, s, *a);
+    else hipLaunchKernelGGL(zstats_bwd_kernel<FOLD_KMAX>, dim3((a->B + 63) / 64, a->nprob), dim3(256), 0, s, *a);
   }
   return launch_status("spv_bn_fold_bwd");
 }

@@ -33,6 +33,12 @@ constexpr int NB_CMAX = 64;      // table rows (counts 0..63)
 constexpr int DEC_KP = 16;       // K slots of the private regressor  (n_p + 1 bias <= 16)
 constexpr int DEC_KS = 32;       // K slots of the shared regressor   (n_s + 1 bias <= 32)
 constexpr int DEC_KPS = DEC_KP + DEC_KS;
+// The WIDE layout (spv_dec_params.kslots = 1) doubles both: K slots 32 / 64, images [.][96].  The kernels that read or write the
+// regressor operand images take KW = 1 (narrow, the layout above) or 2 (wide) as a template argument; inside them DEC_KP / DEC_KS /
+// DEC_KPS are redeclared from DEC_KP_W<KW> ... so that the narrow instantiation is the code it always was.
+template <int KW> constexpr int DEC_KP_W = 16 * KW;
+template <int KW> constexpr int DEC_KS_W = 32 * KW;
+template <int KW> constexpr int DEC_KPS_W = 48 * KW;
 constexpr int DEC_CELLS_PER_WG = 128;
 
 struct DecParams {
@@ -137,32 +143,49 @@ __device__ __forceinline__ void decode_counts4(const DecParams& p, const RawCoun
 
 // y_p / y_s tiles (32 genes x 32 cells) with split-bf16 operands straight from L2 (K = 16 / 32):
 // A fragment = W' rows (natural [g][k], PsW below), B fragment = the wave's resident z fragments.
-struct PsFrags { s8v hi[3], lo[3]; };
-__device__ __forceinline__ void load_ps_cell_frags(const DecParams& p, int cell0, int lane, PsFrags& f) {
+// (wide layout: six K slices, 0..1 private, 2..5 shared)
+template <int KW> struct PsFragsK { s8v hi[3 * KW], lo[3 * KW]; };
+typedef PsFragsK<1> PsFrags;
+template <int KW>
+__device__ __forceinline__ void load_ps_cell_frags(const DecParams& p, int cell0, int lane, PsFragsK<KW>& f) {
+  constexpr int DEC_KPS = DEC_KPS_W<KW>;
   const long off = (long)(cell0 + (lane & 31)) * DEC_KPS + 8 * (lane >> 5);
 #pragma unroll
-  for (int s = 0; s < 3; ++s) {
+  for (int s = 0; s < 3 * KW; ++s) {
     f.hi[s] = *reinterpret_cast<const s8v*>(p.Aps_hi + off + 16 * s);
     f.lo[s] = *reinterpret_cast<const s8v*>(p.Aps_lo + off + 16 * s);
   }
 }
-struct PsW { s8v hi[3], lo[3]; };  // gene-side fragments of one 32-gene tile (K slices 0: private, 1..2: shared)
-__device__ __forceinline__ void load_ps_w(const DecParams& p, int g0, int lane, PsW& w) {
+template <int KW> struct PsWK { s8v hi[3 * KW], lo[3 * KW]; };  // gene-side fragments of one 32-gene tile (K slices 0: private, 1..2: shared)
+typedef PsWK<1> PsW;
+template <int KW>
+__device__ __forceinline__ void load_ps_w(const DecParams& p, int g0, int lane, PsWK<KW>& w) {
+  constexpr int DEC_KPS = DEC_KPS_W<KW>;
   const long off = (long)(g0 + (lane & 31)) * DEC_KPS + 8 * (lane >> 5);
 #pragma unroll
-  for (int s = 0; s < 3; ++s) {
+  for (int s = 0; s < 3 * KW; ++s) {
     w.hi[s] = *reinterpret_cast<const s8v*>(p.Wps_hi + off + 16 * s);
     w.lo[s] = *reinterpret_cast<const s8v*>(p.Wps_lo + off + 16 * s);
   }
 }
 
+// y_p from the private K slices, y_s from the shared ones (narrow: slice 0 | slices 1, 2)
+template <int KW>
+__device__ __forceinline__ void ps_eval(const PsWK<KW>& w, const PsFragsK<KW>& cf, f16v& yp, f16v& ys) {
+#pragma unroll
+  for (int s = 0; s < KW; ++s) yp = mfma32_split<3>(w.hi[s], w.lo[s], cf.hi[s], cf.lo[s], yp);
+#pragma unroll
+  for (int s = KW; s < 3 * KW; ++s) ys = mfma32_split<3>(w.hi[s], w.lo[s], cf.hi[s], cf.lo[s], ys);
+}
+
 constexpr float NB_LOG2E_C = 1.4426950408889634f;
 // ---- pass 1: per-cell log-sum-exp over genes of y_p and y_s (softmax denominators) ------------
+template <int KW = 1>
 __device__ __forceinline__ void dec_lse_body(const DecParams& p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
   const int cell0 = blockIdx.x * DEC_CELLS_PER_WG + 32 * wave;
   const int split = blockIdx.y;
-  PsFrags cf;
+  PsFragsK<KW> cf;
   load_ps_cell_frags(p, cell0, lane, cf);
   float mp = -INFINITY, sp = 0.f, ms = -INFINITY, ss = 0.f;
   const int gbeg = split * p.genes_per_split;
@@ -170,17 +193,15 @@ __device__ __forceinline__ void dec_lse_body(const DecParams& p) {
   if (gend > p.Gp) gend = p.Gp;
   if (gend > ((p.G + 31) & ~31)) gend = (p.G + 31) & ~31;
   const int ntile = (gend - gbeg) >> 5;
-  PsW wA;
+  PsWK<KW> wA;
   if (ntile > 0) load_ps_w(p, gbeg, lane, wA);
   for (int t = 0; t < ntile; ++t) {
     const int g0 = gbeg + 32 * t;
     f16v yp, ys;
 #pragma unroll
     for (int q = 0; q < 16; ++q) { yp[q] = 0.f; ys[q] = 0.f; }
-    yp = mfma32_split<3>(wA.hi[0], wA.lo[0], cf.hi[0], cf.lo[0], yp);
-    ys = mfma32_split<3>(wA.hi[1], wA.lo[1], cf.hi[1], cf.lo[1], ys);
-    ys = mfma32_split<3>(wA.hi[2], wA.lo[2], cf.hi[2], cf.lo[2], ys);
-    PsW wB;
+    ps_eval(wA, cf, yp, ys);
+    PsWK<KW> wB;
     load_ps_w(p, gbeg + 32 * min(t + 1, ntile - 1), lane, wB);  // next tile's fragments fly under this tile's exps
     // 2 exp per element is the kernel's arithmetic; everything around it is kept to one fma and half a max per element: the gene-validity
     // masks only exist in a tile that crosses G (wave-uniform test), the maxima go through v_max3, and exp(y - m) is exp2(fma(y, log2 e, -m log2 e))
@@ -227,11 +248,13 @@ __device__ __forceinline__ void dec_lse_body(const DecParams& p) {
     p.part_max_s[o] = ms; p.part_sum_s[o] = ss;
   }
 }
-__global__ __launch_bounds__(256) void dec_lse_kernel(DecParams p) { dec_lse_body(p); }
+template <int KW = 1>
+__global__ __launch_bounds__(256) void dec_lse_kernel(DecParams p) { dec_lse_body<KW>(p); }
+template <int KW = 1>
 __global__ __launch_bounds__(256) void dec_lse_pair_kernel(DecParams p0, DecParams p1) {
   const DecParams p = blockIdx.z ? p1 : p0;
   if ((int)blockIdx.x * DEC_CELLS_PER_WG >= p.Bp || (int)blockIdx.y >= p.gene_splits) return;   // (workgroup-uniform)
-  dec_lse_body(p);
+  dec_lse_body<KW>(p);
 }
 
 // lse_k[b] = log sum_splits ...;  a_k[b] = library[b] - lse_k[b]   (log of exp(library) * softmax)
@@ -417,8 +440,17 @@ __device__ unsigned long long* g_nb_stamps;
 #ifndef SPV_NB_OCC
 #define SPV_NB_OCC 3   // waves per SIMD the likelihood kernel's register budget is sized for (tools/probes/nb_bench.hip sweeps it)
 #endif
-template <bool TRAIN, typename GT, typename LT, int CM>
+// The wide layout's weight slice is [160][96] at a pitch of 104 bf16 (52 dwords: the 8 rows of a 16-byte read phase still start on
+// distinct 4-bank groups): 2 x 33 KiB + tables = 70 KiB of LDS per workgroup, two workgroups per CU -- its register budget is sized
+// for 2 waves per SIMD.
+constexpr int NB_WPITCH_WIDE = 104;
+constexpr int SPV_NB_OCC_WIDE = 2;
+template <int KW> constexpr int NB_WPITCH_W = KW == 1 ? NB_WPITCH : NB_WPITCH_WIDE;
+template <int KW> constexpr int NB_OCC_W = KW == 1 ? SPV_NB_OCC : SPV_NB_OCC_WIDE;
+template <bool TRAIN, typename GT, typename LT, int CM, int KW = 1>
 __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
+  constexpr int DEC_KP = DEC_KP_W<KW>, DEC_KPS = DEC_KPS_W<KW>, NB_WPITCH = NB_WPITCH_W<KW>;
+  constexpr int NSK = DEC_KS_W<KW> / 32;   // K = 32 MFMA steps of the shared head (the private head is one step: K = 16 zero padded, or 32)
   __shared__ __attribute__((aligned(16))) bf16_t s_whi[NB_GSPL_MAX * NB_WPITCH], s_wlo[NB_GSPL_MAX * NB_WPITCH];
   __shared__ float4 s_gt[NB_GSPL_MAX];
   __shared__ float s_dth[TRAIN ? 4 : 1][NB_GSPL_MAX];
@@ -444,8 +476,8 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
     return;
   }
   // ---- stage this split's regressor weights [ng][48] (hi, lo) and gene table in LDS -------------------------
-  for (int i = tid; i < ng * 6; i += 256) {
-    const int row = i / 6, ch = i % 6;
+  for (int i = tid; i < ng * (DEC_KPS / 8); i += 256) {
+    const int row = i / (DEC_KPS / 8), ch = i % (DEC_KPS / 8);
     *reinterpret_cast<u4v*>(s_whi + row * NB_WPITCH + 8 * ch) = *reinterpret_cast<const u4v*>(p.Wps_hi + (long)(gbeg + row) * DEC_KPS + 8 * ch);
     *reinterpret_cast<u4v*>(s_wlo + row * NB_WPITCH + 8 * ch) = *reinterpret_cast<const u4v*>(p.Wps_lo + (long)(gbeg + row) * DEC_KPS + 8 * ch);
   }
@@ -465,11 +497,16 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
     // resident cell-side fragments: B[k = 8 gq + i][col = cell]
     const long aoff = (long)cell * DEC_KPS + 8 * gq;
     s8v bp_hi = *reinterpret_cast<const s8v*>(p.Aps_hi + aoff), bp_lo = *reinterpret_cast<const s8v*>(p.Aps_lo + aoff);
-    if (gq >= 2) {  // the private regressor only has K = 16: its K = 32 MFMA sees zeros beyond
+    if (DEC_KP == 16 && gq >= 2) {  // the private regressor only has K = 16: its K = 32 MFMA sees zeros beyond
 #pragma unroll
       for (int i = 0; i < 8; ++i) { bp_hi[i] = 0; bp_lo[i] = 0; }
     }
-    const s8v bs_hi = *reinterpret_cast<const s8v*>(p.Aps_hi + aoff + DEC_KP), bs_lo = *reinterpret_cast<const s8v*>(p.Aps_lo + aoff + DEC_KP);
+    s8v bs_hi[NSK], bs_lo[NSK];
+#pragma unroll
+    for (int s = 0; s < NSK; ++s) {
+      bs_hi[s] = *reinterpret_cast<const s8v*>(p.Aps_hi + aoff + DEC_KP + 32 * s);
+      bs_lo[s] = *reinterpret_cast<const s8v*>(p.Aps_lo + aoff + DEC_KP + 32 * s);
+    }
     const float ap2 = p.a_p[cell] * NB_LOG2E, as2 = p.a_s[cell] * NB_LOG2E;   // a_k = library - lse_k, in base-2 units
     const float w = p.w_row[cell];
     const long row_of_cell = ((SPV_NB_ABLATE & 16) != 0) ? 0 : (cell_ok ? (p.rows ? (long)p.rows[cell] : (long)cell) : 0);
@@ -513,14 +550,17 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
       // ---- y_p, y_s for this chunk: A[row = gene][k = 8 gq + i] from the LDS slice ------------------------------
       const int wrow = (16 * c + c16) * NB_WPITCH + 8 * gq;
       const s8v wp_hi = *reinterpret_cast<const s8v*>(s_whi + wrow), wp_lo = *reinterpret_cast<const s8v*>(s_wlo + wrow);
-      const s8v ws_hi = *reinterpret_cast<const s8v*>(s_whi + wrow + DEC_KP), ws_lo = *reinterpret_cast<const s8v*>(s_wlo + wrow + DEC_KP);
       f4acc yp = {0.f, 0.f, 0.f, 0.f}, ys = {0.f, 0.f, 0.f, 0.f};
       yp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp_hi, bp_lo, yp, 0, 0, 0);
       yp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp_lo, bp_hi, yp, 0, 0, 0);
       yp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp_hi, bp_hi, yp, 0, 0, 0);
-      ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_hi, bs_lo, ys, 0, 0, 0);
-      ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_lo, bs_hi, ys, 0, 0, 0);
-      ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_hi, bs_hi, ys, 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < NSK; ++s) {
+        const s8v ws_hi = *reinterpret_cast<const s8v*>(s_whi + wrow + DEC_KP + 32 * s), ws_lo = *reinterpret_cast<const s8v*>(s_wlo + wrow + DEC_KP + 32 * s);
+        ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_hi, bs_lo[s], ys, 0, 0, 0);
+        ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_lo, bs_hi[s], ys, 0, 0, 0);
+        ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_hi, bs_hi[s], ys, 0, 0, 0);
+      }
       // ---- issue the loads of the following chunks (past the end: the last chunk again, unused) ------------------
       const int g1 = gbeg + 16 * min(c + 1, nchunks - 1), g2 = gbeg + 16 * min(c + 2, nchunks - 1);
       float ellB[4];
@@ -653,14 +693,14 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
   }
   NB_STAMP(5);
 }
-template <bool TRAIN, typename GT, typename LT, int CM>
-__global__ __launch_bounds__(256, SPV_NB_OCC) void dec_nb_kernel(DecParams p) { dec_nb_body<TRAIN, GT, LT, CM>(p); }
-template <bool TRAIN, typename GT, typename LT, int CM>
-__global__ __launch_bounds__(256, SPV_NB_OCC) void dec_nb_pair_kernel(DecParams p0, DecParams p1) {
+template <bool TRAIN, typename GT, typename LT, int CM, int KW = 1>
+__global__ __launch_bounds__(256, NB_OCC_W<KW>) void dec_nb_kernel(DecParams p) { dec_nb_body<TRAIN, GT, LT, CM, KW>(p); }
+template <bool TRAIN, typename GT, typename LT, int CM, int KW = 1>
+__global__ __launch_bounds__(256, NB_OCC_W<KW>) void dec_nb_pair_kernel(DecParams p0, DecParams p1) {
   const DecParams p = blockIdx.z ? p1 : p0;
   const int ctiles = (p.Bp + NB_CELLS_PER_WG - 1) / NB_CELLS_PER_WG;
   if ((int)blockIdx.x >= (ctiles + p.nb_cell_tiles - 1) / p.nb_cell_tiles || (int)blockIdx.y >= p.nb_splits) return;   // (workgroup-uniform)
-  dec_nb_body<TRAIN, GT, LT, CM>(p);
+  dec_nb_body<TRAIN, GT, LT, CM, KW>(p);
 }
 
 // ---- materialising path: the decoder outputs the reference's generative() returns ---------------------------------
@@ -668,13 +708,13 @@ __global__ __launch_bounds__(256, SPV_NB_OCC) void dec_nb_pair_kernel(DecParams 
 // (:322-325) as plain row-major fp32 [B][ld].  Off the hot path (the fused likelihood never stores them): same y_k
 // evaluation as dec_lse_kernel (split-bf16 K = 16 / 32 MFMAs), needs lse_k / a_k from spv_dec_lse and the tile-ordered
 // logits from spv_dec_logits.  Lane = cell, registers = genes: every lane writes 16-byte pieces of its own row.
-template <typename LT>
+template <typename LT, int KW = 1>
 __global__ __launch_bounds__(256) void dec_materialize_kernel(DecParams p, float* scale_p, float* scale_s, float* rate_p, float* rate_s,
                                                               float* logits_out, long ld) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, r = lane & 31;
   const int cell_tile = blockIdx.x * (DEC_CELLS_PER_WG / 32) + wave;
   const int cell0 = cell_tile * 32, cell = cell0 + r;
-  PsFrags cf;
+  PsFragsK<KW> cf;
   load_ps_cell_frags(p, cell0, lane, cf);
   const float lp = p.lse_p[cell], ls = p.lse_s[cell], ap = p.a_p[cell], as = p.a_s[cell];
   const int gbeg = blockIdx.y * p.genes_per_split;
@@ -682,14 +722,12 @@ __global__ __launch_bounds__(256) void dec_materialize_kernel(DecParams p, float
   if (gend > p.Gp) gend = p.Gp;
   if (gend > ((p.G + 31) & ~31)) gend = (p.G + 31) & ~31;
   for (int g0 = gbeg; g0 < gend; g0 += 32) {
-    PsW w;
+    PsWK<KW> w;
     load_ps_w(p, g0, lane, w);
     f16v yp, ys;
 #pragma unroll
     for (int q = 0; q < 16; ++q) { yp[q] = 0.f; ys[q] = 0.f; }
-    yp = mfma32_split<3>(w.hi[0], w.lo[0], cf.hi[0], cf.lo[0], yp);
-    ys = mfma32_split<3>(w.hi[1], w.lo[1], cf.hi[1], cf.lo[1], ys);
-    ys = mfma32_split<3>(w.hi[2], w.lo[2], cf.hi[2], cf.lo[2], ys);
+    ps_eval(w, cf, yp, ys);
     const size_t tbase = ((size_t)cell_tile * p.n_gene_tiles + (g0 >> 5)) * 1024 + lane * 4;
 #pragma unroll
     for (int qq = 0; qq < 4; ++qq) {
@@ -774,10 +812,11 @@ constexpr int SMB_PITCH = SMB_SUB + 4;  // bf16 per row: 648 B = 162 dwords = 2 
 // spv_dec_heads_wgrad pass (another 168 MB read) -- the [B, G] traffic of the decoder backward drops from 924 to ~600 MB per group.
 constexpr int SMB_ZPITCH = 96;   // bf16 per row of the latent image in LDS: 48 dwords, a k-major pitch whose transposed reads are conflict free (kmajor_pitch)
 constexpr int SMB_TILE_ELEMS = DEC_CELLS_PER_WG * 32;   // one head's parked tile: [128 cells][32 genes] bf16 (k-major for the transposed reads)
-template <typename GT, bool FUSE, bool WRITE = true, bool HEADS = false>
+template <typename GT, bool FUSE, bool WRITE = true, bool HEADS = false, int KW = 1>
 __global__ __launch_bounds__(256, 2) void dec_softmax_bwd_kernel(DecParams p, const float* Tp, const float* Ts, float* dz_part, float* dwp_part, float* dws_part) {
   typedef typename Raw4<GT>::type raw_t;
   static_assert(!HEADS || (FUSE && !WRITE), "the weight-gradient fusion rides on the read-only fused pass");
+  static_assert(KW == 1 || !FUSE, "the wide layout runs the in-place softmax fix only: its latent / weight gradients are split-K GEMMs");
   const long plane = (long)p.Bp * p.Gp;
   constexpr bool SPLITG = FUSE && sizeof(raw_t) == sizeof(u4v);   // split-bf16 gradient words ("fp32" mode): the fused contraction runs on hi / lo pairs
   __shared__ __attribute__((aligned(16))) bf16_t s_wT[FUSE ? DEC_KPS * SMB_PITCH : 8];
@@ -789,7 +828,7 @@ __global__ __launch_bounds__(256, 2) void dec_softmax_bwd_kernel(DecParams p, co
   const int cell0 = cell_tile * 32;
   const int cell = cell0 + r;
   const int split = blockIdx.y;
-  PsFrags cf;
+  PsFragsK<KW> cf;
   load_ps_cell_frags(p, cell0, lane, cf);
   const float lp = p.lse_p[cell], ls = p.lse_s[cell];
   const float tpb = Tp[cell], tsb = Ts[cell];
@@ -814,7 +853,7 @@ __global__ __launch_bounds__(256, 2) void dec_softmax_bwd_kernel(DecParams p, co
   }
   if (ntile > 0) {   // (block-uniform)
     const long trow = (long)cell_tile * p.n_gene_tiles;
-    PsW wA;
+    PsWK<KW> wA;
     // two register stages for the gradient words, used alternately (the loop below is unrolled by two, so the roles are static):
     // read-modify-write variants request tile t + 1 at the top of tile t; the read-only HEADS variant has nothing to drain and keeps
     // TWO tiles in flight -- tile t + 2 is requested into tile t's registers as soon as they have been decoded (with one barrier per
@@ -880,10 +919,8 @@ __global__ __launch_bounds__(256, 2) void dec_softmax_bwd_kernel(DecParams p, co
       f16v yp, ys;
 #pragma unroll
       for (int q = 0; q < 16; ++q) { yp[q] = 0.f; ys[q] = 0.f; }
-      yp = mfma32_split<3>(wA.hi[0], wA.lo[0], cf.hi[0], cf.lo[0], yp);
-      ys = mfma32_split<3>(wA.hi[1], wA.lo[1], cf.hi[1], cf.lo[1], ys);
-      ys = mfma32_split<3>(wA.hi[2], wA.lo[2], cf.hi[2], cf.lo[2], ys);
-      PsW wB;
+      ps_eval(wA, cf, yp, ys);
+      PsWK<KW> wB;
       load_ps_w(p, gn, lane, wB);
       const long tbase = (trow + (g0 >> 5)) * 1024 + lane * 4;
       if constexpr (!HEADS) request(t + 1, rpB, rsB);

@@ -1081,7 +1081,9 @@ __global__ __launch_bounds__(256) void plan_expert_bwd_kernel(ExpertArgs a) {
 // nn/networks.py:314,318 with scvi FCLayers' BatchNorm1d(eps 1e-3, momentum 0.01)).
 // ---------------------------------------------------------------------------------------------
 typedef spv_zsplit_args ZsplitArgs;
-constexpr int DEC_PACK_KP = 16, DEC_PACK_KPS = 48;   // = SPV_DEC_KP, SPV_DEC_KP + SPV_DEC_KS (layout of the regressor operand image)
+// layout of the regressor operand image: KW = 1: SPV_DEC_KP, SPV_DEC_KP + SPV_DEC_KS (16, 48); KW = 2 (the wide layout): 32, 96
+template <int KW> constexpr int DEC_PACK_KP_W = 16 * KW;
+template <int KW> constexpr int DEC_PACK_KPS_W = 48 * KW;
 
 // Z = cat(private_log_z, poe_log_z); z_private = Z[:, n_s:n_s+n_p], z_shared = Z[:, :n_s]  (the A6 quirk)
 // zcat = [z_private | z_shared] (input of the mixing trunk, nn/networks.py:322)
@@ -1103,7 +1105,9 @@ __device__ __forceinline__ float zcat_value(const ZsplitArgs& a, int g, int b, i
 }
 // zcat AND the decoder's packed bf16 operand images of the same latents (see spv_zsplit_args) in one pass: one thread per image
 // element; the threads of the mixture-operand tail also store zcat (its columns are the first n_p + n_s of that tail)
+template <int KW = 1>
 __global__ __launch_bounds__(256) void zsplit_pack_kernel(ZsplitArgs a) {
+  constexpr int DEC_PACK_KP = DEC_PACK_KP_W<KW>, DEC_PACK_KPS = DEC_PACK_KPS_W<KW>;
   const int g = blockIdx.y;
   const int nt = a.n_p + a.n_s;
   const int wcols = DEC_PACK_KPS + a.am_cols;              // [ aps: 48 | am tail: am_cols ]
@@ -1148,6 +1152,7 @@ __global__ __launch_bounds__(256) void zsplit_bwd_kernel(ZsplitArgs a) {
 typedef spv_fold_prob FoldProb;
 typedef spv_fold_batch FoldBatch;
 constexpr int FOLD_KMAX = 32;
+constexpr int FOLD_KMAX_WIDE = 64;   // the wide decoder layout (spv_fold_batch.kslots = 1): the kernels below take FK = FOLD_KMAX or this
 
 // per gene: BatchNorm over the batch of the linear map z -> w_g . z folded into W'_g = inv * w_g and
 // c_g = beta_g - inv * mean_g, with mean_g = w_g . zbar, var_g = w_g^T C w_g (biased), inv = gamma_g / sqrt(var_g + eps);
@@ -1156,7 +1161,9 @@ constexpr int FOLD_KMAX = 32;
 // of the image row; mean and variance are summed over the four lanes.  (One lane per gene was 40 workgroups per problem on 256 CUs, each
 // lane a K x K chain.)
 constexpr int FOLD_FWD_GENES = 64;
+template <int FK = FOLD_KMAX>
 __global__ __launch_bounds__(256) void bn_fold_fwd_kernel(FoldBatch a) {
+  constexpr int FOLD_KMAX = FK;
   const FoldProb& q = a.p[blockIdx.y];
   __shared__ float s_zbar[FOLD_KMAX], s_C[FOLD_KMAX * FOLD_KMAX];
   const int K = q.K;
@@ -1227,7 +1234,9 @@ __global__ __launch_bounds__(256) void bn_fold_fwd_kernel(FoldBatch a) {
 // per-block partial sums of d zbar [K] and d C [K][K]
 // 256 genes per workgroup (the unit of the block partials), four lanes per gene as in the forward kernel: 1024 threads
 constexpr int FOLD_BWD_THREADS = 1024;
+template <int FK = FOLD_KMAX>
 __global__ __launch_bounds__(FOLD_BWD_THREADS) void bn_fold_bwd_kernel(FoldBatch a) {
+  constexpr int FOLD_KMAX = FK;
   const FoldProb& q = a.p[blockIdx.y];
   __shared__ float s_zbar[FOLD_KMAX], s_C[FOLD_KMAX * FOLD_KMAX], s_w[256 * FOLD_KMAX], s_dm[256], s_dv[256], s_acc[3][17][64];
   const int K = q.K;
@@ -1291,34 +1300,71 @@ __global__ __launch_bounds__(FOLD_BWD_THREADS) void bn_fold_bwd_kernel(FoldBatch
   // One exact-fp32 MFMA tile per wave (v_mfma_f32_32x32x2_f32, two genes per step): dC = (dv . W)^T W is a
   // [K x 256] x [256 x K] product and d zbar rides along as row 0 of a second tile; the four waves' tiles are added in
   // wave order.  (The scalar form -- every thread a 256-term chain of LDS reads per output -- made this the longest
-  // kernel of the small-kernel backward chain.)
-  {
+  // kernel of the small-kernel backward chain.)  K > 32 (FK = 64): the 2 x 2 tiles of dC one after the other, d zbar with the
+  // tiles of row block 0.
+  if constexpr (FK > 32) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, r = lane & 31;
-    f16v accC;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) accC[i] = 0.f;
-    f16v accM = accC;
-    if (wave < 4)   // (waves 4..15 only served the per-gene phase)
-      for (int t = 64 * wave; t < 64 * wave + 64; t += 2) {
-        const float wv = (r < K) ? s_w[(t + h) * FOLD_KMAX + r] : 0.f;
-        accC = mfma_f32(s_dv[t + h] * wv, wv, accC);
-        accM = mfma_f32((r == 0) ? s_dm[t + h] : 0.f, wv, accM);
-      }
-    if (wave > 0 && wave < 4) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s_acc[wave - 1][i][lane] = accC[i];
-      s_acc[wave - 1][16][lane] = accM[0];
-    }
-    __syncthreads();
-    if (wave > 0) return;
     float* out = q.red_part + (long)blockIdx.x * nred;
+    for (int tt = 0; tt < 4; ++tt) {
+      const int ti = tt >> 1, tj = tt & 1;   // row block (k), column block (l) of dC
+      if (32 * ti >= K || 32 * tj >= K) continue;   // (block-uniform)
+      f16v accC;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = crow(i, h);
-      const float v = ((accC[i] + s_acc[0][i][lane]) + s_acc[1][i][lane]) + s_acc[2][i][lane];
-      if (row < K && r < K) out[K + row * K + r] = v;
+      for (int i = 0; i < 16; ++i) accC[i] = 0.f;
+      f16v accM = accC;
+      if (wave < 4)
+        for (int t = 64 * wave; t < 64 * wave + 64; t += 2) {
+          const float wi = (32 * ti + r < K) ? s_w[(t + h) * FOLD_KMAX + 32 * ti + r] : 0.f;
+          const float wj = (32 * tj + r < K) ? s_w[(t + h) * FOLD_KMAX + 32 * tj + r] : 0.f;
+          accC = mfma_f32(s_dv[t + h] * wi, wj, accC);
+          if (ti == 0) accM = mfma_f32((r == 0) ? s_dm[t + h] : 0.f, wj, accM);
+        }
+      if (wave > 0 && wave < 4) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s_acc[wave - 1][i][lane] = accC[i];
+        s_acc[wave - 1][16][lane] = accM[0];
+      }
+      __syncthreads();
+      if (wave == 0) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int row = 32 * ti + crow(i, h), col = 32 * tj + r;
+          const float v = ((accC[i] + s_acc[0][i][lane]) + s_acc[1][i][lane]) + s_acc[2][i][lane];
+          if (row < K && col < K) out[K + row * K + col] = v;
+        }
+        if (ti == 0 && h == 0 && 32 * tj + r < K) out[32 * tj + r] = ((accM[0] + s_acc[0][16][lane]) + s_acc[1][16][lane]) + s_acc[2][16][lane];
+      }
+      __syncthreads();   // s_acc is rewritten by the next tile
     }
-    if (h == 0 && r < K) out[r] = ((accM[0] + s_acc[0][16][lane]) + s_acc[1][16][lane]) + s_acc[2][16][lane];
+  } else {
+    {
+      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, r = lane & 31;
+      f16v accC;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) accC[i] = 0.f;
+      f16v accM = accC;
+      if (wave < 4)   // (waves 4..15 only served the per-gene phase)
+        for (int t = 64 * wave; t < 64 * wave + 64; t += 2) {
+          const float wv = (r < K) ? s_w[(t + h) * FOLD_KMAX + r] : 0.f;
+          accC = mfma_f32(s_dv[t + h] * wv, wv, accC);
+          accM = mfma_f32((r == 0) ? s_dm[t + h] : 0.f, wv, accM);
+        }
+      if (wave > 0 && wave < 4) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s_acc[wave - 1][i][lane] = accC[i];
+        s_acc[wave - 1][16][lane] = accM[0];
+      }
+      __syncthreads();
+      if (wave > 0) return;
+      float* out = q.red_part + (long)blockIdx.x * nred;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = crow(i, h);
+        const float v = ((accC[i] + s_acc[0][i][lane]) + s_acc[1][i][lane]) + s_acc[2][i][lane];
+        if (row < K && r < K) out[K + row * K + r] = v;
+      }
+      if (h == 0 && r < K) out[r] = ((accM[0] + s_acc[0][16][lane]) + s_acc[1][16][lane]) + s_acc[2][16][lane];
+    }
   }
 }
 
@@ -1344,7 +1390,9 @@ __global__ __launch_bounds__(256) void fold_red_finalize_kernel(FoldBatch a) {
 // fold_red_finalize_kernel's association -- that launch is no longer needed in front of this one; workgroup 0 still leaves the sum in
 // row nblk of red_part).  With q.out_priv set the finished d zcat columns of this problem go straight to d private_log_z / d poe_log_z
 // (the latent-slicing backward, zsplit_bwd_kernel) instead of back into q.dz.
+template <int FK = FOLD_KMAX>
 __global__ __launch_bounds__(256) void zstats_bwd_kernel(FoldBatch a) {
+  constexpr int FOLD_KMAX = FK;
   const FoldProb& q = a.p[blockIdx.y];
   __shared__ float s_zbar[FOLD_KMAX], s_dz[FOLD_KMAX], s_S[FOLD_KMAX * FOLD_KMAX], s_red[FOLD_KMAX + FOLD_KMAX * FOLD_KMAX], s_z[64 * (FOLD_KMAX + 1)];
   const int K = q.K, nred = K + K * K;

@@ -17,7 +17,7 @@ from typing import List, Sequence
 import torch
 
 from . import _abi
-from ._abi import (DEC_CELLS_PER_WG, DEC_KP, DEC_KPS, DEC_KS, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecGroup, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
+from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecGroup, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
                    ptr, round_up, stream_ptr)
 from .nn_ops import _add_lin, _fptr, _lin_batch, _wgrad, grad_out
 from . import ops as _ops
@@ -25,6 +25,18 @@ from .ops import N_HIDDEN_MIX, GroupCounts, Workspace, _bf16_image, _gemm_slabs,
 
 N_DEC_PARAMS = 13  # Wp, gamma_p, beta_p, Ws, gamma_s, beta_s, Wa, ba, gamma_a, beta_a, Wm, bm, px_r
 KMP = 320
+
+
+def dec_slots(decoder):
+    """the K-slot layout (_abi.DecSlots) a decoder's regressor operand images use: chosen per module (spVIPESmodule decoder_slots)"""
+    return getattr(decoder, "dec_slots", DEC_NARROW)
+
+
+def _slab_cols(KP: int, KS: int):
+    """the split-K GEMMs' column problems of the two regressor heads: (column offset in the operand image, columns, head, first column
+    of the head): 16 / 32 columns in the narrow layout; the wide layout's 64-column shared head as two 32-column problems (the
+    32-column GEMM configuration; the 320-column kernels never see these)"""
+    return [(0, KP, 0, 0)] + [(KP + c, 32, 1, c) for c in range(0, KS, 32)]
 
 
 def decoder_params(dec, px_r) -> List[torch.Tensor]:
@@ -43,6 +55,12 @@ def _add_red(b: SpvReduceBatch, src: torch.Tensor, nslabs: int, slab_stride: int
     b.nprob += 1
 
 
+def _add_wide_bc(red: SpvReduceBatch, slabs, nslabs: int, G: int, dWp: torch.Tensor, dWs: torch.Tensor, sl, alpha) -> None:
+    """wide layout: the 32-column slabs of d [W'_p | c_p] and d [W'_s | c_s] (_DecoderBwd.gemm_bc) into dWp [G][KP] / dWs [G][KS]"""
+    for slab, n, hd, c0 in slabs:
+        _add_red(red, slab, nslabs, G * n, n, G, n, (dWp, dWs)[hd], (sl.KP, sl.KS)[hd], dst_col=c0, alpha=alpha)
+
+
 def _run_red(b: SpvReduceBatch) -> None:
     if b.nprob:
         _abi.call("spv_reduce_slabs", C.byref(b), stream_ptr())
@@ -59,11 +77,15 @@ class _DecoderBwd:
     (Measured: issuing these from the forward pass right after the group's likelihood kernel, staggered so that the other
     group's VALU-bound likelihood kernel runs beside these memory-bound kernels, changes nothing.)"""
 
-    def __init__(self, g: int, P, S, Wps_g, wsg, B: int, Bp: int, G: int, Gp: int, nsplit: int, grads_f32: bool, pair: bool = False):
+    def __init__(self, g: int, P, S, Wps_g, wsg, B: int, Bp: int, G: int, Gp: int, nsplit: int, grads_f32: bool, pair: bool = False, sl=DEC_NARROW):
         self.g, self.P, self.S, self.Wps_g, self.wsg = g, P, S, Wps_g, wsg
         self.B, self.Bp, self.G, self.Gp, self.nsplit, self.grads_f32 = B, Bp, G, Gp, nsplit, grads_f32
-        self.fused_dz = bool(_ops.FUSED_DZ and (not grads_f32 or _ops.FUSED_DZ_F32))
-        self.dz_part = wsg.get("dec_dz_part", (P.gene_splits, Bp, DEC_KPS), torch.float32) if self.fused_dz else None
+        self.sl = sl
+        # the wide layout (sl.kslots = 1) runs the in-place softmax fix and the split-K GEMMs: the fused one-pass backward kernels are
+        # built for the narrow layout only
+        wide = sl.kslots != 0
+        self.fused_dz = bool(_ops.FUSED_DZ and (not grads_f32 or _ops.FUSED_DZ_F32) and not wide)
+        self.dz_part = wsg.get("dec_dz_part", (P.gene_splits, Bp, sl.KPS), torch.float32) if self.fused_dz else None
         self.T = T = Gp // 32
         bt = Bp // 32
         # K splits (fp32 slabs, reduced in order by spv_reduce_slabs).  The 320-column GEMMs (d A_m, d W_m) get ~1 workgroup
@@ -72,7 +94,7 @@ class _DecoderBwd:
         self.ksp_m, self.ksp_n = max(1, min(T // 8, -(-256 // max(Bp // 64, 1)))), max(1, min(T // 8, -(-512 // max(Bp // 128, 1))))
         self.csp_m, self.csp_n = max(1, min(bt // 8, -(-256 // max(Gp // 64, 1)))), max(1, min(bt // 8, -(-512 // max(Gp // 128, 1))))
         # bf16 mode: one streaming kernel for both regressor weight gradients (csrc/spv_dec_gemm.h)
-        self.heads_dma = bool(_ops.HEADS_DMA and nsplit == 1 and not grads_f32 and Bp % 64 == 0)
+        self.heads_dma = bool(_ops.HEADS_DMA and nsplit == 1 and not grads_f32 and Bp % 64 == 0 and not wide)
         if self.heads_dma:
             mt, kt = -(-G // 128), Bp // 64   # 128-gene workgroup tiles, two workgroups per CU
             self.csp_n = max(1, min(512 // mt if mt <= 512 else 1, max(kt // 4, 1)))
@@ -85,7 +107,7 @@ class _DecoderBwd:
             self.fused_heads = True
         if self.fused_heads:
             self.csp_n = Bp // DEC_CELLS_PER_WG
-            self.dw_part = wsg.get("dec_dW48", (self.csp_n, Gp, DEC_KPS), torch.float32)   # [d W'_p | d W'_s] rows over the padded genes
+            self.dw_part = wsg.get("dec_dW48", (self.csp_n, Gp, sl.KPS), torch.float32)   # [d W'_p | d W'_s] rows over the padded genes
         # bf16 mode: the two 320-column GEMMs run the LDS-DMA 128 x 320 kernels, which want their own split counts
         # (d A_m of the two groups run side by side on the group streams; d W_m one after the other on the side stream)
         self.ksp_m = self._splits(False, B, G, self.ksp_m, 128 if (pair and _ops.DEC_PAIR_SPLITS) else 256)
@@ -156,14 +178,18 @@ class _DecoderBwd:
         if self.fused_heads:   # already produced by softmax() (spv_dec_heads_bwd): hand the partial slabs to the reduction
             return self.dw_part, self.dw_part   # (one 48-column slab: the reductions below pick their columns)
         (Aps_hi, Aps_lo), (tP_hi, tP_lo), (tS_hi, tS_lo) = self.S["Aps"], self._operand("tP"), self._operand("tS")
+        KP, KS, KPS = self.sl.KP, self.sl.KS, self.sl.KPS
         if self.heads_dma:   # bf16 mode: both heads in one LDS-DMA streaming pass (csrc/spv_dec_gemm.h)
-            b = self.wsg.get("dec_dWp", (self.csp_n, self.G, DEC_KP), torch.float32)
-            c = self.wsg.get("dec_dWs", (self.csp_n, self.G, DEC_KS), torch.float32)
+            b = self.wsg.get("dec_dWp", (self.csp_n, self.G, KP), torch.float32)
+            c = self.wsg.get("dec_dWs", (self.csp_n, self.G, KS), torch.float32)
             _abi.call("spv_dec_heads_wgrad", ptr(tP_hi), ptr(tS_hi), self.T, ptr(Aps_hi), self.G, self.Bp, self.csp_n, ptr(b), ptr(c), stream_ptr())
             return b, c
-        b = _gemm_slabs(True, tP_hi, tP_lo, self.Gp, Aps_hi, Aps_lo, DEC_KPS, self.G, DEC_KP, self.Bp, self.nsplit, self.csp_n, self.wsg, "dec_dWp", a_tiles=self.T)
-        c = _gemm_slabs(True, tS_hi, tS_lo, self.Gp, Aps_hi, Aps_lo, DEC_KPS, self.G, DEC_KS, self.Bp, self.nsplit, self.csp_n, self.wsg, "dec_dWs",
-                        b_col_off=DEC_KP, a_tiles=self.T)
+        if self.sl.kslots:   # wide: [(slab, columns, head, first column of the head)] of 32-column problems
+            return [(_gemm_slabs(True, (tP_hi, tS_hi)[hd], (tP_lo, tS_lo)[hd], self.Gp, Aps_hi, Aps_lo, KPS, self.G, n, self.Bp, self.nsplit, self.csp_n,
+                                 self.wsg, f"dec_dW{off}", b_col_off=off, a_tiles=self.T), n, hd, c0) for off, n, hd, c0 in _slab_cols(KP, KS)]
+        b = _gemm_slabs(True, tP_hi, tP_lo, self.Gp, Aps_hi, Aps_lo, KPS, self.G, KP, self.Bp, self.nsplit, self.csp_n, self.wsg, "dec_dWp", a_tiles=self.T)
+        c = _gemm_slabs(True, tS_hi, tS_lo, self.Gp, Aps_hi, Aps_lo, KPS, self.G, KS, self.Bp, self.nsplit, self.csp_n, self.wsg, "dec_dWs",
+                        b_col_off=KP, a_tiles=self.T)
         return b, c
 
     def gemm_a(self):
@@ -186,9 +212,13 @@ class _DecoderBwd:
 
     def gemm_ef(self):
         (tP_hi, tP_lo), (tS_hi, tS_lo) = self._operand("tP"), self._operand("tS")
-        e = _gemm_slabs(False, tP_hi, tP_lo, self.Gp, self.Wps_g[0], self.Wps_g[1], DEC_KPS, self.B, DEC_KP, self.G, self.nsplit, self.ksp_n, self.wsg, "dec_dAp", a_tiles=self.T)
-        f = _gemm_slabs(False, tS_hi, tS_lo, self.Gp, self.Wps_g[0], self.Wps_g[1], DEC_KPS, self.B, DEC_KS, self.G, self.nsplit, self.ksp_n, self.wsg, "dec_dAs",
-                        b_col_off=DEC_KP, a_tiles=self.T)
+        KP, KS, KPS = self.sl.KP, self.sl.KS, self.sl.KPS
+        if self.sl.kslots:   # wide: [(slab, columns, head, first column of the head)] of 32-column problems
+            return [(_gemm_slabs(False, (tP_hi, tS_hi)[hd], (tP_lo, tS_lo)[hd], self.Gp, self.Wps_g[0], self.Wps_g[1], KPS, self.B, n, self.G, self.nsplit,
+                                 self.ksp_n, self.wsg, f"dec_dA{off}", b_col_off=off, a_tiles=self.T), n, hd, c0) for off, n, hd, c0 in _slab_cols(KP, KS)]
+        e = _gemm_slabs(False, tP_hi, tP_lo, self.Gp, self.Wps_g[0], self.Wps_g[1], KPS, self.B, KP, self.G, self.nsplit, self.ksp_n, self.wsg, "dec_dAp", a_tiles=self.T)
+        f = _gemm_slabs(False, tS_hi, tS_lo, self.Gp, self.Wps_g[0], self.Wps_g[1], KPS, self.B, KS, self.G, self.nsplit, self.ksp_n, self.wsg, "dec_dAs",
+                        b_col_off=KP, a_tiles=self.T)
         return e, f
 
 
@@ -214,6 +244,10 @@ class DecoderFused(torch.autograd.Function):
         dev = lat[0][0].device
         n_p, n_s = lat[0][0].shape[1], lat[0][1].shape[1]
         nt = n_p + n_s
+        sl = dec_slots(decoders[0])
+        DEC_KP, DEC_KS, DEC_KPS = sl.KP, sl.KS, sl.KPS
+        if any(dec_slots(d) != sl for d in decoders):
+            raise _abi.SpvError("DecoderFused: the decoders of one call must share their operand layout")
         if n_p + 1 > DEC_KP or n_s + 1 > DEC_KS:
             raise _abi.SpvError(f"decoder kernels support n_private <= {DEC_KP - 1} and n_shared <= {DEC_KS - 1}")
         n_m = par[0][6].shape[0]
@@ -230,7 +264,7 @@ class DecoderFused(torch.autograd.Function):
         # ---- 1. latent slicing: zcat = [z_private | z_shared] --------------------------------------
         zcat = [new(B, nt) for _ in range(NG)]
         za = SpvZsplitArgs()
-        za.B, za.n_p, za.n_s, za.ngroups = B, n_p, n_s, NG
+        za.B, za.n_p, za.n_s, za.ngroups, za.kslots = B, n_p, n_s, NG, sl.kslots
         keep = []
         # ... and, from the same call, the decoder's packed bf16 operand images of these latents
         Am_img = [_bf16_image(ws[g], "dec_Am", Bp, KMP, mlo) for g in range(NG)]
@@ -263,7 +297,7 @@ class DecoderFused(torch.autograd.Function):
         Wps = [_bf16_image(ws[g], "dec_Wps", Gps[g], DEC_KPS, True) for g in range(NG)]
         fstat = [[new(Gs[g], 2), new(Gs[g], 2)] for g in range(NG)]
         fb = SpvFoldBatch()
-        fb.nprob, fb.B, fb.training, fb.eps, fb.momentum = 0, B, int(training), 1e-3, 0.01
+        fb.nprob, fb.B, fb.training, fb.eps, fb.momentum, fb.kslots = 0, B, int(training), 1e-3, 0.01, sl.kslots
         for g in range(NG):
             fp, fs = decoders[g].factor_regressor_private, decoders[g].factor_regressor_shared
             for k, (reg, W, gam, bet, off, slot, n, zoff) in enumerate(((fp, par[g][0], par[g][1], par[g][2], 0, DEC_KP, n_p, 0),
@@ -396,7 +430,7 @@ class DecoderFused(torch.autograd.Function):
                   part_max_p=ptr(part("dec_pmp")), part_sum_p=ptr(part("dec_psp")), part_max_s=ptr(part("dec_pms")), part_sum_s=ptr(part("dec_pss")),
                   rec_part=ptr(nbpart("dec_rec")), tp_part=ptr(nbpart("dec_tp")), ts_part=ptr(nbpart("dec_ts")),
                   dtheta_part=ptr(dth), dL=ptr(dL), tP=ptr(tP), tS=ptr(tS), grads_f32=int(grads_f32), nb_splits=nbs, nb_genes_per_split=nbper,
-                  nb_cell_tiles=_nb_cell_tiles(Bp, Gp),
+                  nb_cell_tiles=_nb_cell_tiles(Bp, Gp), kslots=sl.kslots,
               )
               if pair:
                   lib_keep.append(cont(library[g].flatten()))
@@ -434,6 +468,7 @@ class DecoderFused(torch.autograd.Function):
             ctx.small = (zcat, zsum, zz, fstat, pre_a, m, tstat)
             ctx.trunk = (Wf, cf, zsum_t, zz_t) if trunk_fold else None
             ctx.gkl, ctx.n_kl = gkl, n_kl
+            ctx.sl = sl
             ctx.save_for_backward(*tensors[:2 * NG + NG * N_DEC_PARAMS])
         ctx.mark_non_differentiable(rec_sum, *rec)
         return (loss, rec_sum, *rec)
@@ -458,6 +493,8 @@ class DecoderFused(torch.autograd.Function):
         pg = [[grad_out(par[g][j]) for j in range(N_DEC_PARAMS)] for g in range(NG)]  # (kernel target, autograd return) per parameter
         red, red2 = SpvReduceBatch(), SpvReduceBatch()
         red.nprob = red2.nprob = 0
+        sl = ctx.sl
+        DEC_KP, DEC_KS, DEC_KPS = sl.KP, sl.KS, sl.KPS
         dWp, dWs = [new(Gs[g], DEC_KP) for g in range(NG)], [new(Gs[g], DEC_KS) for g in range(NG)]
         dAm, d_zcat = [new(B, n_m) for _ in range(NG)], [new(B, nt) for _ in range(NG)]
         # ---- schedule ---------------------------------------------------------------------------------------------
@@ -470,7 +507,7 @@ class DecoderFused(torch.autograd.Function):
         cur = torch.cuda.current_stream(dev)
         streams = group_streams(dev, NG) if _ops.BWD_GROUP_STREAMS else [cur] * NG
         side = group_streams(dev, 3)[2] if _ops.DEFER_WM else cur
-        stages = [_DecoderBwd(g, ctx.P[g], ctx.saved_g[g], ctx.Wps[g], ws[g], B, Bp, Gs[g], Gps[g], nsplit, ctx.grads_f32, pair=(NG == 2 and _ops.BWD_GROUP_STREAMS)) for g in range(NG)]
+        stages = [_DecoderBwd(g, ctx.P[g], ctx.saved_g[g], ctx.Wps[g], ws[g], B, Bp, Gs[g], Gps[g], nsplit, ctx.grads_f32, pair=(NG == 2 and _ops.BWD_GROUP_STREAMS), sl=sl) for g in range(NG)]
         d_slabs, bc_slabs, ef_slabs = [None] * NG, [None] * NG, [None] * NG
         # bf16 mode with the regressor GEMMs deferred to the side stream: the critical chain only needs the latent gradient, which
         # the READ-ONLY pass spv_dec_dz gives (168 MB read per group instead of 336 MB read + written); the in-place fix of
@@ -547,7 +584,9 @@ class DecoderFused(torch.autograd.Function):
         for g in range(NG):
             st, G, Gp = stages[g], Gs[g], Gps[g]
             if bc_slabs[g] is not None:
-                if st.fused_heads:
+                if sl.kslots:
+                    _add_wide_bc(red, bc_slabs[g], st.csp_n, G, dWp[g], dWs[g], sl, al)
+                elif st.fused_heads:
                     _add_red(red, bc_slabs[g][0], st.csp_n, st.Gp * DEC_KPS, DEC_KPS, G, DEC_KP, dWp[g], DEC_KP, alpha=al)                  # d [W'_p | c_p]
                     _add_red(red, bc_slabs[g][1], st.csp_n, st.Gp * DEC_KPS, DEC_KPS, G, DEC_KS, dWs[g], DEC_KS, col_off=DEC_KP, alpha=al)  # d [W'_s | c_s]
                 else:
@@ -560,6 +599,11 @@ class DecoderFused(torch.autograd.Function):
             if st.fused_dz:
                 _add_red(red2, st.dz_part, st.P.gene_splits, Bp * DEC_KPS, DEC_KPS, B, n_p, d_zcat[g], nt, accumulate=True, alpha=al)
                 _add_red(red2, st.dz_part, st.P.gene_splits, Bp * DEC_KPS, DEC_KPS, B, n_s, d_zcat[g], nt, col_off=DEC_KP, dst_col=n_p, accumulate=True, alpha=al)
+            elif sl.kslots:   # wide: 32-column slabs; head hd's columns c0 .. c0 + 31 go to d zcat columns (0 | n_p) + c0 ..
+                for slab, n, hd, c0 in ef_slabs[g]:
+                    cols = min(n, (n_p, n_s)[hd] - c0)
+                    if cols > 0:
+                        _add_red(red2, slab, st.ksp_n, B * n, n, B, cols, d_zcat[g], nt, dst_col=(0, n_p)[hd] + c0, accumulate=True, alpha=al)
             else:
                 _add_red(red2, ef_slabs[g][0], st.ksp_n, B * DEC_KP, DEC_KP, B, n_p, d_zcat[g], nt, accumulate=True, alpha=al)
                 _add_red(red2, ef_slabs[g][1], st.ksp_n, B * DEC_KS, DEC_KS, B, n_s, d_zcat[g], nt, dst_col=n_p, accumulate=True, alpha=al)
@@ -584,6 +628,9 @@ class DecoderFused(torch.autograd.Function):
                     st, G = stages[g], Gs[g]
                     if split_fix:
                         st.softmax_fix()
+                    if sl.kslots:
+                        _add_wide_bc(red_bc, st.gemm_bc(), st.csp_n, G, dWp[g], dWs[g], sl, g_loss)
+                        continue
                     b_, c = st.gemm_bc()
                     # (spv_dec_heads_bwd's slabs are [Gp][32] for both heads; the GEMM slabs [G][16] / [G][32])
                     if st.fused_heads:   # spv_dec_heads_bwd's slabs: [Gp][48], private columns first
@@ -670,7 +717,7 @@ class DecoderFused(torch.autograd.Function):
             _wgrad(bw, ws if not isinstance(ws, (list, tuple)) else ws[0])
             _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
         # ---- BatchNorm-fold backward (+ the z statistics it used) ------------------------------------
-        fb = ctx.fb
+        fb = ctx.fb   # (kslots set by the forward pass)
         d_priv, d_poe = [new(B, n_p) for _ in range(NG)], [new(B, n_s) for _ in range(NG)]
         dWraw = [[pg[g][0][0], pg[g][3][0]] for g in range(NG)]
         dgam = [[pg[g][1][0], pg[g][4][0]] for g in range(NG)]
@@ -727,6 +774,8 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     pz, qz = cont(private_log_z), cont(poe_log_z)
     B, n_p, n_s = pz.shape[0], pz.shape[1], qz.shape[1]
     nt = n_p + n_s
+    sl = dec_slots(decoder)
+    DEC_KP, DEC_KS, DEC_KPS = sl.KP, sl.KS, sl.KPS
     if n_p + 1 > DEC_KP or n_s + 1 > DEC_KS:
         raise _abi.SpvError(f"decoder kernels support n_private <= {DEC_KP - 1} and n_shared <= {DEC_KS - 1}")
     n_m = par[6].shape[0]
@@ -738,7 +787,7 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     Am_hi, Am_lo = _bf16_image(ws, "mat_Am", Bp, KMP, mlo)
     Aps_hi, Aps_lo = _bf16_image(ws, "mat_Aps", Bp, DEC_KPS, True)
     za = SpvZsplitArgs()
-    za.B, za.n_p, za.n_s, za.ngroups = B, n_p, n_s, 1
+    za.B, za.n_p, za.n_s, za.ngroups, za.kslots = B, n_p, n_s, 1, sl.kslots
     za.ld_am, za.am_col, za.am_cols, za.Bp = KMP, n_m, KMP - n_m, Bp
     za.priv[0], za.poe[0], za.zcat[0] = ptr(pz), ptr(qz), ptr(zcat)
     za.am_hi[0], za.am_lo[0], za.aps_hi[0], za.aps_lo[0] = ptr(Am_hi), ptr(Am_lo), ptr(Aps_hi), ptr(Aps_lo)
@@ -752,7 +801,7 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     Wps_hi, Wps_lo = _bf16_image(ws, "mat_Wps", Gp, DEC_KPS, True)
     fstat = [new(G, 2), new(G, 2)]
     fb = SpvFoldBatch()
-    fb.nprob, fb.B, fb.training, fb.eps, fb.momentum = 0, B, int(training), 1e-3, 0.0   # momentum 0: running statistics untouched
+    fb.nprob, fb.B, fb.training, fb.eps, fb.momentum, fb.kslots = 0, B, int(training), 1e-3, 0.0, sl.kslots   # momentum 0: running statistics untouched
     fp, fs = decoder.factor_regressor_private, decoder.factor_regressor_shared
     for k, (reg, W, gam, bet, off, slot, n, zoff) in enumerate(((fp, par[0], par[1], par[2], 0, DEC_KP, n_p, 0),
                                                                 (fs, par[3], par[4], par[5], DEC_KP, DEC_KS, n_s, n_p))):
@@ -792,6 +841,7 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
         a_p=ptr(a_p), a_s=ptr(a_s), lse_p=ptr(lse_p), lse_s=ptr(lse_s), w_row=None, gene_splits=splits, genes_per_split=per,
         part_max_p=ptr(part("mat_pmp")), part_sum_p=ptr(part("mat_psp")), part_max_s=ptr(part("mat_pms")), part_sum_s=ptr(part("mat_pss")),
         rec_part=None, tp_part=None, ts_part=None, dtheta_part=None, dL=None, tP=None, tS=None, grads_f32=0, nb_splits=1, nb_genes_per_split=32,
+        kslots=sl.kslots,
     )
     _abi.call("spv_dec_lse", C.byref(p), ptr(cont(library.flatten())), stream_ptr())
     out = {k: new(B, G) for k in ("px_scale_private", "px_scale_shared", "px_rate_private", "px_rate_shared", "px_mixing")}

@@ -65,6 +65,9 @@ class spVIPES:
         # integer codes over the WHOLE AnnData; without a batch_key scvi registers one dummy category, i.e. no covariate column
         batch_codes = _codes(adata.obs[setup["batch_key"]]) if setup.get("batch_key") else None
         n_batch = int(batch_codes.max()) + 1 if batch_codes is not None and len(batch_codes) else 1
+        # the decoder kernels' operand layout: the narrow one wherever it fits (every shape the narrow layout takes builds exactly that),
+        # the wide one for more covariate categories; kept in init_params_ below, so load() rebuilds the same layout
+        model_kwargs.setdefault("decoder_slots", "auto")
         self.module = spVIPESmodule(
             groups_lengths=groups_lengths, groups_obs_names=adata.uns.get("groups_obs_names"),
             groups_var_names=adata.uns.get("groups_var_names"), groups_var_indices=var_idx, groups_obs_indices=self.obs_idx,

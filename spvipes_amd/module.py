@@ -205,6 +205,39 @@ class _GenerativeGroup(dict):
         return [self[k] for k in self.keys()]
 
 
+def decoder_limits(sl, n_private: int, n_shared: int, n_cov: int) -> List[str]:
+    """the limits of the decoder kernels that a shape (covariate columns included) breaks in the operand layout ``sl`` (_abi.DecSlots)"""
+    from .dec_ops import KMP
+
+    bad = []
+    if n_private + n_cov + 1 > sl.KP:
+        bad.append(f"private regressor: n_private + n_batch + 1 = {n_private + n_cov + 1} > {sl.KP} K slots")
+    if n_shared + n_cov + 1 > sl.KS:
+        bad.append(f"shared regressor: n_shared + n_batch + 1 = {n_shared + n_cov + 1} > {sl.KS} K slots")
+    if N_HIDDEN_MIX + n_private + n_shared + 2 * n_cov + 1 > KMP:
+        bad.append(f"mixture GEMM input: {N_HIDDEN_MIX} + n_private + n_shared + 2 n_batch + 1 = {N_HIDDEN_MIX + n_private + n_shared + 2 * n_cov + 1} > {KMP}")
+    return bad
+
+
+def decoder_layout(decoder_slots: str, n_private: int, n_shared: int, n_cov: int):
+    """The K-slot layout of the decoder kernels' regressor operand images for ``decoder_slots`` = "narrow" | "wide" | "auto" ("auto": the
+    narrow layout wherever it fits, else the wide one).  With batch covariates a shape neither fits raises NotImplementedError naming
+    the limits it breaks; without them the decoder kernels report latent sizes they do not support when they run."""
+    from ._abi import DEC_NARROW, DEC_WIDE
+
+    if decoder_slots not in ("narrow", "wide", "auto"):
+        raise ValueError("decoder_slots must be 'narrow', 'wide' or 'auto'")
+    if decoder_slots == "auto":
+        # (only covariate columns widen a module: without them the narrow kernels keep reporting latent sizes they do not take)
+        decoder_slots = "narrow" if not n_cov or not decoder_limits(DEC_NARROW, n_private, n_shared, n_cov) else "wide"
+    sl = DEC_WIDE if decoder_slots == "wide" else DEC_NARROW
+    bad = decoder_limits(sl, n_private, n_shared, n_cov) if n_cov else []
+    if bad:
+        hint = " (decoder_slots='wide' or 'auto' widens the regressor slots to 32 / 64)" if sl is DEC_NARROW and not decoder_limits(DEC_WIDE, n_private, n_shared, n_cov) else ""
+        raise NotImplementedError(f"n_batch = {n_cov} does not fit the decoder kernels' operand slots ({decoder_slots} layout): " + "; ".join(bad) + hint)
+    return sl
+
+
 class spVIPESmodule(nn.Module):
     """See the module docstring.  Constructor arguments as spVIPESmodule.py:74-95; ``precision`` is
     this build's knob: "bf16" (bf16 MFMA operands, fp32 accumulate) or "fp32" (split-bf16 operands)."""
@@ -232,6 +265,7 @@ class spVIPESmodule(nn.Module):
         dispersion: str = "gene",
         precision: str = "bf16",
         allow_more_groups: bool = False,
+        decoder_slots: str = "narrow",
         n_components: Optional[int] = None,
     ):
         super().__init__()
@@ -249,14 +283,12 @@ class spVIPESmodule(nn.Module):
         self.n_batch, self.n_hidden, self.dropout_rate = n_batch, n_hidden, dropout_rate
         # batch covariates (spVIPESmodule.py:132-133, nn/networks.py:60-68): n_batch <= 1 collapses to no covariate column at all
         self.n_cov = n_cov = n_batch if n_batch > 1 else 0
-        if n_cov:
-            from .dec_ops import DEC_KP, DEC_KS, KMP
-            if len(lengths) != 2:
-                raise NotImplementedError("batch covariates are implemented for two groups")
-            if n_dimensions_private + n_cov + 1 > DEC_KP or n_dimensions_shared + n_cov + 1 > DEC_KS or \
-                    N_HIDDEN_MIX + n_dimensions_private + n_dimensions_shared + 2 * n_cov + 1 > KMP:
-                raise NotImplementedError(f"n_batch = {n_batch} does not fit the decoder kernels' operand slots: n_private + n_batch <= {DEC_KP - 1}, "
-                                          f"n_shared + n_batch <= {DEC_KS - 1}")
+        if n_cov and len(lengths) != 2:
+            raise NotImplementedError("batch covariates are implemented for two groups")
+        # the decoder kernels' K-slot layout of the regressor operand images (_abi.DecSlots): "narrow" (16 / 32 slots, the default),
+        # "wide" (32 / 64) or "auto" (narrow where it fits, else wide -- with batch covariates only)
+        self.decoder_slots = decoder_slots
+        self.dec_slots = decoder_layout(decoder_slots, n_dimensions_private, n_dimensions_shared, n_cov)
         self.input_dims = {i: g for i, g in enumerate(lengths)}
         self.groups_barcodes, self.groups_genes = groups_obs_names, groups_var_names
         self.groups_obs_indices = groups_obs_indices
@@ -274,6 +306,7 @@ class spVIPESmodule(nn.Module):
                 "private": Encoder(G + n_cov, n_dimensions_private, n_hidden, dropout_rate),
             }
             dec = LinearDecoderSPVIPE(n_dimensions_private, n_dimensions_shared, G, n_cov=n_cov)
+            dec.dec_slots = self.dec_slots   # (read by dec_ops.DecoderFused / materialize_decoder)
             self.encoders[g], self.decoders[g] = enc, dec
             self.add_module(f"encoder_{g}_shared", enc["shared"])
             self.add_module(f"encoder_{g}_private", enc["private"])

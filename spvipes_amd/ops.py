@@ -18,7 +18,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _abi
-from ._abi import DEC_CELLS_PER_WG, DEC_KP, DEC_KPS, DEC_KS, NB_CMAX, SpvCounts, SpvDecParams, check, ptr, round_up, stream_ptr
+from ._abi import DEC_CELLS_PER_WG, NB_CMAX, SpvCounts, SpvDecParams, check, ptr, round_up, stream_ptr
 
 N_HIDDEN_MIX = 256  # LinearDecoderSPVIPE's own n_hidden default (nn/networks.py:194)
 
