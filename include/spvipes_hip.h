@@ -117,6 +117,39 @@ int spv_prepare_log1p(const spv_counts* x, int32_t n_cells, int32_t G, uint16_t*
  * >= 2 round_up(G, 64) for that kernel, zero padded.  spv_enc_fc1_fwd takes it as xb_all with nsplit 3 and that ld_xb. */
 int spv_prepare_log1p_split(const spv_counts* x, int32_t n_cells, int32_t G, uint16_t* xb, int64_t ld_xb, float* library, void* stream);
 
+/* Count matrix of one group resident in HBM as CSR, densified per minibatch (replaces the AnnTorchDataset row densification of
+ * dataloaders/_ann_dataloader.py for a sparse AnnData.X, plus the slice / log1p / library of module/spVIPESmodule.py:428-435).
+ * Writes exactly the bytes the dense-resident path hands the downstream kernels, so that spv_enc_fc1_*, the likelihood's
+ * spv_dec_params (X, ldx, rows) and the pair grids then run on the minibatch buffers with rows = 0..B-1:
+ *   X       : [B][ldx] counts of cells rows[0..B) in the value dtype, zero where a gene has no stored entry (and for g >= G);
+ *             ldx >= G, a multiple of 8; 16-byte aligned
+ *   xb      : optional: xb_split 0: the f16 image of spv_prepare_log1p ([B][ld_xb], ld_xb >= G, a multiple of 8);
+ *             xb_split 1: the interleaved hi / lo image of spv_prepare_log1p_split (ld_xb a multiple of 128, >= 2 round_up(G, 32));
+ *             bit-identical to those entries' rows rows[b], padding included; 16-byte aligned
+ *   library : [B] log(sum_g log1p(x)) in the summation order of those entries (bit-identical); required with xb, else optional
+ * CSR: indptr int64 [n_rows + 1] (more than 2^31 stored entries are fine), cols int32 [nnz] local gene indices in [0, G), sorted and
+ * unique within a row, vals [nnz] uint16 or fp32 (dtype).  A row index outside [0, n_rows) reads as an empty row.  Every group of
+ * the call runs in one grid; nothing is allocated and the row indices are read on the device (graph capture safe). */
+#define SPV_CSR_GATHER_MAXG 8
+typedef struct spv_csr_gather_args {
+  const int64_t* indptr;
+  const int32_t* cols;
+  const void* vals;
+  int32_t n_rows;
+  int32_t G;
+  int32_t dtype;       /* SPV_COUNT_F32 | SPV_COUNT_U16 (of vals and X) */
+  int32_t B;
+  const int32_t* rows; /* [B] */
+  void* X;
+  int64_t ldx;
+  uint16_t* xb;
+  int64_t ld_xb;
+  int32_t xb_split;
+  int32_t pad_;
+  float* library;
+} spv_csr_gather_args;
+int spv_csr_gather(const spv_csr_gather_args* groups, int32_t n_groups, void* stream);
+
 /* fc1 weight gradient (autograd of nn/networks.py:119):  dW1[N1][G] = dh^T @ log1p(X[rows]).
  *   dh_hi/lo : [round_up(B,64)][ld_dh] (ld_dh >= round_up(N1,128), zero padded) from spv_enc_fc1_bwd_prep: nsplit 3 bf16 hi / lo,
  *              nsplit 1 f16(dpre * scale) with dh_scale = that call's scale_ws ({scale, 1 / scale}: the result is multiplied by [1])

@@ -226,6 +226,16 @@ class SpvTrunkBatch(C.Structure):
     _fields_ = [("p", SpvTrunkProb * 2), ("nprob", C.c_int32), ("B", C.c_int32), ("training", C.c_int32), ("eps", C.c_float), ("momentum", C.c_float)]
 
 
+SPV_CSR_GATHER_MAXG = 8
+
+
+class SpvCsrGatherArgs(C.Structure):
+    """one group's arguments of spv_csr_gather (include/spvipes_hip.h: spv_csr_gather_args)"""
+    _fields_ = [("indptr", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p), ("n_rows", C.c_int32), ("G", C.c_int32),
+                ("dtype", C.c_int32), ("B", C.c_int32), ("rows", C.c_void_p), ("X", C.c_void_p), ("ldx", C.c_int64),
+                ("xb", C.c_void_p), ("ld_xb", C.c_int64), ("xb_split", C.c_int32), ("pad_", C.c_int32), ("library", C.c_void_p)]
+
+
 _SIGNATURES = {
     "spv_version": (C.c_int, []),
     "spv_last_error": (C.c_char_p, []),
@@ -243,6 +253,7 @@ _SIGNATURES = {
     "spv_enc_fc1_bwd_grouped": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "spv_prepare_log1p": (C.c_int, [C.POINTER(SpvCounts), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "spv_prepare_log1p_split": (C.c_int, [C.POINTER(SpvCounts), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spv_csr_gather": (C.c_int, [C.POINTER(SpvCsrGatherArgs), C.c_int32, C.c_void_p]),
     "spv_enc_fc1_wgrad": (C.c_int, [C.POINTER(SpvCounts), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "spv_enc_fc1_bwd_prep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,

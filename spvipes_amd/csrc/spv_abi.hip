@@ -1980,3 +1980,130 @@ extern "C" int spv_prepare_log1p(const spv_counts* x, int32_t n_cells, int32_t G
   return launch_status("spv_prepare_log1p");
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// CSR-resident counts: the minibatch's rows densified into [B][ldx] (+ the log1p image of spv_prepare_log1p or
+// spv_prepare_log1p_split, + the library) -- exactly the bytes the dense-resident path feeds the downstream kernels, which then run
+// on the minibatch buffers with identity rows.  One workgroup per minibatch row, every group of the call in one grid
+// (blockIdx.y = group).  A row is walked in windows of CSR_WIN genes (a multiple of 256): the row's stored entries whose columns fall
+// in the window are scattered into a zeroed fp32 LDS image, every output is then stored 8
+// genes (16 B) per lane, and a separate LDS-only pass adds log1p(x) per thread with stride 256 in increasing gene order -- the
+// accumulation order of prepare_log1p_kernel (absent genes add +0.0 there, which changes no sum) -- followed by the same 256 -> 1 tree.
+// ---------------------------------------------------------------------------------------------
+#define CSR_WIN 8192
+struct CsrGatherBatch { spv_csr_gather_args p[SPV_CSR_GATHER_MAXG]; };
+
+__global__ __launch_bounds__(256) void csr_gather_kernel(CsrGatherBatch a) {
+#pragma clang fp contract(off)   // acc += log1p(x) must stay a multiply then an add, as in prepare_log1p_kernel (no fused v_fmac)
+  __shared__ __attribute__((aligned(16))) float s_c[CSR_WIN];
+  __shared__ float s_sum[256];
+  const spv_csr_gather_args& q = a.p[blockIdx.y];
+  const int b = blockIdx.x;
+  if (b >= q.B) return;   // (uniform per workgroup)
+  const int t = threadIdx.x;
+  const int r = q.rows[b];
+  long p = 0, end = 0;
+  if (r >= 0 && r < q.n_rows) { p = q.indptr[r]; end = q.indptr[r + 1]; }   // (a row outside the matrix reads as empty)
+  const bool u16 = q.dtype == SPV_COUNT_U16;
+  const bool split = q.xb_split != 0;
+  const long ld_img = q.xb ? (split ? q.ld_xb / 2 : q.ld_xb) : 0;   // genes per image row (split: hi words)
+  const long ext = q.ldx > ld_img ? q.ldx : ld_img;
+  const int G = q.G;
+  float acc = 0.f;
+  for (long w0 = 0; w0 < ext; w0 += CSR_WIN) {
+    const int wn = (int)(((long)G - w0) < CSR_WIN ? ((long)G - w0) : CSR_WIN);   // genes of the group in this window (<= 0: padding only)
+    if (wn > 0) {
+      for (int i = 4 * t; i < wn; i += 1024) *reinterpret_cast<f4v*>(s_c + i) = f4v{0.f, 0.f, 0.f, 0.f};
+      __syncthreads();
+      // every window filters the row's entries by column (a row's columns are a few KB; a binary search for the window's range
+      // would put a chain of dependent global loads in front of every window)
+      for (long i = p + t; i < end; i += 256) {
+        const int c = q.cols[i] - (int)w0;
+        if ((unsigned)c < (unsigned)wn)
+          s_c[c] = u16 ? (float)reinterpret_cast<const unsigned short*>(q.vals)[i] : reinterpret_cast<const float*>(q.vals)[i];
+      }
+      __syncthreads();
+    }
+    const long wend = (w0 + CSR_WIN) < ext ? (w0 + CSR_WIN) : ext;
+    for (long g = w0 + 8 * t; g < wend; g += 2048) {
+      float c[8];
+      if (g + 8 <= G) {
+        const f4v c0 = *reinterpret_cast<const f4v*>(s_c + (g - w0)), c1 = *reinterpret_cast<const f4v*>(s_c + (g - w0) + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[j] = c0[j]; c[4 + j] = c1[j]; }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) c[j] = (g + j < G) ? s_c[g + j - w0] : 0.f;
+      }
+      if (g < q.ldx) {
+        if (u16) {
+          u4v w;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w[j] = (unsigned)c[2 * j] | ((unsigned)c[2 * j + 1] << 16);
+          *reinterpret_cast<u4v*>(reinterpret_cast<unsigned short*>(q.X) + (long)b * q.ldx + g) = w;
+        } else {
+          float* dst = reinterpret_cast<float*>(q.X) + (long)b * q.ldx + g;
+          *reinterpret_cast<f4v*>(dst) = f4v{c[0], c[1], c[2], c[3]};
+          *reinterpret_cast<f4v*>(dst + 4) = f4v{c[4], c[5], c[6], c[7]};
+        }
+      }
+      if (g < ld_img) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (g + j < G) ? log1p_count(c[j]) : 0.f;
+        if (!split) {
+          u4v w;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w[j] = (unsigned)f2h(v[2 * j]) | ((unsigned)f2h(v[2 * j + 1]) << 16);
+          *reinterpret_cast<u4v*>(q.xb + (long)b * q.ld_xb + g) = w;
+        } else {
+          u4v wh, wl;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bf16_t h0 = f2bf(v[2 * j]), h1 = f2bf(v[2 * j + 1]);
+            wh[j] = (unsigned)h0 | ((unsigned)h1 << 16);
+            wl[j] = (unsigned)f2bf(v[2 * j] - bf2f(h0)) | ((unsigned)f2bf(v[2 * j + 1] - bf2f(h1)) << 16);
+          }
+          const long o = (long)b * q.ld_xb + (g >> 5) * 64 + (g & 31);
+          *reinterpret_cast<u4v*>(q.xb + o) = wh;
+          *reinterpret_cast<u4v*>(q.xb + o + 32) = wl;
+        }
+      }
+    }
+    if (q.library)   // the dense kernel's order: this thread's genes t, t + 256, ... (windows start at multiples of 256)
+      for (int i = t; i < wn; i += 256) acc += log1p_count(s_c[i]);
+    __syncthreads();   // (the next window re-zeroes s_c)
+  }
+  if (!q.library) return;
+  s_sum[t] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) s_sum[t] += s_sum[t + o];
+    __syncthreads();
+  }
+  if (t == 0) q.library[b] = __logf(s_sum[0]);
+}
+
+extern "C" int spv_csr_gather(const spv_csr_gather_args* groups, int32_t n_groups, void* stream) {
+  if (!groups || n_groups <= 0 || n_groups > SPV_CSR_GATHER_MAXG) return fail(SPV_ERR_ARG, "spv_csr_gather: bad group count%s");
+  CsrGatherBatch a{};
+  int bmax = 0;
+  for (int i = 0; i < n_groups; ++i) {
+    const spv_csr_gather_args& q = groups[i];
+    if (!q.indptr || !q.cols || !q.vals || !q.rows || !q.X) return fail(SPV_ERR_ARG, "spv_csr_gather: null pointer%s");
+    if (q.n_rows <= 0 || q.G <= 0 || q.B <= 0) return fail(SPV_ERR_ARG, "spv_csr_gather: n_rows, G and B must be positive%s");
+    if (q.dtype != SPV_COUNT_U16 && q.dtype != SPV_COUNT_F32) return fail(SPV_ERR_ARG, "spv_csr_gather: unknown count dtype%s");
+    if (q.ldx < q.G || (q.ldx % 8) || (reinterpret_cast<uintptr_t>(q.X) & 15))
+      return fail(SPV_ERR_ARG, "spv_csr_gather: X needs ldx >= G, ldx a multiple of 8 and a 16-byte aligned base%s");
+    if (q.xb) {
+      if (!q.library) return fail(SPV_ERR_ARG, "spv_csr_gather: an image needs the library%s");
+      if (reinterpret_cast<uintptr_t>(q.xb) & 15) return fail(SPV_ERR_ARG, "spv_csr_gather: xb needs a 16-byte aligned base%s");
+      if (q.xb_split ? (q.ld_xb < 2 * (((long)q.G + 31) & ~31L) || (q.ld_xb % 128)) : (q.ld_xb < q.G || (q.ld_xb % 8)))
+        return fail(SPV_ERR_ARG, "spv_csr_gather: ld_xb breaks the image layout (f16: >= G, a multiple of 8; split: a multiple of 128, >= 2 round_up(G, 32))%s");
+    }
+    a.p[i] = q;
+    bmax = q.B > bmax ? q.B : bmax;
+  }
+  hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)bmax, (unsigned)n_groups), dim3(256), 0, (hipStream_t)stream, a);
+  return launch_status("spv_csr_gather");
+}

@@ -16,7 +16,11 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .ops import GroupCounts
+from . import _abi
+from .ops import GroupCounts, SparseGroupCounts
+
+
+_NEGATIVE_COUNTS = "count matrices must be non-negative (the likelihood is evaluated at log1p(count); the reference gives NaN for counts <= -1)"
 
 
 def to_group_counts(X, device, prefer_u16: bool = True, col_off: int = 0, G: Optional[int] = None) -> GroupCounts:
@@ -27,12 +31,83 @@ def to_group_counts(X, device, prefer_u16: bool = True, col_off: int = 0, G: Opt
         Xn = np.asarray(X)
     G = Xn.shape[1] - col_off if G is None else G
     if Xn.size and float(Xn.min()) < 0:
-        raise ValueError("count matrices must be non-negative (the likelihood is evaluated at log1p(count); the reference gives NaN for counts <= -1)")
+        raise ValueError(_NEGATIVE_COUNTS)
     if prefer_u16 and Xn.size and float(Xn.min()) >= 0 and float(Xn.max()) < 65536 and np.all(Xn == np.floor(Xn)):
         t = torch.from_numpy(np.ascontiguousarray(Xn.astype(np.uint16)).view(np.int16))
     else:
         t = torch.from_numpy(np.ascontiguousarray(Xn.astype(np.float32)))
     return GroupCounts(t.to(device), G, col_off, resident=True)
+
+
+def is_sparse(X) -> bool:
+    """a scipy.sparse matrix or array (or anything else with ``.tocsr()``)"""
+    return hasattr(X, "tocsr") and not isinstance(X, (np.ndarray, torch.Tensor))
+
+
+def csr_group_arrays(X, obs_idx, var_idx, prefer_u16: bool = True):
+    """One group's counts ``X[obs_idx][:, var_idx]`` as CSR arrays without densifying them: (indptr int64 [n + 1], cols int32 (sorted
+    within a row, duplicates summed), vals, dtype) with dtype / vals uint16 when every stored value is integral and < 65536, else
+    float32 -- to_group_counts' rule (implicit zeros are integral and in range).  ``X``: anything with ``.tocsr()`` (scipy CSR, CSC, COO,
+    ...; a CSR input is only read), or a dense array.  The group's genes may be any columns (an outer join's ``groups_var_indices``)."""
+    obs_idx = np.asarray(obs_idx, dtype=np.int64).reshape(-1)
+    var_idx = np.asarray(var_idx, dtype=np.int64).reshape(-1)
+    n, G = len(obs_idx), len(var_idx)
+    if len(np.unique(var_idx)) != G:
+        raise ValueError("groups_var_indices must not repeat a gene")
+    if is_sparse(X):
+        M = X.tocsr()
+        n_var = M.shape[1]
+        ip = np.asarray(M.indptr, dtype=np.int64)
+        starts, lens = ip[obs_idx], ip[obs_idx + 1] - ip[obs_idx]
+        row = np.repeat(np.arange(n, dtype=np.int64), lens)
+        src = np.arange(row.size, dtype=np.int64) + np.repeat(starts - (np.cumsum(lens) - lens), lens)
+        gcol, vals = np.asarray(M.indices)[src], np.asarray(M.data)[src]
+        del src
+    else:
+        D = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+        n_var = D.shape[1]
+        sub = D[obs_idx]
+        row, gcol = np.nonzero(sub)
+        vals = sub[row, gcol]
+        del sub
+    colmap = np.full(n_var, -1, dtype=np.int64)
+    colmap[var_idx] = np.arange(G)
+    loc = colmap[gcol]
+    keep = loc >= 0
+    if not keep.all():
+        row, loc, vals = row[keep], loc[keep], vals[keep]
+    del gcol, keep
+    key = row * max(G, 1) + loc
+    if key.size > 1 and not bool(np.all(key[1:] > key[:-1])):   # unsorted columns or duplicate entries: sort, sum duplicates
+        order = np.argsort(key, kind="stable")
+        key, vals = key[order], vals[order]
+        del order
+        first = np.flatnonzero(np.concatenate(([True], key[1:] != key[:-1])))
+        vals = np.add.reduceat(vals, first) if first.size else vals
+        key = key[first]
+    row, loc = key // max(G, 1), key % max(G, 1)
+    del key
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(row, minlength=n), out=indptr[1:])
+    if vals.size and float(vals.min()) < 0:
+        raise ValueError(_NEGATIVE_COUNTS)
+    if prefer_u16 and n * G and (vals.size == 0 or (float(vals.max()) < 65536 and np.all(vals == np.floor(vals)))):
+        return indptr, loc.astype(np.int32), vals.astype(np.uint16), _abi.SPV_COUNT_U16
+    return indptr, loc.astype(np.int32), vals.astype(np.float32), _abi.SPV_COUNT_F32
+
+
+def csr_to_dense(indptr, cols, vals, G: int) -> np.ndarray:
+    """host densification of csr_group_arrays' output (``counts_storage="dense"`` on a sparse AnnData: one group at a time)"""
+    n = len(indptr) - 1
+    out = np.zeros((n, G), dtype=vals.dtype)
+    out[np.repeat(np.arange(n), np.diff(indptr)), cols] = vals
+    return out
+
+
+def to_sparse_group_counts(X, obs_idx, var_idx, device) -> SparseGroupCounts:
+    """One group of an AnnData's counts resident in HBM as CSR (csr_group_arrays, then the three arrays to the device)"""
+    indptr, cols, vals, _ = csr_group_arrays(X, obs_idx, var_idx)
+    return SparseGroupCounts.from_arrays(indptr, cols, vals, len(np.asarray(var_idx).reshape(-1)), device)
 
 
 @dataclass

@@ -4,7 +4,7 @@
 Mirrors /root/reference/src/spVIPES/model/spvipes.py (class ``spVIPES``: ctor :216-283,
 ``setup_anndata`` :285-422, ``get_latent_representation`` :424-650, ``get_loadings`` :652-677) and
 model/base/training_mixin.py (``train`` :19-123).  anndata / scvi-tools / Lightning are not part of
-this build: the AnnData object is duck-typed (``.X`` dense array, ``.obs`` mapping of columns,
+this build: the AnnData object is duck-typed (``.X`` dense array or scipy.sparse matrix, ``.obs`` mapping of columns,
 ``.uns`` dict, ``.n_obs``) and ``prepare_adatas``' output schema is the input contract --
 ``uns["groups_lengths" | "groups_var_indices" | "groups_obs_indices" | ...]``, ``obs["groups"]``,
 ``obs["indices"]`` (data/prepare_adatas.py:97-132).
@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import MinibatchSampler, format_latent_results, latent_loader_mode, latent_steps, to_group_counts
+from .data import (MinibatchSampler, csr_group_arrays, csr_to_dense, format_latent_results, is_sparse, latent_loader_mode, latent_steps,
+                   to_group_counts, to_sparse_group_counts)
 from .module import spVIPESmodule
 from .train import Trainer, default_max_epochs
 
@@ -36,12 +37,17 @@ def _codes(column) -> np.ndarray:
 
 class spVIPES:
     """Shared-private VAE with Product-of-Experts integration, HIP-accelerated.  Constructor arguments as
-    the reference (:216-224); ``precision`` ("bf16" | "fp32") and ``device`` are this build's additions."""
+    the reference (:216-224); ``precision`` ("bf16" | "fp32"), ``device`` and ``counts_storage`` are this build's additions.
+    ``counts_storage``: how the count matrices stay in HBM -- "dense" (uint16 / float32 cells x genes), "sparse" (CSR; every step
+    densifies only its minibatch, bit-identical results) or "auto" (CSR for a scipy.sparse ``adata.X`` / layer, else dense)."""
 
     def __init__(self, adata, n_hidden: int = 128, n_dimensions_shared: int = 25, n_dimensions_private: int = 10,
-                 dropout_rate: float = 0.1, precision: str = "bf16", device: Optional[str] = None, **model_kwargs):
+                 dropout_rate: float = 0.1, precision: str = "bf16", device: Optional[str] = None, counts_storage: str = "auto",
+                 **model_kwargs):
         if _SETUP_KEY not in adata.uns:
             raise ValueError("Please run `spVIPES.setup_anndata(adata, groups_key=...)` before creating the model")
+        if counts_storage not in ("auto", "dense", "sparse"):
+            raise ValueError(f"counts_storage must be 'auto', 'dense' or 'sparse', got {counts_storage!r}")
         if not torch.cuda.is_available():
             raise _abi.SpvError("spvipes_amd needs an MI355X: there is no CPU fallback for the hot path")
         _abi.load()
@@ -76,9 +82,18 @@ class spVIPES:
             n_hidden=n_hidden, n_dimensions_shared=n_dimensions_shared, n_dimensions_private=n_dimensions_private,
             dropout_rate=dropout_rate, precision=precision, **model_kwargs,
         ).to(self.device)
-        # resident per-group count matrices: rows = the group's cells (obs order), columns = its own genes
-        X = np.asarray(adata.X if setup.get("layer") is None else adata.layers[setup["layer"]])
-        self.counts = [to_group_counts(X[self.obs_idx[g]][:, var_idx[g]], self.device) for g in range(2)]
+        # resident per-group count matrices: rows = the group's cells (obs order), columns = its own genes; a scipy.sparse input is
+        # never densified as a whole (csr_group_arrays works on its stored entries)
+        X = adata.X if setup.get("layer") is None else adata.layers[setup["layer"]]
+        sparse_in = is_sparse(X)
+        if (counts_storage == "sparse") or (counts_storage == "auto" and sparse_in):
+            self.counts = [to_sparse_group_counts(X, self.obs_idx[g], var_idx[g], self.device) for g in range(2)]
+        elif sparse_in:   # "dense" storage of a sparse input: one group's slice at a time
+            self.counts = [to_group_counts(csr_to_dense(*csr_group_arrays(X, self.obs_idx[g], var_idx[g])[:3], len(var_idx[g])), self.device)
+                           for g in range(2)]
+        else:
+            X = np.asarray(X)
+            self.counts = [to_group_counts(X[self.obs_idx[g]][:, var_idx[g]], self.device) for g in range(2)]
         obs = adata.obs
         self._labels = [torch.tensor(_codes(obs[setup["label_key"]])[self.obs_idx[g]], device=self.device) for g in range(2)] if use_labels else None
         self._components = ([torch.tensor(_codes(obs["processed_transport_labels"])[self.obs_idx[g]], device=self.device) for g in range(2)]
@@ -90,7 +105,8 @@ class spVIPES:
         self.history: Dict[str, List[float]] = {}
         # what load() re-creates the model from (scvi's BaseModelClass keeps the same record: _get_init_params(locals()), :281)
         self.init_params_ = dict(n_hidden=n_hidden, n_dimensions_shared=n_dimensions_shared, n_dimensions_private=n_dimensions_private,
-                                 dropout_rate=dropout_rate, precision=precision, device=str(self.device), **model_kwargs)
+                                 dropout_rate=dropout_rate, precision=precision, device=str(self.device), counts_storage=counts_storage,
+                                 **model_kwargs)
 
     # ------------------------------------------------------------------------------------------
     @classmethod

@@ -16,7 +16,8 @@ Inputs.  ``tensors_by_group`` is a sequence (one entry per group) of dicts.  Eit
 reference's layout -- ``"X"`` float32 [B, sum G] in HBM, of which only the group's own columns
 ``groups_var_indices[g]`` are read -- or the resident layout this build adds for its own train
 loop: ``"counts"`` (``ops.GroupCounts``) + ``"rows"`` (int32 [B] cell indices), which fuses the
-data loader's row gather into the kernels.
+data loader's row gather into the kernels.  ``"counts"`` may also be an ``ops.SparseGroupCounts`` (CSR in HBM): the step then
+densifies the minibatch's rows first (``ops.gather_minibatches``, one launch for every such group).
 """
 from __future__ import annotations
 
@@ -30,7 +31,7 @@ from torch import nn
 
 from . import _abi
 from ._abi import DEC_CELLS_PER_WG, round_up
-from .ops import N_HIDDEN_MIX, EncoderFC1, GroupCounts, Workspace, fork, group_streams, join
+from .ops import N_HIDDEN_MIX, EncoderFC1, GroupCounts, SparseGroupCounts, Workspace, fork, gather_minibatches, group_streams, join
 
 X_KEY, BATCH_KEY = "X", "batch"  # scvi.REGISTRY_KEYS.X_KEY / BATCH_KEY
 
@@ -436,8 +437,15 @@ class spVIPESmodule(nn.Module):
         h1s, eps_enc = {}, {}
         H = self.n_hidden
         groups_ = sorted(x.keys())
+        # groups whose counts are resident as CSR: their minibatch rows are densified first, all in one launch (ops.gather_minibatches);
+        # everything downstream then runs on the minibatch buffers with rows 0..B-1
+        sparse = [g for g in groups_ if isinstance(x[g].get("counts"), SparseGroupCounts)]
+        gathered = {}
+        if sparse:
+            items = [(x[g]["counts"], x[g]["rows"], self._workspace(g, x[g]["counts"].device)) for g in sparse]
+            gathered = dict(zip(sparse, gather_minibatches(items, self.nsplit, 2 * H)))
         for g, group in x.items():
-            self._step_inputs[g] = self._counts_of(g, group)
+            self._step_inputs[g] = gathered[g] if g in gathered else self._counts_of(g, group)
         dev0 = self._step_inputs[groups_[0]][0].X.device
         self._cov = self._covariates(batch_index, x, dev0)   # None, or per group (batch codes int32 [B], one_hot fp32 [B][n_batch])
         # Everything that does not depend on the encoders is issued BEFORE the fc1 GEMMs, so that it runs in the shadow of the

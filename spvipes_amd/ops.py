@@ -50,6 +50,10 @@ class GroupCounts:
     def n_cells(self) -> int:
         return self.X.shape[0]
 
+    @property
+    def device(self) -> torch.device:
+        return self.X.device
+
     def log1p_image(self):
         """(f16 log1p(x) of every cell [n_cells][ld >= round_up(G, 96), multiple of 128], library = log(sum_g log1p(x)) per cell), built on first use
         by spv_prepare_log1p: the same arithmetic the reference does per minibatch (module/spVIPESmodule.py:428-435)."""
@@ -112,6 +116,121 @@ class Workspace:
             t = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self.device)
             self._buf[key] = t
         return t
+
+
+class SparseGroupCounts:
+    """Count matrix of one group resident in HBM as CSR: indptr int64 [n_cells + 1], cols int32 (the group's own genes 0..G-1,
+    sorted and unique within a row), vals uint16 bit patterns (int16 tensor) or float32 -- about 6 bytes per stored entry instead of
+    the dense path's 2 bytes per cell x gene plus its 2-byte log1p image.  Every step densifies only the minibatch's rows
+    (``gather_minibatches``: spv_csr_gather, one launch for every sparse group of the step) into workspace buffers and hands the
+    kernels a ``GroupCounts`` over them with rows 0..B-1: the same bytes the dense-resident path feeds them."""
+
+    def __init__(self, indptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor, G: int):
+        if not (indptr.is_cuda and cols.is_cuda and vals.is_cuda):
+            raise _abi.SpvError("SparseGroupCounts needs its CSR arrays resident in HBM")
+        if indptr.dtype != torch.int64 or indptr.dim() != 1 or indptr.numel() < 2 or cols.dtype != torch.int32:
+            raise _abi.SpvError("SparseGroupCounts: indptr int64 [n_cells + 1] and int32 cols expected")
+        if vals.dtype == torch.float32:
+            self.dtype = _abi.SPV_COUNT_F32
+        elif vals.dtype in (torch.int16, torch.uint16):
+            self.dtype = _abi.SPV_COUNT_U16
+        else:
+            raise _abi.SpvError(f"unsupported count dtype {vals.dtype} (float32 or uint16)")
+        if cols.numel() != vals.numel() or G <= 0 or not (indptr.is_contiguous() and cols.is_contiguous() and vals.is_contiguous()):
+            raise _abi.SpvError("SparseGroupCounts: contiguous cols and vals of one length and G > 0 expected")
+        if indptr.numel() - 1 > 2**31 - 1:
+            raise _abi.SpvError("SparseGroupCounts: at most 2^31 - 1 cells per group (int32 row indices)")
+        self.indptr, self.cols, self.vals, self.G = indptr, cols, vals, int(G)
+        self._ident: Dict[Tuple, torch.Tensor] = {}
+
+    @property
+    def n_cells(self) -> int:
+        return self.indptr.numel() - 1
+
+    @property
+    def nnz(self) -> int:
+        return self.cols.numel()
+
+    @property
+    def device(self) -> torch.device:
+        return self.indptr.device
+
+    @property
+    def nbytes(self) -> int:
+        """HBM held by the CSR arrays"""
+        return sum(t.numel() * t.element_size() for t in (self.indptr, self.cols, self.vals))
+
+    @classmethod
+    def from_arrays(cls, indptr, cols, vals, G: int, device) -> "SparseGroupCounts":
+        """host CSR arrays (data.csr_group_arrays) -> HBM; uint16 values travel as their int16 bit patterns"""
+        import numpy as np
+
+        vals = np.ascontiguousarray(vals)
+        vt = torch.from_numpy(vals.view(np.int16) if vals.dtype == np.uint16 else vals.astype(np.float32, copy=False))
+        return cls(torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(device),
+                   torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int32)).to(device), vt.to(device), G)
+
+    @classmethod
+    def from_dense(cls, counts: GroupCounts, chunk: int = 4096) -> "SparseGroupCounts":
+        """CSR of a dense resident GroupCounts, built on the device (tests and tools: no host round trip); explicit zeros dropped"""
+        X, G, c0 = counts.X, counts.G, counts.col_off
+        lens, cols, vals = [], [], []
+        for lo in range(0, counts.n_cells, chunk):
+            sub = X[lo:lo + chunk, c0:c0 + G]
+            mask = sub != 0
+            nz = mask.nonzero()   # row-major: rows ascending, columns ascending within a row
+            lens.append(mask.sum(1))
+            cols.append(nz[:, 1].to(torch.int32))
+            vals.append(sub[mask])
+        indptr = torch.zeros(counts.n_cells + 1, dtype=torch.int64, device=X.device)
+        torch.cumsum(torch.cat(lens), 0, out=indptr[1:])
+        return cls(indptr, torch.cat(cols).contiguous(), torch.cat(vals).contiguous(), G)
+
+    def identity_rows(self, B: int) -> torch.Tensor:
+        """rows 0..B-1 (int32, kept: a captured graph reads the same buffer on every replay)"""
+        key = (B, self.device)
+        t = self._ident.get(key)
+        if t is None:
+            t = self._ident[key] = torch.arange(B, dtype=torch.int32, device=self.device)
+        return t
+
+
+def gather_minibatches(items, nsplit: int, N1: int):
+    """Densify the minibatch rows of every sparse group of a step in ONE launch (spv_csr_gather).  items: [(SparseGroupCounts, rows
+    int32 [B], Workspace)]; returns [(GroupCounts over the minibatch buffer, rows 0..B-1, B)] per item.  The log1p image is written
+    exactly where the dense-resident path would hand one to the fc1 kernels (GroupCounts.fc1_image): the f16 image in the one-MFMA
+    mode, the split image in "fp32" mode where the LDS-DMA kernel takes the shape (elsewhere the fc1 kernels decode the counts and
+    take the library themselves, as they do on a dense matrix)."""
+    lib = _abi.load()
+    args = (_abi.SpvCsrGatherArgs * len(items))()
+    out = []
+    if not 0 < len(items) <= _abi.SPV_CSR_GATHER_MAXG:
+        raise _abi.SpvError(f"gather_minibatches: 1 .. {_abi.SPV_CSR_GATHER_MAXG} groups per call")
+    for a, (sc, rows, ws) in zip(args, items):
+        if rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous():
+            raise _abi.SpvError("row index must be a contiguous int32 tensor in HBM")
+        B, G = int(rows.numel()), sc.G
+        ldx = round_up(G, 8)
+        X = ws.get("csr_X", (B, ldx), torch.float32 if sc.dtype == _abi.SPV_COUNT_F32 else torch.int16)
+        ldh = round_up(round_up(G, 96), 128)   # GroupCounts.log1p_image / log1p_image_split
+        split = None
+        if nsplit == 1:
+            split = 0
+        elif lib.spv_enc_fc1_fwd_uses_dma(B, G, N1, nsplit, 1, round_up(G, 64), 2 * ldh):
+            split = 1
+        xb = ws.get("csr_xb", (B, ldh if split == 0 else 2 * ldh), torch.int16) if split is not None else None
+        lib_t = ws.get("csr_library", (B,), torch.float32) if split is not None else None
+        a.indptr, a.cols, a.vals, a.n_rows, a.G, a.dtype, a.B = ptr(sc.indptr), ptr(sc.cols), ptr(sc.vals), sc.n_cells, G, sc.dtype, B
+        a.rows, a.X, a.ldx = ptr(rows), ptr(X), ldx
+        a.xb, a.ld_xb, a.xb_split, a.library = ptr(xb), (xb.shape[1] if xb is not None else 0), int(split or 0), ptr(lib_t)
+        mb = GroupCounts(X, G, 0, resident=True)
+        if split == 0:
+            mb._xb = (xb, lib_t)
+        elif split == 1:
+            mb._xb_split = (xb, lib_t)
+        out.append((mb, sc.identity_rows(B), B))
+    _abi.call("spv_csr_gather", args, len(items), stream_ptr())
+    return out
 
 
 def image_token(*tensors) -> Tuple:

@@ -171,7 +171,7 @@ class Trainer:
         if getattr(module, "n_cov", 0):
             if batch_codes is None or len(batch_codes) != len(self.counts):
                 raise ValueError(f"the module was built with n_batch = {module.n_batch}: pass batch_codes (one code per cell and group)")
-            self.batch_codes = [b.flatten().to(device=counts[0].X.device, dtype=torch.int32).contiguous() for b in batch_codes]
+            self.batch_codes = [b.flatten().to(device=counts[0].device, dtype=torch.int32).contiguous() for b in batch_codes]
             for g, b in enumerate(self.batch_codes):   # (the fc1 epilogue indexes its covariate table with them: validated once, here)
                 if b.numel() and not bool(((b >= 0) & (b < module.n_cov)).all()):
                     raise ValueError(f"batch codes of group {g} must lie in [0, n_batch = {module.n_batch})")
@@ -185,7 +185,7 @@ class Trainer:
                 n_comp = getattr(module, "n_components", None)
                 if what == "cluster components" and module.n_groups > 2 and n_comp is not None and lf.numel() and float(lf.max()) >= n_comp:
                     raise ValueError(f"cluster components of group {g} must be codes in [0, n_components = {n_comp})")
-        self.device = counts[0].X.device
+        self.device = counts[0].device
         self.fp = FlatParams(module, late=lambda name: name.startswith("encoder_"))
         self.opt = HipAdam(self.fp, lr=lr, eps=eps, weight_decay=weight_decay)
         self.n_epochs_kl_warmup, self.n_steps_kl_warmup = n_epochs_kl_warmup, n_steps_kl_warmup
