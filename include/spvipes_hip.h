@@ -330,6 +330,28 @@ int spv_dec_heads_bwd_grouped(const spv_dec_group* groups, int32_t n_groups, voi
 int spv_dec_materialize(const spv_dec_params* p, float* scale_private, float* scale_shared, float* rate_private, float* rate_shared,
                         float* mixing_logits, int64_t ld, void* stream);
 
+/* Denoised-expression read-out over a selected list of genes (get_normalized_expression): for one group and one minibatch, ONE
+ * row-major fp32 array out[B][ld_out] of the NB mixture's mean or of one of its ingredients (nn/networks.py:314-325,
+ * module/spVIPESmodule.py:751-759; pi = sigmoid(mixing logits) weights component 1, the private rate):
+ *   what = 0  pi * rate_private + (1 - pi) * rate_shared      1  pi * rate_private      2  (1 - pi) * rate_shared      3  pi
+ *   out[b][j] = alpha * value(b, genes[j])   or, with accumulate != 0,   out[b][j] += alpha * value(b, genes[j])
+ * `p` is the operand set as spv_dec_lse leaves it (Wps, Aps, a_p / a_s = library - lse over ALL G genes, either kslots layout; hand
+ * spv_dec_lse a library vector filled with log L for a fixed library size L).  Am / Wm are the mixing operands spv_dec_logits takes
+ * (bf16 [Bp][K] / [Gp][K], bias in the ones column, lo planes when nsplit == 3; K % 32 == 0, K <= 320, 16-byte aligned): the logits
+ * of the selected genes are accumulated inside the kernel, p->logits is not read.  genes: int32 device array of n_genes ids in
+ * [0, G), any order, repeats allowed (ids outside the range are clamped into it, never dereferenced out of bounds); NULL = genes
+ * 0 .. n_genes - 1 (n_genes <= G).  An element's value depends on its own gene and cell only: the output over a selection equals
+ * the same columns of the all-genes output bit for bit, and its rates equal spv_dec_materialize's.  Rows >= B and columns >= n_genes
+ * of `out` are never written.  Nothing is allocated; one launch on `stream`. */
+typedef struct spv_dec_expected_args {
+  const uint16_t* Am_hi; const uint16_t* Am_lo; const uint16_t* Wm_hi; const uint16_t* Wm_lo;
+  int32_t K, nsplit;
+  const int32_t* genes; int32_t n_genes; int32_t what;
+  float* out; int64_t ld_out;
+  float alpha; int32_t accumulate;
+} spv_dec_expected_args;
+int spv_dec_expected(const spv_dec_params* p, const spv_dec_expected_args* a, void* stream);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

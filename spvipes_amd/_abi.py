@@ -212,6 +212,13 @@ class SpvDecGroup(C.Structure):
                 ("Tp", C.c_void_p), ("Ts", C.c_void_p), ("dz_part", C.c_void_p), ("dw_part", C.c_void_p)]
 
 
+class SpvDecExpectedArgs(C.Structure):
+    """the read-out arguments of spv_dec_expected (include/spvipes_hip.h: spv_dec_expected_args)"""
+    _fields_ = [("Am_hi", C.c_void_p), ("Am_lo", C.c_void_p), ("Wm_hi", C.c_void_p), ("Wm_lo", C.c_void_p), ("K", C.c_int32), ("nsplit", C.c_int32),
+                ("genes", C.c_void_p), ("n_genes", C.c_int32), ("what", C.c_int32), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("alpha", C.c_float), ("accumulate", C.c_int32)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -270,6 +277,7 @@ _SIGNATURES = {
     "spv_dec_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_int32, C.c_void_p]),
     "spv_dec_materialize": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spv_dec_expected": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecExpectedArgs), C.c_void_p]),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -5,6 +5,7 @@
 #include "spv_fc1.h"
 #include "spv_dec_gemm.h"
 #include "spv_decoder.h"
+#include "spv_dec_expected.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -801,6 +802,38 @@ extern "C" int spv_dec_materialize(const spv_dec_params* q, float* scale_p, floa
   else if (wide) hipLaunchKernelGGL((dec_materialize_kernel<_Float16, 2>), grid, dim3(256), 0, s, p, scale_p, scale_s, rate_p, rate_s, logits_out, (long)ld);
   else hipLaunchKernelGGL((dec_materialize_kernel<_Float16>), grid, dim3(256), 0, s, p, scale_p, scale_s, rate_p, rate_s, logits_out, (long)ld);
   return launch_status("spv_dec_materialize");
+}
+
+extern "C" int spv_dec_expected(const spv_dec_params* q, const spv_dec_expected_args* x, void* stream) {
+  DecParams p;
+  int rc = to_dec(q, p);
+  if (rc != SPV_OK) return rc;
+  if (!x) return fail(SPV_ERR_ARG, "spv_dec_expected: null arguments%s");
+  if (!p.a_p || !p.a_s || !x->Am_hi || !x->Wm_hi || !x->out) return fail(SPV_ERR_ARG, "spv_dec_expected: null pointer%s");
+  if (x->K <= 0 || (x->K % 32) || x->K > DX_KMAX) return fail(SPV_ERR_ARG, "spv_dec_expected: K must be a multiple of 32, at most 320%s");
+  if (x->nsplit != 1 && x->nsplit != 3) return fail(SPV_ERR_ARG, "spv_dec_expected: nsplit must be 1 or 3%s");
+  if (x->nsplit == 3 && (!x->Am_lo || !x->Wm_lo)) return fail(SPV_ERR_ARG, "spv_dec_expected: nsplit=3 needs lo images%s");
+  if ((reinterpret_cast<uintptr_t>(x->Am_hi) | reinterpret_cast<uintptr_t>(x->Wm_hi) | reinterpret_cast<uintptr_t>(x->Am_lo) | reinterpret_cast<uintptr_t>(x->Wm_lo)) & 15)
+    return fail(SPV_ERR_ARG, "spv_dec_expected: operand images must be 16-byte aligned%s");
+  if (x->n_genes <= 0 || (!x->genes && x->n_genes > p.G)) return fail(SPV_ERR_ARG, "spv_dec_expected: n_genes must be positive (and at most G without a gene list)%s");
+  if (x->what < 0 || x->what > 3) return fail(SPV_ERR_ARG, "spv_dec_expected: what must be 0 (mixture), 1 (private), 2 (shared) or 3 (mixing weight)%s");
+  if (x->ld_out < x->n_genes) return fail(SPV_ERR_ARG, "spv_dec_expected: ld_out < n_genes%s");
+  const DecExpArgs a{(const bf16_t*)x->Am_hi, (const bf16_t*)x->Am_lo, (const bf16_t*)x->Wm_hi, (const bf16_t*)x->Wm_lo, x->K,
+                     x->genes, x->n_genes, x->what, x->out, (long)x->ld_out, x->alpha, x->accumulate};
+  // one workgroup per 32 cells and gene slice; each of its 4 waves walks every (4 gy)-th 32-gene tile.  ~8 workgroups per CU keep
+  // the gathers of the gene rows covered; never more slices than there are tiles for the waves.
+  const int gx = p.Bp / DX_CELLS, tiles = (x->n_genes + 31) / 32;
+  int gy = (2048 + gx - 1) / gx;
+  if (gy > (tiles + 3) / 4) gy = (tiles + 3) / 4;
+  if (gy < 1) gy = 1;
+  const dim3 grid(gx, gy);
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = dec_kw(q) == 2;
+  if (x->nsplit == 3 && wide) hipLaunchKernelGGL((dec_expected_kernel<3, 2>), grid, dim3(256), 0, s, p, a);
+  else if (x->nsplit == 3) hipLaunchKernelGGL((dec_expected_kernel<3, 1>), grid, dim3(256), 0, s, p, a);
+  else if (wide) hipLaunchKernelGGL((dec_expected_kernel<1, 2>), grid, dim3(256), 0, s, p, a);
+  else hipLaunchKernelGGL((dec_expected_kernel<1, 1>), grid, dim3(256), 0, s, p, a);
+  return launch_status("spv_dec_expected");
 }
 
 extern "C" int spv_dec_dz(const spv_dec_params* q, const float* Tp, const float* Ts, float* dz_part, void* stream) {

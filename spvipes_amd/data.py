@@ -10,6 +10,7 @@ kernels gather through.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -260,3 +261,104 @@ def format_latent_results(private0, private1, shared0, shared1, indices1, n0: in
     s = {0: np.concatenate(shared0)[:n0], 1: np.concatenate(shared1)[:n1]}
     order = np.argsort(i1)
     return {"shared": s, "private": p, "shared_reordered": {0: s[0], 1: s[1][order]}, "private_reordered": {0: p[0], 1: p[1][order]}}
+
+
+# ---- denoised-expression read-out (model.get_normalized_expression): host-side argument handling ------------------------------
+EXPRESSION_COMPONENTS = {"mixture": 0, "private": 1, "shared": 2, "mixing": 3}   # -> ``what`` of spv_dec_expected
+
+
+def expression_what(component) -> int:
+    """"mixture" | "private" | "shared" | "mixing" (or the code 0..3 itself) -> the ``what`` code of spv_dec_expected"""
+    if isinstance(component, str) and component in EXPRESSION_COMPONENTS:
+        return EXPRESSION_COMPONENTS[component]
+    if isinstance(component, (int, np.integer)) and not isinstance(component, bool) and 0 <= int(component) <= 3:
+        return int(component)
+    raise ValueError(f"component must be one of {sorted(EXPRESSION_COMPONENTS)}, got {component!r}")
+
+
+def expression_log_library(library_size) -> Optional[float]:
+    """``library_size``: "latent" -> None (the model's own library), a positive finite number L -> log L, the value the library
+    vector handed to spv_dec_lse is filled with (rate = L * softmax)"""
+    if isinstance(library_size, str):
+        if library_size != "latent":
+            raise ValueError(f"library_size must be 'latent' or a positive number, got {library_size!r}")
+        return None
+    try:
+        L = float(library_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"library_size must be 'latent' or a positive number, got {library_size!r}") from None
+    if not (L > 0.0 and math.isfinite(L)):
+        raise ValueError(f"library_size must be 'latent' or a positive number, got {library_size!r}")
+    return math.log(L)
+
+
+def check_expression_args(component, library_size, n_samples, use_mean: bool):
+    """The argument checks of get_normalized_expression: -> (what code, log L or None, n_samples).  ``n_samples`` must be a
+    positive integer and, when the posterior means are decoded (``use_mean``), 1: there is nothing to average."""
+    what, log_l = expression_what(component), expression_log_library(library_size)
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or int(n_samples) < 1:
+        raise ValueError(f"n_samples must be a positive integer, got {n_samples!r}")
+    if use_mean and int(n_samples) > 1:
+        raise ValueError("n_samples > 1 needs use_mean=False: decoding the posterior means is deterministic, there is nothing to average")
+    return what, log_l, int(n_samples)
+
+
+def group_var_names(adata, n_groups: int = 2):
+    """Per group the names of its own genes, as get_loadings labels them: ``adata.var_names`` cut by ``uns["groups_var_indices"]``,
+    else ``uns["groups_var_names"]`` (list or dict), else None"""
+    out = []
+    for g in range(n_groups):
+        names = None
+        if getattr(adata, "var_names", None) is not None:
+            names = np.asarray(adata.var_names)[np.asarray(adata.uns["groups_var_indices"][g])]
+        elif adata.uns.get("groups_var_names") is not None:
+            gv = adata.uns["groups_var_names"]
+            names = np.asarray(gv[g] if not isinstance(gv, dict) else list(gv.values())[g])
+        out.append(names)
+    return out
+
+
+def resolve_gene_list(gene_list, n_genes: Sequence[int], var_names=None) -> List[Optional[np.ndarray]]:
+    """``gene_list`` of get_normalized_expression -> per group None (all genes in order) or an int32 array of positions within the
+    group's own genes.  ``gene_list``: None, or one entry per group, each None | integer positions | gene names (looked up in
+    ``var_names[g]``, the group's own names; the first occurrence of a repeated name).  Any order, repeats allowed.  Unknown names
+    raise KeyError and positions outside [0, n_genes[g]) IndexError, both naming the offender."""
+    ng = len(n_genes)
+    if gene_list is None:
+        return [None] * ng
+    if isinstance(gene_list, (str, bytes)) or not hasattr(gene_list, "__len__") or len(gene_list) != ng:
+        raise ValueError(f"gene_list must be None or hold one entry per group ({ng}): None, positions or names")
+    out = []
+    for g in range(ng):
+        sel = gene_list[g] if not isinstance(gene_list, dict) else gene_list.get(g)
+        if sel is None:
+            out.append(None)
+            continue
+        if isinstance(sel, (str, bytes)):
+            sel = [sel]
+        arr = np.asarray(sel)
+        if arr.ndim != 1 or arr.size == 0:
+            raise ValueError(f"gene_list[{g}] must be a non-empty 1-d sequence of positions or names")
+        if arr.dtype == bool:
+            raise TypeError(f"gene_list[{g}]: boolean masks are not supported, pass positions or names")
+        if np.issubdtype(arr.dtype, np.integer):
+            bad = np.nonzero((arr < 0) | (arr >= n_genes[g]))[0]
+            if bad.size:
+                raise IndexError(f"gene_list[{g}]: position {int(arr[bad[0]])} is out of range for a group of {n_genes[g]} genes")
+            out.append(arr.astype(np.int32))
+            continue
+        if arr.dtype.kind not in "USO":
+            raise TypeError(f"gene_list[{g}] must hold integer positions or gene names, got dtype {arr.dtype}")
+        names = None if var_names is None else var_names[g]
+        if names is None:
+            raise KeyError(f"gene_list[{g}] holds names ({arr[0]!r}, ...) but the AnnData carries neither var_names nor uns['groups_var_names']")
+        first = {}
+        for i, nme in enumerate(np.asarray(names).astype(str)):
+            first.setdefault(nme, i)
+        pos = np.empty(arr.size, np.int32)
+        for i, nme in enumerate(arr.astype(str)):
+            if nme not in first:
+                raise KeyError(f"gene_list[{g}]: gene {nme!r} is not among the genes of group {g}")
+            pos[i] = first[nme]
+        out.append(pos)
+    return out

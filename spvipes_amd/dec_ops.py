@@ -12,12 +12,13 @@ likelihood} forward; backward per group {softmax fix, 6 GEMMs} + 8 small batched
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _abi
-from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecGroup, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
+from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
                    ptr, round_up, stream_ptr)
 from .nn_ops import _add_lin, _fptr, _lin_batch, _wgrad, grad_out
 from . import ops as _ops
@@ -759,15 +760,18 @@ class DecoderFused(torch.autograd.Function):
         return (None,) * 11 + tuple(grads)
 
 
+class _DecOperands:
+    """one group's decoder operand set as ``spv_dec_lse`` leaves it (the inputs of spv_dec_materialize and spv_dec_expected)"""
+    __slots__ = ("p", "B", "G", "Bp", "Gp", "Am", "Wm", "par", "keep")
+
+
 @torch.no_grad()
-def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
-                        training: bool, nsplit: int, ws: Workspace, par=None) -> dict:
-    """The decoder outputs the reference's ``generative`` returns for ONE group (module/spVIPESmodule.py:751-768,
-    nn/networks.py:314-325): {"px_scale_private", "px_scale_shared", "px_rate_private", "px_rate_shared", "px_mixing"}
-    as fp32 [B, G] tensors + "px_r" = exp(px_r).  The training step never needs them (the fused likelihood kernel consumes
-    the same quantities in registers); this runs the same operand preparation as ``DecoderFused.forward`` for one group
-    -- latent slicing quirk, BatchNorm fold (batch statistics in training mode, WITHOUT touching the running statistics:
-    momentum 0), mixing trunk, logits GEMM, softmax statistics -- and then ``spv_dec_materialize``."""
+def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
+                     training: bool, nsplit: int, ws: Workspace, par=None, *, logits: bool) -> _DecOperands:
+    """The operand preparation of ``DecoderFused.forward`` for ONE group, outside autograd -- latent slicing quirk, BatchNorm fold
+    (batch statistics in training mode, WITHOUT touching the running statistics: momentum 0), mixing trunk, the Wm / Am operand
+    images, the tiled logits GEMM (``logits``: only spv_dec_materialize reads that array) and the softmax statistics over all G
+    genes (spv_dec_lse).  Shared by ``materialize_decoder`` and ``expected_expression``."""
     dev = private_log_z.device
     cont = lambda t: t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
     par = list(par) if par is not None else decoder_params(decoder, px_r)   # (``par``: spVIPESmodule._decoder_operands' covariate-extended set)
@@ -779,6 +783,8 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     if n_p + 1 > DEC_KP or n_s + 1 > DEC_KS:
         raise _abi.SpvError(f"decoder kernels support n_private <= {DEC_KP - 1} and n_shared <= {DEC_KS - 1}")
     n_m = par[6].shape[0]
+    if n_m + nt + 1 > KMP:
+        raise _abi.SpvError("mixture input wider than 320 columns is not supported")
     G = par[0].shape[0]
     Bp, Gp = round_up(B, DEC_CELLS_PER_WG), round_up(G, 256)
     mlo = nsplit == 3
@@ -829,23 +835,100 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     q.part = ptr(ws.get("mat_bn_part", (nblk, n_m, 2), torch.float32))
     q.img_hi, q.img_lo, q.ld_img, q.img_rows = ptr(Am_hi), ptr(Am_lo), KMP, Bp
     _abi.call("spv_bn_fwd", C.byref(bn), stream_ptr())
-    logits = ws.get("mat_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
-    _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(logits), int(mlo), stream_ptr())
+    tiled = None
+    if logits:
+        tiled = ws.get("mat_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
+        _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(tiled), int(mlo), stream_ptr())
     splits, per = _gene_splits(Bp, Gp)
     vec = lambda nme: ws.get(nme, (Bp,), torch.float32)
     part = lambda nme: ws.get(nme, (splits, Bp), torch.float32)
     lse_p, lse_s, a_p, a_s = vec("mat_lse_p"), vec("mat_lse_s"), vec("mat_a_p"), vec("mat_a_s")
     p = SpvDecParams(
-        X=None, ldx=0, rows=None, col_off=0, count_is_u16=0, B=B, G=G, Bp=Bp, Gp=Gp, logits=ptr(logits), n_gene_tiles=Gp // 32, logits_f32=int(mlo),
+        X=None, ldx=0, rows=None, col_off=0, count_is_u16=0, B=B, G=G, Bp=Bp, Gp=Gp, logits=ptr(tiled), n_gene_tiles=Gp // 32, logits_f32=int(mlo),
         Wps_hi=ptr(Wps_hi), Wps_lo=ptr(Wps_lo), Aps_hi=ptr(Aps_hi), Aps_lo=ptr(Aps_lo), gene_tab=None, cnt_tab=None,
         a_p=ptr(a_p), a_s=ptr(a_s), lse_p=ptr(lse_p), lse_s=ptr(lse_s), w_row=None, gene_splits=splits, genes_per_split=per,
         part_max_p=ptr(part("mat_pmp")), part_sum_p=ptr(part("mat_psp")), part_max_s=ptr(part("mat_pms")), part_sum_s=ptr(part("mat_pss")),
         rec_part=None, tp_part=None, ts_part=None, dtheta_part=None, dL=None, tP=None, tS=None, grads_f32=0, nb_splits=1, nb_genes_per_split=32,
         kslots=sl.kslots,
     )
-    _abi.call("spv_dec_lse", C.byref(p), ptr(cont(library.flatten())), stream_ptr())
+    lib = cont(library.flatten())
+    if lib.numel() != B:
+        raise _abi.SpvError("decoder: the library vector must hold one value per cell")
+    _abi.call("spv_dec_lse", C.byref(p), ptr(lib), stream_ptr())
+    o = _DecOperands()
+    o.p, o.B, o.G, o.Bp, o.Gp, o.Am, o.Wm, o.par = p, B, G, Bp, Gp, (Am_hi, Am_lo), (Wm_hi, Wm_lo), par
+    o.keep = (pz, qz, lib)
+    return o
+
+
+@torch.no_grad()
+def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
+                        training: bool, nsplit: int, ws: Workspace, par=None) -> dict:
+    """The decoder outputs the reference's ``generative`` returns for ONE group (module/spVIPESmodule.py:751-768,
+    nn/networks.py:314-325): {"px_scale_private", "px_scale_shared", "px_rate_private", "px_rate_shared", "px_mixing"}
+    as fp32 [B, G] tensors + "px_r" = exp(px_r).  The training step never needs them (the fused likelihood kernel consumes
+    the same quantities in registers); this runs the same operand preparation as ``DecoderFused.forward`` for one group
+    (``_prepare_decoder``) and then ``spv_dec_materialize``."""
+    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, logits=True)
+    B, G = o.B, o.G
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=private_log_z.device)
     out = {k: new(B, G) for k in ("px_scale_private", "px_scale_shared", "px_rate_private", "px_rate_shared", "px_mixing")}
-    _abi.call("spv_dec_materialize", C.byref(p), ptr(out["px_scale_private"]), ptr(out["px_scale_shared"]), ptr(out["px_rate_private"]),
+    _abi.call("spv_dec_materialize", C.byref(o.p), ptr(out["px_scale_private"]), ptr(out["px_scale_shared"]), ptr(out["px_rate_private"]),
               ptr(out["px_rate_shared"]), ptr(out["px_mixing"]), G, stream_ptr())
-    out["px_r"] = torch.exp(cont(par[12]))
+    p12 = o.par[12]
+    out["px_r"] = torch.exp(p12 if (p12.is_contiguous() and p12.dtype == torch.float32) else p12.contiguous().float())
     return out
+
+
+@torch.no_grad()
+def expected_expression(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
+                        training: bool, nsplit: int, ws: Workspace, par=None, *, genes=None, what="mixture", library_size="latent",
+                        out: Optional[torch.Tensor] = None, alpha: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+    """The mean of ONE group's NB mixture, or one of its ingredients, over a selection of genes as fp32 [B, n_genes]
+    (spv_dec_expected; nn/networks.py:314-325, module/spVIPESmodule.py:751-759):
+        what = "mixture"  pi * rate_private + (1 - pi) * rate_shared,   "private"  pi * rate_private,
+               "shared"   (1 - pi) * rate_shared,                       "mixing"   pi = sigmoid(mixing logits)
+    ``genes``: None (all G genes in order), an int32 device tensor of ids in [0, G) (taken as checked: the kernel clamps ids, it
+    does not report them), or any host sequence of integers (checked here: IndexError names the first offender); any order,
+    repeats allowed.  ``library_size``: "latent" (exp(``library``)) or a positive number L (rate = L * softmax).
+    ``out``: fp32 device tensor [>= B, >= n_genes] with unit column stride to write into (rows >= B and columns >= n_genes stay
+    untouched); ``out = alpha * value`` or, with ``accumulate``, ``out += alpha * value``.  Same operand preparation as
+    ``materialize_decoder``; the softmax denominators always run over all G genes."""
+    from .data import expression_log_library, expression_what
+
+    code = expression_what(what)
+    logL = expression_log_library(library_size)
+    dev = private_log_z.device
+    B = private_log_z.shape[0]
+    lib = library if logL is None else torch.full((B,), logL, dtype=torch.float32, device=dev)
+    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
+    G = o.G
+    if genes is None:
+        gidx, n = None, G
+    elif isinstance(genes, torch.Tensor) and genes.is_cuda:
+        if genes.dtype != torch.int32 or genes.dim() != 1 or not genes.is_contiguous():
+            raise _abi.SpvError("expected_expression: a device gene list must be a contiguous 1-d int32 tensor")
+        gidx, n = genes, int(genes.numel())
+    else:
+        host = np.asarray(genes.cpu() if isinstance(genes, torch.Tensor) else genes)
+        if host.ndim != 1 or (host.size and not np.issubdtype(host.dtype, np.integer)):
+            raise TypeError("expected_expression: genes must be a 1-d sequence of integer gene positions")
+        bad = np.nonzero((host < 0) | (host >= G))[0]
+        if bad.size:
+            raise IndexError(f"gene position {int(host[bad[0]])} is out of range for a group of {G} genes")
+        gidx, n = torch.as_tensor(host.astype(np.int32), device=dev), int(host.size)
+    if n <= 0:
+        raise ValueError("expected_expression: the gene selection is empty")
+    if out is None:
+        if accumulate:
+            raise ValueError("expected_expression: accumulate=True needs the ``out`` array to add to")
+        out = torch.empty((B, n), dtype=torch.float32, device=dev)
+    elif (not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B or out.shape[1] < n
+          or (out.shape[1] > 1 and out.stride(1) != 1) or (out.shape[0] > 1 and out.stride(0) < n)):
+        raise _abi.SpvError(f"expected_expression: out must be an fp32 device tensor [>= {B}, >= {n}] with unit column stride")
+    a = SpvDecExpectedArgs()
+    a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.nsplit = ptr(o.Am[0]), ptr(o.Am[1]), ptr(o.Wm[0]), ptr(o.Wm[1]), KMP, nsplit
+    a.genes, a.n_genes, a.what = ptr(gidx), n, code
+    a.out, a.ld_out, a.alpha, a.accumulate = ptr(out), (out.stride(0) if out.shape[0] > 1 else max(out.shape[1], n)), float(alpha), int(bool(accumulate))
+    _abi.call("spv_dec_expected", C.byref(o.p), C.byref(a), stream_ptr())
+    return out[:B, :n]

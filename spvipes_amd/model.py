@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, csr_group_arrays, csr_to_dense, format_latent_results, is_sparse, latent_loader_mode, latent_steps,
-                   to_group_counts, to_sparse_group_counts)
+from .data import (MinibatchSampler, check_expression_args, csr_group_arrays, csr_to_dense, format_latent_results, group_var_names, is_sparse,
+                   latent_loader_mode, latent_steps, resolve_gene_list, to_group_counts, to_sparse_group_counts)
 from .module import spVIPESmodule
 from .train import Trainer, default_max_epochs
 
@@ -204,25 +204,77 @@ class spVIPES:
         callable (step, B0, B1) -> dict of injected standard-normal draws for module.inference."""
         if normalized:
             raise NotImplementedError("normalized=True is broken in the reference (nothing is collected for the shared latents, :542-544)")
-        batch_size = batch_size or 128
         n1, n2 = (len(g) for g in group_indices_list)
-        local = [self._local_rows(g, group_indices_list[g]) for g in range(2)]
-        drop_last, use_cycling = latent_loader_mode(self.module.use_labels, self.module.use_transport_plan, self.module.pair_data, drop_last)   # :468-503
         res = {k: [] for k in ("s0", "s1", "p0", "p1", "i1")}
-        was_training = self.module.training
-        self.module.eval()
-        for step, (r0, r1) in enumerate(latent_steps(local, batch_size, drop_last, use_cycling)):
-            rows = [torch.as_tensor(r, dtype=torch.int32, device=self.device) for r in (r0, r1)]
-            tensors = self._minibatch(rows)
-            kw = {} if _noise is None else {"noise": _noise(step, len(r0), len(r1))}
-            out = self.module.inference(**self.module._get_inference_input(tensors), **kw)
+        for step, tensors, (B0, B1) in self._eval_minibatches(group_indices_list, batch_size, drop_last):
+            out = self._infer(tensors, _noise, step, B0, B1)
             res["s0"].append(out["poe_stats"][0]["logtheta_log_z"].cpu().numpy())
             res["s1"].append(out["poe_stats"][1]["logtheta_log_z"].cpu().numpy())
             res["p0"].append(out["private_stats"][0]["log_z"].cpu().numpy())
             res["p1"].append(out["private_stats"][1]["log_z"].cpu().numpy())
             res["i1"].append(tensors[1]["indices"].cpu().numpy())
-        self.module.train(was_training)
         return format_latent_results(res["p0"], res["p1"], res["s0"], res["s1"], res["i1"], n1, n2)
+
+    def _eval_minibatches(self, group_indices_list, batch_size: Optional[int], drop_last: Optional[bool]):
+        """The minibatch pairs the read-out methods walk, in order, with the module in eval mode (its mode is restored when the
+        walk ends): (step, per-group minibatch tensors, (B0, B1)) for every step of ``latent_steps`` under ``latent_loader_mode``
+        (model/spvipes.py:468-523, the cycling path of the paired PoE :578-626).  Concatenating a group's per-step rows and cutting
+        at the group's size gives one row per cell of ``group_indices_list[g]``, in its order."""
+        batch_size = batch_size or 128
+        local = [self._local_rows(g, group_indices_list[g]) for g in range(2)]
+        drop_last, use_cycling = latent_loader_mode(self.module.use_labels, self.module.use_transport_plan, self.module.pair_data, drop_last)   # :468-503
+        was_training = self.module.training
+        self.module.eval()
+        try:
+            for step, (r0, r1) in enumerate(latent_steps(local, batch_size, drop_last, use_cycling)):
+                rows = [torch.as_tensor(r, dtype=torch.int32, device=self.device) for r in (r0, r1)]
+                yield step, self._minibatch(rows), (len(r0), len(r1))
+        finally:
+            self.module.train(was_training)
+
+    def _infer(self, tensors, _noise, draw: int, B0: int, B1: int):
+        kw = {} if _noise is None else {"noise": _noise(draw, B0, B1)}
+        return self.module.inference(**self.module._get_inference_input(tensors), **kw)
+
+    @torch.no_grad()
+    def get_normalized_expression(self, group_indices_list: List[List[int]], gene_list=None, library_size="latent", component: str = "mixture",
+                                  n_samples: int = 1, use_mean: bool = True, batch_size: Optional[int] = None, return_numpy: bool = True,
+                                  _noise=None) -> dict:
+        """The expression the decoder predicts for every cell (scvi-tools' ``get_normalized_expression``): {0: [n_cells_0, n_sel_0],
+        1: [n_cells_1, n_sel_1]}, row i of group g being the cell row i of ``get_latent_representation(...)["shared"][g]`` describes
+        (the same minibatch walk).  The decoder is an NB mixture whose component 1 is driven by the private factors and component 2
+        by the shared ones (spVIPESmodule.py:751-759, nn/networks.py:314-325); with pi = sigmoid(mixing logits)
+
+        ``component``: "mixture" the mixture's mean pi * rate_private + (1 - pi) * rate_shared | "private" pi * rate_private |
+        "shared" (1 - pi) * rate_shared | "mixing" pi itself.
+        ``gene_list``: None, or one entry per group: None (all the group's genes) | integer positions within the group's own genes |
+        gene names (``adata.var_names`` / ``uns["groups_var_names"]``, as ``get_loadings`` labels them); any order, repeats allowed;
+        unknown names raise KeyError, positions out of range IndexError.  Only the selected genes are computed and stored.
+        ``library_size``: "latent" -- the model's own exp(library); the library the encoder sees is the log of the summed LOG1P
+        counts, so this scale lives in the log1p domain, not in raw counts -- or a positive number L
+        (every cell's rates then sum to L over the group's genes).
+        ``use_mean``: decode the posterior means (deterministic: two calls agree bit for bit); else decode sampled latents and
+        average ``n_samples`` draws on the device.  ``n_samples > 1`` with ``use_mean`` is a ValueError.
+        ``return_numpy``: each step's block is copied to the host as it completes (device memory holds one [batch, n_sel] block per
+        group); False returns device tensors.  A full [n_cells, G] result returned as numpy is bounded by that copy, not by the kernel.
+        Each cell is decoded with its own batch covariate.  ``_noise`` (tests only): callable (draw, B0, B1) -> injected standard-normal
+        draws for module.inference, draw = step * n_samples + sample."""
+        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
+        n = [len(g) for g in group_indices_list]
+        sel = resolve_gene_list(gene_list, [int(self.module.input_dims[g]) for g in range(2)], group_var_names(self.adata))
+        dev_sel = [None if s is None else torch.as_tensor(s, dtype=torch.int32, device=self.device) for s in sel]
+        blocks = {0: [], 1: []}
+        for step, tensors, (B0, B1) in self._eval_minibatches(group_indices_list, batch_size, None):
+            blk = [None, None]
+            for smp in range(n_samples):
+                out = self._infer(tensors, _noise, step * n_samples + smp, B0, B1)
+                for g in range(2):
+                    blk[g] = self.module.expected_expression(out, g, genes=dev_sel[g], what=component, library_size=library_size, use_mean=use_mean,
+                                                             out=blk[g], alpha=1.0 / n_samples, accumulate=smp > 0)
+            for g in range(2):
+                blocks[g].append(blk[g].cpu().numpy() if return_numpy else blk[g])
+        cat = np.concatenate if return_numpy else torch.cat
+        return {g: cat(blocks[g])[:n[g]] for g in range(2)}
 
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}
@@ -231,14 +283,9 @@ class spVIPES:
         import pandas as pd
 
         out = {}
-        var_idx = [np.asarray(v) for v in self.adata.uns["groups_var_indices"]]
+        all_names = group_var_names(self.adata, len(self.module.input_dims))
         for i in range(len(self.module.input_dims)):
-            names = None
-            if getattr(self.adata, "var_names", None) is not None:
-                names = np.asarray(self.adata.var_names)[var_idx[i]]
-            elif self.adata.uns.get("groups_var_names") is not None:
-                gv = self.adata.uns["groups_var_names"]
-                names = np.asarray(gv[i] if not isinstance(gv, dict) else list(gv.values())[i])
+            names = all_names[i]
             cols = {"private": [f"Z_private_{n}" for n in range(self.module.n_dimensions_private)],
                     "shared": [f"Z_shared_{n}" for n in range(self.module.n_dimensions_shared)]}
             for t in ("private", "shared"):

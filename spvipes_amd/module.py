@@ -705,6 +705,28 @@ class spVIPESmodule(nn.Module):
             out[str(g)] = _GenerativeGroup(LazyNBMixture(g, pl, ql, library[g], module=self), pz)
         return {"private_shared": {}, "private_poe": out}
 
+    @torch.no_grad()
+    def expected_expression(self, inference_outputs, group: int, *, genes=None, what="mixture", library_size="latent", use_mean: bool = False,
+                            out=None, alpha: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+        """The decoder's expected expression for one group of the minibatch ``inference_outputs`` describes (the output of this
+        module's LATEST ``inference`` call: the batch covariates of that call extend the decoder operands), fp32 [B, n_genes]:
+        ``what`` = "mixture" (the NB mixture's mean pi * rate_private + (1 - pi) * rate_shared, pi = sigmoid(mixing logits);
+        spVIPESmodule.py:751-759, nn/networks.py:314-325), "private" / "shared" (its two terms) or "mixing" (pi), over ``genes``
+        (None = all, or positions within the group's genes).  Decodes the sampled latents (``log_z`` / ``logtheta_log_z``, what
+        ``generative`` decodes) or, with ``use_mean``, the posterior means (``logtheta_loc``).  ``library_size``: "latent" (the
+        encoder's library) or a positive number.  Honours ``self.training`` as ``generative`` does: batch statistics in training mode
+        without touching the running statistics, running statistics in eval mode.  ``out`` / ``alpha`` / ``accumulate``:
+        dec_ops.expected_expression (one fused HIP kernel, spv_dec_expected; no [B, G] intermediate is written)."""
+        from .dec_ops import expected_expression
+
+        ps, qs = inference_outputs["private_stats"][group], inference_outputs["poe_stats"][group]
+        pl, ql = (ps["logtheta_loc"], qs["logtheta_loc"]) if use_mean else (ps["log_z"], qs["logtheta_log_z"])
+        lib = inference_outputs["library"][group].detach()
+        first, second, par = self._decoder_operands(group, pl.detach(), ql.detach())
+        return expected_expression(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
+                                   self._workspace(group, lib.device), par=par, genes=genes, what=what, library_size=library_size,
+                                   out=out, alpha=alpha, accumulate=accumulate)
+
     def loss(self, tensors_by_group, inference_outputs, generative_outputs, kl_weight: float = 1.0):
         """spVIPESmodule.py:809-899."""
         from .dec_ops import DecoderFused, decoder_params
