@@ -352,6 +352,31 @@ typedef struct spv_dec_expected_args {
 } spv_dec_expected_args;
 int spv_dec_expected(const spv_dec_params* p, const spv_dec_expected_args* a, void* stream);
 
+/* Differential expression in "change" mode (spVIPES.differential_expression): per gene j < n_genes the statistics, over n_pairs
+ * pairs m of bank rows, of
+ *   lfc_m = log2(max(x1 + eps, FLT_MIN)) - log2(max(x2 + eps, FLT_MIN)),   x1 = bank1[rows1[m]][j],  x2 = bank2[rows2[m]][j]
+ * written as seven fp32 rows of stats[7][ld_stats]:
+ *   0 mean of lfc   1 its standard deviation (population form, / n_pairs)   2 its minimum   3 its maximum
+ *   4 the COUNT of pairs with |lfc_m| >= delta (a whole number, exact: n_pairs <= 2^24)   5 mean of x1   6 mean of x2
+ * bank1 / bank2: fp32 device arrays [n_rows][ld], ld >= n_genes; rows1 / rows2: int32 device arrays [n_pairs]; a row number outside
+ * [0, n_rows) is clamped into it before it indexes anything.  log2 is the hardware's v_log_f32 (1 ulp).  Every pair's term is formed
+ * in fp32; a lane sums at most ceil(ceil(n_pairs / S) / 4) of them in fp32, shifted by the chunk's first lfc (so the sums of squares
+ * are those of the deviations), S = spv_de_pairs_splits(n_genes, n_pairs); everything above that is merged in fp64 with Chan's
+ * pairwise formula, in a fixed order.  There are no floating-point atomics: two calls with the same inputs agree bit for bit, and a
+ * constant column has std == 0 and mean == min == max exactly.  S depends on n_genes, so a gene's last bits may differ between runs
+ * over different gene selections.  ws: caller's scratch of at least S * 7 * n_genes doubles (8-byte aligned), overwritten.  Columns
+ * >= n_genes of `stats` are never written.  Nothing is allocated; two launches on `stream`. */
+typedef struct spv_de_pairs_args {
+  const float* bank1; const float* bank2; int64_t ld1, ld2;
+  const int32_t* rows1; const int32_t* rows2; int32_t n_rows1, n_rows2;
+  int32_t n_genes, n_pairs; float delta, eps;
+  float* stats; int64_t ld_stats;
+  void* ws; int64_t ws_bytes;
+} spv_de_pairs_args;
+int spv_de_pairs(const spv_de_pairs_args* a, void* stream);
+/* the number of pair splits S spv_de_pairs uses for this shape (0 for a non-positive argument) */
+int32_t spv_de_pairs_splits(int32_t n_genes, int32_t n_pairs);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

@@ -219,6 +219,13 @@ class SpvDecExpectedArgs(C.Structure):
                 ("alpha", C.c_float), ("accumulate", C.c_int32)]
 
 
+class SpvDePairsArgs(C.Structure):
+    """the arguments of spv_de_pairs (include/spvipes_hip.h: spv_de_pairs_args)"""
+    _fields_ = [("bank1", C.c_void_p), ("bank2", C.c_void_p), ("ld1", C.c_int64), ("ld2", C.c_int64), ("rows1", C.c_void_p), ("rows2", C.c_void_p),
+                ("n_rows1", C.c_int32), ("n_rows2", C.c_int32), ("n_genes", C.c_int32), ("n_pairs", C.c_int32), ("delta", C.c_float), ("eps", C.c_float),
+                ("stats", C.c_void_p), ("ld_stats", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -278,6 +285,8 @@ _SIGNATURES = {
                                  C.c_void_p, C.c_int32, C.c_void_p]),
     "spv_dec_materialize": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "spv_dec_expected": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecExpectedArgs), C.c_void_p]),
+    "spv_de_pairs": (C.c_int, [C.POINTER(SpvDePairsArgs), C.c_void_p]),
+    "spv_de_pairs_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -6,6 +6,7 @@
 #include "spv_dec_gemm.h"
 #include "spv_decoder.h"
 #include "spv_dec_expected.h"
+#include "spv_de.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -834,6 +835,31 @@ extern "C" int spv_dec_expected(const spv_dec_params* q, const spv_dec_expected_
   else if (wide) hipLaunchKernelGGL((dec_expected_kernel<1, 2>), grid, dim3(256), 0, s, p, a);
   else hipLaunchKernelGGL((dec_expected_kernel<1, 1>), grid, dim3(256), 0, s, p, a);
   return launch_status("spv_dec_expected");
+}
+
+extern "C" int32_t spv_de_pairs_splits(int32_t n_genes, int32_t n_pairs) {
+  if (n_genes <= 0 || n_pairs <= 0) return 0;
+  return de_splits(n_genes, n_pairs);
+}
+
+extern "C" int spv_de_pairs(const spv_de_pairs_args* x, void* stream) {
+  if (!x) return fail(SPV_ERR_ARG, "spv_de_pairs: null arguments%s");
+  if (!x->bank1 || !x->bank2 || !x->rows1 || !x->rows2 || !x->stats || !x->ws) return fail(SPV_ERR_ARG, "spv_de_pairs: null pointer%s");
+  if (x->n_pairs <= 0 || x->n_pairs > (1 << 24)) return fail(SPV_ERR_ARG, "spv_de_pairs: n_pairs must lie in [1, 2^24]%s");
+  if (x->n_genes <= 0 || x->n_rows1 <= 0 || x->n_rows2 <= 0) return fail(SPV_ERR_ARG, "spv_de_pairs: n_genes and the banks' row counts must be positive%s");
+  if (x->ld1 < x->n_genes || x->ld2 < x->n_genes || x->ld_stats < x->n_genes) return fail(SPV_ERR_ARG, "spv_de_pairs: ld < n_genes%s");
+  if (!(x->delta >= 0.f) || !(x->eps >= 0.f)) return fail(SPV_ERR_ARG, "spv_de_pairs: delta and eps must be non-negative numbers%s");
+  const int splits = de_splits(x->n_genes, x->n_pairs), tiles = (x->n_genes + 63) / 64;
+  if (x->ws_bytes < (int64_t)splits * DE_FIELDS * x->n_genes * (int64_t)sizeof(double) || (reinterpret_cast<uintptr_t>(x->ws) & 7))
+    return fail(SPV_ERR_ARG, "spv_de_pairs: the workspace must be 8-byte aligned and hold spv_de_pairs_splits() * 7 * n_genes doubles%s");
+  const DeArgs a{x->bank1, x->bank2, (long)x->ld1, (long)x->ld2, x->rows1, x->rows2, x->n_rows1, x->n_rows2, x->n_genes, x->n_pairs,
+                 x->delta, x->eps, x->stats, (long)x->ld_stats, (double*)x->ws, splits};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(de_pairs_kernel, dim3((tiles * splits + 7) & ~7), dim3(64 * DE_WAVES), 0, s, a);
+  int rc = launch_status("spv_de_pairs");
+  if (rc != SPV_OK) return rc;
+  hipLaunchKernelGGL(de_finish_kernel, dim3(tiles), dim3(64 * DE_FIN_WAVES), 0, s, a);
+  return launch_status("spv_de_pairs (final combine)");
 }
 
 extern "C" int spv_dec_dz(const spv_dec_params* q, const float* Tp, const float* Ts, float* dz_part, void* stream) {

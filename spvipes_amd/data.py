@@ -362,3 +362,116 @@ def resolve_gene_list(gene_list, n_genes: Sequence[int], var_names=None) -> List
             pos[i] = first[nme]
         out.append(pos)
     return out
+
+
+# ---- differential expression (model.differential_expression): host-side argument handling, pairing and the result table ---------
+DE_COLUMNS = ("proba_de", "proba_not_de", "bayes_factor", "scale1", "scale2", "lfc_mean", "lfc_std", "lfc_min", "lfc_max")
+DE_MAX_PAIRS = 1 << 24   # spv_de_pairs carries the exceedance count as fp32 whole numbers
+
+
+def check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells=None):
+    """The argument checks of differential_expression that are its own (component / library_size / n_samples / use_mean go through
+    ``check_expression_args``): -> (n_pairs, delta, pseudocount, fdr_target, max_cells) as plain numbers"""
+    if isinstance(n_pairs, bool) or not isinstance(n_pairs, (int, np.integer)) or not 1 <= int(n_pairs) <= DE_MAX_PAIRS:
+        raise ValueError(f"n_pairs must be an integer between 1 and 2^24, got {n_pairs!r}")
+
+    def number(v, name, ok):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if isinstance(v, (bool, str)) or not (math.isfinite(f) and ok(f)):
+            raise ValueError(f"{name} got {v!r}")
+        return f
+
+    delta = number(delta, "delta must be a non-negative number,", lambda f: f >= 0.0)
+    pseudocount = number(pseudocount, "pseudocount must be a non-negative number,", lambda f: f >= 0.0)
+    fdr_target = number(fdr_target, "fdr_target must lie in [0, 1],", lambda f: 0.0 <= f <= 1.0)
+    if max_cells is not None and (isinstance(max_cells, bool) or not isinstance(max_cells, (int, np.integer)) or int(max_cells) < 1):
+        raise ValueError(f"max_cells must be None or a positive integer, got {max_cells!r}")
+    return int(n_pairs), delta, pseudocount, fdr_target, (None if max_cells is None else int(max_cells))
+
+
+def de_populations(group_indices, idx1, idx2=None, group: int = 0):
+    """The two populations of differential_expression as POSITIONS within ``group_indices`` (= ``group_indices_list[group]``, adata row
+    numbers; position i is row i of what the read-out methods return for the group).  ``idx1`` / ``idx2``: adata row numbers;
+    ``idx2=None`` takes every cell of ``group_indices`` that is not in ``idx1``.  ValueError for a cell that is not in
+    ``group_indices`` (naming it), a cell listed twice, overlapping populations and an empty population."""
+    gi = np.asarray(group_indices).astype(np.int64).ravel()
+    where = {}
+    for i, c in enumerate(gi.tolist()):
+        where.setdefault(c, i)
+
+    def resolve(idx, name):
+        arr = np.asarray(idx)
+        if arr.dtype == bool or (arr.size and not np.issubdtype(arr.dtype, np.integer)):
+            raise ValueError(f"{name} must hold adata row numbers (integers), got dtype {arr.dtype}")
+        arr = arr.astype(np.int64).ravel()
+        if arr.size == 0:
+            raise ValueError(f"{name} is empty: a population needs at least one cell")
+        for c in arr.tolist():
+            if c not in where:
+                raise ValueError(f"{name}: cell {c} is not in group_indices_list[{group}]")
+        if len(set(arr.tolist())) != arr.size:
+            u, k = np.unique(arr, return_counts=True)
+            raise ValueError(f"{name}: cell {int(u[k > 1][0])} is listed more than once")
+        return np.array([where[c] for c in arr.tolist()], dtype=np.int64)
+
+    p1 = resolve(idx1, "idx1")
+    if idx2 is None:
+        rest = np.ones(len(gi), bool)
+        rest[p1] = False
+        rest &= np.array([where[c] == i for i, c in enumerate(gi.tolist())], dtype=bool)   # a repeated cell counts once
+        p2 = np.nonzero(rest)[0].astype(np.int64)
+        if p2.size == 0:
+            raise ValueError(f"idx2=None leaves no cell: idx1 covers all of group_indices_list[{group}]")
+        return p1, p2
+    p2 = resolve(idx2, "idx2")
+    both = np.intersect1d(p1, p2)
+    if both.size:
+        raise ValueError(f"idx1 and idx2 overlap: cell {int(gi[both[0]])} is in both populations")
+    return p1, p2
+
+
+def de_subsample(pos: np.ndarray, max_cells: Optional[int], seed: int) -> np.ndarray:
+    """At most ``max_cells`` of a population's positions, drawn without replacement from ``default_rng(seed)``, in their original order"""
+    if max_cells is None or len(pos) <= max_cells:
+        return pos
+    keep = np.sort(np.random.default_rng(seed).choice(len(pos), size=max_cells, replace=False))
+    return pos[keep]
+
+
+def de_pair_rows(rows_1: int, rows_2: int, n_pairs: int, seed: int = 0):
+    """``n_pairs`` pairs of bank rows drawn with replacement: (r1 in [0, rows_1), r2 in [0, rows_2)) as int32 arrays, from ONE
+    ``np.random.default_rng(seed)`` (r1 first, then r2)"""
+    if min(int(rows_1), int(rows_2)) < 1:
+        raise ValueError(f"both banks need at least one row, got {rows_1} and {rows_2}")
+    if isinstance(n_pairs, bool) or not isinstance(n_pairs, (int, np.integer)) or not 1 <= int(n_pairs) <= DE_MAX_PAIRS:
+        raise ValueError(f"n_pairs must be an integer between 1 and 2^24, got {n_pairs!r}")
+    rng = np.random.default_rng(seed)
+    r1 = rng.integers(0, int(rows_1), int(n_pairs)).astype(np.int32)
+    r2 = rng.integers(0, int(rows_2), int(n_pairs)).astype(np.int32)
+    return r1, r2
+
+
+def de_table(stats, n_pairs: int, fdr_target: float = 0.05) -> dict:
+    """The result table of differential_expression from the kernel's per-gene statistics (``stats``: mapping with "lfc_mean",
+    "lfc_std", "lfc_min", "lfc_max", "count_de", "scale1", "scale2" -> arrays [n_genes]), column name -> numpy array, in column order:
+    proba_de = count_de / n_pairs, proba_not_de = 1 - proba_de, bayes_factor = log(proba_de + 1e-8) - log(proba_not_de + 1e-8), the
+    scales and lfc statistics as given, and ``is_de_fdr_<fdr_target>``: the largest set of genes, taken in order of decreasing
+    proba_de (equal values in the order of the genes), whose mean proba_not_de -- the posterior expected false discovery rate -- is
+    <= fdr_target (scvi-tools 0.20 ``differential_expression``, mode "change")."""
+    count = np.asarray(stats["count_de"], dtype=np.float64)
+    proba_de = count / float(n_pairs)
+    proba_not = 1.0 - proba_de
+    out = {"proba_de": proba_de, "proba_not_de": proba_not, "bayes_factor": np.log(proba_de + 1e-8) - np.log(proba_not + 1e-8)}
+    for k in DE_COLUMNS[3:]:
+        out[k] = np.asarray(stats[k])
+    order = np.argsort(-proba_de, kind="stable")
+    fdr = np.cumsum(proba_not[order]) / (1.0 + np.arange(len(order)))
+    ok = np.nonzero(fdr <= fdr_target)[0]
+    is_de = np.zeros(len(order), bool)
+    if ok.size:
+        is_de[order[: ok[-1] + 1]] = True
+    out[f"is_de_fdr_{fdr_target}"] = is_de
+    return out

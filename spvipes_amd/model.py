@@ -20,8 +20,9 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, check_expression_args, csr_group_arrays, csr_to_dense, format_latent_results, group_var_names, is_sparse,
-                   latent_loader_mode, latent_steps, resolve_gene_list, to_group_counts, to_sparse_group_counts)
+from .data import (MinibatchSampler, check_de_args, check_expression_args, csr_group_arrays, csr_to_dense, de_pair_rows, de_populations,
+                   de_subsample, de_table, format_latent_results, group_var_names, is_sparse, latent_loader_mode, latent_steps, resolve_gene_list,
+                   to_group_counts, to_sparse_group_counts)
 from .module import spVIPESmodule
 from .train import Trainer, default_max_epochs
 
@@ -275,6 +276,89 @@ class spVIPES:
                 blocks[g].append(blk[g].cpu().numpy() if return_numpy else blk[g])
         cat = np.concatenate if return_numpy else torch.cat
         return {g: cat(blocks[g])[:n[g]] for g in range(2)}
+
+    @torch.no_grad()
+    def differential_expression(self, group_indices_list: List[List[int]], group: int, idx1, idx2=None, gene_list=None, component: str = "mixture",
+                                library_size=1.0, n_samples: int = 1, use_mean: bool = False, n_pairs: int = 10_000, delta: float = 0.25,
+                                pseudocount: float = 0.0, fdr_target: float = 0.05, max_cells: Optional[int] = None, seed: int = 0,
+                                batch_size: Optional[int] = None, _noise=None, _pair_rows=None):
+        """Which genes differ between two sets of cells of ONE group (scvi-tools 0.20 ``differential_expression``, mode "change"):
+        a pandas DataFrame, one row per selected gene in selection order, indexed by the genes' names as ``get_loadings`` labels
+        them (their positions when the AnnData has none), with the columns
+
+            proba_de       the share of pairs with |lfc| >= ``delta``,  lfc = log2(x1 + pseudocount) - log2(x2 + pseudocount)
+            proba_not_de   1 - proba_de           bayes_factor   log(proba_de + 1e-8) - log(proba_not_de + 1e-8)
+            scale1, scale2 the mean decoded expression of the two populations over the pairs
+            lfc_mean, lfc_std (population form), lfc_min, lfc_max
+            is_de_fdr_<fdr_target>   the largest set of genes, by decreasing proba_de, whose mean proba_not_de is <= fdr_target
+
+        ``lfc_median`` is left out on purpose: it needs a per-gene selection over the pairs, not a streaming reduction.
+        ``idx1`` / ``idx2``: adata row numbers of cells of ``group_indices_list[group]``; ``idx2=None`` = every other cell of it.  A cell
+        outside it, overlapping or empty populations are ValueErrors.  ``gene_list``: None | positions | names of THIS group's genes.
+        How it is computed: the minibatches are walked exactly as ``get_normalized_expression`` walks them (a cell's latents depend on its
+        minibatch partners, so a cell's decoded row IS the row that method returns for it; steps without a population cell are
+        skipped), each of ``n_samples`` draws is decoded with ``component`` / ``library_size`` (1.0: normalised scales, what scvi-tools
+        compares) into a device-resident fp32 bank per population, ``n_pairs`` pairs of bank rows are drawn with replacement from
+        ``default_rng(seed)``, and ONE fused HIP kernel (spv_de_pairs) compares and reduces them: only the per-gene table leaves the
+        device.  Bank memory is (n_1 + n_2) * n_samples * n_sel * 4 bytes; ``max_cells`` caps each population by a seeded subsample
+        before the walk.  ``use_mean=True`` (needs ``n_samples == 1``) compares decoded posterior means and is deterministic.
+        ``_noise`` (tests only): as in ``get_normalized_expression``; ``_pair_rows`` (tests only): (r1, r2) bank rows instead of drawn ones."""
+        import pandas as pd
+
+        from .de_ops import de_pairs
+
+        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
+        n_pairs, delta, pseudocount, fdr_target, max_cells = check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells)
+        if group not in (0, 1):
+            raise ValueError(f"group must be 0 or 1, got {group!r}")
+        g = int(group)
+        gl = [None, None]
+        gl[g] = gene_list
+        sel = resolve_gene_list(None if gene_list is None else gl, [int(self.module.input_dims[k]) for k in range(2)], group_var_names(self.adata))[g]
+        dev_sel = None if sel is None else torch.as_tensor(sel, dtype=torch.int32, device=self.device)
+        n_sel = int(self.module.input_dims[g]) if sel is None else len(sel)
+        n_g = len(group_indices_list[g])
+        pops = de_populations(group_indices_list[g], idx1, idx2, group=g)
+        pops = [de_subsample(p, max_cells, seed + 1 + k) for k, p in enumerate(pops)]
+        slot, banks = [], []
+        for p in pops:   # position within group_indices_list[g] -> the cell's place in its population (-1: not in it)
+            s = np.full(n_g, -1, dtype=np.int64)
+            s[p] = np.arange(len(p))
+            slot.append(s)
+            banks.append(torch.empty((len(p) * n_samples, n_sel), dtype=torch.float32, device=self.device))
+        off, blk = 0, None
+        for step, tensors, (B0, B1) in self._eval_minibatches(group_indices_list, batch_size, None):
+            Bg = (B0, B1)[g]
+            cpos = off + np.arange(Bg)   # the rows this step contributes to the group's concatenated read-out, which is cut at n_g
+            off += Bg
+            keep = cpos < n_g
+            moves = []
+            for k in range(2):
+                sl = np.full(Bg, -1, dtype=np.int64)
+                sl[keep] = slot[k][cpos[keep]]
+                src = np.nonzero(sl >= 0)[0]
+                if src.size:
+                    moves.append((k, torch.as_tensor(src, device=self.device), torch.as_tensor(sl[src], device=self.device)))
+            if not moves:
+                continue   # eval mode: steps are independent of each other
+            for smp in range(n_samples):
+                out = self._infer(tensors, _noise, step * n_samples + smp, B0, B1)
+                if blk is None or blk.shape[0] < Bg:
+                    blk = torch.empty((Bg, n_sel), dtype=torch.float32, device=self.device)
+                rows = self.module.expected_expression(out, g, genes=dev_sel, what=component, library_size=library_size, use_mean=use_mean, out=blk)
+                for k, src, dst in moves:
+                    banks[k].index_copy_(0, dst + smp * len(pops[k]), rows.index_select(0, src))
+        if _pair_rows is None:
+            r1, r2 = de_pair_rows(banks[0].shape[0], banks[1].shape[0], n_pairs, seed)
+        else:
+            r1, r2 = (np.asarray(r).astype(np.int32) for r in _pair_rows)
+            n_pairs = len(r1)
+        stats = de_pairs(banks[0], banks[1], torch.as_tensor(r1, device=self.device), torch.as_tensor(r2, device=self.device),
+                         delta=delta, eps=pseudocount)
+        table = de_table({k: v.cpu().numpy() for k, v in stats.items()}, n_pairs, fdr_target)
+        names = group_var_names(self.adata)[g]
+        index = (np.arange(n_sel) if sel is None else np.asarray(sel)) if names is None else (np.asarray(names) if sel is None else np.asarray(names)[sel])
+        return pd.DataFrame(table, index=index)
 
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}
