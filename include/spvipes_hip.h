@@ -377,6 +377,29 @@ int spv_de_pairs(const spv_de_pairs_args* a, void* stream);
 /* the number of pair splits S spv_de_pairs uses for this shape (0 for a non-positive argument) */
 int32_t spv_de_pairs_splits(int32_t n_genes, int32_t n_pairs);
 
+/* The exact per-gene median of the same lfc_m over the same pairs (the column "lfc_median" of the user API): with the n_pairs fp32
+ * values lfc_m of gene j sorted ascending, mid[0][j] = the value of rank (n_pairs - 1) / 2 and mid[1][j] = the value of rank
+ * n_pairs / 2 (0-based, integer division: numpy's two middle elements, equal for odd n_pairs; the median is their mean).  Banks,
+ * row arrays, clamping of row numbers, eps and 1 <= n_pairs <= 2^24 as for spv_de_pairs; every lfc_m is formed by the same fp32
+ * operations, so the outputs are ELEMENTS of the multiset spv_de_pairs reduces (min <= mid[0] <= mid[1] <= max), not an
+ * interpolation or a histogram estimate.  -0.0 and +0.0 count as equal (either may be returned); NaN in a bank is outside the
+ * contract.  How: a radix select on the order-preserving uint32 image of the values, 8 bits per pass -- four passes that gather
+ * the rows again and count, per gene, the keys under the prefix found so far (uint32 counters throughout), each followed by a
+ * small per-gene bin pick; the upper middle value rides along (no pass of its own).  Nothing of size n_pairs x n_genes is stored.
+ * Integer atomics only: two calls agree bit for bit.  ws: caller's scratch of at least spv_de_median_ws_bytes(n_genes, n_pairs)
+ * bytes = (256 + 5) * n_genes * 4 (4-byte aligned), overwritten.  Columns >= n_genes of `mid` are never written, bank columns
+ * >= n_genes never read.  Nothing is allocated; nine launches on `stream`. */
+typedef struct spv_de_median_args {
+  const float* bank1; const float* bank2; int64_t ld1, ld2;
+  const int32_t* rows1; const int32_t* rows2; int32_t n_rows1, n_rows2;
+  int32_t n_genes, n_pairs; float eps;
+  float* mid; int64_t ld_mid;
+  void* ws; int64_t ws_bytes;
+} spv_de_median_args;
+int spv_de_median(const spv_de_median_args* a, void* stream);
+/* the workspace spv_de_median needs for this shape, in bytes (0 for a non-positive argument) */
+int64_t spv_de_median_ws_bytes(int32_t n_genes, int32_t n_pairs);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

@@ -226,6 +226,13 @@ class SpvDePairsArgs(C.Structure):
                 ("stats", C.c_void_p), ("ld_stats", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+class SpvDeMedianArgs(C.Structure):
+    """the arguments of spv_de_median (include/spvipes_hip.h: spv_de_median_args)"""
+    _fields_ = [("bank1", C.c_void_p), ("bank2", C.c_void_p), ("ld1", C.c_int64), ("ld2", C.c_int64), ("rows1", C.c_void_p), ("rows2", C.c_void_p),
+                ("n_rows1", C.c_int32), ("n_rows2", C.c_int32), ("n_genes", C.c_int32), ("n_pairs", C.c_int32), ("eps", C.c_float),
+                ("mid", C.c_void_p), ("ld_mid", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -287,6 +294,8 @@ _SIGNATURES = {
     "spv_dec_expected": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecExpectedArgs), C.c_void_p]),
     "spv_de_pairs": (C.c_int, [C.POINTER(SpvDePairsArgs), C.c_void_p]),
     "spv_de_pairs_splits": (C.c_int32, [C.c_int32, C.c_int32]),
+    "spv_de_median": (C.c_int, [C.POINTER(SpvDeMedianArgs), C.c_void_p]),
+    "spv_de_median_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

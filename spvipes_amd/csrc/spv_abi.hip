@@ -7,6 +7,7 @@
 #include "spv_decoder.h"
 #include "spv_dec_expected.h"
 #include "spv_de.h"
+#include "spv_de_median.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -860,6 +861,43 @@ extern "C" int spv_de_pairs(const spv_de_pairs_args* x, void* stream) {
   if (rc != SPV_OK) return rc;
   hipLaunchKernelGGL(de_finish_kernel, dim3(tiles), dim3(64 * DE_FIN_WAVES), 0, s, a);
   return launch_status("spv_de_pairs (final combine)");
+}
+
+extern "C" int64_t spv_de_median_ws_bytes(int32_t n_genes, int32_t n_pairs) {
+  if (n_genes <= 0 || n_pairs <= 0) return 0;
+  return dm_ws_words(n_genes) * (int64_t)sizeof(unsigned);
+}
+
+template <int PASS>
+static int de_median_pass(const DmArgs& a, int tiles, hipStream_t s) {
+  hipLaunchKernelGGL((de_median_pass_kernel<PASS>), dim3((tiles * a.splits + 7) & ~7), dim3(64 * DM_WAVES), 0, s, a);
+  int rc = launch_status("spv_de_median (gather pass)");
+  if (rc != SPV_OK) return rc;
+  hipLaunchKernelGGL(de_median_pick_kernel, dim3(tiles), dim3(256), 0, s, a, PASS);
+  return launch_status("spv_de_median (bin pick)");
+}
+
+extern "C" int spv_de_median(const spv_de_median_args* x, void* stream) {
+  if (!x) return fail(SPV_ERR_ARG, "spv_de_median: null arguments%s");
+  if (!x->bank1 || !x->bank2 || !x->rows1 || !x->rows2 || !x->mid || !x->ws) return fail(SPV_ERR_ARG, "spv_de_median: null pointer%s");
+  if (x->n_pairs <= 0 || x->n_pairs > (1 << 24)) return fail(SPV_ERR_ARG, "spv_de_median: n_pairs must lie in [1, 2^24]%s");
+  if (x->n_genes <= 0 || x->n_rows1 <= 0 || x->n_rows2 <= 0) return fail(SPV_ERR_ARG, "spv_de_median: n_genes and the banks' row counts must be positive%s");
+  if (x->ld1 < x->n_genes || x->ld2 < x->n_genes || x->ld_mid < x->n_genes) return fail(SPV_ERR_ARG, "spv_de_median: ld < n_genes%s");
+  if (!(x->eps >= 0.f)) return fail(SPV_ERR_ARG, "spv_de_median: eps must be a non-negative number%s");
+  if (x->ws_bytes < dm_ws_words(x->n_genes) * (int64_t)sizeof(unsigned) || (reinterpret_cast<uintptr_t>(x->ws) & 3))
+    return fail(SPV_ERR_ARG, "spv_de_median: the workspace must be 4-byte aligned and hold spv_de_median_ws_bytes() bytes%s");
+  const int tiles = (x->n_genes + 63) / 64;
+  const DmArgs a{x->bank1, x->bank2, (long)x->ld1, (long)x->ld2, x->rows1, x->rows2, x->n_rows1, x->n_rows2, x->n_genes, x->n_pairs,
+                 x->eps, x->mid, (long)x->ld_mid, (unsigned*)x->ws, dm_splits(x->n_genes, x->n_pairs)};
+  hipStream_t s = (hipStream_t)stream;
+  const long words = (long)DM_BINS * x->n_genes;
+  hipLaunchKernelGGL(de_median_zero_kernel, dim3((unsigned)((words + 1023) / 1024 < 2048 ? (words + 1023) / 1024 : 2048)), dim3(256), 0, s, a.ws, words);
+  int rc = launch_status("spv_de_median (clear)");
+  if (rc == SPV_OK) rc = de_median_pass<0>(a, tiles, s);
+  if (rc == SPV_OK) rc = de_median_pass<1>(a, tiles, s);
+  if (rc == SPV_OK) rc = de_median_pass<2>(a, tiles, s);
+  if (rc == SPV_OK) rc = de_median_pass<3>(a, tiles, s);
+  return rc;
 }
 
 extern "C" int spv_dec_dz(const spv_dec_params* q, const float* Tp, const float* Ts, float* dz_part, void* stream) {

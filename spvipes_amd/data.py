@@ -441,6 +441,56 @@ def de_subsample(pos: np.ndarray, max_cells: Optional[int], seed: int) -> np.nda
     return pos[keep]
 
 
+def de_label_populations(cell_labels, labels=None, max_cells: Optional[int] = None, seed: int = 0):
+    """The bookkeeping of differential_expression_by: every label of ``cell_labels`` (one label per cell of the group, position i =
+    row i of the group's read-out) against the rest.  -> (names, compared, kept, places):
+      names     the label set, ``np.unique(cell_labels)`` (sorted)
+      compared  the places k in ``names`` of the labels to compare, ascending: all of them, or those listed in ``labels``
+                (an unknown label is a KeyError)
+      kept      the positions of every cell that enters the bank, ascending: label k's cells capped by
+                ``de_subsample(positions, max_cells, seed + 1 + k)``, all labels together
+      places    per k in ``compared``: (p1, p2) -- where in ``kept`` the label's kept cells and the rest (the other labels' kept
+                cells) are, each in position order
+    Fewer than two distinct labels is a ValueError."""
+    lab = np.asarray(cell_labels).ravel()
+    if lab.size == 0:
+        raise ValueError("groupby: the group has no cells")
+    names, code = np.unique(lab, return_inverse=True)
+    if len(names) < 2:
+        raise ValueError(f"groupby: one label against the rest needs at least two distinct labels among the group's cells, got {names.tolist()!r}")
+    if labels is None:
+        compared = list(range(len(names)))
+    else:
+        where = {v: k for k, v in enumerate(names.tolist())}
+        wanted = np.asarray(labels).ravel().tolist()
+        for v in wanted:
+            if v not in where:
+                raise KeyError(f"labels: {v!r} is not among the labels {names.tolist()!r}")
+        compared = sorted({where[v] for v in wanted})
+        if not compared:
+            raise ValueError("labels is empty: name at least one label to compare")
+    per = [de_subsample(np.nonzero(code == k)[0].astype(np.int64), max_cells, seed + 1 + k) for k in range(len(names))]
+    kept = np.sort(np.concatenate(per))
+    own = np.full(lab.size, -1, dtype=np.int64)   # position -> the label whose kept cell it is
+    for k, p in enumerate(per):
+        own[p] = k
+    own = own[kept]
+    places = {k: (np.nonzero(own == k)[0].astype(np.int64), np.nonzero(own != k)[0].astype(np.int64)) for k in compared}
+    return names, compared, kept, places
+
+
+def de_bank_rows(index, place: np.ndarray, n_kept: int) -> np.ndarray:
+    """Pair rows of ONE population -> rows of the shared bank of differential_expression_by.  Index i of a population of n_pop
+    cells means draw i // n_pop, the population's (i % n_pop)-th cell in position order (the row numbering of
+    differential_expression's per-population banks); that cell sits at ``place[i % n_pop]`` among the ``n_kept`` kept cells, and
+    the bank's row is draw * n_kept + place.  int32."""
+    i, n_pop = np.asarray(index).astype(np.int64), len(place)
+    rows = (i // n_pop) * int(n_kept) + np.asarray(place)[i % n_pop]
+    if rows.size and int(rows.max()) > np.iinfo(np.int32).max:
+        raise ValueError("the bank has more rows than an int32 row number can address")
+    return rows.astype(np.int32)
+
+
 def de_pair_rows(rows_1: int, rows_2: int, n_pairs: int, seed: int = 0):
     """``n_pairs`` pairs of bank rows drawn with replacement: (r1 in [0, rows_1), r2 in [0, rows_2)) as int32 arrays, from ONE
     ``np.random.default_rng(seed)`` (r1 first, then r2)"""
@@ -460,13 +510,16 @@ def de_table(stats, n_pairs: int, fdr_target: float = 0.05) -> dict:
     proba_de = count_de / n_pairs, proba_not_de = 1 - proba_de, bayes_factor = log(proba_de + 1e-8) - log(proba_not_de + 1e-8), the
     scales and lfc statistics as given, and ``is_de_fdr_<fdr_target>``: the largest set of genes, taken in order of decreasing
     proba_de (equal values in the order of the genes), whose mean proba_not_de -- the posterior expected false discovery rate -- is
-    <= fdr_target (scvi-tools 0.20 ``differential_expression``, mode "change")."""
+    <= fdr_target (scvi-tools 0.20 ``differential_expression``, mode "change").  A ``stats`` that also carries "lfc_median" puts that
+    column directly after ``lfc_mean`` (scvi's order); without the key the table is the one above."""
     count = np.asarray(stats["count_de"], dtype=np.float64)
     proba_de = count / float(n_pairs)
     proba_not = 1.0 - proba_de
     out = {"proba_de": proba_de, "proba_not_de": proba_not, "bayes_factor": np.log(proba_de + 1e-8) - np.log(proba_not + 1e-8)}
     for k in DE_COLUMNS[3:]:
         out[k] = np.asarray(stats[k])
+        if k == "lfc_mean" and "lfc_median" in stats:
+            out["lfc_median"] = np.asarray(stats["lfc_median"])
     order = np.argsort(-proba_de, kind="stable")
     fdr = np.cumsum(proba_not[order]) / (1.0 + np.arange(len(order)))
     ok = np.nonzero(fdr <= fdr_target)[0]

@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, check_de_args, check_expression_args, csr_group_arrays, csr_to_dense, de_pair_rows, de_populations,
-                   de_subsample, de_table, format_latent_results, group_var_names, is_sparse, latent_loader_mode, latent_steps, resolve_gene_list,
+from .data import (MinibatchSampler, check_de_args, check_expression_args, csr_group_arrays, csr_to_dense, de_bank_rows, de_label_populations,
+                   de_pair_rows, de_populations, de_subsample, de_table, format_latent_results, group_var_names, is_sparse, latent_loader_mode, latent_steps, resolve_gene_list,
                    to_group_counts, to_sparse_group_counts)
 from .module import spVIPESmodule
 from .train import Trainer, default_max_epochs
@@ -292,7 +292,8 @@ class spVIPES:
             lfc_mean, lfc_std (population form), lfc_min, lfc_max
             is_de_fdr_<fdr_target>   the largest set of genes, by decreasing proba_de, whose mean proba_not_de is <= fdr_target
 
-        ``lfc_median`` is left out on purpose: it needs a per-gene selection over the pairs, not a streaming reduction.
+        ``lfc_median`` is not a column of this table: it needs a per-gene selection over the pairs, not a streaming reduction, and so
+        a kernel of its own; ``differential_expression_median`` is this method with that column.
         ``idx1`` / ``idx2``: adata row numbers of cells of ``group_indices_list[group]``; ``idx2=None`` = every other cell of it.  A cell
         outside it, overlapping or empty populations are ValueErrors.  ``gene_list``: None | positions | names of THIS group's genes.
         How it is computed: the minibatches are walked exactly as ``get_normalized_expression`` walks them (a cell's latents depend on its
@@ -303,23 +304,38 @@ class spVIPES:
         device.  Bank memory is (n_1 + n_2) * n_samples * n_sel * 4 bytes; ``max_cells`` caps each population by a seeded subsample
         before the walk.  ``use_mean=True`` (needs ``n_samples == 1``) compares decoded posterior means and is deterministic.
         ``_noise`` (tests only): as in ``get_normalized_expression``; ``_pair_rows`` (tests only): (r1, r2) bank rows instead of drawn ones."""
-        import pandas as pd
+        return self._differential_expression(group_indices_list, group, idx1, idx2, gene_list, component, library_size, n_samples, use_mean, n_pairs,
+                                             delta, pseudocount, fdr_target, max_cells, seed, batch_size, _noise, _pair_rows, lfc_median=False)
 
-        from .de_ops import de_pairs
+    @torch.no_grad()
+    def differential_expression_median(self, group_indices_list: List[List[int]], group: int, idx1, idx2=None, gene_list=None, component: str = "mixture",
+                                       library_size=1.0, n_samples: int = 1, use_mean: bool = False, n_pairs: int = 10_000, delta: float = 0.25,
+                                       pseudocount: float = 0.0, fdr_target: float = 0.05, max_cells: Optional[int] = None, seed: int = 0,
+                                       batch_size: Optional[int] = None, lfc_median: bool = True, _noise=None, _pair_rows=None):
+        """``differential_expression`` (same arguments, same banks, same pairs, every column of its table bit for bit) with scvi-tools'
+        column ``lfc_median`` directly after ``lfc_mean``: the exact median of the pairs' fp32 lfc values, 0.5 * (mid_lo + mid_hi) of
+        the two middle order statistics in float64.  They come from a second HIP kernel (spv_de_median, a radix select in four gather
+        passes) on the banks the first one read; ``lfc_min <= lfc_median <= lfc_max`` holds exactly.  ``lfc_median=False`` launches
+        nothing more and returns ``differential_expression``'s frame."""
+        return self._differential_expression(group_indices_list, group, idx1, idx2, gene_list, component, library_size, n_samples, use_mean, n_pairs,
+                                             delta, pseudocount, fdr_target, max_cells, seed, batch_size, _noise, _pair_rows, lfc_median=bool(lfc_median))
 
-        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
-        n_pairs, delta, pseudocount, fdr_target, max_cells = check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells)
-        if group not in (0, 1):
-            raise ValueError(f"group must be 0 or 1, got {group!r}")
-        g = int(group)
+    def _de_genes(self, g: int, gene_list):
+        """-> (positions or None, their device copy or None, how many, the index of the result table) for a selection of group g's genes"""
         gl = [None, None]
         gl[g] = gene_list
         sel = resolve_gene_list(None if gene_list is None else gl, [int(self.module.input_dims[k]) for k in range(2)], group_var_names(self.adata))[g]
         dev_sel = None if sel is None else torch.as_tensor(sel, dtype=torch.int32, device=self.device)
         n_sel = int(self.module.input_dims[g]) if sel is None else len(sel)
+        names = group_var_names(self.adata)[g]
+        index = (np.arange(n_sel) if sel is None else np.asarray(sel)) if names is None else (np.asarray(names) if sel is None else np.asarray(names)[sel])
+        return sel, dev_sel, n_sel, index
+
+    def _de_banks(self, group_indices_list, g: int, pops, dev_sel, n_sel: int, component, library_size, n_samples: int, use_mean: bool, batch_size, _noise):
+        """One device-resident fp32 bank [len(p) * n_samples, n_sel] per population p of ``pops`` (positions within
+        ``group_indices_list[g]``): row draw * len(p) + i holds draw ``draw`` of the decoded expression of the population's i-th cell.
+        ONE walk of the eval minibatches fills them all; steps without a population cell are skipped."""
         n_g = len(group_indices_list[g])
-        pops = de_populations(group_indices_list[g], idx1, idx2, group=g)
-        pops = [de_subsample(p, max_cells, seed + 1 + k) for k, p in enumerate(pops)]
         slot, banks = [], []
         for p in pops:   # position within group_indices_list[g] -> the cell's place in its population (-1: not in it)
             s = np.full(n_g, -1, dtype=np.int64)
@@ -333,7 +349,7 @@ class spVIPES:
             off += Bg
             keep = cpos < n_g
             moves = []
-            for k in range(2):
+            for k in range(len(pops)):
                 sl = np.full(Bg, -1, dtype=np.int64)
                 sl[keep] = slot[k][cpos[keep]]
                 src = np.nonzero(sl >= 0)[0]
@@ -348,17 +364,89 @@ class spVIPES:
                 rows = self.module.expected_expression(out, g, genes=dev_sel, what=component, library_size=library_size, use_mean=use_mean, out=blk)
                 for k, src, dst in moves:
                     banks[k].index_copy_(0, dst + smp * len(pops[k]), rows.index_select(0, src))
+        return banks
+
+    def _de_compare(self, bank1, bank2, r1, r2, delta: float, pseudocount: float, fdr_target: float, lfc_median: bool) -> dict:
+        """The result table (column -> array) of one comparison: spv_de_pairs, and spv_de_median when asked, on the same banks and pair rows"""
+        from .de_ops import de_median, de_pairs
+
+        t1, t2 = torch.as_tensor(r1, device=self.device), torch.as_tensor(r2, device=self.device)
+        stats = {k: v.cpu().numpy() for k, v in de_pairs(bank1, bank2, t1, t2, delta=delta, eps=pseudocount).items()}
+        if lfc_median:
+            mid = de_median(bank1, bank2, t1, t2, eps=pseudocount)
+            stats["lfc_median"] = 0.5 * (mid["mid_lo"].cpu().numpy().astype(np.float64) + mid["mid_hi"].cpu().numpy().astype(np.float64))
+        return de_table(stats, len(r1), fdr_target)
+
+    def _differential_expression(self, group_indices_list, group, idx1, idx2, gene_list, component, library_size, n_samples, use_mean, n_pairs, delta,
+                                 pseudocount, fdr_target, max_cells, seed, batch_size, _noise, _pair_rows, lfc_median: bool):
+        import pandas as pd
+
+        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
+        n_pairs, delta, pseudocount, fdr_target, max_cells = check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells)
+        if group not in (0, 1):
+            raise ValueError(f"group must be 0 or 1, got {group!r}")
+        g = int(group)
+        _sel, dev_sel, n_sel, index = self._de_genes(g, gene_list)
+        pops = de_populations(group_indices_list[g], idx1, idx2, group=g)
+        pops = [de_subsample(p, max_cells, seed + 1 + k) for k, p in enumerate(pops)]
+        banks = self._de_banks(group_indices_list, g, pops, dev_sel, n_sel, component, library_size, n_samples, use_mean, batch_size, _noise)
         if _pair_rows is None:
             r1, r2 = de_pair_rows(banks[0].shape[0], banks[1].shape[0], n_pairs, seed)
         else:
             r1, r2 = (np.asarray(r).astype(np.int32) for r in _pair_rows)
-            n_pairs = len(r1)
-        stats = de_pairs(banks[0], banks[1], torch.as_tensor(r1, device=self.device), torch.as_tensor(r2, device=self.device),
-                         delta=delta, eps=pseudocount)
-        table = de_table({k: v.cpu().numpy() for k, v in stats.items()}, n_pairs, fdr_target)
-        names = group_var_names(self.adata)[g]
-        index = (np.arange(n_sel) if sel is None else np.asarray(sel)) if names is None else (np.asarray(names) if sel is None else np.asarray(names)[sel])
-        return pd.DataFrame(table, index=index)
+        return pd.DataFrame(self._de_compare(banks[0], banks[1], r1, r2, delta, pseudocount, fdr_target, lfc_median), index=index)
+
+    @torch.no_grad()
+    def differential_expression_by(self, group_indices_list: List[List[int]], group: int, groupby, labels=None, gene_list=None, component: str = "mixture",
+                                   library_size=1.0, n_samples: int = 1, use_mean: bool = False, n_pairs: int = 10_000, delta: float = 0.25,
+                                   pseudocount: float = 0.0, fdr_target: float = 0.05, max_cells: Optional[int] = None, seed: int = 0,
+                                   batch_size: Optional[int] = None, lfc_median: bool = True, _noise=None):
+        """One label against the rest, for every label of a column (scvi-tools' ``differential_expression(groupby=...)``): the
+        tables of ``differential_expression_median`` for label k's cells against every other cell of ``group_indices_list[group]``,
+        concatenated in label order, with the columns ``comparison`` ("<label> vs Rest"), ``group1`` (the label) and ``group2``
+        ("Rest") appended; the index repeats the gene names once per label, ``is_de_fdr_*`` is computed per comparison.
+
+        ``groupby``: the name of an ``adata.obs`` column, or an array with one label per cell of ``group_indices_list[group]``.  The
+        label set is ``np.unique`` of those labels (sorted); ``labels`` restricts which of them are compared (KeyError for an unknown
+        one); fewer than two distinct labels is a ValueError.  ``max_cells`` caps EACH label's cells (``de_subsample`` with seed
+        ``seed + 1 + k``, k = the label's place in the sorted set); "rest" is the other labels' kept cells.  Label k's pairs are
+        ``de_pair_rows(n_label * n_samples, n_rest * n_samples, n_pairs, seed + k)``.
+        How it is computed: the eval minibatches are walked ONCE and every kept cell is decoded ONCE per draw into one device bank
+        (row = draw * n_kept + the cell's place among the kept cells in position order); every comparison then runs the two kernels
+        with that bank on both sides and its own pair rows.  With ``max_cells=None`` label k's block equals
+        ``differential_expression_median(group_indices_list, group, idx1=<the label's cells in position order>, idx2=None,
+        seed=seed + k, ...)`` bit for bit, which decodes the whole group again for every label.  The other arguments are
+        ``differential_expression``'s."""
+        import pandas as pd
+
+        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
+        n_pairs, delta, pseudocount, fdr_target, max_cells = check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells)
+        if group not in (0, 1):
+            raise ValueError(f"group must be 0 or 1, got {group!r}")
+        g = int(group)
+        cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
+        if isinstance(groupby, str):
+            if groupby not in self.adata.obs:
+                raise KeyError(f"groupby: adata.obs has no column {groupby!r}")
+            cell_labels = np.asarray(self.adata.obs[groupby])[cells]
+        else:
+            cell_labels = np.asarray(groupby).ravel()
+            if cell_labels.shape[0] != len(cells):
+                raise ValueError(f"groupby: an array must hold one label per cell of group_indices_list[{g}] ({len(cells)}), got {cell_labels.shape[0]}")
+        if len(np.unique(cells)) != len(cells):
+            raise ValueError(f"group_indices_list[{g}] lists a cell more than once")
+        names, compared, kept, places = de_label_populations(cell_labels, labels, max_cells, seed)
+        _sel, dev_sel, n_sel, index = self._de_genes(g, gene_list)
+        bank, = self._de_banks(group_indices_list, g, [kept], dev_sel, n_sel, component, library_size, n_samples, use_mean, batch_size, _noise)
+        frames = []
+        for k in compared:
+            p1, p2 = places[k]
+            r1, r2 = de_pair_rows(len(p1) * n_samples, len(p2) * n_samples, n_pairs, seed + k)
+            table = self._de_compare(bank, bank, de_bank_rows(r1, p1, len(kept)), de_bank_rows(r2, p2, len(kept)), delta, pseudocount, fdr_target, bool(lfc_median))
+            df = pd.DataFrame(table, index=index)
+            df["comparison"], df["group1"], df["group2"] = f"{names[k]} vs Rest", names[k], "Rest"
+            frames.append(df)
+        return pd.concat(frames)
 
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}
