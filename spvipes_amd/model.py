@@ -200,19 +200,28 @@ class spVIPES:
     def get_latent_representation(self, group_indices_list: List[List[int]], adata=None, indices=None, normalized: bool = False,
                                   give_mean: bool = True, mc_samples: int = 5000, batch_size: Optional[int] = None,
                                   drop_last: Optional[bool] = None, _noise=None) -> dict:
-        """model/spvipes.py:424-650.  Returns the SAMPLED ``log_z`` (as the reference does) as
-        {"shared","private","shared_reordered","private_reordered"} -> {0: ndarray, 1: ndarray}.  ``_noise`` (tests only):
-        callable (step, B0, B1) -> dict of injected standard-normal draws for module.inference."""
-        if normalized:
-            raise NotImplementedError("normalized=True is broken in the reference (nothing is collected for the shared latents, :542-544)")
+        """model/spvipes.py:424-650.  {"shared","private","shared_reordered","private_reordered"} -> {0: ndarray, 1: ndarray}, one row
+        per cell of ``group_indices_list[g]``.
+
+        ``normalized=False``: the SAMPLED ``log_z`` (as the reference does).
+        ``normalized=True, give_mean=False``: the softmaxed embedding, each cell's topic proportions (:448-454) -- ``softmax`` of the
+          very ``log_z`` that ``normalized=False`` returns, i.e. the ``theta`` the inference kernels write next to it; same keys,
+          shapes and row order.
+        ``normalized=True, give_mean=True`` (the Monte-Carlo mean of the logistic-normal over ``mc_samples`` draws, :555-564) is not
+          built: NotImplementedError, raised before any device work.  ``mc_samples`` is otherwise unused.
+        ``_noise`` (tests only): callable (step, B0, B1) -> dict of injected standard-normal draws for module.inference."""
+        if normalized and give_mean:
+            raise NotImplementedError("normalized=True with give_mean=True (the Monte-Carlo mean of the logistic-normal) is not built; "
+                                      "give_mean=False returns softmax(log_z)")
         n1, n2 = (len(g) for g in group_indices_list)
         res = {k: [] for k in ("s0", "s1", "p0", "p1", "i1")}
+        private_key, shared_key = ("theta", "logtheta_theta") if normalized else ("log_z", "logtheta_log_z")
         for step, tensors, (B0, B1) in self._eval_minibatches(group_indices_list, batch_size, drop_last):
             out = self._infer(tensors, _noise, step, B0, B1)
-            res["s0"].append(out["poe_stats"][0]["logtheta_log_z"].cpu().numpy())
-            res["s1"].append(out["poe_stats"][1]["logtheta_log_z"].cpu().numpy())
-            res["p0"].append(out["private_stats"][0]["log_z"].cpu().numpy())
-            res["p1"].append(out["private_stats"][1]["log_z"].cpu().numpy())
+            res["s0"].append(out["poe_stats"][0][shared_key].cpu().numpy())
+            res["s1"].append(out["poe_stats"][1][shared_key].cpu().numpy())
+            res["p0"].append(out["private_stats"][0][private_key].cpu().numpy())
+            res["p1"].append(out["private_stats"][1][private_key].cpu().numpy())
             res["i1"].append(tensors[1]["indices"].cpu().numpy())
         return format_latent_results(res["p0"], res["p1"], res["s0"], res["s1"], res["i1"], n1, n2)
 
