@@ -509,6 +509,29 @@ int spv_linear_dgrad(const spv_linear_batch* a, void* stream);  /* dX (+)= mask(
  * elements (the batch is reduced in 16 slices, then summed in slice order)                          */
 int spv_linear_wgrad(const spv_linear_batch* a, float* wpart, int64_t wpart_elems, void* stream);
 
+/* A layer's input gradient (batch d: what spv_linear_dgrad computes) and weight gradient (batch w: spv_linear_wgrad) as ONE launch, the
+ * input-gradient workgroups first.  The two batches may list different problems (the mu / logvar heads: 8 weight-gradient problems,
+ * 4 input-gradient problems with W2 / n_w2); B, relu and drop_p must agree, accumulate belongs to d (w->accumulate must be 0).
+ * For B > 256 the launch leaves the 16 slice partials of w in wpart (>= nprob * 16 * Nmax * (Kmax + 1) elements, as for
+ * spv_linear_wgrad) and does NOT sum them: describe them with a spv_linear_pending record -- p[i] = w->p[i]'s (dW, db, N, K), nprob,
+ * wpart, prob_stride = 16 * Nmax * (Kmax + 1) -- and hand it to the NEXT spv_linear_bwd call on the same stream, whose launch sums them
+ * in slice order beside its own work, or to spv_linear_reduce_pending (the last reduction of a chain, or a reduction the next launch
+ * waits for).  For B <= 256 the weight gradients are complete after the launch (one slice: no partials, nothing pending).
+ * d or w may be NULL (then `pending` rides with one part only; with both NULL the call is spv_linear_reduce_pending).  wpart must not
+ * overlap the workspace named in `pending`.
+ * THE OUTPUTS OF ONE PART MUST NOT ALIAS THE INPUTS OF THE OTHER (d's dX against w's X / Y / dY, w's dW / db against d's W / W2), nor
+ * may the pending dW / db be read by d or w: the parts run concurrently in one grid.  Every result has the bits the separate
+ * spv_linear_dgrad / spv_linear_wgrad launches give. */
+typedef struct spv_linear_pending_prob { float* dW; float* db; int32_t N, K; } spv_linear_pending_prob;
+typedef struct spv_linear_pending {
+  spv_linear_pending_prob p[SPV_MAXP];
+  int32_t nprob;
+  const float* wpart; int64_t prob_stride;   /* problem i's partials: wpart + i * prob_stride, [16][N][K + 1] */
+} spv_linear_pending;
+int spv_linear_bwd(const spv_linear_batch* d, const spv_linear_batch* w, float* wpart, int64_t wpart_elems,
+                   const spv_linear_pending* pending, void* stream);
+int spv_linear_reduce_pending(const spv_linear_pending* pending, void* stream);
+
 typedef struct spv_bn_prob {
   const float* X; int64_t ldx;     /* [B][N], N <= 256                                              */
   float* Y; int64_t ldy;

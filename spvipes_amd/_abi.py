@@ -69,6 +69,8 @@ class SpvReduceBatch(C.Structure):
 SPV_MAXP = 8
 POE_LMAX = 1024  # label codes the pairing kernel accepts: integers in [0, POE_LMAX)
 BN_ROWS = 32  # rows per workgroup of the BatchNorm kernels (sizes their partial-sum workspace)
+WG_SLICES = 16  # batch slices of the small layers' weight-gradient kernel (sizes its partial workspace)
+WG_DIRECT_MAX_B = 256  # minibatches up to this size: one slice, no partials and no pending reduce (csrc/spv_small.h)
 
 
 class SpvLinearProb(C.Structure):
@@ -81,6 +83,14 @@ class SpvLinearProb(C.Structure):
 class SpvLinearBatch(C.Structure):
     _fields_ = [("p", SpvLinearProb * SPV_MAXP), ("nprob", C.c_int32), ("B", C.c_int32), ("relu", C.c_int32), ("drop_p", C.c_float),
                 ("seed", C.c_uint64), ("seed_ptr", C.c_void_p), ("accumulate", C.c_int32)]
+
+
+class SpvLinearPendingProb(C.Structure):
+    _fields_ = [("dW", C.c_void_p), ("db", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32)]
+
+
+class SpvLinearPending(C.Structure):
+    _fields_ = [("p", SpvLinearPendingProb * SPV_MAXP), ("nprob", C.c_int32), ("wpart", C.c_void_p), ("prob_stride", C.c_int64)]
 
 
 class SpvBnProb(C.Structure):
@@ -308,6 +318,8 @@ _SIGNATURES = {
     "spv_linear_fwd": (C.c_int, [C.POINTER(SpvLinearBatch), C.c_void_p]),
     "spv_linear_dgrad": (C.c_int, [C.POINTER(SpvLinearBatch), C.c_void_p]),
     "spv_linear_wgrad": (C.c_int, [C.POINTER(SpvLinearBatch), C.c_void_p, C.c_int64, C.c_void_p]),
+    "spv_linear_bwd": (C.c_int, [C.POINTER(SpvLinearBatch), C.POINTER(SpvLinearBatch), C.c_void_p, C.c_int64, C.POINTER(SpvLinearPending), C.c_void_p]),
+    "spv_linear_reduce_pending": (C.c_int, [C.POINTER(SpvLinearPending), C.c_void_p]),
     "spv_bn_fwd": (C.c_int, [C.POINTER(SpvBnBatch), C.c_void_p]),
     "spv_bn_bwd": (C.c_int, [C.POINTER(SpvBnBatch), C.c_void_p]),
     "spv_enc_sample_fwd": (C.c_int, [C.POINTER(SpvSampleBatch), C.c_void_p]),

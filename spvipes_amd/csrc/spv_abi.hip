@@ -1253,6 +1253,76 @@ extern "C" int spv_linear_wgrad(const spv_linear_batch* a, float* wpart, int64_t
   return launch_status("spv_linear_wgrad");
 }
 
+// checks a pending-reduce record; rgx = workgroups per problem of its reduction (linear_wgrad_reduce_kernel's grid x)
+static int check_pending(const spv_linear_pending* r, const char* who, int& rgx) {
+  if (r->nprob <= 0 || r->nprob > SPV_MAXP || !r->wpart) return fail(SPV_ERR_ARG, "%s: bad pending record", who);
+  int nmax = 0, kmax = 0;
+  for (int i = 0; i < r->nprob; ++i) {
+    const spv_linear_pending_prob& t = r->p[i];
+    if (t.N <= 0 || t.K <= 0 || !t.dW) return fail(SPV_ERR_ARG, "%s: bad pending problem", who);
+    nmax = t.N > nmax ? t.N : nmax; kmax = t.K > kmax ? t.K : kmax;
+  }
+  if (r->prob_stride < (int64_t)WG_SLICES * nmax * (kmax + 1)) return fail(SPV_ERR_ARG, "%s: pending problem stride too small", who);
+  rgx = (int)(((long)nmax * (kmax + 1) + 255) / 256);
+  return SPV_OK;
+}
+extern "C" int spv_linear_reduce_pending(const spv_linear_pending* pending, void* stream) {
+  if (!pending) return fail(SPV_ERR_ARG, "spv_linear_reduce_pending: null record%s");
+  int rgx = 0;
+  int rc = check_pending(pending, "spv_linear_reduce_pending", rgx);
+  if (rc) return rc;
+  hipLaunchKernelGGL(linear_pending_reduce_kernel, dim3(rgx, pending->nprob), dim3(256), 0, (hipStream_t)stream, *pending);
+  return launch_status("spv_linear_reduce_pending");
+}
+extern "C" int spv_linear_bwd(const spv_linear_batch* d, const spv_linear_batch* w, float* wpart, int64_t wpart_elems,
+                              const spv_linear_pending* pending, void* stream) {
+  if (!d && !w) {
+    if (!pending) return fail(SPV_ERR_ARG, "spv_linear_bwd: nothing to do%s");
+    return spv_linear_reduce_pending(pending, stream);
+  }
+  static const spv_linear_batch none = {};
+  LinearBwdGrid g = {};
+  long prob_stride = 0;
+  if (d) {   // spv_linear_dgrad's checks and grid
+    int rc = check_linear(d, "spv_linear_bwd");
+    if (rc) return rc;
+    for (int i = 0; i < d->nprob; ++i)
+      if (!d->p[i].dY || !d->p[i].dX || ((d->relu || d->drop_p > 0.f) && !d->p[i].Y)) return fail(SPV_ERR_ARG, "spv_linear_bwd: null pointer%s");
+    int nmax, kmax; linear_extents(d, nmax, kmax);
+    g.dgx = (d->B + 63) / 64; g.dgy = (kmax + 63) / 64;
+    g.nd = g.dgx * g.dgy * d->nprob;
+  }
+  if (w) {   // spv_linear_wgrad's
+    int rc = check_linear(w, "spv_linear_bwd");
+    if (rc) return rc;
+    for (int i = 0; i < w->nprob; ++i)
+      if (!w->p[i].dY || !w->p[i].X || !w->p[i].dW || ((w->relu || w->drop_p > 0.f) && !w->p[i].Y)) return fail(SPV_ERR_ARG, "spv_linear_bwd: null pointer%s");
+    if (w->accumulate) return fail(SPV_ERR_ARG, "spv_linear_bwd: accumulate belongs to the input-gradient batch%s");
+    if (!wpart) return fail(SPV_ERR_ARG, "spv_linear_bwd: workspace missing%s");
+    int nmax, kmax; linear_extents(w, nmax, kmax);
+    prob_stride = (long)WG_SLICES * nmax * (kmax + 1);
+    if (wpart_elems < prob_stride * w->nprob) return fail(SPV_ERR_ARG, "spv_linear_bwd: workspace too small%s");
+    g.wgx = (nmax + 31) / 32; g.wgy = (kmax + 31) / 32;
+    g.nw = g.wgx * g.wgy * w->nprob * (w->B <= WG_DIRECT_MAX_B ? 1 : WG_SLICES);
+  }
+  if (d && w && (d->B != w->B || (d->relu != 0) != (w->relu != 0) || d->drop_p != w->drop_p))
+    return fail(SPV_ERR_ARG, "spv_linear_bwd: the two batches disagree in B / relu / drop_p%s");
+  int nr = 0;
+  if (pending) {
+    int rc = check_pending(pending, "spv_linear_bwd", g.rgx);
+    if (rc) return rc;
+    if (w) {   // this launch's partials must not land in the workspace it sums
+      const float* pe = pending->wpart + pending->prob_stride * pending->nprob;
+      if (wpart < pe && pending->wpart < wpart + wpart_elems) return fail(SPV_ERR_ARG, "spv_linear_bwd: wpart overlaps the pending workspace%s");
+    }
+    nr = g.rgx * pending->nprob;
+  }
+  static const spv_linear_pending no_pending = {};
+  hipLaunchKernelGGL(linear_bwd_kernel, dim3((unsigned)(g.nd + g.nw + nr)), dim3(256), 0, (hipStream_t)stream, d ? *d : none, w ? *w : none,
+                     pending ? *pending : no_pending, g, wpart, prob_stride);
+  return launch_status("spv_linear_bwd");
+}
+
 static int check_bn(const spv_bn_batch* a, const char* who) {
   if (!a || a->nprob <= 0 || a->nprob > SPV_MAXP || a->B <= 0) return fail(SPV_ERR_ARG, "%s: bad batch", who);
   for (int i = 0; i < a->nprob; ++i) {

@@ -144,11 +144,13 @@ __device__ __forceinline__ void apply_mask8(const LinearBatch& a, float (&g)[8],
 }
 
 // dX (+)= mask(dY) W : rows = cells, columns = k, contraction over the N outputs of the layer
+// (prob, bx, by): the problem and the 64 x 64 tile of this workgroup -- linear_dgrad_kernel passes blockIdx.z / .x / .y, linear_bwd_kernel
+// decodes them from its 1-D grid
 template <bool VEC, bool MASKED>   // (compile-time for the same reason as load8's VEC: no load may sit in the arm of a run-time branch)
-__device__ __forceinline__ void linear_dgrad_body(const LinearBatch& a) {
-  const LinearProb& q = a.p[blockIdx.z];
+__device__ __forceinline__ void linear_dgrad_body(const LinearBatch& a, int prob, int bx, int by) {
+  const LinearProb& q = a.p[prob];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, r = lane & 31;
-  const int b0 = blockIdx.x * 64 + 32 * (wave >> 1), k0 = blockIdx.y * 64 + 32 * (wave & 1);
+  const int b0 = bx * 64 + 32 * (wave >> 1), k0 = by * 64 + 32 * (wave & 1);
   if (k0 >= q.K || b0 >= a.B) return;
   const int row = b0 + r, col = k0 + r;
   const float* gr = q.dY + (long)min(row, a.B - 1) * q.lddy;
@@ -193,8 +195,9 @@ __global__ __launch_bounds__(256) void linear_dgrad_kernel(LinearBatch a) {
   const LinearProb& q = a.p[blockIdx.z];
   const bool masked = a.relu || a.drop_p > 0.f;
   const bool vec = ((q.lddy & 3) == 0) && aligned16(q.dY) && ((q.N & 7) == 0) && (!masked || (((q.ldy & 3) == 0) && aligned16(q.Y)));
-  if (masked) { if (vec) linear_dgrad_body<true, true>(a); else linear_dgrad_body<false, true>(a); }
-  else { if (vec) linear_dgrad_body<true, false>(a); else linear_dgrad_body<false, false>(a); }
+  const int prob = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
+  if (masked) { if (vec) linear_dgrad_body<true, true>(a, prob, bx, by); else linear_dgrad_body<false, true>(a, prob, bx, by); }
+  else { if (vec) linear_dgrad_body<true, false>(a, prob, bx, by); else linear_dgrad_body<false, false>(a, prob, bx, by); }
 }
 
 // dW = mask(dY)^T X, db = colsum(mask(dY)): rows = n, columns = k, contraction over the batch.  The batch is cut into
@@ -205,14 +208,16 @@ constexpr int WG_SLICES = 16;
 // DIRECT (minibatches of at most WG_DIRECT_MAX_B rows): ONE slice per problem holds every row, and its workgroup writes dW / db itself --
 // no partials, no linear_wgrad_reduce_kernel launch (at 128 cells a launch is mostly fixed cost, and 14 of the 16 slices were empty)
 constexpr int WG_DIRECT_MAX_B = 256;
+// (prob, slice, bx, by): the problem, the batch slice and the 32 x 32 tile of this workgroup; s_acc / s_b: the calling kernel's LDS
+typedef float WgAcc[16][64];
+typedef float WgBias[32];
 template <bool MASKED, bool DIRECT>
-__device__ __forceinline__ void linear_wgrad_body(const LinearBatch& a, float* wpart, long prob_stride) {
+__device__ __forceinline__ void linear_wgrad_body(const LinearBatch& a, float* wpart, long prob_stride, int prob, int slice, int bx, int by,
+                                                  WgAcc* s_acc /*[3]*/, WgBias* s_b /*[3]*/) {
   constexpr int NSL = DIRECT ? 1 : WG_SLICES;
-  const int prob = blockIdx.z / NSL, slice = blockIdx.z % NSL;
   const LinearProb& q = a.p[prob];
-  const int n0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+  const int n0 = bx * 32, k0 = by * 32;
   if (n0 >= q.N || k0 >= q.K) return;  // block-uniform
-  __shared__ float s_acc[3][16][64], s_b[3][32];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, r = lane & 31;
   constexpr bool masked = MASKED;
   const int per = ((a.B + NSL * 64 - 1) / (NSL * 64)) * 64;   // rows per slice, a multiple of 64 (16 per wave and step)
@@ -257,7 +262,7 @@ __device__ __forceinline__ void linear_wgrad_body(const LinearBatch& a, float* w
       const int n = n0 + crow(i, h);
       if (n < q.N && k < q.K) q.dW[(long)n * q.K + k] = acc[i];
     }
-    if (blockIdx.y == 0 && h == 0 && n0 + r < q.N && q.db) q.db[n0 + r] = bsum;
+    if (by == 0 && h == 0 && n0 + r < q.N && q.db) q.db[n0 + r] = bsum;
     return;
   }
   // partial layout per problem: [slice][N][K + 1] (last column = bias partial)
@@ -267,30 +272,85 @@ __device__ __forceinline__ void linear_wgrad_body(const LinearBatch& a, float* w
     const int n = n0 + crow(i, h);
     if (n < q.N && k < q.K) base[(long)n * (q.K + 1) + k] = acc[i];
   }
-  if (blockIdx.y == 0 && h == 0 && n0 + r < q.N) base[(long)(n0 + r) * (q.K + 1) + q.K] = bsum;
+  if (by == 0 && h == 0 && n0 + r < q.N) base[(long)(n0 + r) * (q.K + 1) + q.K] = bsum;
 }
 __global__ __launch_bounds__(256) void linear_wgrad_kernel(LinearBatch a, float* wpart, long prob_stride) {
-  if (a.relu || a.drop_p > 0.f) linear_wgrad_body<true, false>(a, wpart, prob_stride);
-  else linear_wgrad_body<false, false>(a, wpart, prob_stride);
+  __shared__ float s_acc[3][16][64], s_b[3][32];
+  const int prob = blockIdx.z / WG_SLICES, slice = blockIdx.z % WG_SLICES, bx = blockIdx.x, by = blockIdx.y;
+  if (a.relu || a.drop_p > 0.f) linear_wgrad_body<true, false>(a, wpart, prob_stride, prob, slice, bx, by, s_acc, s_b);
+  else linear_wgrad_body<false, false>(a, wpart, prob_stride, prob, slice, bx, by, s_acc, s_b);
 }
 __global__ __launch_bounds__(256) void linear_wgrad_direct_kernel(LinearBatch a) {
-  if (a.relu || a.drop_p > 0.f) linear_wgrad_body<true, true>(a, nullptr, 0);
-  else linear_wgrad_body<false, true>(a, nullptr, 0);
+  __shared__ float s_acc[3][16][64], s_b[3][32];
+  const int prob = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
+  if (a.relu || a.drop_p > 0.f) linear_wgrad_body<true, true>(a, nullptr, 0, prob, 0, bx, by, s_acc, s_b);
+  else linear_wgrad_body<false, true>(a, nullptr, 0, prob, 0, bx, by, s_acc, s_b);
 }
 
-__global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(LinearBatch a, const float* wpart, long prob_stride) {
-  const LinearProb& q = a.p[blockIdx.y];
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long tot = (long)q.N * (q.K + 1);
+// dW / db of problem `prob` ([N][K], [N] or null) = its WG_SLICES partials added in slice order; workgroup bx takes elements 256 bx ..
+__device__ __forceinline__ void linear_wgrad_reduce_body(float* dW, float* db, int N, int K, const float* wpart, long prob_stride, int prob, int bx) {
+  const long i = (long)bx * 256 + threadIdx.x;
+  const long tot = (long)N * (K + 1);
   if (i >= tot) return;
-  const float* src = wpart + blockIdx.y * prob_stride + i;
+  const float* src = wpart + prob * prob_stride + i;
   float s = 0.f;
 #pragma unroll
   for (int k = 0; k < WG_SLICES; ++k) s += src[(long)k * tot];
-  const int n = (int)(i / (q.K + 1)), c = (int)(i % (q.K + 1));
-  if (c < q.K) q.dW[(long)n * q.K + c] = s;
-  else if (q.db) q.db[n] = s;
+  const int n = (int)(i / (K + 1)), c = (int)(i % (K + 1));
+  if (c < K) dW[(long)n * K + c] = s;
+  else if (db) db[n] = s;
 }
+__global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(LinearBatch a, const float* wpart, long prob_stride) {
+  const LinearProb& q = a.p[blockIdx.y];
+  linear_wgrad_reduce_body(q.dW, q.db, q.N, q.K, wpart, prob_stride, blockIdx.y, blockIdx.x);
+}
+
+// ---- a small layer's input and weight gradients as ONE launch ------------------------------------------------------------------------
+// Both read the same dY and neither reads what the other writes, so they need no order between them: a 1-D grid of three block ranges,
+//   [0, nd)            linear_dgrad_kernel's blocks of batch d (first: they are what the next layer of the backward chain waits for),
+//   [nd, nd + nw)      linear_wgrad_kernel's (B > WG_DIRECT_MAX_B: partials into wpart) or linear_wgrad_direct_kernel's blocks of batch w,
+//   [nd + nw, ...)     linear_wgrad_reduce_kernel's blocks for the partials of an EARLIER launch (complete by stream order),
+// each running the body of the kernel it stands for with that kernel's block coordinates: the results have the bits of the separate launches.
+typedef spv_linear_pending LinearPending;
+struct LinearBwdGrid { int nd, nw, dgx, dgy, wgx, wgy, rgx; };   // blocks of the first two ranges, and the x / y extents of the three decodes
+
+__global__ __launch_bounds__(256) void linear_pending_reduce_kernel(LinearPending pend) {
+  const spv_linear_pending_prob& t = pend.p[blockIdx.y];
+  linear_wgrad_reduce_body(t.dW, t.db, t.N, t.K, pend.wpart, pend.prob_stride, blockIdx.y, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void linear_bwd_kernel(LinearBatch d, LinearBatch w, LinearPending pend, LinearBwdGrid g, float* wpart, long prob_stride) {
+  __shared__ float s_acc[3][16][64], s_b[3][32];
+  int bid = blockIdx.x;   // (every test below is block-uniform)
+  if (bid < g.nd) {
+    const int bx = bid % g.dgx, by = (bid / g.dgx) % g.dgy, prob = bid / (g.dgx * g.dgy);
+    const LinearProb& q = d.p[prob];
+    const bool masked = d.relu || d.drop_p > 0.f;   // linear_dgrad_kernel's selection
+    const bool vec = ((q.lddy & 3) == 0) && aligned16(q.dY) && ((q.N & 7) == 0) && (!masked || (((q.ldy & 3) == 0) && aligned16(q.Y)));
+    if (masked) { if (vec) linear_dgrad_body<true, true>(d, prob, bx, by); else linear_dgrad_body<false, true>(d, prob, bx, by); }
+    else { if (vec) linear_dgrad_body<true, false>(d, prob, bx, by); else linear_dgrad_body<false, false>(d, prob, bx, by); }
+    return;
+  }
+  bid -= g.nd;
+  if (bid < g.nw) {
+    const int bx = bid % g.wgx, by = (bid / g.wgx) % g.wgy, z = bid / (g.wgx * g.wgy);
+    const bool masked = w.relu || w.drop_p > 0.f;
+    if (w.B <= WG_DIRECT_MAX_B) {
+      if (masked) linear_wgrad_body<true, true>(w, nullptr, 0, z, 0, bx, by, s_acc, s_b);
+      else linear_wgrad_body<false, true>(w, nullptr, 0, z, 0, bx, by, s_acc, s_b);
+    } else {
+      const int prob = z / WG_SLICES, slice = z % WG_SLICES;
+      if (masked) linear_wgrad_body<true, false>(w, wpart, prob_stride, prob, slice, bx, by, s_acc, s_b);
+      else linear_wgrad_body<false, false>(w, wpart, prob_stride, prob, slice, bx, by, s_acc, s_b);
+    }
+    return;
+  }
+  bid -= g.nw;
+  const int prob = bid / g.rgx;
+  const spv_linear_pending_prob& t = pend.p[prob];
+  linear_wgrad_reduce_body(t.dW, t.db, t.N, t.K, pend.wpart, pend.prob_stride, prob, bid % g.rgx);
+}
+static_assert(sizeof(LinearBatch) * 2 + sizeof(LinearPending) + sizeof(LinearBwdGrid) + 16 < 4096, "linear_bwd_kernel: kernel arguments must stay below 4096 bytes");
 
 // ---------------------------------------------------------------------------------------------
 // BatchNorm1d over the batch dimension, batched problems, N <= 256 columns

@@ -20,7 +20,7 @@ import torch
 from . import _abi
 from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
                    ptr, round_up, stream_ptr)
-from .nn_ops import _add_lin, _fptr, _lin_batch, _wgrad, grad_out
+from .nn_ops import _add_lin, _fptr, _lin_batch, _linear_bwd, _reduce_pending, _wgrad, grad_out
 from . import ops as _ops
 from .ops import N_HIDDEN_MIX, GroupCounts, Workspace, _bf16_image, _gemm_slabs, _gene_splits, _nb_cell_tiles, _nb_splits, _pack, fork, group_streams, join
 
@@ -684,8 +684,11 @@ class DecoderFused(torch.autograd.Function):
             for g in range(NG):
                 _add_lin(bw, N=n_m, K=nt, W=ptr(Wf[g]), X=ptr(zcat[g]), ldx=nt, Y=ptr(m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dW=ptr(dWf[g]), db=ptr(dcf[g]))
                 _add_lin(bd, N=n_m, K=nt, W=ptr(Wf[g]), Y=ptr(m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
-            _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
-            _wgrad(bw, ws if not isinstance(ws, (list, tuple)) else ws[0])
+            if _ops.LINEAR_BWD:   # one launch; spv_trunk_fold_bwd reads the summed d W', so the slice sum stays on the chain
+                _reduce_pending(_linear_bwd(bd, bw, ws if not isinstance(ws, (list, tuple)) else ws[0], "wgrad_part_trunk"))
+            else:
+                _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
+                _wgrad(bw, ws if not isinstance(ws, (list, tuple)) else ws[0])
             tb_ = SpvTrunkBatch()
             tb_.nprob, tb_.B, tb_.training, tb_.eps, tb_.momentum = NG, B, int(training), 1e-3, 0.01
             wa_c = [par[g][6] if par[g][6].is_contiguous() else par[g][6].contiguous() for g in range(NG)]
@@ -715,8 +718,11 @@ class DecoderFused(torch.autograd.Function):
             for g in range(NG):
                 _add_lin(bw, N=n_m, K=nt, W=ptr(par[g][6]), X=ptr(zcat[g]), ldx=nt, dY=ptr(d_pre[g]), lddy=n_m, dW=ptr(dWa[g]), db=ptr(dba[g]))
                 _add_lin(bd, N=n_m, K=nt, W=ptr(par[g][6]), dY=ptr(d_pre[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
-            _wgrad(bw, ws if not isinstance(ws, (list, tuple)) else ws[0])
-            _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
+            if _ops.LINEAR_BWD:
+                _reduce_pending(_linear_bwd(bd, bw, ws if not isinstance(ws, (list, tuple)) else ws[0], "wgrad_part_trunk"))
+            else:
+                _wgrad(bw, ws if not isinstance(ws, (list, tuple)) else ws[0])
+                _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
         # ---- BatchNorm-fold backward (+ the z statistics it used) ------------------------------------
         fb = ctx.fb   # (kslots set by the forward pass)
         d_priv, d_poe = [new(B, n_p) for _ in range(NG)], [new(B, n_s) for _ in range(NG)]

@@ -15,7 +15,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _abi
-from ._abi import SpvBnBatch, SpvLinearBatch, SpvSampleBatch, ptr, stream_ptr
+from ._abi import SpvBnBatch, SpvLinearBatch, SpvLinearPending, SpvSampleBatch, ptr, stream_ptr
 
 
 def _lin_batch(B: int, relu: bool = False, drop_p: float = 0.0, seed=0, accumulate: bool = False) -> SpvLinearBatch:
@@ -64,6 +64,34 @@ def _wgrad(b: SpvLinearBatch, ws) -> None:
     _abi.call("spv_linear_wgrad", C.byref(b), ptr(part), n, stream_ptr())
 
 
+def _linear_bwd(bd: Optional[SpvLinearBatch], bw: Optional[SpvLinearBatch], ws, key: str, pending: Optional[SpvLinearPending] = None) -> Optional[SpvLinearPending]:
+    """spv_linear_bwd: the input gradients of ``bd`` and the weight gradients of ``bw`` in one launch, which also sums the slice partials an
+    earlier call left behind (``pending``).  ``key``: the workspace name of THIS call's partials -- a chain of calls needs one name per link,
+    since a link's partials are read while the next link writes its own.  Returns the record of the partials this launch leaves (to be passed
+    to the next call or to ``_reduce_pending``), or None when the weight gradients are already complete (B <= WG_DIRECT_MAX_B, or no ``bw``)."""
+    part, n, rec = None, 0, None
+    if bw is not None:
+        nmax = max(bw.p[i].N for i in range(bw.nprob))
+        kmax = max(bw.p[i].K for i in range(bw.nprob))
+        stride = _abi.WG_SLICES * nmax * (kmax + 1)
+        n = bw.nprob * stride
+        part = ws.get(key, (n,), torch.float32)
+        if bw.B > _abi.WG_DIRECT_MAX_B:
+            rec = SpvLinearPending()
+            rec.nprob, rec.wpart, rec.prob_stride = bw.nprob, ptr(part), stride
+            for i in range(bw.nprob):
+                rec.p[i].dW, rec.p[i].db, rec.p[i].N, rec.p[i].K = bw.p[i].dW, bw.p[i].db, bw.p[i].N, bw.p[i].K
+    _abi.call("spv_linear_bwd", C.byref(bd) if bd is not None else None, C.byref(bw) if bw is not None else None, ptr(part), n,
+              C.byref(pending) if pending is not None else None, stream_ptr())
+    return rec
+
+
+def _reduce_pending(rec: Optional[SpvLinearPending]) -> None:
+    """the slice sum of the last link of a ``_linear_bwd`` chain (or one whose result the next launch reads)"""
+    if rec is not None:
+        _abi.call("spv_linear_reduce_pending", C.byref(rec), stream_ptr())
+
+
 def _fptr(t: torch.Tensor, col: int = 0) -> int:
     """device address of t[0, col] for a row-major fp32 matrix (or of t[col] for a vector)."""
     return t.data_ptr() + 4 * col
@@ -86,8 +114,9 @@ N_ENC_PARAMS = 10
 
 
 class EncoderTails(torch.autograd.Function):
-    """All encoders' tails in 4 forward / 8 backward launches (fc2, heads, BatchNorm statistics, [finalise + normalise + sample + KL];
-    backward: [sampling + BatchNorm partial sums], [finalise + apply], heads wgrad + reduce, 2 x heads dgrad, fc2 wgrad + reduce, fc2 dgrad).
+    """All encoders' tails in 4 forward / 5 backward launches (fc2, heads, BatchNorm statistics, [finalise + normalise + sample + KL];
+    backward: [sampling + BatchNorm partial sums], [finalise + apply], heads [dgrad + wgrad], fc2 [dgrad + wgrad + the heads' slice sum], fc2's
+    slice sum; with ops.LINEAR_BWD off 8: heads wgrad + reduce, heads dgrad, fc2 wgrad + reduce, fc2 dgrad).
 
     inputs : h1 per group ([B, 2H]: private | shared halves), then per encoder its 10 parameters
     outputs: per encoder (loc, logvar, scale, log_z, theta, kl)  -- theta is not differentiable here
@@ -224,20 +253,25 @@ class EncoderTails(torch.autograd.Function):
             _abi.call("spv_bn_bwd", C.byref(bn), stream_ptr())
         # 3. head weight gradients
         dWmu, dbmu, dWlv, dblv = ([pg[i][2][0] for i in range(E)], [pg[i][3][0] for i in range(E)], [pg[i][4][0] for i in range(E)], [pg[i][5][0] for i in range(E)])
-        b = _lin_batch(B)
+        bwh = _lin_batch(B)
         for i, s in enumerate(specs):
-            _add_lin(b, N=s.n, K=H, W=ptr(par[i][2]), X=ptr(h2[i]), ldx=H, dY=_fptr(d_pre[i], 0), lddy=2 * s.n, dW=ptr(dWmu[i]), db=ptr(dbmu[i]))
-            _add_lin(b, N=s.n, K=H, W=ptr(par[i][4]), X=ptr(h2[i]), ldx=H, dY=_fptr(d_pre[i], s.n), lddy=2 * s.n, dW=ptr(dWlv[i]), db=ptr(dblv[i]))
+            _add_lin(bwh, N=s.n, K=H, W=ptr(par[i][2]), X=ptr(h2[i]), ldx=H, dY=_fptr(d_pre[i], 0), lddy=2 * s.n, dW=ptr(dWmu[i]), db=ptr(dbmu[i]))
+            _add_lin(bwh, N=s.n, K=H, W=ptr(par[i][4]), X=ptr(h2[i]), ldx=H, dY=_fptr(d_pre[i], s.n), lddy=2 * s.n, dW=ptr(dWlv[i]), db=ptr(dblv[i]))
         from . import ops as _ops
         wsw = ws if not isinstance(ws, (list, tuple)) else ws[0]
-        _wgrad(b, wsw)
+        one_launch = _ops.LINEAR_BWD   # (spv_linear_bwd: nothing a launch writes is read by its other part -- d h2 / h2, d h1 / h1 are distinct buffers)
+        if not one_launch:
+            _wgrad(bwh, wsw)
         # 4. d h2 = d_pre_mu Wmu + d_pre_lv Wlv
         #    one launch: the contraction runs over the 2n columns of d_pre, rows 0..n-1 of the weight from Wmu, rows n.. from Wlv
         dh2 = [new(B, H) for _ in specs]
         b = _lin_batch(B)
         for i, s in enumerate(specs):
             _add_lin(b, N=2 * s.n, K=H, W=ptr(par[i][2]), W2=ptr(par[i][4]), n_w2=s.n, dY=ptr(d_pre[i]), lddy=2 * s.n, dX=ptr(dh2[i]), lddx=H)
-        _abi.call("spv_linear_dgrad", C.byref(b), stream_ptr())
+        if one_launch:
+            pend = _linear_bwd(b, bwh, wsw, "wgrad_part_heads")
+        else:
+            _abi.call("spv_linear_dgrad", C.byref(b), stream_ptr())
         # 5./6. fc2 backward (relu + dropout mask recovered from the saved h2 > 0)
         dW2, db2 = [pg[i][0][0] for i in range(E)], [pg[i][1][0] for i in range(E)]
         # every column block of h1 that an encoder reads gets written by the dgrad below; zero only what none covers
@@ -251,8 +285,11 @@ class EncoderTails(torch.autograd.Function):
             x, ldx = _fptr(h1[s.h1_group], s.h1_col), h1[s.h1_group].shape[1]
             _add_lin(bw, N=H, K=H, W=ptr(par[i][0]), X=x, ldx=ldx, Y=ptr(h2[i]), ldy=H, dY=ptr(dh2[i]), lddy=H, dW=ptr(dW2[i]), db=ptr(db2[i]))
             _add_lin(bd, N=H, K=H, W=ptr(par[i][0]), Y=ptr(h2[i]), ldy=H, dY=ptr(dh2[i]), lddy=H, dX=_fptr(dh1[s.h1_group], s.h1_col), lddx=ldx)
-        _wgrad(bw, wsw)
-        _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
+        if one_launch:   # the heads' slice sum rides in the fc2 launch; fc2's own is the last of the chain
+            _reduce_pending(_linear_bwd(bd, bw, wsw, "wgrad_part_fc2", pend))
+        else:
+            _wgrad(bw, wsw)
+            _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
         grads: List[Optional[torch.Tensor]] = list(dh1)
         for i in range(E):
             grads += [pg[i][j][1] for j in range(N_ENC_PARAMS)]

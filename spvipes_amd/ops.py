@@ -360,6 +360,9 @@ FUSED_DZ_F32 = os.environ.get("SPV_FUSED_DZ_F32", "1") != "0"   # "fp32" mode: t
 # 3.797 3.793.  "1" = on wherever the LDS-DMA kernels run, "fp32" = split-word mode only.  (tests/test_gpu_gemm_fixup.py keeps the
 # entry point bit-exact against the slab sum.)
 DA_FIXUP = os.environ.get("SPV_DA_FIXUP", "0")
+# a small layer's input and weight gradients as ONE launch (spv_linear_bwd; the slice sum of the weight gradient rides in the next such launch or runs
+# alone) instead of dgrad, wgrad and wgrad-reduce launches one after the other; "0": the separate launches.  Same kernel bodies, same bits.
+LINEAR_BWD = os.environ.get("SPV_LINEAR_BWD", "1") != "0"
 TRUNK_FOLD = os.environ.get("SPV_TRUNK_FOLD", "1") != "0"  # the mixing trunk's BatchNorm folded into its Linear (spv_trunk_fold_fwd / _bwd)
 FUSED_PACK = os.environ.get("SPV_FUSED_PACK", "1") != "0"  # latent / trunk kernels also write the decoder's bf16 operand images
 DEFER_WM = os.environ.get("SPV_DEFER_WM", "1") != "0"  # mixture-weight gradient GEMMs on the late side stream

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
 
+import gc
 import os
 
 import torch
@@ -431,20 +432,32 @@ class Trainer:
         # parameters updated instead of leaving a host launch (and its ~15-20 us of idle GPU) behind it.  Data-parallel jobs keep
         # Adam outside: the all-reduce comes between.
         self._adam_in_graph = bool(self.ADAM_IN_GRAPH and self.world == 1 and not self.overlap)
-        with torch.cuda.graph(g, **mode):
-            self._static_lo = self._forward_backward(self._static_rows, self._klw)
-            if self._adam_in_graph:
-                self.opt.launch(grad_scale=1.0, images=self._img_plan, counter=getattr(self.module, "_rng_counter", None))
-        if keep:
-            g.instantiate()
-        self.graph = g
-        if self.overlap:
-            g2 = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, pool=g.pool(), **mode):
-                self._backward_encoders()
+        # No Python garbage collection while a capture is open: a collection that starts inside it runs the finalisers of whatever dead
+        # reference cycles exist -- an earlier trainer's autograd contexts with its graph, memory pool, events -- and these are not
+        # capture-safe (a process that captured several trainers in a row aborted inside such a collection, in the first event record
+        # of the captured forward pass).  torch.cuda.graph no longer collects before it begins a capture, so do it here, then hold the
+        # collector off until the captures are closed.
+        gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, **mode):
+                self._static_lo = self._forward_backward(self._static_rows, self._klw)
+                if self._adam_in_graph:
+                    self.opt.launch(grad_scale=1.0, images=self._img_plan, counter=getattr(self.module, "_rng_counter", None))
             if keep:
-                g2.instantiate()
-            self.graph2 = g2
+                g.instantiate()
+            self.graph = g
+            if self.overlap:
+                g2 = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g2, pool=g.pool(), **mode):
+                    self._backward_encoders()
+                if keep:
+                    g2.instantiate()
+                self.graph2 = g2
+        finally:
+            if gc_was_on:
+                gc.enable()
 
     def step(self, rows: Sequence[torch.Tensor], kl_weight: Optional[float] = None, noise=None, optimizer_step: bool = True):
         """forward + loss + backward + (all-reduce) + Adam for one minibatch; returns the LossOutput.  ``noise`` (eager steps
