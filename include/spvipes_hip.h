@@ -400,6 +400,57 @@ int spv_de_median(const spv_de_median_args* a, void* stream);
 /* the workspace spv_de_median needs for this shape, in bytes (0 for a non-positive argument) */
 int64_t spv_de_median_ws_bytes(int32_t n_genes, int32_t n_pairs);
 
+/* Statistics of the OBSERVED counts per population (the columns raw_mean / non_zeros_proportion / raw_normalized_mean of scvi-tools'
+ * differential-expression tables; spVIPES.count_statistics of the user API): a segmented column reduction over LISTED rows of a dense
+ * resident count matrix.  The list has n positions; position p names the cell x.rows[p - pos_off] (x.rows == NULL: cell p - pos_off);
+ * the same cell may be listed more than once, in any order.  The list is cut into slabs, contiguous ranges of positions that each
+ * belong to ONE segment (label): slabs int32 [n_slabs][3] = {begin, end, segment} (positions, end exclusive, end - begin <=
+ * spv_count_stats_slab() is what the host plans; up to 32768 is accepted), ascending and segment by segment, and seg_slabs int32
+ * [n_seg + 1]: segment k owns slabs [seg_slabs[k], seg_slabs[k + 1]) (none: an empty segment, which yields zeros).  For segment k
+ * and selected gene j (genes int32 [n_sel] with ids in [0, G), repeats allowed; NULL: all genes, n_sel <= G), with c = the count
+ * of gene genes[j] in a listed cell:
+ *     out[k][0][j] = sum c      out[k][1][j] = the number of listed cells with c != 0      out[k][2][j] = sum fl64(c * w[p])
+ * out fp64 [n_seg][3][ld_out]; columns >= n_sel are never written.  w fp64, indexed by LIST POSITION p (not by matrix row), NULL = 1.
+ * Arithmetic: a uint16 count adds into 32-bit integer lane sums (exact; a lane sees at most one slab), an fp32 count is widened
+ * exactly and added in fp64; the tally is an integer; the weighted term is one fp64 multiply, added in fp64 (never fused).  Lanes
+ * hold genes; the waves of a workgroup take a slab's cells round-robin and merge through LDS in wave order; slabs merge in slab
+ * order.  No floating-point atomics: two calls agree bit for bit, and because the partial pass always covers all G genes a selected
+ * column equals the same column of an all-genes call bit for bit.  A row number outside [0, n_rows) contributes nothing and is
+ * never dereferenced; NaN counts are outside the contract.  16-byte loads are used when the matrix base, ld and col_off put every
+ * row's first gene on a 16-byte boundary, element loads otherwise (same results).
+ * Two launches: spv_count_stats_partial writes one record per (slab, gene) for slabs [slab_first, slab_first + slab_count) into
+ * ws fp64 [n_slabs][3][G] (spv_count_stats_ws_bytes(G, n_slabs) bytes, 8-byte aligned; it reads x, G, n_rows, n, pos_off, w, the
+ * tables and ws); spv_count_stats_merge adds each segment's records in slab order and applies the gene selection (it reads the
+ * tables, ws, genes, n_sel, out, ld_out).  spv_count_stats is both on the whole list (slab_first = pos_off = 0, slab_count =
+ * n_slabs).  A caller that holds the listed rows in pieces (a CSR matrix densified chunk by chunk) runs the partial pass once per
+ * piece with pos_off = the list position of the piece's first row, then merges once.  Nothing is allocated. */
+typedef struct spv_count_stats_args {
+  spv_counts x;
+  int32_t G, n_rows, n, pos_off;
+  const double* w;
+  const int32_t* genes;
+  const int32_t* slabs;
+  const int32_t* seg_slabs;
+  int32_t n_sel, n_slabs, n_seg, slab_first, slab_count, pad_;
+  double* out; int64_t ld_out;
+  void* ws; int64_t ws_bytes;
+} spv_count_stats_args;
+int spv_count_stats(const spv_count_stats_args* a, void* stream);
+int spv_count_stats_partial(const spv_count_stats_args* a, void* stream);
+int spv_count_stats_merge(const spv_count_stats_args* a, void* stream);
+/* the gene tile T and the slab length S of the partial pass, and its workspace in bytes (0 for a non-positive argument) */
+int32_t spv_count_stats_tile(void);
+int32_t spv_count_stats_slab(void);
+int64_t spv_count_stats_ws_bytes(int32_t G, int32_t n_slabs);
+
+/* total[c] = the sum over all G genes of cell c's counts, fp64 [n_cells], for a dense resident matrix (x->rows is ignored) and for
+ * CSR arrays (indptr int64 [n_cells + 1], cols int32 sorted and unique within a row, vals of `dtype`; one wave per row).  uint16
+ * counts add as integers (exact); fp32 counts are widened and added in fp64 in ONE fixed order for both forms -- lane t of the cell's
+ * wave adds the genes g = t (mod 64) in ascending g, then the 64 lane sums fold by halves -- so the two agree bit for bit (a gene
+ * without a stored entry adds an exact zero).  cols is only read for fp32 values. */
+int spv_count_totals(const spv_counts* x, int32_t n_cells, int32_t G, double* total, void* stream);
+int spv_csr_totals(const int64_t* indptr, const int32_t* cols, const void* vals, int32_t dtype, int32_t n_cells, int32_t G, double* total, void* stream);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

@@ -243,6 +243,14 @@ class SpvDeMedianArgs(C.Structure):
                 ("mid", C.c_void_p), ("ld_mid", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+class SpvCountStatsArgs(C.Structure):
+    """the arguments of spv_count_stats / _partial / _merge (include/spvipes_hip.h: spv_count_stats_args)"""
+    _fields_ = [("x", SpvCounts), ("G", C.c_int32), ("n_rows", C.c_int32), ("n", C.c_int32), ("pos_off", C.c_int32), ("w", C.c_void_p),
+                ("genes", C.c_void_p), ("slabs", C.c_void_p), ("seg_slabs", C.c_void_p), ("n_sel", C.c_int32), ("n_slabs", C.c_int32),
+                ("n_seg", C.c_int32), ("slab_first", C.c_int32), ("slab_count", C.c_int32), ("pad_", C.c_int32), ("out", C.c_void_p),
+                ("ld_out", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -306,6 +314,14 @@ _SIGNATURES = {
     "spv_de_pairs_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_de_median": (C.c_int, [C.POINTER(SpvDeMedianArgs), C.c_void_p]),
     "spv_de_median_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "spv_count_stats": (C.c_int, [C.POINTER(SpvCountStatsArgs), C.c_void_p]),
+    "spv_count_stats_partial": (C.c_int, [C.POINTER(SpvCountStatsArgs), C.c_void_p]),
+    "spv_count_stats_merge": (C.c_int, [C.POINTER(SpvCountStatsArgs), C.c_void_p]),
+    "spv_count_stats_tile": (C.c_int32, []),
+    "spv_count_stats_slab": (C.c_int32, []),
+    "spv_count_stats_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "spv_count_totals": (C.c_int, [C.POINTER(SpvCounts), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spv_csr_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -8,6 +8,7 @@
 #include "spv_dec_expected.h"
 #include "spv_de.h"
 #include "spv_de_median.h"
+#include "spv_count_stats.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -898,6 +899,102 @@ extern "C" int spv_de_median(const spv_de_median_args* x, void* stream) {
   if (rc == SPV_OK) rc = de_median_pass<2>(a, tiles, s);
   if (rc == SPV_OK) rc = de_median_pass<3>(a, tiles, s);
   return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// statistics of the observed counts (spv_count_stats.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_count_stats_tile(void) { return CS_TILE; }
+extern "C" int32_t spv_count_stats_slab(void) { return CS_SLAB; }
+extern "C" int64_t spv_count_stats_ws_bytes(int32_t G, int32_t n_slabs) {
+  if (G <= 0 || n_slabs <= 0) return 0;
+  return (int64_t)n_slabs * 3 * G * (int64_t)sizeof(double);
+}
+
+static int count_stats_check(const spv_count_stats_args* x, const char* who, bool partial, bool merge, CsArgs& a) {
+  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
+  if (!x->slabs || !x->seg_slabs || !x->ws) return fail(SPV_ERR_ARG, "%s: null pointer (slabs, seg_slabs, ws)", who);
+  if (x->G <= 0 || x->n_slabs <= 0 || x->n_seg <= 0) return fail(SPV_ERR_ARG, "%s: G, n_slabs and n_seg must be positive", who);
+  if (x->ws_bytes < spv_count_stats_ws_bytes(x->G, x->n_slabs) || (reinterpret_cast<uintptr_t>(x->ws) & 7))
+    return fail(SPV_ERR_ARG, "%s: the workspace must be 8-byte aligned and hold spv_count_stats_ws_bytes() bytes", who);
+  if (partial) {
+    if (!x->x.X) return fail(SPV_ERR_ARG, "%s: null count matrix", who);
+    if (x->x.dtype != SPV_COUNT_U16 && x->x.dtype != SPV_COUNT_F32) return fail(SPV_ERR_ARG, "%s: unknown count dtype", who);
+    if (x->n_rows <= 0 || x->n <= 0 || x->pos_off < 0 || (int64_t)x->pos_off + x->n > INT32_MAX) return fail(SPV_ERR_ARG, "%s: n_rows and n must be positive, pos_off non-negative", who);
+    if (x->x.col_off < 0 || x->x.ld < (int64_t)x->x.col_off + x->G) return fail(SPV_ERR_ARG, "%s: ld < col_off + G", who);
+    if (!x->x.rows && x->n > x->n_rows) return fail(SPV_ERR_ARG, "%s: without a row list n must not exceed n_rows", who);
+    if (x->slab_first < 0 || x->slab_count <= 0 || (int64_t)x->slab_first + x->slab_count > x->n_slabs) return fail(SPV_ERR_ARG, "%s: slab range outside the table", who);
+    if ((int64_t)x->slab_count * ((x->G + CS_TILE - 1) / CS_TILE) > INT32_MAX) return fail(SPV_ERR_ARG, "%s: too many (slab, gene tile) workgroups for one launch", who);
+  }
+  if (merge) {
+    if (!x->out) return fail(SPV_ERR_ARG, "%s: null output", who);
+    if (x->n_sel <= 0 || (!x->genes && x->n_sel > x->G)) return fail(SPV_ERR_ARG, "%s: n_sel must be positive (and at most G without a gene list)", who);
+    if (x->ld_out < x->n_sel || x->n_seg > 65535) return fail(SPV_ERR_ARG, "%s: ld_out < n_sel, or more than 65535 segments", who);
+  }
+  a = CsArgs{x->x.X, (long)x->x.ld, x->x.rows, x->x.col_off, x->G, x->n_rows, x->n, x->pos_off, x->w, x->genes, x->n_sel, x->slabs, x->seg_slabs,
+             x->n_slabs, x->n_seg, x->slab_first, x->slab_count, x->out, (long)x->ld_out, (double*)x->ws};
+  return SPV_OK;
+}
+
+static int count_stats_partial_launch(const spv_count_stats_args* x, const CsArgs& a, hipStream_t s) {
+  const bool u16 = x->x.dtype == SPV_COUNT_U16;
+  const int64_t es = u16 ? 2 : 4;
+  // 16-byte loads need every row's first gene on a 16-byte boundary (and a row that holds one whole piece: cs_load)
+  const bool vec = ((reinterpret_cast<uintptr_t>(x->x.X) + (uintptr_t)(x->x.col_off * es)) & 15) == 0 && ((x->x.ld * es) & 15) == 0 && x->G * es >= 16;
+  const dim3 grid((unsigned)(x->slab_count * ((x->G + CS_TILE - 1) / CS_TILE))), block(64 * CS_WAVES);
+  if (u16 && vec) hipLaunchKernelGGL((count_stats_partial_kernel<true, true>), grid, block, 0, s, a);
+  else if (u16) hipLaunchKernelGGL((count_stats_partial_kernel<true, false>), grid, block, 0, s, a);
+  else if (vec) hipLaunchKernelGGL((count_stats_partial_kernel<false, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((count_stats_partial_kernel<false, false>), grid, block, 0, s, a);
+  return launch_status("spv_count_stats (partial pass)");
+}
+
+static int count_stats_merge_launch(const CsArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(count_stats_merge_kernel, dim3((unsigned)((a.n_sel + 255) / 256), (unsigned)a.n_seg), dim3(256), 0, s, a);
+  return launch_status("spv_count_stats (merge pass)");
+}
+
+extern "C" int spv_count_stats_partial(const spv_count_stats_args* x, void* stream) {
+  CsArgs a;
+  int rc = count_stats_check(x, "spv_count_stats_partial", true, false, a);
+  if (rc != SPV_OK) return rc;
+  return count_stats_partial_launch(x, a, (hipStream_t)stream);
+}
+
+extern "C" int spv_count_stats_merge(const spv_count_stats_args* x, void* stream) {
+  CsArgs a;
+  int rc = count_stats_check(x, "spv_count_stats_merge", false, true, a);
+  if (rc != SPV_OK) return rc;
+  return count_stats_merge_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int spv_count_stats(const spv_count_stats_args* x, void* stream) {
+  CsArgs a;
+  int rc = count_stats_check(x, "spv_count_stats", true, true, a);
+  if (rc != SPV_OK) return rc;
+  if (x->slab_first != 0 || x->slab_count != x->n_slabs || x->pos_off != 0) return fail(SPV_ERR_ARG, "spv_count_stats: the whole list in one call (slab_first = pos_off = 0, slab_count = n_slabs)%s");
+  rc = count_stats_partial_launch(x, a, (hipStream_t)stream);
+  if (rc != SPV_OK) return rc;
+  return count_stats_merge_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int spv_count_totals(const spv_counts* x, int32_t n_cells, int32_t G, double* total, void* stream) {
+  if (!x || !x->X || !total) return fail(SPV_ERR_ARG, "spv_count_totals: null pointer%s");
+  if (n_cells <= 0 || G <= 0 || x->col_off < 0 || x->ld < (int64_t)x->col_off + G) return fail(SPV_ERR_ARG, "spv_count_totals: bad shape%s");
+  const dim3 grid((unsigned)((n_cells + 3) / 4)), block(256);
+  if (x->dtype == SPV_COUNT_U16) hipLaunchKernelGGL((count_totals_kernel<true>), grid, block, 0, (hipStream_t)stream, x->X, (long)x->ld, x->col_off, n_cells, G, total);
+  else if (x->dtype == SPV_COUNT_F32) hipLaunchKernelGGL((count_totals_kernel<false>), grid, block, 0, (hipStream_t)stream, x->X, (long)x->ld, x->col_off, n_cells, G, total);
+  else return fail(SPV_ERR_ARG, "spv_count_totals: unknown count dtype%s");
+  return launch_status("spv_count_totals");
+}
+
+extern "C" int spv_csr_totals(const int64_t* indptr, const int32_t* cols, const void* vals, int32_t dtype, int32_t n_cells, int32_t G, double* total, void* stream) {
+  if (!indptr || !total || n_cells <= 0 || G <= 0) return fail(SPV_ERR_ARG, "spv_csr_totals: bad arguments%s");
+  const dim3 grid((unsigned)((n_cells + 3) / 4)), block(256);
+  if (dtype == SPV_COUNT_U16) hipLaunchKernelGGL((csr_totals_kernel<true>), grid, block, 0, (hipStream_t)stream, (const long*)indptr, cols, vals, n_cells, G, total);
+  else if (dtype == SPV_COUNT_F32) hipLaunchKernelGGL((csr_totals_kernel<false>), grid, block, 0, (hipStream_t)stream, (const long*)indptr, cols, vals, n_cells, G, total);
+  else return fail(SPV_ERR_ARG, "spv_csr_totals: unknown count dtype%s");
+  return launch_status("spv_csr_totals");
 }
 
 extern "C" int spv_dec_dz(const spv_dec_params* q, const float* Tp, const float* Ts, float* dz_part, void* stream) {

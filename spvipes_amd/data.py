@@ -528,3 +528,68 @@ def de_table(stats, n_pairs: int, fdr_target: float = 0.05) -> dict:
         is_de[order[: ok[-1] + 1]] = True
     out[f"is_de_fdr_{fdr_target}"] = is_de
     return out
+
+
+# ---- statistics of the observed counts (model.count_statistics): slab plan, "rest" sums and the result table ---------------------
+COUNT_COLUMNS = ("raw_mean1", "raw_mean2", "non_zeros_proportion1", "non_zeros_proportion2", "raw_normalized_mean1", "raw_normalized_mean2")
+
+
+def check_target_sum(target_sum) -> float:
+    """``target_sum`` of count_statistics as a float: a positive finite number, else ValueError"""
+    try:
+        f = float(target_sum)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if isinstance(target_sum, (bool, str)) or not (math.isfinite(f) and f > 0.0):
+        raise ValueError(f"target_sum must be a positive finite number, got {target_sum!r}")
+    return f
+
+
+def count_slab_plan(seg_sizes, slab: int):
+    """The slab table of spv_count_stats for a list whose first ``seg_sizes[0]`` positions are segment 0, and so on (zeros allowed):
+    -> (slabs int32 [n_slabs, 3] = begin, end, segment, seg_slabs int32 [n_seg + 1]).  Every segment is cut into slabs of ``slab``
+    positions, the last one shorter; no slab crosses a segment, every position lies in exactly one slab, an empty segment owns none
+    (``seg_slabs[k] == seg_slabs[k + 1]``)."""
+    sizes = [int(s) for s in np.asarray(seg_sizes).ravel().tolist()]
+    if isinstance(slab, bool) or not isinstance(slab, (int, np.integer)) or int(slab) < 1:
+        raise ValueError(f"slab must be a positive integer, got {slab!r}")
+    if any(s < 0 for s in sizes):
+        raise ValueError(f"seg_sizes must be non-negative, got {sizes!r}")
+    if sum(sizes) > np.iinfo(np.int32).max:
+        raise ValueError("the list has more positions than an int32 can address")
+    slabs, seg_slabs, pos = [], [0], 0
+    for k, s in enumerate(sizes):
+        for b in range(pos, pos + s, int(slab)):
+            slabs.append((b, min(b + int(slab), pos + s), k))
+        pos += s
+        seg_slabs.append(len(slabs))
+    return np.asarray(slabs, dtype=np.int32).reshape(-1, 3), np.asarray(seg_slabs, dtype=np.int32)
+
+
+def count_rest(stats) -> np.ndarray:
+    """One-vs-rest from per-segment sums: ``stats`` fp64 [n_seg, ...] -> rest[k] = the sum of every segment but k, formed as the sum
+    of the segments before k (added in ascending order) plus the sum of the segments after k (added in descending order).  Every term
+    is non-negative, so nothing cancels as it would in ``total - own``; integral sums below 2^53 stay exact."""
+    s = np.asarray(stats, dtype=np.float64)
+    n = s.shape[0]
+    before, after = np.zeros_like(s), np.zeros_like(s)
+    for k in range(1, n):
+        before[k] = before[k - 1] + s[k - 1]
+    for k in range(n - 2, -1, -1):
+        after[k] = after[k + 1] + s[k + 1]
+    return before + after
+
+
+def count_table(own, n_own: int, other, n_other: int) -> dict:
+    """The six raw-count columns of one comparison from the kernel's sums: ``own`` / ``other`` fp64 [3, n_sel] = (sum of counts,
+    number of cells with a non-zero count, sum of count * w) of the two populations of ``n_own`` / ``n_other`` cells (both positive)
+    -> column name -> float64 array, in COUNT_COLUMNS order: raw_mean = S0 / n, non_zeros_proportion = S1 / n, raw_normalized_mean =
+    S2 / n."""
+    if int(n_own) < 1 or int(n_other) < 1:
+        raise ValueError(f"both populations need at least one cell, got {n_own} and {n_other}")
+    a, b = np.asarray(own, dtype=np.float64), np.asarray(other, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != 3 or b.shape != a.shape:
+        raise ValueError(f"own and other must both be [3, n_sel], got {a.shape} and {b.shape}")
+    n1, n2 = float(int(n_own)), float(int(n_other))
+    return {"raw_mean1": a[0] / n1, "raw_mean2": b[0] / n2, "non_zeros_proportion1": a[1] / n1, "non_zeros_proportion2": b[1] / n2,
+            "raw_normalized_mean1": a[2] / n1, "raw_normalized_mean2": b[2] / n2}

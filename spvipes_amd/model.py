@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, check_de_args, check_expression_args, csr_group_arrays, csr_to_dense, de_bank_rows, de_label_populations,
+from .data import (MinibatchSampler, check_de_args, check_expression_args, check_target_sum, count_rest, count_table, csr_group_arrays, csr_to_dense, de_bank_rows, de_label_populations,
                    de_pair_rows, de_populations, de_subsample, de_table, format_latent_results, group_var_names, is_sparse, latent_loader_mode, latent_steps, resolve_gene_list,
                    to_group_counts, to_sparse_group_counts)
 from .module import spVIPESmodule
@@ -453,6 +453,76 @@ class spVIPES:
             r1, r2 = de_pair_rows(len(p1) * n_samples, len(p2) * n_samples, n_pairs, seed + k)
             table = self._de_compare(bank, bank, de_bank_rows(r1, p1, len(kept)), de_bank_rows(r2, p2, len(kept)), delta, pseudocount, fdr_target, bool(lfc_median))
             df = pd.DataFrame(table, index=index)
+            df["comparison"], df["group1"], df["group2"] = f"{names[k]} vs Rest", names[k], "Rest"
+            frames.append(df)
+        return pd.concat(frames)
+
+    @torch.no_grad()
+    def count_statistics(self, group_indices_list: List[List[int]], group: int, idx1=None, idx2=None, groupby=None, labels=None, gene_list=None,
+                         target_sum: float = 1e4):
+        """The raw-count columns of scvi-tools' differential-expression tables (``all_stats=True``), from the OBSERVED counts of ONE
+        group: a pandas DataFrame of float64 columns
+
+            raw_mean1, raw_mean2                          the mean count of the gene over the population's cells
+            non_zeros_proportion1, non_zeros_proportion2  the share of the population's cells with a non-zero count
+            raw_normalized_mean1, raw_normalized_mean2    the mean of count * target_sum / (the cell's total count)
+
+        It needs no trained model and decodes nothing.  Exactly one of ``idx1`` / ``groupby`` selects the mode (else ValueError):
+        ``idx1`` (with ``idx2``, None = every other cell of ``group_indices_list[group]``): the two populations of
+        ``differential_expression``, resolved by the same rules with the same errors; the frame has that method's index and gene order
+        for the same ``gene_list``.  ``groupby`` (with ``labels``): every label against every other cell of the group, as
+        ``differential_expression_by`` compares them -- the same label set, the same ``labels`` restriction (KeyError for an unknown
+        one), blocks concatenated in label order with ``comparison`` / ``group1`` / ``group2`` appended, rows exactly in that method's
+        order for the same ``groupby`` / ``labels`` / ``gene_list``, so ``pd.concat([de, stats[list(data.COUNT_COLUMNS)]], axis=1)`` lines up.
+        There is no ``max_cells``: the statistics always cover the full populations.  A cell's total runs over ALL of the group's
+        genes whatever ``gene_list`` selects; a cell without counts gets the weight 0 (scvi-tools would divide by zero).
+        ``target_sum``: a positive finite number.
+        How it is computed: the cells' rows, sorted by population, go through ONE segmented reduction on the device
+        (spv_count_stats: integer sums of the uint16 counts, fp64 elsewhere, a fixed order throughout) with the per-cell totals of
+        spv_count_totals / spv_csr_totals, kept on the resident matrix; "rest" is the sum of the other labels' sums.  Dense and sparse
+        ``counts_storage`` give the same frame bit for bit."""
+        import pandas as pd
+
+        from .count_ops import count_stats, count_totals
+
+        target_sum = check_target_sum(target_sum)
+        if (idx1 is None) == (groupby is None):
+            raise ValueError("count_statistics: give exactly one of idx1 (two populations) and groupby (every label against the rest)")
+        if group not in (0, 1):
+            raise ValueError(f"group must be 0 or 1, got {group!r}")
+        g = int(group)
+        cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
+        if groupby is None:
+            if labels is not None:
+                raise ValueError("count_statistics: labels goes with groupby")
+            p1, p2 = de_populations(cells, idx1, idx2, group=g)
+            order, sizes = np.concatenate([p1, p2]), [len(p1), len(p2)]
+        else:
+            if idx2 is not None:
+                raise ValueError("count_statistics: idx2 goes with idx1")
+            if isinstance(groupby, str):
+                if groupby not in self.adata.obs:
+                    raise KeyError(f"groupby: adata.obs has no column {groupby!r}")
+                cell_labels = np.asarray(self.adata.obs[groupby])[cells]
+            else:
+                cell_labels = np.asarray(groupby).ravel()
+                if cell_labels.shape[0] != len(cells):
+                    raise ValueError(f"groupby: an array must hold one label per cell of group_indices_list[{g}] ({len(cells)}), got {cell_labels.shape[0]}")
+            if len(np.unique(cells)) != len(cells):
+                raise ValueError(f"group_indices_list[{g}] lists a cell more than once")
+            names, compared, _kept, _places = de_label_populations(cell_labels, labels, None, 0)
+            code = np.unique(cell_labels, return_inverse=True)[1].ravel()
+            order, sizes = np.argsort(code, kind="stable"), np.bincount(code, minlength=len(names)).tolist()
+        _sel, dev_sel, _n_sel, index = self._de_genes(g, gene_list)
+        rows = torch.as_tensor(self._local_rows(g, cells[order]).astype(np.int32), device=self.device)
+        total = count_totals(self.counts[g]).index_select(0, rows.long())
+        w = torch.where(total > 0, target_sum / total, torch.zeros_like(total))
+        sums = count_stats(self.counts[g], rows, sizes, w=w, genes=dev_sel).cpu().numpy()
+        if groupby is None:
+            return pd.DataFrame(count_table(sums[0], sizes[0], sums[1], sizes[1]), index=index)
+        rest, n_all, frames = count_rest(sums), int(sum(sizes)), []
+        for k in compared:
+            df = pd.DataFrame(count_table(sums[k], sizes[k], rest[k], n_all - sizes[k]), index=index)
             df["comparison"], df["group1"], df["group2"] = f"{names[k]} vs Rest", names[k], "Rest"
             frames.append(df)
         return pd.concat(frames)
