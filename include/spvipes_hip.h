@@ -352,6 +352,37 @@ typedef struct spv_dec_expected_args {
 } spv_dec_expected_args;
 int spv_dec_expected(const spv_dec_params* p, const spv_dec_expected_args* a, void* stream);
 
+/* Posterior-predictive counts (posterior_predictive_sample): for one group and one minibatch, one draw per (cell, selected gene) from
+ * the decoder's NB mixture, NegativeBinomialMixture(mu1 = rate_private, mu2 = rate_shared, theta1 = exp(px_r), mixture_logits) of
+ * module/spVIPESmodule.py:751-759 (no theta2: both components share theta), sampled as scvi-tools samples it:
+ *   c ~ Bernoulli(pi), pi = sigmoid(mixing logit) weights component 1 (the private rate);  mu = c ? rate_private : rate_shared;
+ *   lam = Gamma(shape = theta, scale = mu / theta) clamped at 1e8;  x ~ Poisson(lam)
+ *   out[b * ld_out + j * ld_gene] = x(b, genes[j])      (int32; ld_gene >= 1, ld_out >= (n_genes - 1) * ld_gene + 1)
+ * `p`, Am / Wm, K, nsplit, genes / n_genes: exactly as spv_dec_expected takes them -- the rates and the logit of an element are the
+ * values that entry point computes.  theta: fp32 device array [G] of exp(px_r).  The random bits of an element are Philox 4x32-10
+ * blocks addressed by (key; gene id, cell id, sample, block number), cell id = cell_ids ? cell_ids[b] : b (int32 device array [B]):
+ * a value depends on its own gene, cell, sample and key only, so a gene subset equals the same columns of the all-genes output bit
+ * for bit, and [B][n_genes][S] is filled in place by S calls with sample = s, out + s, ld_gene = S.  Rows >= B, columns >=
+ * n_genes and the elements between the ld_gene strides are never written.  Nothing is allocated; one launch on `stream`. */
+typedef struct spv_dec_sample_args {
+  const uint16_t* Am_hi; const uint16_t* Am_lo; const uint16_t* Wm_hi; const uint16_t* Wm_lo;
+  int32_t K, nsplit;
+  const int32_t* genes; int32_t n_genes; int32_t ld_gene;
+  const float* theta;
+  const int32_t* cell_ids;
+  uint64_t key; uint32_t sample;
+  int32_t* out; int64_t ld_out;
+} spv_dec_sample_args;
+int spv_dec_sample(const spv_dec_params* p, const spv_dec_sample_args* a, void* stream);
+
+/* The same sampler over given parameters (the law of module/spVIPESmodule.py:751-759 for anyone who holds its parameters):
+ *   out[r * ld_out + g] ~ NBMix(rate_p[r * ld_in + g], rate_s[r * ld_in + g], theta[g], logit[r * ld_in + g]),  r < R, g < G
+ * fp32 device inputs, int32 device output; ld_in, ld_out >= G.  key / sample / cell_ids (int32 [R] or NULL = the row number) mean
+ * what they mean for spv_dec_sample, with gene id = g: equal parameters give the draws of spv_dec_sample bit for bit.  An element
+ * whose selected rate or whose theta is NaN, zero or negative gives 0 (both entry points). */
+int spv_nbmix_sample(const float* rate_p, const float* rate_s, const float* logit, int64_t ld_in, const float* theta, int32_t R, int32_t G,
+                     const int32_t* cell_ids, uint64_t key, uint32_t sample, int32_t* out, int64_t ld_out, void* stream);
+
 /* Differential expression in "change" mode (spVIPES.differential_expression): per gene j < n_genes the statistics, over n_pairs
  * pairs m of bank rows, of
  *   lfc_m = log2(max(x1 + eps, FLT_MIN)) - log2(max(x2 + eps, FLT_MIN)),   x1 = bank1[rows1[m]][j],  x2 = bank2[rows2[m]][j]

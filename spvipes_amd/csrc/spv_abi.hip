@@ -6,6 +6,7 @@
 #include "spv_dec_gemm.h"
 #include "spv_decoder.h"
 #include "spv_dec_expected.h"
+#include "spv_dec_sample.h"
 #include "spv_de.h"
 #include "spv_de_median.h"
 #include "spv_count_stats.h"
@@ -839,6 +840,50 @@ extern "C" int spv_dec_expected(const spv_dec_params* q, const spv_dec_expected_
   return launch_status("spv_dec_expected");
 }
 
+extern "C" int spv_dec_sample(const spv_dec_params* q, const spv_dec_sample_args* x, void* stream) {
+  DecParams p;
+  int rc = to_dec(q, p);
+  if (rc != SPV_OK) return rc;
+  if (!x) return fail(SPV_ERR_ARG, "spv_dec_sample: null arguments%s");
+  if (!p.a_p || !p.a_s || !x->Am_hi || !x->Wm_hi || !x->theta || !x->out) return fail(SPV_ERR_ARG, "spv_dec_sample: null pointer%s");
+  if (x->K <= 0 || (x->K % 32) || x->K > DX_KMAX) return fail(SPV_ERR_ARG, "spv_dec_sample: K must be a multiple of 32, at most 320%s");
+  if (x->nsplit != 1 && x->nsplit != 3) return fail(SPV_ERR_ARG, "spv_dec_sample: nsplit must be 1 or 3%s");
+  if (x->nsplit == 3 && (!x->Am_lo || !x->Wm_lo)) return fail(SPV_ERR_ARG, "spv_dec_sample: nsplit=3 needs lo images%s");
+  if ((reinterpret_cast<uintptr_t>(x->Am_hi) | reinterpret_cast<uintptr_t>(x->Wm_hi) | reinterpret_cast<uintptr_t>(x->Am_lo) | reinterpret_cast<uintptr_t>(x->Wm_lo)) & 15)
+    return fail(SPV_ERR_ARG, "spv_dec_sample: operand images must be 16-byte aligned%s");
+  if (x->n_genes <= 0 || (!x->genes && x->n_genes > p.G)) return fail(SPV_ERR_ARG, "spv_dec_sample: n_genes must be positive (and at most G without a gene list)%s");
+  if (x->ld_gene < 1) return fail(SPV_ERR_ARG, "spv_dec_sample: ld_gene < 1%s");
+  if (x->ld_out < (int64_t)(x->n_genes - 1) * x->ld_gene + 1) return fail(SPV_ERR_ARG, "spv_dec_sample: ld_out < (n_genes - 1) * ld_gene + 1%s");
+  const DecSampleArgs a{(const bf16_t*)x->Am_hi, (const bf16_t*)x->Am_lo, (const bf16_t*)x->Wm_hi, (const bf16_t*)x->Wm_lo, x->K,
+                        x->genes, x->n_genes, x->theta, x->cell_ids, (unsigned long long)x->key, x->sample, x->out, (long)x->ld_out, x->ld_gene};
+  // the grid of spv_dec_expected: one workgroup per 32 cells and gene slice, each of its 4 waves walks every (4 gy)-th 32-gene tile
+  const int gx = p.Bp / DX_CELLS, tiles = (x->n_genes + 31) / 32;
+  int gy = (2048 + gx - 1) / gx;
+  if (gy > (tiles + 3) / 4) gy = (tiles + 3) / 4;
+  if (gy < 1) gy = 1;
+  const dim3 grid(gx, gy);
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = dec_kw(q) == 2;
+  if (x->nsplit == 3 && wide) hipLaunchKernelGGL((dec_sample_kernel<3, 2>), grid, dim3(256), 0, s, p, a);
+  else if (x->nsplit == 3) hipLaunchKernelGGL((dec_sample_kernel<3, 1>), grid, dim3(256), 0, s, p, a);
+  else if (wide) hipLaunchKernelGGL((dec_sample_kernel<1, 2>), grid, dim3(256), 0, s, p, a);
+  else hipLaunchKernelGGL((dec_sample_kernel<1, 1>), grid, dim3(256), 0, s, p, a);
+  return launch_status("spv_dec_sample");
+}
+
+extern "C" int spv_nbmix_sample(const float* rate_p, const float* rate_s, const float* logit, int64_t ld_in, const float* theta, int32_t R, int32_t G,
+                                const int32_t* cell_ids, uint64_t key, uint32_t sample, int32_t* out, int64_t ld_out, void* stream) {
+  if (!rate_p || !rate_s || !logit || !theta || !out) return fail(SPV_ERR_ARG, "spv_nbmix_sample: null pointer%s");
+  if (R < 0 || G <= 0) return fail(SPV_ERR_ARG, "spv_nbmix_sample: R must not be negative, G must be positive%s");
+  if (ld_in < G || ld_out < G) return fail(SPV_ERR_ARG, "spv_nbmix_sample: ld_in and ld_out must be at least G%s");
+  if (R == 0) return SPV_OK;
+  const long n = (long)R * G;
+  if ((n + 255) / 256 > 0x7fffffffL) return fail(SPV_ERR_ARG, "spv_nbmix_sample: R * G exceeds the grid%s");
+  const NbMixArgs a{rate_p, rate_s, logit, (long)ld_in, theta, R, G, cell_ids, (unsigned long long)key, sample, out, (long)ld_out};
+  hipLaunchKernelGGL(nbmix_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return launch_status("spv_nbmix_sample");
+}
+
 extern "C" int32_t spv_de_pairs_splits(int32_t n_genes, int32_t n_pairs) {
   if (n_genes <= 0 || n_pairs <= 0) return 0;
   return de_splits(n_genes, n_pairs);
@@ -1145,19 +1190,13 @@ extern "C" int spv_gather_u32(const spv_gather_prob* probs, int32_t nprob, void*
 // comes out of ONE launch that reads a device-resident step counter, so a captured hipGraph needs no generator state from the host
 // (torch's graph-safe generator costs two fill launches per replay + its own kernel, at the head of the step's critical path).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
-  const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
 __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, long n, const long long* __restrict__ counter, unsigned long long key) {
   const long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i4 >= n) return;
   const unsigned long long step = counter ? (unsigned long long)*counter : 0ull;
   unsigned c[4] = {(unsigned)(i4 >> 2), (unsigned)((unsigned long long)(i4 >> 2) >> 32), (unsigned)step, (unsigned)(step >> 32)};
-  unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+  const unsigned k[2] = {(unsigned)key, (unsigned)(key >> 32)};
+  philox4x32_10(c, k);
   float z[4];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {

@@ -184,6 +184,20 @@ __device__ __forceinline__ float half_sum(float v) {
 }
 __device__ __forceinline__ float other_half(float v) { return __shfl_xor(v, 32, 64); }
 
+// ---- counter-based random bits: Philox 4x32-10 (Salmon et al., SC'11) ---------------------------------------------------
+// 128 bits out of a 128-bit counter and a 64-bit key; a value depends on (counter, key) only, so a draw can be addressed by what
+// it belongs to (spv_randn: element and step; the count sampler of spv_dec_sample.h: gene, cell, sample, block).
+__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
+  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
+  const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], const unsigned (&key)[2]) {
+  unsigned k0 = key[0], k1 = key[1];
+#pragma unroll
+  for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+}
+
 // ---- special functions (fp32, a > 0) -----------------------------------------
 // lgamma(a) and digamma(a) by an 8-step upward shift (while a < 8) + Stirling / asymptotic
 // series at z >= 8.  Both share log z, 1/z, 1/P.  The error is a few fp32 roundings of the largest term, so it grows with the

@@ -303,6 +303,20 @@ def check_expression_args(component, library_size, n_samples, use_mean: bool):
     return what, log_l, int(n_samples)
 
 
+SAMPLE_MAX_SEED = (1 << 32) - 1   # the seed is the low word of the sampler's Philox key (dec_ops.sample_key)
+
+
+def check_sample_args(n_samples, seed, library_size):
+    """The argument checks of posterior_predictive_sample: -> (n_samples, seed, log L or None).  ``n_samples`` a positive integer,
+    ``seed`` an integer in [0, 2^32), ``library_size`` "latent" or a positive number (as get_normalized_expression takes it)."""
+    log_l = expression_log_library(library_size)
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or int(n_samples) < 1:
+        raise ValueError(f"n_samples must be a positive integer, got {n_samples!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= SAMPLE_MAX_SEED:
+        raise ValueError(f"seed must be an integer in [0, 2^32), got {seed!r}")
+    return int(n_samples), int(seed), log_l
+
+
 def group_var_names(adata, n_groups: int = 2):
     """Per group the names of its own genes, as get_loadings labels them: ``adata.var_names`` cut by ``uns["groups_var_indices"]``,
     else ``uns["groups_var_names"]`` (list or dict), else None"""

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
+from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecSampleArgs, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
                    ptr, round_up, stream_ptr)
 from .nn_ops import _add_lin, _fptr, _lin_batch, _linear_bwd, _reduce_pending, _wgrad, grad_out
 from . import ops as _ops
@@ -886,6 +886,27 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     return out
 
 
+def _gene_selection(genes, G: int, dev, who: str):
+    """``genes`` of expected_expression / sample_counts -> (int32 device tensor of ids or None for all genes in order, n_genes)"""
+    if genes is None:
+        gidx, n = None, G
+    elif isinstance(genes, torch.Tensor) and genes.is_cuda:
+        if genes.dtype != torch.int32 or genes.dim() != 1 or not genes.is_contiguous():
+            raise _abi.SpvError(f"{who}: a device gene list must be a contiguous 1-d int32 tensor")
+        gidx, n = genes, int(genes.numel())
+    else:
+        host = np.asarray(genes.cpu() if isinstance(genes, torch.Tensor) else genes)
+        if host.ndim != 1 or (host.size and not np.issubdtype(host.dtype, np.integer)):
+            raise TypeError(f"{who}: genes must be a 1-d sequence of integer gene positions")
+        bad = np.nonzero((host < 0) | (host >= G))[0]
+        if bad.size:
+            raise IndexError(f"gene position {int(host[bad[0]])} is out of range for a group of {G} genes")
+        gidx, n = torch.as_tensor(host.astype(np.int32), device=dev), int(host.size)
+    if n <= 0:
+        raise ValueError(f"{who}: the gene selection is empty")
+    return gidx, n
+
+
 @torch.no_grad()
 def expected_expression(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
                         training: bool, nsplit: int, ws: Workspace, par=None, *, genes=None, what="mixture", library_size="latent",
@@ -909,22 +930,7 @@ def expected_expression(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     lib = library if logL is None else torch.full((B,), logL, dtype=torch.float32, device=dev)
     o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
     G = o.G
-    if genes is None:
-        gidx, n = None, G
-    elif isinstance(genes, torch.Tensor) and genes.is_cuda:
-        if genes.dtype != torch.int32 or genes.dim() != 1 or not genes.is_contiguous():
-            raise _abi.SpvError("expected_expression: a device gene list must be a contiguous 1-d int32 tensor")
-        gidx, n = genes, int(genes.numel())
-    else:
-        host = np.asarray(genes.cpu() if isinstance(genes, torch.Tensor) else genes)
-        if host.ndim != 1 or (host.size and not np.issubdtype(host.dtype, np.integer)):
-            raise TypeError("expected_expression: genes must be a 1-d sequence of integer gene positions")
-        bad = np.nonzero((host < 0) | (host >= G))[0]
-        if bad.size:
-            raise IndexError(f"gene position {int(host[bad[0]])} is out of range for a group of {G} genes")
-        gidx, n = torch.as_tensor(host.astype(np.int32), device=dev), int(host.size)
-    if n <= 0:
-        raise ValueError("expected_expression: the gene selection is empty")
+    gidx, n = _gene_selection(genes, G, dev, "expected_expression")
     if out is None:
         if accumulate:
             raise ValueError("expected_expression: accumulate=True needs the ``out`` array to add to")
@@ -938,3 +944,71 @@ def expected_expression(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     a.out, a.ld_out, a.alpha, a.accumulate = ptr(out), (out.stride(0) if out.shape[0] > 1 else max(out.shape[1], n)), float(alpha), int(bool(accumulate))
     _abi.call("spv_dec_expected", C.byref(o.p), C.byref(a), stream_ptr())
     return out[:B, :n]
+
+
+def sample_key(seed: int) -> int:
+    """the 64-bit Philox key of a user seed: the seed in the low word, a fixed tag in the high word (so that the count sampler's
+    key space is not the one spv_randn is keyed from for the same seed)"""
+    return ((0x53504C43 << 32) | (int(seed) & 0xFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
+
+
+@torch.no_grad()
+def sample_counts(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
+                  training: bool, nsplit: int, ws: Workspace, par=None, *, genes=None, library_size="latent", key: int = 0, sample: int = 0,
+                  cell_ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One draw per (cell, selected gene) from ONE group's NB mixture as int32 [B, n_genes] (spv_dec_sample;
+    module/spVIPESmodule.py:751-759): c ~ Bernoulli(pi), lam ~ Gamma(theta, (c ? rate_private : rate_shared) / theta) clamped at
+    1e8, x ~ Poisson(lam), with the rates, pi and theta = exp(px_r) of ``expected_expression`` (same operand preparation, same
+    ``genes`` and ``library_size`` handling, same honouring of ``training``).  The random bits of an element depend on
+    (``key``, gene id, cell id, ``sample``) only: ``cell_ids`` (int32 device tensor [B]; None = the row number) names the cells,
+    ``sample`` (0 .. 2^32 - 1) the draw, ``key`` (0 .. 2^64 - 1) the stream.  ``out``: int32 device tensor to write into, either
+    [>= B, >= n_genes] with unit column stride or [>= B, >= n_genes, S] viewed at one sample (``out3[:, :, s]``: column stride S);
+    rows >= B, columns >= n_genes and the other samples' elements stay untouched."""
+    from .data import expression_log_library
+
+    logL = expression_log_library(library_size)
+    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 64:
+        raise ValueError(f"sample_counts: key must be an integer in [0, 2^64), got {key!r}")
+    if isinstance(sample, bool) or not isinstance(sample, (int, np.integer)) or not 0 <= int(sample) < 1 << 32:
+        raise ValueError(f"sample_counts: sample must be an integer in [0, 2^32), got {sample!r}")
+    dev = private_log_z.device
+    B = private_log_z.shape[0]
+    lib = library if logL is None else torch.full((B,), logL, dtype=torch.float32, device=dev)
+    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
+    gidx, n = _gene_selection(genes, o.G, dev, "sample_counts")
+    if cell_ids is not None and (not isinstance(cell_ids, torch.Tensor) or not cell_ids.is_cuda or cell_ids.dtype != torch.int32 or cell_ids.dim() != 1
+                                 or cell_ids.numel() < B or not cell_ids.is_contiguous()):
+        raise _abi.SpvError(f"sample_counts: cell_ids must be a contiguous int32 device tensor of at least {B} entries")
+    if out is None:
+        out = torch.empty((B, n), dtype=torch.int32, device=dev)
+    elif (not out.is_cuda or out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] < B or out.shape[1] < n
+          or (out.shape[1] > 1 and out.stride(1) < 1) or (out.shape[0] > 1 and out.stride(0) < (n - 1) * max(out.stride(1), 1) + 1)):
+        raise _abi.SpvError(f"sample_counts: out must be an int32 device tensor [>= {B}, >= {n}] (a [B, n, S] array viewed at one sample is fine)")
+    p12 = o.par[12]
+    theta = torch.exp(p12 if (p12.is_contiguous() and p12.dtype == torch.float32) else p12.contiguous().float())
+    ld_gene = out.stride(1) if out.shape[1] > 1 else 1
+    a = SpvDecSampleArgs()
+    a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.nsplit = ptr(o.Am[0]), ptr(o.Am[1]), ptr(o.Wm[0]), ptr(o.Wm[1]), KMP, nsplit
+    a.genes, a.n_genes, a.ld_gene, a.theta, a.cell_ids = ptr(gidx), n, ld_gene, ptr(theta), ptr(cell_ids)
+    a.key, a.sample = int(key), int(sample)
+    a.out, a.ld_out = ptr(out), (out.stride(0) if out.shape[0] > 1 else (n - 1) * ld_gene + 1)
+    _abi.call("spv_dec_sample", C.byref(o.p), C.byref(a), stream_ptr())
+    return out[:B, :n]
+
+
+@torch.no_grad()
+def nbmix_sample(rate_p: torch.Tensor, rate_s: torch.Tensor, logit: torch.Tensor, theta: torch.Tensor, *, key: int = 0, sample: int = 0,
+                 cell_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [R, G] draws of the NB mixture over given fp32 device parameters [R, G] (``theta``: [G]) -- spv_nbmix_sample, the
+    sampler of ``sample_counts`` with gene id = column and cell id = ``cell_ids[row]`` (None: the row number)"""
+    R, G = rate_p.shape
+    for t in (rate_p, rate_s, logit):
+        if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (R, G) or not t.is_contiguous():
+            raise _abi.SpvError("nbmix_sample: the parameters must be contiguous fp32 device tensors of one shape [R, G]")
+    if not theta.is_cuda or theta.dtype != torch.float32 or tuple(theta.shape) != (G,) or not theta.is_contiguous():
+        raise _abi.SpvError("nbmix_sample: theta must be a contiguous fp32 device tensor [G]")
+    if cell_ids is not None and (not cell_ids.is_cuda or cell_ids.dtype != torch.int32 or tuple(cell_ids.shape) != (R,) or not cell_ids.is_contiguous()):
+        raise _abi.SpvError("nbmix_sample: cell_ids must be a contiguous int32 device tensor [R]")
+    out = torch.empty((R, G), dtype=torch.int32, device=rate_p.device)
+    _abi.call("spv_nbmix_sample", ptr(rate_p), ptr(rate_s), ptr(logit), G, ptr(theta), R, G, ptr(cell_ids), int(key), int(sample), ptr(out), G, stream_ptr())
+    return out

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, check_de_args, check_expression_args, check_target_sum, count_rest, count_table, csr_group_arrays, csr_to_dense, de_bank_rows, de_label_populations,
+from .data import (MinibatchSampler, check_de_args, check_expression_args, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays, csr_to_dense, de_bank_rows, de_label_populations,
                    de_pair_rows, de_populations, de_subsample, de_table, format_latent_results, group_var_names, is_sparse, latent_loader_mode, latent_steps, resolve_gene_list,
                    to_group_counts, to_sparse_group_counts)
 from .module import spVIPESmodule
@@ -283,6 +283,49 @@ class spVIPES:
                                                              out=blk[g], alpha=1.0 / n_samples, accumulate=smp > 0)
             for g in range(2):
                 blocks[g].append(blk[g].cpu().numpy() if return_numpy else blk[g])
+        cat = np.concatenate if return_numpy else torch.cat
+        return {g: cat(blocks[g])[:n[g]] for g in range(2)}
+
+    @torch.no_grad()
+    def posterior_predictive_sample(self, group_indices_list: List[List[int]], n_samples: int = 1, gene_list=None, library_size="latent", seed: int = 0,
+                                    batch_size: Optional[int] = None, return_numpy: bool = True, _noise=None) -> dict:
+        """Counts drawn from the model for every cell (scvi-tools' ``posterior_predictive_sample``): {0: int32 [n_cells_0, n_sel_0],
+        1: int32 [n_cells_1, n_sel_1]}, or [n_cells, n_sel, n_samples] (scvi-tools' layout) for ``n_samples > 1``; row i of group g
+        is the cell row i of ``get_latent_representation(...)["shared"][g]`` describes (the same minibatch walk).  Every sample runs
+        the encoders with freshly sampled latents (posterior predictive) and then draws, per cell and gene, from the decoder's NB
+        mixture (spVIPESmodule.py:751-759): c ~ Bernoulli(pi), lam ~ Gamma(theta, mu_c / theta), x ~ Poisson(lam), with
+        mu_1 = rate_private, mu_2 = rate_shared, pi = sigmoid(mixing logits), theta = exp(px_r) -- decode and draw in one HIP kernel.
+
+        ``gene_list`` / ``library_size``: as ``get_normalized_expression`` takes them.  "latent" is the model's own exp(library); the
+        library the encoder sees is the log of the summed LOG1P counts, so counts drawn at this scale
+        live in the log1p domain, not in raw counts; pass a positive number L for rates that sum to L over the group's genes.
+        ``seed`` (0 .. 2^32 - 1) keys the count draws: the draw of (cell, gene, sample) depends on the seed, the cell's adata row
+        number, the gene's position within the group and the sample index only, not on ``batch_size``, the gene selection or the
+        device.  The latents' noise is the module's own (torch's generator) unless ``_noise`` injects it, so two calls agree bit for
+        bit only with the same seed AND the same latent noise.
+        ``return_numpy``: each step's block is copied to the host as it completes; False returns device tensors.
+        ``_noise`` (tests only): callable (draw, B0, B1) -> injected standard-normal draws, draw = step * n_samples + sample."""
+        from .dec_ops import sample_key
+
+        n_samples, seed, _log_l = check_sample_args(n_samples, seed, library_size)
+        n = [len(g) for g in group_indices_list]
+        sel = resolve_gene_list(gene_list, [int(self.module.input_dims[g]) for g in range(2)], group_var_names(self.adata))
+        dev_sel = [None if s is None else torch.as_tensor(s, dtype=torch.int32, device=self.device) for s in sel]
+        n_sel = [int(self.module.input_dims[g]) if sel[g] is None else int(sel[g].size) for g in range(2)]
+        obs = [torch.as_tensor(np.asarray(self.obs_idx[g]), dtype=torch.int32, device=self.device) for g in range(2)]
+        key = sample_key(seed)
+        blocks = {0: [], 1: []}
+        for step, tensors, B in self._eval_minibatches(group_indices_list, batch_size, None):
+            blk = [torch.empty((B[g], n_sel[g], n_samples), dtype=torch.int32, device=self.device) for g in range(2)]
+            ids = [obs[g][tensors[g]["rows"].long()].contiguous() for g in range(2)]
+            for smp in range(n_samples):
+                out = self._infer(tensors, _noise, step * n_samples + smp, B[0], B[1])
+                for g in range(2):
+                    self.module.sample_counts(out, g, genes=dev_sel[g], library_size=library_size, key=key, sample=smp, cell_ids=ids[g],
+                                              out=blk[g][:, :, smp])
+            for g in range(2):
+                b = blk[g] if n_samples > 1 else blk[g][:, :, 0]
+                blocks[g].append(b.cpu().numpy() if return_numpy else b)
         cat = np.concatenate if return_numpy else torch.cat
         return {g: cat(blocks[g])[:n[g]] for g in range(2)}
 

@@ -727,6 +727,26 @@ class spVIPESmodule(nn.Module):
                                    self._workspace(group, lib.device), par=par, genes=genes, what=what, library_size=library_size,
                                    out=out, alpha=alpha, accumulate=accumulate)
 
+    @torch.no_grad()
+    def sample_counts(self, inference_outputs, group: int, *, genes=None, library_size="latent", use_mean: bool = False, key: int = 0,
+                      sample: int = 0, cell_ids=None, out=None) -> torch.Tensor:
+        """One draw of counts from the decoder's NB mixture for one group of the minibatch ``inference_outputs`` describes (the output
+        of this module's LATEST ``inference`` call, as for ``expected_expression``), int32 [B, n_genes]: per (cell, gene)
+        c ~ Bernoulli(pi), lam ~ Gamma(theta, mu_c / theta), x ~ Poisson(lam) with mu_1 = rate_private, mu_2 = rate_shared,
+        pi = sigmoid(mixing logits), theta = exp(px_r) (NegativeBinomialMixture, spVIPESmodule.py:751-759).  Decodes the sampled
+        latents or, with ``use_mean``, the posterior means; ``genes`` / ``library_size`` and the handling of ``self.training`` are
+        ``expected_expression``'s.  ``key`` / ``sample`` / ``cell_ids`` / ``out``: dec_ops.sample_counts (one fused HIP kernel,
+        spv_dec_sample; neither the rates nor the logits are written anywhere)."""
+        from .dec_ops import sample_counts
+
+        ps, qs = inference_outputs["private_stats"][group], inference_outputs["poe_stats"][group]
+        pl, ql = (ps["logtheta_loc"], qs["logtheta_loc"]) if use_mean else (ps["log_z"], qs["logtheta_log_z"])
+        lib = inference_outputs["library"][group].detach()
+        first, second, par = self._decoder_operands(group, pl.detach(), ql.detach())
+        return sample_counts(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
+                             self._workspace(group, lib.device), par=par, genes=genes, library_size=library_size, key=key, sample=sample,
+                             cell_ids=cell_ids, out=out)
+
     def loss(self, tensors_by_group, inference_outputs, generative_outputs, kl_weight: float = 1.0):
         """spVIPESmodule.py:809-899."""
         from .dec_ops import DecoderFused, decoder_params
