@@ -808,29 +808,39 @@ extern "C" int spv_dec_materialize(const spv_dec_params* q, float* scale_p, floa
   return launch_status("spv_dec_materialize");
 }
 
-extern "C" int spv_dec_expected(const spv_dec_params* q, const spv_dec_expected_args* x, void* stream) {
-  DecParams p;
+// What spv_dec_expected and spv_dec_sample share ahead of their launches: the decoder parameters, the checks of the logits operands and
+// of the gene selection (reported under the entry point's name ``who``), and the grid.  X: either argument struct.
+template <typename X>
+static int readout_prepare(const spv_dec_params* q, const char* who, const X* x, DecParams& p, dim3& grid) {
   int rc = to_dec(q, p);
   if (rc != SPV_OK) return rc;
-  if (!x) return fail(SPV_ERR_ARG, "spv_dec_expected: null arguments%s");
-  if (!p.a_p || !p.a_s || !x->Am_hi || !x->Wm_hi || !x->out) return fail(SPV_ERR_ARG, "spv_dec_expected: null pointer%s");
-  if (x->K <= 0 || (x->K % 32) || x->K > DX_KMAX) return fail(SPV_ERR_ARG, "spv_dec_expected: K must be a multiple of 32, at most 320%s");
-  if (x->nsplit != 1 && x->nsplit != 3) return fail(SPV_ERR_ARG, "spv_dec_expected: nsplit must be 1 or 3%s");
-  if (x->nsplit == 3 && (!x->Am_lo || !x->Wm_lo)) return fail(SPV_ERR_ARG, "spv_dec_expected: nsplit=3 needs lo images%s");
+  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
+  if (!p.a_p || !p.a_s || !x->Am_hi || !x->Wm_hi || !x->out) return fail(SPV_ERR_ARG, "%s: null pointer", who);
+  if (x->K <= 0 || (x->K % 32) || x->K > DX_KMAX) return fail(SPV_ERR_ARG, "%s: K must be a multiple of 32, at most 320", who);
+  if (x->nsplit != 1 && x->nsplit != 3) return fail(SPV_ERR_ARG, "%s: nsplit must be 1 or 3", who);
+  if (x->nsplit == 3 && (!x->Am_lo || !x->Wm_lo)) return fail(SPV_ERR_ARG, "%s: nsplit=3 needs lo images", who);
   if ((reinterpret_cast<uintptr_t>(x->Am_hi) | reinterpret_cast<uintptr_t>(x->Wm_hi) | reinterpret_cast<uintptr_t>(x->Am_lo) | reinterpret_cast<uintptr_t>(x->Wm_lo)) & 15)
-    return fail(SPV_ERR_ARG, "spv_dec_expected: operand images must be 16-byte aligned%s");
-  if (x->n_genes <= 0 || (!x->genes && x->n_genes > p.G)) return fail(SPV_ERR_ARG, "spv_dec_expected: n_genes must be positive (and at most G without a gene list)%s");
-  if (x->what < 0 || x->what > 3) return fail(SPV_ERR_ARG, "spv_dec_expected: what must be 0 (mixture), 1 (private), 2 (shared) or 3 (mixing weight)%s");
-  if (x->ld_out < x->n_genes) return fail(SPV_ERR_ARG, "spv_dec_expected: ld_out < n_genes%s");
-  const DecExpArgs a{(const bf16_t*)x->Am_hi, (const bf16_t*)x->Am_lo, (const bf16_t*)x->Wm_hi, (const bf16_t*)x->Wm_lo, x->K,
-                     x->genes, x->n_genes, x->what, x->out, (long)x->ld_out, x->alpha, x->accumulate};
+    return fail(SPV_ERR_ARG, "%s: operand images must be 16-byte aligned", who);
+  if (x->n_genes <= 0 || (!x->genes && x->n_genes > p.G)) return fail(SPV_ERR_ARG, "%s: n_genes must be positive (and at most G without a gene list)", who);
   // one workgroup per 32 cells and gene slice; each of its 4 waves walks every (4 gy)-th 32-gene tile.  ~8 workgroups per CU keep
   // the gathers of the gene rows covered; never more slices than there are tiles for the waves.
   const int gx = p.Bp / DX_CELLS, tiles = (x->n_genes + 31) / 32;
   int gy = (2048 + gx - 1) / gx;
   if (gy > (tiles + 3) / 4) gy = (tiles + 3) / 4;
   if (gy < 1) gy = 1;
-  const dim3 grid(gx, gy);
+  grid = dim3(gx, gy);
+  return SPV_OK;
+}
+
+extern "C" int spv_dec_expected(const spv_dec_params* q, const spv_dec_expected_args* x, void* stream) {
+  DecParams p;
+  dim3 grid;
+  int rc = readout_prepare(q, "spv_dec_expected", x, p, grid);
+  if (rc != SPV_OK) return rc;
+  if (x->what < 0 || x->what > 3) return fail(SPV_ERR_ARG, "spv_dec_expected: what must be 0 (mixture), 1 (private), 2 (shared) or 3 (mixing weight)%s");
+  if (x->ld_out < x->n_genes) return fail(SPV_ERR_ARG, "spv_dec_expected: ld_out < n_genes%s");
+  const DecExpArgs a{(const bf16_t*)x->Am_hi, (const bf16_t*)x->Am_lo, (const bf16_t*)x->Wm_hi, (const bf16_t*)x->Wm_lo, x->K,
+                     x->genes, x->n_genes, x->what, x->out, (long)x->ld_out, x->alpha, x->accumulate};
   hipStream_t s = (hipStream_t)stream;
   const bool wide = dec_kw(q) == 2;
   if (x->nsplit == 3 && wide) hipLaunchKernelGGL((dec_expected_kernel<3, 2>), grid, dim3(256), 0, s, p, a);
@@ -842,26 +852,14 @@ extern "C" int spv_dec_expected(const spv_dec_params* q, const spv_dec_expected_
 
 extern "C" int spv_dec_sample(const spv_dec_params* q, const spv_dec_sample_args* x, void* stream) {
   DecParams p;
-  int rc = to_dec(q, p);
+  dim3 grid;
+  int rc = readout_prepare(q, "spv_dec_sample", x, p, grid);
   if (rc != SPV_OK) return rc;
-  if (!x) return fail(SPV_ERR_ARG, "spv_dec_sample: null arguments%s");
-  if (!p.a_p || !p.a_s || !x->Am_hi || !x->Wm_hi || !x->theta || !x->out) return fail(SPV_ERR_ARG, "spv_dec_sample: null pointer%s");
-  if (x->K <= 0 || (x->K % 32) || x->K > DX_KMAX) return fail(SPV_ERR_ARG, "spv_dec_sample: K must be a multiple of 32, at most 320%s");
-  if (x->nsplit != 1 && x->nsplit != 3) return fail(SPV_ERR_ARG, "spv_dec_sample: nsplit must be 1 or 3%s");
-  if (x->nsplit == 3 && (!x->Am_lo || !x->Wm_lo)) return fail(SPV_ERR_ARG, "spv_dec_sample: nsplit=3 needs lo images%s");
-  if ((reinterpret_cast<uintptr_t>(x->Am_hi) | reinterpret_cast<uintptr_t>(x->Wm_hi) | reinterpret_cast<uintptr_t>(x->Am_lo) | reinterpret_cast<uintptr_t>(x->Wm_lo)) & 15)
-    return fail(SPV_ERR_ARG, "spv_dec_sample: operand images must be 16-byte aligned%s");
-  if (x->n_genes <= 0 || (!x->genes && x->n_genes > p.G)) return fail(SPV_ERR_ARG, "spv_dec_sample: n_genes must be positive (and at most G without a gene list)%s");
+  if (!x->theta) return fail(SPV_ERR_ARG, "spv_dec_sample: null pointer%s");
   if (x->ld_gene < 1) return fail(SPV_ERR_ARG, "spv_dec_sample: ld_gene < 1%s");
   if (x->ld_out < (int64_t)(x->n_genes - 1) * x->ld_gene + 1) return fail(SPV_ERR_ARG, "spv_dec_sample: ld_out < (n_genes - 1) * ld_gene + 1%s");
   const DecSampleArgs a{(const bf16_t*)x->Am_hi, (const bf16_t*)x->Am_lo, (const bf16_t*)x->Wm_hi, (const bf16_t*)x->Wm_lo, x->K,
                         x->genes, x->n_genes, x->theta, x->cell_ids, (unsigned long long)x->key, x->sample, x->out, (long)x->ld_out, x->ld_gene};
-  // the grid of spv_dec_expected: one workgroup per 32 cells and gene slice, each of its 4 waves walks every (4 gy)-th 32-gene tile
-  const int gx = p.Bp / DX_CELLS, tiles = (x->n_genes + 31) / 32;
-  int gy = (2048 + gx - 1) / gx;
-  if (gy > (tiles + 3) / 4) gy = (tiles + 3) / 4;
-  if (gy < 1) gy = 1;
-  const dim3 grid(gx, gy);
   hipStream_t s = (hipStream_t)stream;
   const bool wide = dec_kw(q) == 2;
   if (x->nsplit == 3 && wide) hipLaunchKernelGGL((dec_sample_kernel<3, 2>), grid, dim3(256), 0, s, p, a);

@@ -25,6 +25,7 @@ constexpr int DX_CELLS = 32;     // cells per workgroup
 constexpr int DX_KMAX = 320;     // widest logits operand
 constexpr int DX_APITCH = 328;   // LDS row pitch of the staged Am rows in bf16 (164 dwords = 4 mod 32: conflict-free 16-byte row reads)
 constexpr int DX_TPITCH = 36;    // row pitch of a wave's transpose tile in floats
+constexpr int DX_PLANE = DX_CELLS * DX_APITCH;   // one staged plane of Am (the lo plane follows the hi plane in fp32 mode)
 
 struct DecExpArgs {
   const bf16_t *Am_hi, *Am_lo, *Wm_hi, *Wm_lo;   // [Bp][K], [Gp][K]
@@ -54,33 +55,76 @@ __device__ __forceinline__ float dx_value(int what, float rp, float rs, float lo
 
 // one K step of 16 of the logits contraction: A = the lane's gene row of Wm (global), B = the lane's cell row of Am (LDS)
 template <int NSPLIT>
-__device__ __forceinline__ f16v dx_logit_step(const DecExpArgs& a, long wrow, const bf16_t* arow, int plane, int k, f16v acc) {
-  const s8v wh = *reinterpret_cast<const s8v*>(a.Wm_hi + wrow + k);
+__device__ __forceinline__ f16v dx_logit_step(const bf16_t* wm_hi, const bf16_t* wm_lo, long wrow, const bf16_t* arow, int k, f16v acc) {
+  const s8v wh = *reinterpret_cast<const s8v*>(wm_hi + wrow + k);
   const s8v ah = *reinterpret_cast<const s8v*>(arow + k);
   s8v wl = wh, al = ah;
   if constexpr (NSPLIT == 3) {
-    wl = *reinterpret_cast<const s8v*>(a.Wm_lo + wrow + k);
-    al = *reinterpret_cast<const s8v*>(arow + plane + k);
+    wl = *reinterpret_cast<const s8v*>(wm_lo + wrow + k);
+    al = *reinterpret_cast<const s8v*>(arow + DX_PLANE + k);
   }
   return mfma32_split<NSPLIT>(wh, wl, ah, al, acc);
 }
 
+// The decode front-end that dec_expected_kernel and dec_sample_kernel (spv_dec_sample.h) share: everything up to a tile's yp / ys / logit
+// accumulators.  Pointers are parameters, so a kernel may hand in laundered copies (nbs_in_vgpr).
+
+// stage the workgroup's 32 cells' rows of Am (s_am: one plane, two in fp32 mode); the caller's __syncthreads() publishes them
+template <int NSPLIT>
+__device__ __forceinline__ void dx_stage_am(bf16_t* s_am, const bf16_t* Am_hi, const bf16_t* Am_lo, int K, int cell0, int tid) {
+  const int kch = K >> 3;   // 16-byte pieces per row
+  for (int i = tid; i < DX_CELLS * kch; i += 256) {
+    const int row = i / kch, ch = i - row * kch;
+    const long src = (long)(cell0 + row) * K + 8 * ch;
+    *reinterpret_cast<u4v*>(s_am + row * DX_APITCH + 8 * ch) = *reinterpret_cast<const u4v*>(Am_hi + src);
+    if constexpr (NSPLIT == 3) *reinterpret_cast<u4v*>(s_am + DX_PLANE + row * DX_APITCH + 8 * ch) = *reinterpret_cast<const u4v*>(Am_lo + src);
+  }
+}
+
+// lane r's gene of the tile at sel0: a column beyond the selection re-reads the last one (never stored); ids are clamped into [0, G)
+__device__ __forceinline__ int dx_tile_gene(const int* genes, int n_genes, int sel0, int r, int G) {
+  const int si = min(sel0 + r, n_genes - 1);
+  const int g = genes ? genes[si] : si;
+  return min(max(g, 0), G - 1);
+}
+
+// gene g's 32 x 32 tile against the staged cells: yp / ys by ps_eval, acc = the mixing logits (arow: the lane's staged row of Am)
+template <int NSPLIT, int KW>
+__device__ __forceinline__ void dx_decode_tile(const bf16_t* wps_hi, const bf16_t* wps_lo, const bf16_t* wm_hi, const bf16_t* wm_lo, int K, int g, int h,
+                                               const bf16_t* arow, const PsFragsK<KW>& cf, f16v& yp, f16v& ys, f16v& acc) {
+  // ---- rate heads: the gene's rows of the folded regressor image ------------------------------------------------------
+  PsWK<KW> w;
+  {
+    const long off = (long)g * DEC_KPS_W<KW> + 8 * h;
+#pragma unroll
+    for (int s = 0; s < 3 * KW; ++s) {
+      w.hi[s] = *reinterpret_cast<const s8v*>(wps_hi + off + 16 * s);
+      w.lo[s] = *reinterpret_cast<const s8v*>(wps_lo + off + 16 * s);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) { yp[q] = 0.f; ys[q] = 0.f; acc[q] = 0.f; }
+  ps_eval(w, cf, yp, ys);
+  // ---- mixing logits of the tile: K steps of 16 in order ---------------------------------------------------------------
+  const long wrow = (long)g * K + 8 * h;
+  if (K == DX_KMAX) {   // the width dec_ops packs: fully unrolled, so the gathers of the gene's row are all issued ahead of the MFMA chain
+#pragma unroll
+    for (int k = 0; k < DX_KMAX; k += 16) acc = dx_logit_step<NSPLIT>(wm_hi, wm_lo, wrow, arow, k, acc);
+  } else {
+    for (int k0 = 0; k0 < K; k0 += 32) {   // (K % 32 == 0)
+      acc = dx_logit_step<NSPLIT>(wm_hi, wm_lo, wrow, arow, k0, acc);
+      acc = dx_logit_step<NSPLIT>(wm_hi, wm_lo, wrow, arow, k0 + 16, acc);
+    }
+  }
+}
+
 template <int NSPLIT, int KW>
 __global__ __launch_bounds__(256) void dec_expected_kernel(DecParams p, DecExpArgs a) {
-  constexpr int DEC_KPS = DEC_KPS_W<KW>;
-  constexpr int PLANE = DX_CELLS * DX_APITCH;
-  __shared__ __attribute__((aligned(16))) bf16_t s_am[(NSPLIT == 3 ? 2 : 1) * PLANE];
+  __shared__ __attribute__((aligned(16))) bf16_t s_am[(NSPLIT == 3 ? 2 : 1) * DX_PLANE];
   __shared__ __attribute__((aligned(16))) float s_t[4][32 * DX_TPITCH];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r = lane & 31;
   const int cell0 = blockIdx.x * DX_CELLS;   // (cell0 + 32 <= Bp: the grid has Bp / 32 columns)
-  // ---- stage the 32 cells' rows of Am --------------------------------------------------------------------------------
-  const int kch = a.K >> 3;   // 16-byte pieces per row
-  for (int i = tid; i < DX_CELLS * kch; i += 256) {
-    const int row = i / kch, ch = i - row * kch;
-    const long src = (long)(cell0 + row) * a.K + 8 * ch;
-    *reinterpret_cast<u4v*>(s_am + row * DX_APITCH + 8 * ch) = *reinterpret_cast<const u4v*>(a.Am_hi + src);
-    if constexpr (NSPLIT == 3) *reinterpret_cast<u4v*>(s_am + PLANE + row * DX_APITCH + 8 * ch) = *reinterpret_cast<const u4v*>(a.Am_lo + src);
-  }
+  dx_stage_am<NSPLIT>(s_am, a.Am_hi, a.Am_lo, a.K, cell0, tid);
   PsFragsK<KW> cf;
   load_ps_cell_frags(p, cell0, lane, cf);
   const float ap = p.a_p[cell0 + r], as = p.a_s[cell0 + r];
@@ -90,35 +134,8 @@ __global__ __launch_bounds__(256) void dec_expected_kernel(DecParams p, DecExpAr
   const bf16_t* const arow = s_am + r * DX_APITCH + 8 * h;
   for (int t = blockIdx.y * 4 + wave; t < ntiles; t += gridDim.y * 4) {
     const int sel0 = t * 32;
-    // this lane's gene: a column beyond the selection re-reads the last one (never stored); ids are clamped into [0, G)
-    const int si = min(sel0 + r, a.n_genes - 1);
-    int g = a.genes ? a.genes[si] : si;
-    g = min(max(g, 0), p.G - 1);
-    // ---- rate heads: the gene's rows of the folded regressor image ------------------------------------------------------
-    PsWK<KW> w;
-    {
-      const long off = (long)g * DEC_KPS + 8 * h;
-#pragma unroll
-      for (int s = 0; s < 3 * KW; ++s) {
-        w.hi[s] = *reinterpret_cast<const s8v*>(p.Wps_hi + off + 16 * s);
-        w.lo[s] = *reinterpret_cast<const s8v*>(p.Wps_lo + off + 16 * s);
-      }
-    }
     f16v yp, ys, acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { yp[q] = 0.f; ys[q] = 0.f; acc[q] = 0.f; }
-    ps_eval(w, cf, yp, ys);
-    // ---- mixing logits of the tile: K steps of 16 in order ---------------------------------------------------------------
-    const long wrow = (long)g * a.K + 8 * h;
-    if (a.K == DX_KMAX) {   // the width dec_ops packs: fully unrolled, so the gathers of the gene's row are all issued ahead of the MFMA chain
-#pragma unroll
-      for (int k = 0; k < DX_KMAX; k += 16) acc = dx_logit_step<NSPLIT>(a, wrow, arow, PLANE, k, acc);
-    } else {
-      for (int k0 = 0; k0 < a.K; k0 += 32) {   // (K % 32 == 0)
-        acc = dx_logit_step<NSPLIT>(a, wrow, arow, PLANE, k0, acc);
-        acc = dx_logit_step<NSPLIT>(a, wrow, arow, PLANE, k0 + 16, acc);
-      }
-    }
+    dx_decode_tile<NSPLIT, KW>(p.Wps_hi, p.Wps_lo, a.Wm_hi, a.Wm_lo, a.K, dx_tile_gene(a.genes, a.n_genes, sel0, r, p.G), h, arow, cf, yp, ys, acc);
     // ---- values -> the wave's LDS tile [cell r][gene crow(q, h)] ---------------------------------------------------------
 #pragma unroll
     for (int qq = 0; qq < 4; ++qq) {

@@ -163,8 +163,9 @@ __global__ __launch_bounds__(256) void nbmix_sample_kernel(NbMixArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// decode and draw: dec_expected_kernel's workgroup, staging, gene-row gathers, ps_eval and logits steps; then one nbmix_draw per
-// accumulator element in place of dx_value, and the same turn through the wave's LDS tile for the store.
+// decode and draw: dec_expected_kernel's workgroup and its decode front-end, shared as code (dx_stage_am, dx_tile_gene, dx_decode_tile
+// of spv_dec_expected.h); then one nbmix_draw per accumulator element in place of dx_value, and the same turn through the wave's LDS
+// tile for the store.
 //   * The accumulator layout is lane = cell, registers = genes: the id and theta of the tile's 32 genes, which lane r < 32 holds
 //     for gene r, go through 32-entry LDS rows of the wave before the draws.
 //   * The 16 draws of a lane run as a ROLLED loop (the sampler's rejection loops sixteen times over would be ~16x the code); the
@@ -195,23 +196,14 @@ __device__ __forceinline__ f16v nbs_rot(const f16v& v) { return __builtin_shuffl
 
 template <int NSPLIT, int KW>
 __global__ __launch_bounds__(256) void dec_sample_kernel(DecParams p, DecSampleArgs a) {
-  constexpr int DEC_KPS = DEC_KPS_W<KW>;
-  constexpr int PLANE = DX_CELLS * DX_APITCH;
-  __shared__ __attribute__((aligned(16))) bf16_t s_am[(NSPLIT == 3 ? 2 : 1) * PLANE];
+  __shared__ __attribute__((aligned(16))) bf16_t s_am[(NSPLIT == 3 ? 2 : 1) * DX_PLANE];
   __shared__ __attribute__((aligned(16))) int s_t[4][32 * DX_TPITCH];
   __shared__ int s_gid[4][32];
   __shared__ float s_th[4][32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r = lane & 31;
   const int cell0 = blockIdx.x * DX_CELLS;   // (cell0 + 32 <= Bp: the grid has Bp / 32 columns)
   const bf16_t* const wps_hi = nbs_in_vgpr(p.Wps_hi), * const wps_lo = nbs_in_vgpr(p.Wps_lo);
-  // ---- stage the 32 cells' rows of Am --------------------------------------------------------------------------------
-  const int kch = a.K >> 3;   // 16-byte pieces per row
-  for (int i = tid; i < DX_CELLS * kch; i += 256) {
-    const int row = i / kch, ch = i - row * kch;
-    const long src = (long)(cell0 + row) * a.K + 8 * ch;
-    *reinterpret_cast<u4v*>(s_am + row * DX_APITCH + 8 * ch) = *reinterpret_cast<const u4v*>(a.Am_hi + src);
-    if constexpr (NSPLIT == 3) *reinterpret_cast<u4v*>(s_am + PLANE + row * DX_APITCH + 8 * ch) = *reinterpret_cast<const u4v*>(a.Am_lo + src);
-  }
+  dx_stage_am<NSPLIT>(s_am, a.Am_hi, a.Am_lo, a.K, cell0, tid);
   PsFragsK<KW> cf;
   load_ps_cell_frags(p, cell0, lane, cf);
   const float ap = p.a_p[cell0 + r], as = p.a_s[cell0 + r];
@@ -220,7 +212,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(DecParams p, DecSampleA
   NbStream st{{(unsigned)a.key, (unsigned)(a.key >> 32)}, 0u, (unsigned)cell_id, a.sample};
   __syncthreads();
   const int ntiles = (a.n_genes + 31) >> 5;
-  const DecExpArgs xa{nullptr, nullptr, nbs_in_vgpr(a.Wm_hi), NSPLIT == 3 ? nbs_in_vgpr(a.Wm_lo) : nullptr, a.K, nullptr, 0, 0, nullptr, 0, 0.f, 0};
+  const bf16_t* const wm_hi = nbs_in_vgpr(a.Wm_hi), * const wm_lo = NSPLIT == 3 ? nbs_in_vgpr(a.Wm_lo) : nullptr;
   const int* const genes = a.genes ? nbs_in_vgpr(a.genes) : nullptr;
   const float* const theta = nbs_in_vgpr(a.theta);
   int* const out = nbs_in_vgpr(a.out);
@@ -228,36 +220,10 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(DecParams p, DecSampleA
   const bf16_t* const arow = s_am + r * DX_APITCH + 8 * h;
   for (int t = blockIdx.y * 4 + wave; t < ntiles; t += gridDim.y * 4) {
     const int sel0 = t * 32;
-    // this lane's gene: a column beyond the selection re-reads the last one (never drawn, never stored); ids are clamped into [0, G)
-    const int si = min(sel0 + r, a.n_genes - 1);
-    int g = genes ? genes[si] : si;
-    g = min(max(g, 0), p.G - 1);
+    const int g = dx_tile_gene(genes, a.n_genes, sel0, r, p.G);   // (a column beyond the selection: never drawn, never stored)
     if (h == 0) { s_gid[wave][r] = g; s_th[wave][r] = theta[g]; }
-    // ---- rate heads: the gene's rows of the folded regressor image ------------------------------------------------------
-    PsWK<KW> w;
-    {
-      const long off = (long)g * DEC_KPS + 8 * h;
-#pragma unroll
-      for (int s = 0; s < 3 * KW; ++s) {
-        w.hi[s] = *reinterpret_cast<const s8v*>(wps_hi + off + 16 * s);
-        w.lo[s] = *reinterpret_cast<const s8v*>(wps_lo + off + 16 * s);
-      }
-    }
     f16v yp, ys, acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { yp[q] = 0.f; ys[q] = 0.f; acc[q] = 0.f; }
-    ps_eval(w, cf, yp, ys);
-    // ---- mixing logits of the tile: K steps of 16 in order ---------------------------------------------------------------
-    const long wrow = (long)g * a.K + 8 * h;
-    if (a.K == DX_KMAX) {
-#pragma unroll
-      for (int k = 0; k < DX_KMAX; k += 16) acc = dx_logit_step<NSPLIT>(xa, wrow, arow, PLANE, k, acc);
-    } else {
-      for (int k0 = 0; k0 < a.K; k0 += 32) {   // (K % 32 == 0)
-        acc = dx_logit_step<NSPLIT>(xa, wrow, arow, PLANE, k0, acc);
-        acc = dx_logit_step<NSPLIT>(xa, wrow, arow, PLANE, k0 + 16, acc);
-      }
-    }
+    dx_decode_tile<NSPLIT, KW>(wps_hi, wps_lo, wm_hi, wm_lo, a.K, g, h, arow, cf, yp, ys, acc);
     dx_wave_sync();   // s_gid / s_th of this tile are visible to the wave
     // ---- draws (lane-divergent from here to the hand-over) -> the wave's LDS tile [cell r][gene crow(q, h)] ------------------
 #pragma clang loop unroll(disable)

@@ -28,6 +28,16 @@ N_DEC_PARAMS = 13  # Wp, gamma_p, beta_p, Ws, gamma_s, beta_s, Wa, ba, gamma_a, 
 KMP = 320
 
 
+def _cont(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself if it is contiguous fp32, else such a copy"""
+    return t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
+
+
+def _theta(par) -> torch.Tensor:
+    """theta = exp(px_r) of a decoder parameter set (module/spVIPESmodule.py:758)"""
+    return torch.exp(_cont(par[12]))
+
+
 def dec_slots(decoder):
     """the K-slot layout (_abi.DecSlots) a decoder's regressor operand images use: chosen per module (spVIPESmodule decoder_slots)"""
     return getattr(decoder, "dec_slots", DEC_NARROW)
@@ -239,7 +249,7 @@ class DecoderFused(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         lat = [(tensors[2 * g], tensors[2 * g + 1]) for g in range(NG)]
         par = [tensors[2 * NG + g * N_DEC_PARAMS: 2 * NG + (g + 1) * N_DEC_PARAMS] for g in range(NG)]
-        kls = [t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float() for t in tensors[2 * NG + NG * N_DEC_PARAMS:]]
+        kls = [_cont(t) for t in tensors[2 * NG + NG * N_DEC_PARAMS:]]
         if len(kls) != n_kl or n_kl > 4:
             raise _abi.SpvError("DecoderFused: expected n_kl <= 4 KL vectors after the parameters")
         dev = lat[0][0].device
@@ -261,7 +271,6 @@ class DecoderFused(torch.autograd.Function):
         Gps = [round_up(G, 256) for G in Gs]  # 256: the logits GEMM runs 256-gene workgroup tiles
         mlo = nsplit == 3
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        cont = lambda t: t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
         # ---- 1. latent slicing: zcat = [z_private | z_shared] --------------------------------------
         zcat = [new(B, nt) for _ in range(NG)]
         za = SpvZsplitArgs()
@@ -273,7 +282,7 @@ class DecoderFused(torch.autograd.Function):
         fused_pack = bool(_ops.FUSED_PACK)
         za.ld_am, za.am_col, za.am_cols, za.Bp = KMP, n_m, KMP - n_m, Bp
         for g in range(NG):
-            pz, qz = cont(lat[g][0]), cont(lat[g][1])
+            pz, qz = _cont(lat[g][0]), _cont(lat[g][1])
             keep += [pz, qz]
             za.priv[g], za.poe[g], za.zcat[g] = ptr(pz), ptr(qz), ptr(zcat[g])
             if fused_pack:
@@ -321,16 +330,16 @@ class DecoderFused(torch.autograd.Function):
             for g in range(NG):
                 Wm_hi, Wm_lo = _bf16_image(ws[g], "dec_Wm", Gps[g], KMP, mlo)
                 if Wm_lo is not None or ws[g].fresh.get("dec_Wm") != _ops.image_token(par[g][10], par[g][11]):   # (else: Adam has just rewritten it)
-                    _pack(cont(par[g][10]), Wm_hi, Wm_lo, extra_col=cont(par[g][11]))
+                    _pack(_cont(par[g][10]), Wm_hi, Wm_lo, extra_col=_cont(par[g][11]))
                 gene_tab = ws[g].get("dec_gene_tab", (Gps[g], 4), torch.float32)
                 cnt_tab = ws[g].get("dec_cnt_tab", (NB_CMAX, Gps[g], 2), torch.float32)
                 if not pair:
-                    _abi.call("spv_dec_tables", ptr(cont(par[g][12])), Gs[g], Gps[g], ptr(gene_tab), ptr(cnt_tab), stream_ptr())
+                    _abi.call("spv_dec_tables", ptr(_cont(par[g][12])), Gs[g], Gps[g], ptr(gene_tab), ptr(cnt_tab), stream_ptr())
                 Wm_img.append((Wm_hi, Wm_lo))
                 tabs.append((gene_tab, cnt_tab))
             if pair:   # one grid for both groups' tables
                 tg = (SpvDecGroup * NG)()
-                px_keep = [cont(par[g][12]) for g in range(NG)]
+                px_keep = [_cont(par[g][12]) for g in range(NG)]
                 for g in range(NG):
                     tg[g].px_r, tg[g].p.G, tg[g].p.Gp, tg[g].p.gene_tab, tg[g].p.cnt_tab = ptr(px_keep[g]), Gs[g], Gps[g], ptr(tabs[g][0]), ptr(tabs[g][1])
                 _abi.call("spv_dec_tables_grouped", tg, NG, stream_ptr())
@@ -347,7 +356,7 @@ class DecoderFused(torch.autograd.Function):
             for g in range(NG):
                 bnm = decoders[g].sigmoid_decoder.bn
                 q = tb_.p[g]
-                q.W, q.bias, q.gamma, q.beta = ptr(cont(par[g][6])), ptr(par[g][7]), ptr(par[g][8]), ptr(par[g][9])
+                q.W, q.bias, q.gamma, q.beta = ptr(_cont(par[g][6])), ptr(par[g][7]), ptr(par[g][8]), ptr(par[g][9])
                 q.running_mean, q.running_var = ptr(bnm.running_mean), ptr(bnm.running_var)
                 q.zsum, q.zz, q.Wf, q.cf, q.stat, q.N, q.K = ptr(zsum_t[g]), ptr(zz_t[g]), ptr(Wf[g]), ptr(cf[g]), ptr(tstat[g]), n_m, nt
             _abi.call("spv_trunk_fold_fwd", C.byref(tb_), stream_ptr())
@@ -434,12 +443,12 @@ class DecoderFused(torch.autograd.Function):
                   nb_cell_tiles=_nb_cell_tiles(Bp, Gp), kslots=sl.kslots,
               )
               if pair:
-                  lib_keep.append(cont(library[g].flatten()))
+                  lib_keep.append(_cont(library[g].flatten()))
                   q = dgrp[g]
                   q.p, q.library = p, ptr(lib_keep[-1])
                   q.Am_hi, q.Am_lo, q.Wm_hi, q.Wm_lo, q.K, q.nsplit = ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, nsplit
               else:
-                  _abi.call("spv_dec_lse", C.byref(p), ptr(cont(library[g].flatten())), stream_ptr())
+                  _abi.call("spv_dec_lse", C.byref(p), ptr(_cont(library[g].flatten())), stream_ptr())
                   if lse_first:
                       _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(logits), int(mlo), stream_ptr())
                   _abi.call("spv_dec_nb_fwd", C.byref(p), int(need_grad), stream_ptr())
@@ -779,9 +788,8 @@ def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, p
     images, the tiled logits GEMM (``logits``: only spv_dec_materialize reads that array) and the softmax statistics over all G
     genes (spv_dec_lse).  Shared by ``materialize_decoder`` and ``expected_expression``."""
     dev = private_log_z.device
-    cont = lambda t: t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
     par = list(par) if par is not None else decoder_params(decoder, px_r)   # (``par``: spVIPESmodule._decoder_operands' covariate-extended set)
-    pz, qz = cont(private_log_z), cont(poe_log_z)
+    pz, qz = _cont(private_log_z), _cont(poe_log_z)
     B, n_p, n_s = pz.shape[0], pz.shape[1], qz.shape[1]
     nt = n_p + n_s
     sl = dec_slots(decoder)
@@ -825,7 +833,7 @@ def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, p
         fb.nprob += 1
     _abi.call("spv_bn_fold_fwd", C.byref(fb), stream_ptr())
     Wm_hi, Wm_lo = _bf16_image(ws, "mat_Wm", Gp, KMP, mlo)
-    _pack(cont(par[10]), Wm_hi, Wm_lo, extra_col=cont(par[11]))
+    _pack(_cont(par[10]), Wm_hi, Wm_lo, extra_col=_cont(par[11]))
     # mixing trunk
     pre_a, m, tstat = new(B, n_m), new(B, n_m), new(n_m, 2)
     b = _lin_batch(B)
@@ -857,7 +865,7 @@ def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, p
         rec_part=None, tp_part=None, ts_part=None, dtheta_part=None, dL=None, tP=None, tS=None, grads_f32=0, nb_splits=1, nb_genes_per_split=32,
         kslots=sl.kslots,
     )
-    lib = cont(library.flatten())
+    lib = _cont(library.flatten())
     if lib.numel() != B:
         raise _abi.SpvError("decoder: the library vector must hold one value per cell")
     _abi.call("spv_dec_lse", C.byref(p), ptr(lib), stream_ptr())
@@ -881,8 +889,7 @@ def materialize_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     out = {k: new(B, G) for k in ("px_scale_private", "px_scale_shared", "px_rate_private", "px_rate_shared", "px_mixing")}
     _abi.call("spv_dec_materialize", C.byref(o.p), ptr(out["px_scale_private"]), ptr(out["px_scale_shared"]), ptr(out["px_rate_private"]),
               ptr(out["px_rate_shared"]), ptr(out["px_mixing"]), G, stream_ptr())
-    p12 = o.par[12]
-    out["px_r"] = torch.exp(p12 if (p12.is_contiguous() and p12.dtype == torch.float32) else p12.contiguous().float())
+    out["px_r"] = _theta(o.par)
     return out
 
 
@@ -907,6 +914,23 @@ def _gene_selection(genes, G: int, dev, who: str):
     return gidx, n
 
 
+def _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, who: str):
+    """the shared prelude of expected_expression / sample_counts: ``library_size`` override of the library, operand preparation
+    without the tiled logits, gene selection -> (_DecOperands, gene ids or None, n_genes)"""
+    from .data import expression_log_library
+
+    logL = expression_log_library(library_size)
+    lib = library if logL is None else torch.full((private_log_z.shape[0],), logL, dtype=torch.float32, device=private_log_z.device)
+    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
+    return (o, *_gene_selection(genes, o.G, private_log_z.device, who))
+
+
+def _fill_readout(a, o: _DecOperands, nsplit: int, gidx, n: int) -> None:
+    """the fields SpvDecExpectedArgs and SpvDecSampleArgs share: logits operand images, their width, the gene selection"""
+    a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.nsplit = ptr(o.Am[0]), ptr(o.Am[1]), ptr(o.Wm[0]), ptr(o.Wm[1]), KMP, nsplit
+    a.genes, a.n_genes = ptr(gidx), n
+
+
 @torch.no_grad()
 def expected_expression(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
                         training: bool, nsplit: int, ws: Workspace, par=None, *, genes=None, what="mixture", library_size="latent",
@@ -921,16 +945,11 @@ def expected_expression(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
     ``out``: fp32 device tensor [>= B, >= n_genes] with unit column stride to write into (rows >= B and columns >= n_genes stay
     untouched); ``out = alpha * value`` or, with ``accumulate``, ``out += alpha * value``.  Same operand preparation as
     ``materialize_decoder``; the softmax denominators always run over all G genes."""
-    from .data import expression_log_library, expression_what
+    from .data import expression_what
 
     code = expression_what(what)
-    logL = expression_log_library(library_size)
-    dev = private_log_z.device
-    B = private_log_z.shape[0]
-    lib = library if logL is None else torch.full((B,), logL, dtype=torch.float32, device=dev)
-    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
-    G = o.G
-    gidx, n = _gene_selection(genes, G, dev, "expected_expression")
+    o, gidx, n = _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, "expected_expression")
+    B, dev = o.B, private_log_z.device
     if out is None:
         if accumulate:
             raise ValueError("expected_expression: accumulate=True needs the ``out`` array to add to")
@@ -939,9 +958,8 @@ def expected_expression(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor
           or (out.shape[1] > 1 and out.stride(1) != 1) or (out.shape[0] > 1 and out.stride(0) < n)):
         raise _abi.SpvError(f"expected_expression: out must be an fp32 device tensor [>= {B}, >= {n}] with unit column stride")
     a = SpvDecExpectedArgs()
-    a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.nsplit = ptr(o.Am[0]), ptr(o.Am[1]), ptr(o.Wm[0]), ptr(o.Wm[1]), KMP, nsplit
-    a.genes, a.n_genes, a.what = ptr(gidx), n, code
-    a.out, a.ld_out, a.alpha, a.accumulate = ptr(out), (out.stride(0) if out.shape[0] > 1 else max(out.shape[1], n)), float(alpha), int(bool(accumulate))
+    _fill_readout(a, o, nsplit, gidx, n)
+    a.what, a.out, a.ld_out, a.alpha, a.accumulate = code, ptr(out), (out.stride(0) if out.shape[0] > 1 else max(out.shape[1], n)), float(alpha), int(bool(accumulate))
     _abi.call("spv_dec_expected", C.byref(o.p), C.byref(a), stream_ptr())
     return out[:B, :n]
 
@@ -964,18 +982,12 @@ def sample_counts(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_
     ``sample`` (0 .. 2^32 - 1) the draw, ``key`` (0 .. 2^64 - 1) the stream.  ``out``: int32 device tensor to write into, either
     [>= B, >= n_genes] with unit column stride or [>= B, >= n_genes, S] viewed at one sample (``out3[:, :, s]``: column stride S);
     rows >= B, columns >= n_genes and the other samples' elements stay untouched."""
-    from .data import expression_log_library
-
-    logL = expression_log_library(library_size)
     if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 64:
         raise ValueError(f"sample_counts: key must be an integer in [0, 2^64), got {key!r}")
     if isinstance(sample, bool) or not isinstance(sample, (int, np.integer)) or not 0 <= int(sample) < 1 << 32:
         raise ValueError(f"sample_counts: sample must be an integer in [0, 2^32), got {sample!r}")
-    dev = private_log_z.device
-    B = private_log_z.shape[0]
-    lib = library if logL is None else torch.full((B,), logL, dtype=torch.float32, device=dev)
-    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
-    gidx, n = _gene_selection(genes, o.G, dev, "sample_counts")
+    o, gidx, n = _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, "sample_counts")
+    B, dev = o.B, private_log_z.device
     if cell_ids is not None and (not isinstance(cell_ids, torch.Tensor) or not cell_ids.is_cuda or cell_ids.dtype != torch.int32 or cell_ids.dim() != 1
                                  or cell_ids.numel() < B or not cell_ids.is_contiguous()):
         raise _abi.SpvError(f"sample_counts: cell_ids must be a contiguous int32 device tensor of at least {B} entries")
@@ -984,12 +996,11 @@ def sample_counts(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_
     elif (not out.is_cuda or out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] < B or out.shape[1] < n
           or (out.shape[1] > 1 and out.stride(1) < 1) or (out.shape[0] > 1 and out.stride(0) < (n - 1) * max(out.stride(1), 1) + 1)):
         raise _abi.SpvError(f"sample_counts: out must be an int32 device tensor [>= {B}, >= {n}] (a [B, n, S] array viewed at one sample is fine)")
-    p12 = o.par[12]
-    theta = torch.exp(p12 if (p12.is_contiguous() and p12.dtype == torch.float32) else p12.contiguous().float())
+    theta = _theta(o.par)
     ld_gene = out.stride(1) if out.shape[1] > 1 else 1
     a = SpvDecSampleArgs()
-    a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.nsplit = ptr(o.Am[0]), ptr(o.Am[1]), ptr(o.Wm[0]), ptr(o.Wm[1]), KMP, nsplit
-    a.genes, a.n_genes, a.ld_gene, a.theta, a.cell_ids = ptr(gidx), n, ld_gene, ptr(theta), ptr(cell_ids)
+    _fill_readout(a, o, nsplit, gidx, n)
+    a.ld_gene, a.theta, a.cell_ids = ld_gene, ptr(theta), ptr(cell_ids)
     a.key, a.sample = int(key), int(sample)
     a.out, a.ld_out = ptr(out), (out.stride(0) if out.shape[0] > 1 else (n - 1) * ld_gene + 1)
     _abi.call("spv_dec_sample", C.byref(o.p), C.byref(a), stream_ptr())

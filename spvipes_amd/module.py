@@ -705,6 +705,13 @@ class spVIPESmodule(nn.Module):
             out[str(g)] = _GenerativeGroup(LazyNBMixture(g, pl, ql, library[g], module=self), pz)
         return {"private_shared": {}, "private_poe": out}
 
+    def _readout_operands(self, inference_outputs, group: int, use_mean: bool):
+        """(first latent, second latent, decoder parameters, library) of one group's read-out: the sampled latents or, with ``use_mean``,
+        the posterior means, detached, as ``_decoder_operands`` extends them"""
+        ps, qs = inference_outputs["private_stats"][group], inference_outputs["poe_stats"][group]
+        pl, ql = (ps["logtheta_loc"], qs["logtheta_loc"]) if use_mean else (ps["log_z"], qs["logtheta_log_z"])
+        return (*self._decoder_operands(group, pl.detach(), ql.detach()), inference_outputs["library"][group].detach())
+
     @torch.no_grad()
     def expected_expression(self, inference_outputs, group: int, *, genes=None, what="mixture", library_size="latent", use_mean: bool = False,
                             out=None, alpha: float = 1.0, accumulate: bool = False) -> torch.Tensor:
@@ -719,10 +726,7 @@ class spVIPESmodule(nn.Module):
         dec_ops.expected_expression (one fused HIP kernel, spv_dec_expected; no [B, G] intermediate is written)."""
         from .dec_ops import expected_expression
 
-        ps, qs = inference_outputs["private_stats"][group], inference_outputs["poe_stats"][group]
-        pl, ql = (ps["logtheta_loc"], qs["logtheta_loc"]) if use_mean else (ps["log_z"], qs["logtheta_log_z"])
-        lib = inference_outputs["library"][group].detach()
-        first, second, par = self._decoder_operands(group, pl.detach(), ql.detach())
+        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
         return expected_expression(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
                                    self._workspace(group, lib.device), par=par, genes=genes, what=what, library_size=library_size,
                                    out=out, alpha=alpha, accumulate=accumulate)
@@ -739,10 +743,7 @@ class spVIPESmodule(nn.Module):
         spv_dec_sample; neither the rates nor the logits are written anywhere)."""
         from .dec_ops import sample_counts
 
-        ps, qs = inference_outputs["private_stats"][group], inference_outputs["poe_stats"][group]
-        pl, ql = (ps["logtheta_loc"], qs["logtheta_loc"]) if use_mean else (ps["log_z"], qs["logtheta_log_z"])
-        lib = inference_outputs["library"][group].detach()
-        first, second, par = self._decoder_operands(group, pl.detach(), ql.detach())
+        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
         return sample_counts(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
                              self._workspace(group, lib.device), par=par, genes=genes, library_size=library_size, key=key, sample=sample,
                              cell_ids=cell_ids, out=out)

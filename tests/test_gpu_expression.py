@@ -316,6 +316,42 @@ def test_abi_argument_errors_are_reported(ident, dev):
     torch.cuda.synchronize()
 
 
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_a_narrower_operand_width_gives_the_same_bits(dev, precision):
+    """K < 320 takes the kernel's rolled logits loop (dec_ops always packs 320 columns: the unrolled one).  No batch covariates, 10 shared
+    and 5 private dimensions: the mixture input is 256 + 5 + 10 + 1 = 272 columns wide, so columns 288..319 of every operand image
+    hold zero bits (asserted: the 320-wide contraction relies on that padding), and a call with K = 288 on contiguous 288-column
+    copies adds the same products in the same step order less exact zeros: equal bit for bit.  B = 200, G = 1003 / 517; 45 selected
+    genes are two tiles, the second partial."""
+    import ctypes as C
+    from spvipes_amd import _abi, dec_ops
+    module, _g, _r, _c, noise, tensors = _synthetic_module(dev, precision, 200, (1003, 517), 10, 5, 0, H=64, seed=3)
+    with torch.no_grad():
+        inf = module.inference(**module._get_inference_input(tensors), noise={k: v.to(dev) for k, v in noise.items()})
+    for grp in range(2):
+        first, second, par = module._decoder_operands(grp, inf["private_stats"][grp]["log_z"], inf["poe_stats"][grp]["logtheta_log_z"])
+        o = dec_ops._prepare_decoder(module.decoders[grp], module.px_r[grp], first, second, inf["library"][grp], False, module.nsplit,
+                                     module._workspace(grp, dev), par, logits=False)
+        wide = [*o.Am, *o.Wm]
+        assert [t is not None for t in wide] == [True, precision == "fp32"] * 2
+        for t in wide:
+            assert t is None or (t.dtype == torch.int16 and t.shape[1] == 320 and not bool(t[:, 288:].any()))
+        narrow = [None if t is None else t[:, :288].contiguous() for t in wide]
+        sel = torch.tensor(np.random.default_rng(5).integers(0, module.input_dims[grp], size=45), dtype=torch.int32, device=dev)
+
+        def run(images, K, what):
+            out = torch.full((200, 45), -7.25, device=dev)
+            a = _abi.SpvDecExpectedArgs()
+            a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.nsplit = *[_abi.ptr(t) for t in images], K, module.nsplit
+            a.genes, a.n_genes, a.what, a.out, a.ld_out, a.alpha, a.accumulate = _abi.ptr(sel), 45, what, _abi.ptr(out), 45, 1.0, 0
+            _abi.call("spv_dec_expected", C.byref(o.p), C.byref(a), _abi.stream_ptr())
+            return out
+
+        for what in range(4):
+            want = run(wide, 320, what)
+            assert bool((want >= 0).all()) and torch.equal(run(narrow, 288, what), want), (grp, what)
+
+
 # ---- 4. user API ---------------------------------------------------------------------------------------------------------------
 def _noise_fn(dev, n_s=10, n_p=5):
     def noise(draw, b0, b1):

@@ -226,6 +226,45 @@ def test_pooled_variance_of_the_draws_on_a_gene_subset(case, cubes):
         assert ratio <= 1.0
 
 
+# ---- the operand width ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_a_narrower_operand_width_gives_the_same_draws(dev, precision):
+    """K < 320 takes the kernel's rolled logits loop (dec_ops always packs 320 columns: the unrolled one).  No batch covariates, 10 shared
+    and 5 private dimensions: the mixture input is 256 + 5 + 10 + 1 = 272 columns wide, so columns 288..319 of every operand image
+    hold zero bits (asserted: the 320-wide contraction relies on that padding), and a call with K = 288 on contiguous 288-column
+    copies adds the same products in the same step order less exact zeros: the same logits, so the same draws.  B = 200, G = 1003 /
+    517; 45 selected genes are two tiles, the second partial."""
+    import ctypes as C
+    from spvipes_amd import _abi, dec_ops
+    Bn, Gs = 200, (1003, 517)
+    module, noise, tensors = _synthetic_module(dev, precision, Bn, Gs, 10, 5, 0)
+    with torch.no_grad():
+        inf = module.inference(**module._get_inference_input(tensors), noise={k: v.to(dev) for k, v in noise.items()})
+    for g in range(2):
+        first, second, par = module._decoder_operands(g, inf["private_stats"][g]["log_z"], inf["poe_stats"][g]["logtheta_log_z"])
+        o = dec_ops._prepare_decoder(module.decoders[g], module.px_r[g], first, second, inf["library"][g], False, module.nsplit,
+                                     module._workspace(g, dev), par, logits=False)
+        wide = [*o.Am, *o.Wm]
+        assert [t is not None for t in wide] == [True, precision == "fp32"] * 2
+        for t in wide:
+            assert t is None or (t.dtype == torch.int16 and t.shape[1] == 320 and not bool(t[:, 288:].any()))
+        narrow = [None if t is None else t[:, :288].contiguous() for t in wide]
+        sel = torch.tensor(np.random.default_rng(5).integers(0, Gs[g], size=NSEL), dtype=torch.int32, device=dev)
+        theta = torch.exp(module.px_r[g].detach().float()).contiguous()
+
+        def run(images, K):
+            out = torch.full((Bn, NSEL), -77, dtype=torch.int32, device=dev)
+            a = _abi.SpvDecSampleArgs()
+            a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.nsplit = *[_abi.ptr(t) for t in images], K, module.nsplit
+            a.genes, a.n_genes, a.ld_gene, a.theta, a.cell_ids, a.key, a.sample = _abi.ptr(sel), NSEL, 1, _abi.ptr(theta), None, 0x5EED, 2
+            a.out, a.ld_out = _abi.ptr(out), NSEL
+            _abi.call("spv_dec_sample", C.byref(o.p), C.byref(a), _abi.stream_ptr())
+            return out
+
+        want = run(wide, 320)
+        assert int(want.min()) >= 0 and int(want.max()) > 0 and torch.equal(run(narrow, 288), want), g
+
+
 # ---- the ABI's argument errors -------------------------------------------------------------------------------------------------------
 def test_abi_argument_errors_are_reported(case, dev):
     import ctypes as C
