@@ -33,6 +33,48 @@ static int launch_status(const char* what) {
   return SPV_OK;
 }
 
+// ---- launch idioms the wrappers below share ---------------------------------------------------------------------------------------------
+// every pointer on a 16-byte boundary (a null pointer counts as aligned)
+template <typename... P>
+static bool aligned16(const P*... ptrs) { return ((reinterpret_cast<uintptr_t>(ptrs) | ... | uintptr_t(0)) & 15) == 0; }
+
+static inline int max2(int a, int b) { return a > b ? a : b; }
+
+// launch of kernel K with `bytes` of dynamic LDS (more than the 64 KiB a kernel gets unasked): the one-time opt-in ahead of K's first
+// launch, never again (every K has its own flag).  A kernel picked at run time (a `kfn` pointer) sets the attribute per call instead.
+template <auto K, typename... Args>
+static void launch_lds(dim3 grid, dim3 block, int bytes, hipStream_t s, Args... args) {
+  static bool raised = false;
+  if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); raised = true; }
+  hipLaunchKernelGGL(K, grid, block, bytes, s, args...);
+}
+
+// The *_grouped entry points: groups go out two at a time while `try_pair(i)` takes groups i and i + 1 as one grid, the rest one by one
+// through `run_one(i)` (the per-group entry point).  try_pair returns SPV_OK (launched), NOT_A_PAIR (nothing launched: the two take
+// different kernel variants, which ends pairing for this form) or an error code; a second pair form starts where the first one stopped.
+static constexpr int NOT_A_PAIR = 1;
+template <typename Pair>
+static int run_pairs(int& i, int n, Pair try_pair) {
+  for (; i + 1 < n; i += 2) {
+    const int rc = try_pair(i);
+    if (rc == NOT_A_PAIR) break;
+    if (rc != SPV_OK) return rc;
+  }
+  return SPV_OK;
+}
+template <typename PairA, typename PairB, typename One>
+static int pairs_then_rest(int n, PairA try_pair_a, PairB try_pair_b, One run_one) {
+  int i = 0;
+  int rc = run_pairs(i, n, try_pair_a);
+  if (rc == SPV_OK) rc = run_pairs(i, n, try_pair_b);
+  for (; rc == SPV_OK && i < n; ++i) rc = run_one(i);
+  return rc;
+}
+template <typename Pair, typename One>
+static int pairs_then_rest(int n, Pair try_pair, One run_one) {
+  return pairs_then_rest(n, try_pair, [](int) { return NOT_A_PAIR; }, run_one);
+}
+
 #ifndef SPV_BUILD_ID
 #define SPV_BUILD_ID "00000000000000000000000000000000"
 #endif
@@ -140,9 +182,9 @@ extern "C" int spv_pack_f16(const float* src, int64_t ld_src, int32_t R, int32_t
 // ---------------------------------------------------------------------------------------------
 // encoder fc1
 // ---------------------------------------------------------------------------------------------
-__global__ void fc1_epilogue_kernel(const float* slabs, const float* rowsum_ws, int splits, int B, int N1, const float* bias,
-                                    const float* bias2, int n_first, float* h1, float* library, const float* library_all,
-                                    const int* rows, float acc_scale, const float* cov, const int* cov_idx) {
+__device__ __forceinline__ void fc1_epilogue_body(const float* slabs, const float* rowsum_ws, int splits, int B, int N1, const float* bias,
+                                                  const float* bias2, int n_first, float* h1, float* library, const float* library_all,
+                                                  const int* rows, float acc_scale, const float* cov, const int* cov_idx) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)B * N1;
   if (idx < total) {
@@ -163,30 +205,17 @@ __global__ void fc1_epilogue_kernel(const float* slabs, const float* rowsum_ws, 
     }
   }
 }
+__global__ void fc1_epilogue_kernel(const float* slabs, const float* rowsum_ws, int splits, int B, int N1, const float* bias,
+                                    const float* bias2, int n_first, float* h1, float* library, const float* library_all,
+                                    const int* rows, float acc_scale, const float* cov, const int* cov_idx) {
+  fc1_epilogue_body(slabs, rowsum_ws, splits, B, N1, bias, bias2, n_first, h1, library, library_all, rows, acc_scale, cov, cov_idx);
+}
 
 struct Fc1EpiPlainArgs { const float* slabs; const float* rowsum_ws; int splits, B, N1; const float* bias; const float* bias2; int n_first; float* h1; float* library;
                          const float* library_all; const int* rows; float acc_scale; const float* cov; const int* cov_idx; };
-__global__ void fc1_epilogue_pair_kernel(Fc1EpiPlainArgs a0, Fc1EpiPlainArgs a1) {   // blockIdx.y = group; the same arithmetic as fc1_epilogue_kernel
+__global__ void fc1_epilogue_pair_kernel(Fc1EpiPlainArgs a0, Fc1EpiPlainArgs a1) {   // blockIdx.y = group
   const Fc1EpiPlainArgs a = blockIdx.y ? a1 : a0;
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)a.B * a.N1;
-  if (idx < total) {
-    const int col = (int)(idx % a.N1);
-    const float bv = (a.bias2 != nullptr && col >= a.n_first) ? a.bias2[col - a.n_first] : a.bias[col];
-    const float cv = a.cov ? a.cov[(long)a.cov_idx[idx / a.N1] * a.N1 + col] : 0.f;
-    float v = 0.f;
-    for (int s = 0; s < a.splits; ++s) v += a.slabs[(long)s * total + idx];
-    a.h1[idx] = fmaxf(v * a.acc_scale + bv + cv, 0.f);
-  }
-  if (idx < a.B) {
-    if (a.library_all != nullptr) {
-      a.library[idx] = a.library_all[a.rows ? a.rows[idx] : (int)idx];
-    } else {
-      float v = 0.f;
-      for (int s = 0; s < a.splits; ++s) v += a.rowsum_ws[(long)s * a.B + idx];
-      a.library[idx] = __logf(v);
-    }
-  }
+  fc1_epilogue_body(a.slabs, a.rowsum_ws, a.splits, a.B, a.N1, a.bias, a.bias2, a.n_first, a.h1, a.library, a.library_all, a.rows, a.acc_scale, a.cov, a.cov_idx);
 }
 
 // every 8-gene chunk of a row is one aligned 16-byte load when base, row pitch and column offset are
@@ -209,16 +238,32 @@ static int fc1_fwd_dispatch(const GemmParams& p, int N1, int splits, hipStream_t
 // Shapes the LDS-DMA fc1 forward kernel (spv_fc1.h) takes: the resident bf16 log1p image, both encoders' 2H = 256 output columns,
 // operand images zero padded to multiples of 64 genes with 16-byte aligned rows.  The host asks through this entry point
 // because the path fixes the slab workspace: [splits][round_up(B, 128)][256] fp32 in accumulator-tile order.
-// SPV_FC1_DMA_SPLIT=0: "fp32" mode keeps the count-decoding register-staged fc1 kernels (A/B switch)
-static const bool g_fc1_dma_split = []() { const char* e = getenv("SPV_FC1_DMA_SPLIT"); return !(e && e[0] == '0'); }();
 extern "C" int spv_enc_fc1_fwd_uses_dma(int32_t B, int32_t G, int32_t N1, int32_t nsplit, int32_t have_xb, int64_t ldw, int64_t ld_xb) {
   const long G64 = (G + 63) & ~63L;
   if (nsplit == 3)   // "fp32" mode: the resident image holds [hi | lo] halves per row (spv_prepare_log1p_split): ld_xb is the pitch of both
-    return g_fc1_dma_split && have_xb && (N1 == F1_BN || N1 == 2 * F1_BN) && B > 0 && G > 0 && ldw >= G64 && ld_xb >= 2 * G64 && (ldw % 8) == 0 && (ld_xb % 16) == 0;
+    return have_xb && (N1 == F1_BN || N1 == 2 * F1_BN) && B > 0 && G > 0 && ldw >= G64 && ld_xb >= 2 * G64 && (ldw % 8) == 0 && (ld_xb % 16) == 0;
   return have_xb && nsplit == 1 && (N1 == F1_BN || N1 == 2 * F1_BN) && B > 0 && G > 0 && ldw >= G64 && ld_xb >= G64 && (ldw % 8) == 0 && (ld_xb % 8) == 0;
 }
 
 static int fc1_bn(int N1) { return N1 <= 32 ? 32 : (N1 <= 128 ? 128 : 256); }
+
+// operands of the fc1 forward GEMM, `bk`-deep k steps: the counts themselves (decoded by the kernel, which also sums the rows), or --
+// xb_all -- the resident log1p image of the data set (spv_prepare_log1p): a plain gathered operand, no decode
+// (nsplit 3: hi / lo planes interleaved inside the image rows, spv_prepare_log1p_split)
+static GemmParams fc1_fwd_params(const spv_fc1_fwd_args& a, int bk) {
+  GemmParams p{};
+  p.A = a.x->X; p.A_lo = nullptr; p.lda = a.x->ld;
+  p.B = a.W1_hi; p.B_lo = a.W1_lo; p.ldb = a.ldw;
+  p.rows = a.x->rows; p.counts_aligned = counts_aligned(a.x); p.col_off = a.x->col_off; p.n_cells = a.B; p.n_genes = a.G;
+  p.rowsum = a.rowsum_ws;
+  if (a.xb_all != nullptr) { p.A = a.xb_all; p.lda = a.ld_xb; p.rowsum = nullptr; }
+  p.C = a.slabs; p.ldc = a.N1; p.slab_stride = (long)a.B * a.N1;
+  p.M = a.B; p.N = a.N1; p.K = a.G;
+  const int ktiles = (a.G + bk - 1) / bk;
+  p.k_per_split = ((ktiles + a.splits - 1) / a.splits) * bk;
+  p.epi = EPI_STORE;
+  return p;
+}
 
 extern "C" int spv_enc_fc1_fwd(const spv_counts* x, int32_t B, int32_t G, const uint16_t* W1_hi, const uint16_t* W1_lo,
                                int64_t ldw, int32_t N1, const float* bias, const float* bias2, int32_t n_first, int32_t nsplit,
@@ -229,59 +274,39 @@ extern "C" int spv_enc_fc1_fwd(const spv_counts* x, int32_t B, int32_t G, const 
   if (B <= 0 || G <= 0 || N1 <= 0 || splits <= 0 || (ldw % 32) != 0 || ldw < ((G + 31) & ~31)) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd: bad shape%s");
   if (nsplit != 1 && nsplit != 3) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd: nsplit must be 1 or 3%s");
   if (nsplit == 3 && !W1_lo) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd: nsplit=3 needs W1_lo%s");
-  GemmParams p{};
-  p.A = x->X; p.A_lo = nullptr; p.lda = x->ld;
-  p.B = W1_hi; p.B_lo = W1_lo; p.ldb = ldw;
-  p.rows = x->rows; p.counts_aligned = counts_aligned(x); p.col_off = x->col_off; p.n_cells = B; p.n_genes = G;
-  p.rowsum = rowsum_ws;
-  if (xb_all != nullptr) {  // log1p(x) of the whole data set is resident as bf16 (spv_prepare_log1p): plain gathered operand, no decode
+  if (xb_all != nullptr) {
     if (!library_all || ld_xb < ((G + 31) & ~31) || (ld_xb % 8)) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd: xb_all needs library_all and ld_xb >= round_up(G, 32)%s");
     if (nsplit == 3 && !spv_enc_fc1_fwd_uses_dma(B, G, N1, nsplit, 1, ldw, ld_xb)) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd: a split (nsplit 3) resident image is only taken by the LDS-DMA kernel (ask spv_enc_fc1_fwd_uses_dma)%s");
-    p.A = xb_all; p.lda = ld_xb; p.rowsum = nullptr;
-    // (nsplit 3: hi / lo planes interleaved inside the rows, spv_prepare_log1p_split)
   }
-  p.C = slabs; p.ldc = N1; p.slab_stride = (long)B * N1;
-  p.M = B; p.N = N1; p.K = G;
   // resident-image path with both encoders' 2H > 128 columns: 128 x 256 tiles, 64-deep k steps and ONE register stage
   // (the 64 x 128 wave tile holds 128 accumulator registers; a deeper prefetch ring spills at two workgroups per CU --
   // measured 88 -> 62 us) when both images are zero padded to a multiple of 64 genes, else 32-deep steps
   const int G64 = (G + 63) & ~63;
   const bool wide64 = xb_all != nullptr && N1 > 128 && ld_xb >= G64 && ldw >= G64;
-  const int bk = wide64 ? 64 : 32;
-  const int ktiles = (G + bk - 1) / bk;
-  p.k_per_split = ((ktiles + splits - 1) / splits) * bk;
-  p.epi = EPI_STORE;
+  const spv_fc1_fwd_args a{x, B, G, W1_hi, W1_lo, ldw, N1, bias, bias2, n_first, nsplit, splits, slabs, rowsum_ws, h1, library, xb_all, ld_xb, library_all, cov, cov_idx};
+  GemmParams p = fc1_fwd_params(a, wide64 ? 64 : 32);
   hipStream_t s = (hipStream_t)stream;
   int rc;
   const float acc_scale = (nsplit == 1) ? 1.0f / SPV_FC1_W_SCALE : 1.0f;   // the f16 weight image holds W * SPV_FC1_W_SCALE (spv_pack_f16)
-  if (nsplit == 3 && xb_all != nullptr) {
-    // "fp32" mode on a resident split image: the LDS-DMA kernel on hi / lo planes (spv_fc1.h: fc1_fwd_dma_body<true>)
-    if (((reinterpret_cast<uintptr_t>(xb_all) | reinterpret_cast<uintptr_t>(W1_hi) | reinterpret_cast<uintptr_t>(W1_lo)) & 15) != 0) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd: images must be 16-byte aligned%s");
-    const int mtiles = (B + F1_BM - 1) / F1_BM, kt = (G + F1_BK - 1) / F1_BK;
-    p.k_per_split = ((kt + splits - 1) / splits) * F1_BK;
-    p.c_split_row = splits;
-    static bool raised = false;
-    if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fc1_fwd_dma_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F1_LDS_BYTES); raised = true; }
-    hipLaunchKernelGGL(fc1_fwd_dma_split_kernel, dim3(mtiles * splits, N1 / F1_BN), dim3(512), F1_LDS_BYTES, s, p);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_fwd dma split gemm");
-    const long slab_elems = (long)mtiles * F1_BM * N1;
-    hipLaunchKernelGGL(fc1_epilogue_tiled_kernel, dim3((unsigned)((slab_elems / 4 + 255) / 256)), dim3(256), 0, s, slabs, splits, slab_elems, B, N1, bias, bias2, n_first, h1, library,
-                       library_all, x->rows, 1.0f, cov, cov_idx);
-    return launch_status("spv_enc_fc1_fwd dma split epilogue");
-  }
-  if (spv_enc_fc1_fwd_uses_dma(B, G, N1, nsplit, xb_all != nullptr, ldw, ld_xb) && ((reinterpret_cast<uintptr_t>(xb_all) | reinterpret_cast<uintptr_t>(W1_hi)) & 15) == 0) {
-    // LDS-DMA kernel (spv_fc1.h): 128-cell tiles, K split `splits` ways, slabs in accumulator-tile order [splits][Mp128][256]
-    const int mtiles = (B + F1_BM - 1) / F1_BM, kt = (G + F1_BK - 1) / F1_BK;
-    p.k_per_split = ((kt + splits - 1) / splits) * F1_BK;
-    p.c_split_row = splits;
-    static bool raised = false;
-    if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fc1_fwd_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F1_LDS_BYTES); raised = true; }
-    hipLaunchKernelGGL(fc1_fwd_dma_kernel, dim3(mtiles * splits, N1 / F1_BN), dim3(512), F1_LDS_BYTES, s, p);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_fwd dma gemm");
-    const long slab_elems = (long)mtiles * F1_BM * N1;
-    hipLaunchKernelGGL(fc1_epilogue_tiled_kernel, dim3((unsigned)((slab_elems / 4 + 255) / 256)), dim3(256), 0, s, slabs, splits, slab_elems, B, N1, bias, bias2, n_first, h1, library,
-                       library_all, x->rows, acc_scale, cov, cov_idx);
-    return launch_status("spv_enc_fc1_fwd dma epilogue");
+  if (spv_enc_fc1_fwd_uses_dma(B, G, N1, nsplit, xb_all != nullptr, ldw, ld_xb)) {
+    // LDS-DMA kernel (spv_fc1.h): 128-cell tiles, K split `splits` ways, slabs in accumulator-tile order [splits][Mp128][256].
+    // "fp32" mode on a resident split image: the same kernel on hi / lo planes (fc1_fwd_dma_body<true>), which is that image's only
+    // consumer (checked above); a misaligned 16-bit image goes to the register-staged kernels below
+    const bool split = nsplit == 3, aligned = aligned16(xb_all, W1_hi, split ? W1_lo : nullptr);
+    if (split && !aligned) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd: images must be 16-byte aligned%s");
+    if (aligned) {
+      const int mtiles = (B + F1_BM - 1) / F1_BM, kt = (G + F1_BK - 1) / F1_BK;
+      p.k_per_split = ((kt + splits - 1) / splits) * F1_BK;
+      p.c_split_row = splits;
+      const dim3 grid(mtiles * splits, N1 / F1_BN);
+      if (split) launch_lds<fc1_fwd_dma_split_kernel>(grid, dim3(512), F1_LDS_BYTES, s, p);
+      else launch_lds<fc1_fwd_dma_kernel>(grid, dim3(512), F1_LDS_BYTES, s, p);
+      if ((rc = launch_status(split ? "spv_enc_fc1_fwd dma split gemm" : "spv_enc_fc1_fwd dma gemm")) != SPV_OK) return rc;
+      const long slab_elems = (long)mtiles * F1_BM * N1;
+      hipLaunchKernelGGL(fc1_epilogue_tiled_kernel, dim3((unsigned)((slab_elems / 4 + 255) / 256)), dim3(256), 0, s, slabs, splits, slab_elems, B, N1, bias, bias2, n_first, h1, library,
+                         library_all, x->rows, acc_scale, cov, cov_idx);
+      return launch_status(split ? "spv_enc_fc1_fwd dma split epilogue" : "spv_enc_fc1_fwd dma epilogue");
+    }
   }
   if (xb_all != nullptr) {
     if (N1 <= 128) rc = launch_gemm<GemmCfg<64, 128, 2, 2, false, false, SRC_GATHER, SRC_PLAIN, unsigned short, 1, 32, 4, 1, true>>(p, splits, s);
@@ -298,21 +323,19 @@ extern "C" int spv_enc_fc1_fwd(const spv_counts* x, int32_t B, int32_t G, const 
 
 // 1 when spv_enc_fc1_wgrad takes a split (nsplit 3) resident image for these shapes (the LDS-DMA kernel is its only consumer)
 extern "C" int spv_enc_fc1_wgrad_split_uses_dma(int32_t B, int32_t G, int32_t N1, int64_t ld_dh, int64_t ld_xb) {
-  if (!g_fc1_dma_split || B <= 0 || G <= 0) return 0;
+  if (B <= 0 || G <= 0) return 0;
   const int Kpad = (B + FW_BK - 1) / FW_BK * FW_BK;
   return (N1 == FW_BM || N1 == 2 * FW_BM) && ld_dh == N1 && ld_xb >= 2 * (((long)G + 95) / 96 * 96) && (ld_xb % 128) == 0 && fw_lds_bytes(96, Kpad) <= 160 * 1024;
 }
-extern "C" int spv_enc_fc1_wgrad(const spv_counts* x, int32_t B, int32_t G, const uint16_t* dh_hi, const uint16_t* dh_lo,
-                                 int64_t ld_dh, int32_t N1, int32_t nsplit, float* dW, float* dW2, int32_t rows_first, int64_t ldc,
-                                 const uint16_t* xb, int64_t ld_xb, const float* dh_scale, void* stream) {
-  if (!x || !x->X || !dh_hi || !dW) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: null pointer%s");
-  if (nsplit == 1 && !dh_scale) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: nsplit=1 needs the dh image's scale record (spv_enc_fc1_bwd_prep)%s");
-  if (B <= 0 || G <= 0 || N1 <= 0 || ld_dh < ((N1 + 127) & ~127) || (ld_dh % 8) != 0 || ldc < G) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: bad shape%s");
-  if (nsplit != 1 && nsplit != 3) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: nsplit must be 1 or 3%s");
-  if (nsplit == 3 && !dh_lo) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: nsplit=3 needs dh_lo%s");
+
+// operands of the fc1 weight-gradient GEMM (the arguments of spv_enc_fc1_wgrad): dh image x the counts, or -- xb -- x the resident
+// log1p image of the data set: a gathered plain k-major operand, no decode
+static GemmParams fc1_wgrad_params(const spv_counts* x, int B, int G, const uint16_t* dh_hi, const uint16_t* dh_lo, long ld_dh, int N1, int nsplit, float* dW,
+                                   float* dW2, int rows_first, long ldc, const uint16_t* xb, long ld_xb, const float* dh_scale) {
   GemmParams p{};
   p.A = dh_hi; p.A_lo = dh_lo; p.lda = ld_dh;
   p.B = x->X; p.B_lo = nullptr; p.ldb = x->ld;
+  if (xb != nullptr) { p.B = xb; p.ldb = ld_xb; }
   p.rows = x->rows; p.counts_aligned = counts_aligned(x); p.col_off = x->col_off; p.n_cells = B; p.n_genes = G;
   p.rowsum = nullptr;
   p.C = dW; p.ldc = ldc; p.slab_stride = 0;
@@ -321,38 +344,44 @@ extern "C" int spv_enc_fc1_wgrad(const spv_counts* x, int32_t B, int32_t G, cons
   p.M = N1; p.N = G; p.K = B;
   p.k_per_split = (B + 63) & ~63;
   p.epi = EPI_STORE;
+  return p;
+}
+
+extern "C" int spv_enc_fc1_wgrad(const spv_counts* x, int32_t B, int32_t G, const uint16_t* dh_hi, const uint16_t* dh_lo,
+                                 int64_t ld_dh, int32_t N1, int32_t nsplit, float* dW, float* dW2, int32_t rows_first, int64_t ldc,
+                                 const uint16_t* xb, int64_t ld_xb, const float* dh_scale, void* stream) {
+  if (!x || !x->X || !dh_hi || !dW) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: null pointer%s");
+  if (nsplit == 1 && !dh_scale) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: nsplit=1 needs the dh image's scale record (spv_enc_fc1_bwd_prep)%s");
+  if (B <= 0 || G <= 0 || N1 <= 0 || ld_dh < ((N1 + 127) & ~127) || (ld_dh % 8) != 0 || ldc < G) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: bad shape%s");
+  if (nsplit != 1 && nsplit != 3) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: nsplit must be 1 or 3%s");
+  if (nsplit == 3 && !dh_lo) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: nsplit=3 needs dh_lo%s");
+  const GemmParams p = fc1_wgrad_params(x, B, G, dh_hi, dh_lo, ld_dh, N1, nsplit, dW, dW2, rows_first, ldc, xb, ld_xb, dh_scale);
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if (xb != nullptr && nsplit == 3) {
     // "fp32" mode on the resident split image (spv_prepare_log1p_split): the LDS-DMA kernel on hi / lo planes, 96-gene tiles
     const int Kpad = (B + FW_BK - 1) / FW_BK * FW_BK;
-    if (!spv_enc_fc1_wgrad_split_uses_dma(B, G, N1, ld_dh, ld_xb) || rows_first != N1 / 2 || dW2 == nullptr ||
-        ((reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(dh_hi) | reinterpret_cast<uintptr_t>(dh_lo)) & 15) != 0)
+    if (!spv_enc_fc1_wgrad_split_uses_dma(B, G, N1, ld_dh, ld_xb) || rows_first != N1 / 2 || dW2 == nullptr || !aligned16(xb, dh_hi, dh_lo))
       return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: a split (nsplit 3) resident image is only taken by the LDS-DMA kernel (ask spv_enc_fc1_wgrad_split_uses_dma)%s");
-    p.B = xb; p.ldb = ld_xb;
     // gene tile: 128 where that saves a round of one-per-CU workgroups over 96 (and its LDS need -- 144 KiB of stages + the row table -- fits)
     const int mth = N1 / FW_BM, nb96 = (G + 95) / 96, nb128 = (G + 127) / 128;
-    static const int force_bn = getenv("SPV_FC1W_SPLIT_BN") ? atoi(getenv("SPV_FC1W_SPLIT_BN")) : 0;   // (A/B switch)
     const bool fits128 = fw_lds_bytes(128, Kpad) <= 160 * 1024 && ld_xb >= 2 * (long)nb128 * 128;
-    const bool use128 = fits128 && (force_bn ? force_bn == 128 : (nb128 * mth + 255) / 256 < (nb96 * mth + 255) / 256);
+    const bool use128 = fits128 && (nb128 * mth + 255) / 256 < (nb96 * mth + 255) / 256;
     void (*kfn)(GemmParams) = use128 ? fc1_wgrad_dma_split_kernel<128> : fc1_wgrad_dma_split_kernel<96>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(kfn, dim3(use128 ? nb128 : nb96, mth), dim3(512), fw_lds_bytes(use128 ? 128 : 96, Kpad), s, p);
     return launch_status("spv_enc_fc1_wgrad dma split");
   }
-  if (xb != nullptr) {  // resident bf16 log1p(x) of the data set (spv_prepare_log1p): gathered plain k-major operand, no decode
+  if (xb != nullptr) {
     if (nsplit != 1 || ld_xb < ((G + 63) & ~63) || (ld_xb % 8)) return fail(SPV_ERR_ARG, "spv_enc_fc1_wgrad: xb needs nsplit 1 and ld_xb >= round_up(G, 64)%s");
-    p.B = xb; p.ldb = ld_xb;
     const int Kpad = (B + FW_BK - 1) / FW_BK * FW_BK;
-    if ((N1 == FW_BM || N1 == 2 * FW_BM) && ld_dh == N1 && rows_first == N1 / 2 && dW2 != nullptr && fw_lds_bytes(64, Kpad) <= 160 * 1024 &&
-        ((reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(dh_hi)) & 15) == 0) {
+    if ((N1 == FW_BM || N1 == 2 * FW_BM) && ld_dh == N1 && rows_first == N1 / 2 && dW2 != nullptr && fw_lds_bytes(64, Kpad) <= 160 * 1024 && aligned16(xb, dh_hi)) {
       // LDS-DMA kernel (spv_fc1.h): all 256 rows x 64 genes per workgroup over the whole batch, results straight into dW / dW2
       // (measured at C2, tools/probes/fc1w_bench.hip: 51 us alone against 75 us for the register-staged kernel below)
       // 96-gene tiles when they put TWO groups' launches (two streams, one workgroup per CU) into one round of the 256 CUs and
       // 64-gene tiles do not (C2: 2 x 105 against 2 x 157 workgroups; alone the 64-gene tile is the faster one)
       const int nb64 = (G + 63) / 64, nb96 = (G + 95) / 96;
-      static const int force_bn = getenv("SPV_FC1W_BN") ? atoi(getenv("SPV_FC1W_BN")) : 0;   // (A/B switch)
-      const bool use96 = force_bn ? force_bn == 96 : (2 * nb96 <= 256 && 2 * nb64 > 256 && fw_lds_bytes(96, Kpad) <= 160 * 1024);
+      const bool use96 = 2 * nb96 <= 256 && 2 * nb64 > 256 && fw_lds_bytes(96, Kpad) <= 160 * 1024;
       void (*kfn)(GemmParams) = use96 ? fc1_wgrad_dma_kernel<96> : fc1_wgrad_dma_kernel<64>;
       const int lds = fw_lds_bytes(use96 ? 96 : 64, Kpad);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -386,11 +415,8 @@ static int gemm_dispatch(const GemmParams& p, int splits, hipStream_t s) {
 // Shapes the LDS-DMA 320-column kernels (spv_dec_gemm.h) take: bf16 mode, a tile-ordered [cells][genes] A operand, a 320-wide
 // k-major B image.  The tiled array must cover round_up(M, 128) x round_up(K, 64) (cells x genes, a_kmajor 0) or
 // round_up(K, 64) x round_up(M, 128) (a_kmajor 1): the decoder's Bp / Gp paddings (multiples of 128 / 256) do.
-// SPV_GEMM_DMA_SPLIT=0: "fp32" mode keeps the register-staged 64 x 320 kernel for the two 320-column GEMMs (A/B switch)
-static const bool g_dma_split = []() { const char* e = getenv("SPV_GEMM_DMA_SPLIT"); return !(e && e[0] == '0'); }();
 extern "C" int spv_gemm_bf16_uses_dma(int32_t a_kmajor, int32_t M, int32_t N, int32_t K, int32_t nsplit, int32_t a_tiles, int64_t ldb) {
   if ((nsplit != 1 && nsplit != 3) || a_tiles <= 0 || N <= 32 || N > DG_BN || ldb != DG_BN || M <= 0 || K <= 0) return 0;
-  if (nsplit == 3 && !g_dma_split) return 0;
   const long genes_needed = a_kmajor ? ((long)M + DG_BM - 1) / DG_BM * DG_BM : ((long)K + DG_BK - 1) / DG_BK * DG_BK;
   if ((long)a_tiles * 32 < genes_needed) return 0;
   return 1;
@@ -408,11 +434,11 @@ extern "C" int spv_gemm_bf16_fix(int32_t a_kmajor, const uint16_t* A_hi, const u
   if (!A_hi || !B_hi || !C) return fail(SPV_ERR_ARG, "spv_gemm_bf16: null pointer%s");
   if (fix) {
     if (!spv_gemm_bf16_uses_dma(a_kmajor, M, N, K, nsplit, a_tiles, ldb)) return fail(SPV_ERR_UNSUPPORTED, "spv_gemm_bf16_fix: only the LDS-DMA 320-column kernels sum their slabs in the launch%s");
-    if (!fix->counters || !fix->dst0 || fix->n0 <= 0 || fix->n0 > N || fix->ld0 < fix->n0 || (ldc & 3) || (slab_stride & 3) || (reinterpret_cast<uintptr_t>(C) & 15) ||
+    if (!fix->counters || !fix->dst0 || fix->n0 <= 0 || fix->n0 > N || fix->ld0 < fix->n0 || (ldc & 3) || (slab_stride & 3) || !aligned16(C) ||
         (fix->dst1 && (fix->c1 < fix->n0 || fix->n1 <= 0 || fix->c1 + fix->n1 > N || fix->ld1 < fix->n1)) || ldc < N)
       return fail(SPV_ERR_ARG, "spv_gemm_bf16_fix: bad fix-up description%s");
     // (the LDS-DMA kernels want 16-byte aligned planes; the register-staged kernels they would fall back to know nothing of the fix-up)
-    if (((reinterpret_cast<uintptr_t>(A_hi) | reinterpret_cast<uintptr_t>(B_hi) | (nsplit == 3 ? (reinterpret_cast<uintptr_t>(A_lo) | reinterpret_cast<uintptr_t>(B_lo)) : 0)) & 15) != 0)
+    if (!aligned16(A_hi, B_hi) || (nsplit == 3 && !aligned16(A_lo, B_lo)))
       return fail(SPV_ERR_ARG, "spv_gemm_bf16_fix: operand planes must be 16-byte aligned%s");
   }
   if (M <= 0 || N <= 0 || K <= 0 || splits <= 0 || (!a_tiles && (lda % 8)) || (ldb % 8) || a_tiles < 0) return fail(SPV_ERR_ARG, "spv_gemm_bf16: bad shape%s");
@@ -434,35 +460,22 @@ extern "C" int spv_gemm_bf16_fix(int32_t a_kmajor, const uint16_t* A_hi, const u
     p.fix_d1 = fix->dst1; p.fix_ld1 = fix->ld1; p.fix_c1 = fix->c1; p.fix_n1 = fix->n1;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (nsplit == 3 && spv_gemm_bf16_uses_dma(a_kmajor, M, N, K, nsplit, a_tiles, ldb) &&
-      ((reinterpret_cast<uintptr_t>(A_hi) | reinterpret_cast<uintptr_t>(B_hi) | reinterpret_cast<uintptr_t>(A_lo) | reinterpret_cast<uintptr_t>(B_lo)) & 15) == 0) {
+  if (nsplit == 3 && spv_gemm_bf16_uses_dma(a_kmajor, M, N, K, nsplit, a_tiles, ldb) && aligned16(A_hi, B_hi, A_lo, B_lo)) {
     // split-bf16 operands ("fp32" mode): the same tiles from hi and lo planes, 16-deep stages, three MFMAs per fragment pair
     const int mtiles = (M + DG_BM - 1) / DG_BM;
     p.c_split_row = splits;
-    static bool raised = false;
-    if (!raised) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_gemm320_dma4s_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, D4S_LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_gemm320_dma4s_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, D4S_LDS_BYTES);
-      raised = true;
-    }
-    if (a_kmajor) hipLaunchKernelGGL(dec_gemm320_dma4s_kernel<true>, dim3(mtiles * splits), dim3(512), D4S_LDS_BYTES, s, p);
-    else hipLaunchKernelGGL(dec_gemm320_dma4s_kernel<false>, dim3(mtiles * splits), dim3(512), D4S_LDS_BYTES, s, p);
+    if (a_kmajor) launch_lds<dec_gemm320_dma4s_kernel<true>>(dim3(mtiles * splits), dim3(512), D4S_LDS_BYTES, s, p);
+    else launch_lds<dec_gemm320_dma4s_kernel<false>>(dim3(mtiles * splits), dim3(512), D4S_LDS_BYTES, s, p);
     return launch_status("spv_gemm_bf16 dma split");
   }
-  if (nsplit == 1 && spv_gemm_bf16_uses_dma(a_kmajor, M, N, K, nsplit, a_tiles, ldb) && ((reinterpret_cast<uintptr_t>(A_hi) | reinterpret_cast<uintptr_t>(B_hi)) & 15) == 0) {
+  if (nsplit == 1 && spv_gemm_bf16_uses_dma(a_kmajor, M, N, K, nsplit, a_tiles, ldb) && aligned16(A_hi, B_hi)) {
     // LDS-DMA kernels (spv_dec_gemm.h): 128 x 320 workgroup tiles, `splits` K ranges, four 28 KiB stages (measured at C2,
     // tools/probes/dec_gemm_bench.hip: d A_m 37.5 us, d W_m 38.9 us against 76.5 / 84.8 us for the register-staged 64 x 320 kernel below;
     // the two-stage x 64-deep version of the same kernel: 38.2 / 41.5 us)
     const int mtiles = (M + DG_BM - 1) / DG_BM;
     p.c_split_row = splits;
-    static bool raised = false;
-    if (!raised) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_gemm320_dma4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, D4_LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_gemm320_dma4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, D4_LDS_BYTES);
-      raised = true;
-    }
-    if (a_kmajor) hipLaunchKernelGGL(dec_gemm320_dma4_kernel<true>, dim3(mtiles * splits), dim3(512), D4_LDS_BYTES, s, p);
-    else hipLaunchKernelGGL(dec_gemm320_dma4_kernel<false>, dim3(mtiles * splits), dim3(512), D4_LDS_BYTES, s, p);
+    if (a_kmajor) launch_lds<dec_gemm320_dma4_kernel<true>>(dim3(mtiles * splits), dim3(512), D4_LDS_BYTES, s, p);
+    else launch_lds<dec_gemm320_dma4_kernel<false>>(dim3(mtiles * splits), dim3(512), D4_LDS_BYTES, s, p);
     return launch_status("spv_gemm_bf16 dma");
   }
   if (a_tiles) {
@@ -478,8 +491,7 @@ extern "C" int spv_gemm_bf16_fix(int32_t a_kmajor, const uint16_t* A_hi, const u
 // both groups' 320-column GEMMs of the decoder backward (same direction, bf16 words, LDS-DMA shapes) as one grid; anything else: per group
 static bool gemm_pair_ok(const spv_gemm_args& a) {
   return a.A_hi && a.B_hi && a.C && a.nsplit == 1 && a.M > 0 && a.N > 0 && a.K > 0 && a.splits > 0 &&
-         spv_gemm_bf16_uses_dma(a.a_kmajor, a.M, a.N, a.K, a.nsplit, a.a_tiles, a.ldb) &&
-         ((reinterpret_cast<uintptr_t>(a.A_hi) | reinterpret_cast<uintptr_t>(a.B_hi)) & 15) == 0;
+         spv_gemm_bf16_uses_dma(a.a_kmajor, a.M, a.N, a.K, a.nsplit, a.a_tiles, a.ldb) && aligned16(a.A_hi, a.B_hi);
 }
 static GemmParams gemm_pair_params(const spv_gemm_args& a) {
   GemmParams p{};
@@ -493,28 +505,20 @@ static GemmParams gemm_pair_params(const spv_gemm_args& a) {
 extern "C" int spv_gemm_bf16_grouped(const spv_gemm_args* g, int32_t n, void* stream) {
   if (!g || n <= 0) return fail(SPV_ERR_ARG, "spv_gemm_bf16_grouped: bad arguments%s");
   hipStream_t s = (hipStream_t)stream;
-  int i = 0;
-  for (; i + 1 < n; i += 2) {
-    const spv_gemm_args &a = g[i], &b = g[i + 1];
-    if (!(gemm_pair_ok(a) && gemm_pair_ok(b) && a.a_kmajor == b.a_kmajor)) break;
-    const GemmParams p0 = gemm_pair_params(a), p1 = gemm_pair_params(b);
-    const int n0 = (a.M + DG_BM - 1) / DG_BM * a.splits, n1 = (b.M + DG_BM - 1) / DG_BM * b.splits;
-    static bool raised = false;
-    if (!raised) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_gemm320_dma4_pair_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, D4_LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_gemm320_dma4_pair_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, D4_LDS_BYTES);
-      raised = true;
-    }
-    if (a.a_kmajor) hipLaunchKernelGGL(dec_gemm320_dma4_pair_kernel<true>, dim3(n0 > n1 ? n0 : n1, 2), dim3(512), D4_LDS_BYTES, s, p0, p1);
-    else hipLaunchKernelGGL(dec_gemm320_dma4_pair_kernel<false>, dim3(n0 > n1 ? n0 : n1, 2), dim3(512), D4_LDS_BYTES, s, p0, p1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_gemm_bf16_grouped");
-  }
-  for (; i < n; ++i) {
-    const spv_gemm_args& a = g[i];
-    const int rc = spv_gemm_bf16(a.a_kmajor, a.A_hi, a.A_lo, a.lda, a.B_hi, a.B_lo, a.ldb, a.C, a.ldc, a.M, a.N, a.K, a.nsplit, a.splits, a.slab_stride, a.a_tiles, stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n,
+    [&](int i) {
+      const spv_gemm_args &a = g[i], &b = g[i + 1];
+      if (!(gemm_pair_ok(a) && gemm_pair_ok(b) && a.a_kmajor == b.a_kmajor)) return NOT_A_PAIR;
+      const GemmParams p0 = gemm_pair_params(a), p1 = gemm_pair_params(b);
+      const int n0 = (a.M + DG_BM - 1) / DG_BM * a.splits, n1 = (b.M + DG_BM - 1) / DG_BM * b.splits;
+      if (a.a_kmajor) launch_lds<dec_gemm320_dma4_pair_kernel<true>>(dim3(max2(n0, n1), 2), dim3(512), D4_LDS_BYTES, s, p0, p1);
+      else launch_lds<dec_gemm320_dma4_pair_kernel<false>>(dim3(max2(n0, n1), 2), dim3(512), D4_LDS_BYTES, s, p0, p1);
+      return launch_status("spv_gemm_bf16_grouped");
+    },
+    [&](int i) {
+      const spv_gemm_args& a = g[i];
+      return spv_gemm_bf16(a.a_kmajor, a.A_hi, a.A_lo, a.lda, a.B_hi, a.B_lo, a.ldb, a.C, a.ldc, a.M, a.N, a.K, a.nsplit, a.splits, a.slab_stride, a.a_tiles, stream);
+    });
 }
 
 extern "C" int spv_dec_heads_wgrad(const uint16_t* tP, const uint16_t* tS, int32_t a_tiles, const uint16_t* Aps, int32_t G, int32_t Bp,
@@ -522,14 +526,11 @@ extern "C" int spv_dec_heads_wgrad(const uint16_t* tP, const uint16_t* tS, int32
   if (!tP || !tS || !Aps || !slabP || !slabS) return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: null pointer%s");
   if (G <= 0 || Bp <= 0 || (Bp % DH_BK) != 0 || splits <= 0 || (long)a_tiles * 32 < ((long)G + DH_BM - 1) / DH_BM * DH_BM)
     return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: Bp must be a multiple of 64 and the tile arrays must cover round_up(G, 256) genes%s");
-  if (((reinterpret_cast<uintptr_t>(tP) | reinterpret_cast<uintptr_t>(tS) | reinterpret_cast<uintptr_t>(Aps)) & 15) != 0)
-    return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: operands must be 16-byte aligned%s");
-  static bool raised = false;
-  if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_heads_wgrad_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DH_LDS_BYTES); raised = true; }
+  if (!aligned16(tP, tS, Aps)) return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: operands must be 16-byte aligned%s");
   const int mtiles = (G + DH_BM - 1) / DH_BM, ktiles = Bp / DH_BK;
   const int k_per_split = (ktiles + splits - 1) / splits * DH_BK;
-  hipLaunchKernelGGL(dec_heads_wgrad_dma_kernel, dim3(mtiles * splits), dim3(512), DH_LDS_BYTES, (hipStream_t)stream, (const bf16_t*)tP, (const bf16_t*)tS, a_tiles,
-                     (const bf16_t*)Aps, G, Bp, k_per_split, splits, slabP, slabS);
+  launch_lds<dec_heads_wgrad_dma_kernel>(dim3(mtiles * splits), dim3(512), DH_LDS_BYTES, (hipStream_t)stream, (const bf16_t*)tP, (const bf16_t*)tS, a_tiles,
+                                         (const bf16_t*)Aps, G, Bp, k_per_split, splits, slabP, slabS);
   return launch_status("spv_dec_heads_wgrad");
 }
 
@@ -574,21 +575,16 @@ extern "C" int spv_dec_tables(const float* px_r, int32_t G, int32_t Gp, void* ge
 // per-group entry points in order.
 extern "C" int spv_dec_tables_grouped(const spv_dec_group* g, int32_t n, void* stream) {
   if (!g || n <= 0) return fail(SPV_ERR_ARG, "spv_dec_tables_grouped: bad arguments%s");
-  int i = 0;
-  for (; i + 1 < n; i += 2) {
-    const spv_dec_group &a = g[i], &b = g[i + 1];
-    if (!a.px_r || !b.px_r || !a.p.gene_tab || !b.p.gene_tab || !a.p.cnt_tab || !b.p.cnt_tab || a.p.G <= 0 || b.p.G <= 0 || a.p.Gp < a.p.G || b.p.Gp < b.p.G)
-      return fail(SPV_ERR_ARG, "spv_dec_tables_grouped: bad arguments%s");
-    const NbTabArgs a0{a.px_r, a.p.G, a.p.Gp, (float4*)a.p.gene_tab, (float2*)a.p.cnt_tab}, a1{b.px_r, b.p.G, b.p.Gp, (float4*)b.p.gene_tab, (float2*)b.p.cnt_tab};
-    const int gp = a.p.Gp > b.p.Gp ? a.p.Gp : b.p.Gp;
-    hipLaunchKernelGGL(nb_tables_pair_kernel, dim3((gp + 255) / 256, NB_CMAX, 2), dim3(256), 0, (hipStream_t)stream, a0, a1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_dec_tables_grouped");
-  }
-  for (; i < n; ++i) {
-    const int rc = spv_dec_tables(g[i].px_r, g[i].p.G, g[i].p.Gp, const_cast<void*>(g[i].p.gene_tab), const_cast<void*>(g[i].p.cnt_tab), stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n,
+    [&](int i) {
+      const spv_dec_group &a = g[i], &b = g[i + 1];
+      if (!a.px_r || !b.px_r || !a.p.gene_tab || !b.p.gene_tab || !a.p.cnt_tab || !b.p.cnt_tab || a.p.G <= 0 || b.p.G <= 0 || a.p.Gp < a.p.G || b.p.Gp < b.p.G)
+        return fail(SPV_ERR_ARG, "spv_dec_tables_grouped: bad arguments%s");
+      const NbTabArgs a0{a.px_r, a.p.G, a.p.Gp, (float4*)a.p.gene_tab, (float2*)a.p.cnt_tab}, a1{b.px_r, b.p.G, b.p.Gp, (float4*)b.p.gene_tab, (float2*)b.p.cnt_tab};
+      hipLaunchKernelGGL(nb_tables_pair_kernel, dim3((max2(a.p.Gp, b.p.Gp) + 255) / 256, NB_CMAX, 2), dim3(256), 0, (hipStream_t)stream, a0, a1);
+      return launch_status("spv_dec_tables_grouped");
+    },
+    [&](int i) { return spv_dec_tables(g[i].px_r, g[i].p.G, g[i].p.Gp, const_cast<void*>(g[i].p.gene_tab), const_cast<void*>(g[i].p.cnt_tab), stream); });
 }
 
 static int lse_prepare(const spv_dec_params* q, const float* library, DecParams& p) {
@@ -613,47 +609,60 @@ extern "C" int spv_dec_lse(const spv_dec_params* q, const float* library, void* 
 extern "C" int spv_dec_lse_grouped(const spv_dec_group* g, int32_t n, void* stream) {
   if (!g || n <= 0) return fail(SPV_ERR_ARG, "spv_dec_lse_grouped: bad arguments%s");
   hipStream_t s = (hipStream_t)stream;
-  int i = 0;
-  for (; i + 1 < n; i += 2) {
-    DecParams p0, p1;
-    int rc = lse_prepare(&g[i].p, g[i].library, p0);
-    if (rc != SPV_OK) return rc;
-    rc = lse_prepare(&g[i + 1].p, g[i + 1].library, p1);
-    if (rc != SPV_OK) return rc;
-    if (dec_kw(&g[i].p) != dec_kw(&g[i + 1].p)) break;   // (one grid needs one operand layout)
-    const int bp = p0.Bp > p1.Bp ? p0.Bp : p1.Bp, gs = p0.gene_splits > p1.gene_splits ? p0.gene_splits : p1.gene_splits;
-    if (dec_kw(&g[i].p) == 2) hipLaunchKernelGGL(dec_lse_pair_kernel<2>, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, s, p0, p1);
-    else hipLaunchKernelGGL(dec_lse_pair_kernel<1>, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, s, p0, p1);
-    const LseCombArgs c0{p0.part_max_p, p0.part_sum_p, p0.part_max_s, p0.part_sum_s, p0.gene_splits, p0.Bp, p0.B, g[i].library, (float*)p0.lse_p, (float*)p0.lse_s, (float*)p0.a_p, (float*)p0.a_s};
-    const LseCombArgs c1{p1.part_max_p, p1.part_sum_p, p1.part_max_s, p1.part_sum_s, p1.gene_splits, p1.Bp, p1.B, g[i + 1].library, (float*)p1.lse_p, (float*)p1.lse_s, (float*)p1.a_p, (float*)p1.a_s};
-    hipLaunchKernelGGL(dec_lse_combine_pair_kernel, dim3((bp + 63) / 64, 1, 2), dim3(256), 0, s, c0, c1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_dec_lse_grouped");
-  }
-  for (; i < n; ++i) {
-    const int rc = spv_dec_lse(&g[i].p, g[i].library, stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n,
+    [&](int i) {
+      DecParams p0, p1;
+      int rc = lse_prepare(&g[i].p, g[i].library, p0);
+      if (rc != SPV_OK) return rc;
+      rc = lse_prepare(&g[i + 1].p, g[i + 1].library, p1);
+      if (rc != SPV_OK) return rc;
+      if (dec_kw(&g[i].p) != dec_kw(&g[i + 1].p)) return NOT_A_PAIR;   // (one grid needs one operand layout)
+      const int bp = max2(p0.Bp, p1.Bp), gs = max2(p0.gene_splits, p1.gene_splits);
+      if (dec_kw(&g[i].p) == 2) hipLaunchKernelGGL(dec_lse_pair_kernel<2>, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, s, p0, p1);
+      else hipLaunchKernelGGL(dec_lse_pair_kernel<1>, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, s, p0, p1);
+      const LseCombArgs c0{p0.part_max_p, p0.part_sum_p, p0.part_max_s, p0.part_sum_s, p0.gene_splits, p0.Bp, p0.B, g[i].library, (float*)p0.lse_p, (float*)p0.lse_s, (float*)p0.a_p, (float*)p0.a_s};
+      const LseCombArgs c1{p1.part_max_p, p1.part_sum_p, p1.part_max_s, p1.part_sum_s, p1.gene_splits, p1.Bp, p1.B, g[i + 1].library, (float*)p1.lse_p, (float*)p1.lse_s, (float*)p1.a_p, (float*)p1.a_s};
+      hipLaunchKernelGGL(dec_lse_combine_pair_kernel, dim3((bp + 63) / 64, 1, 2), dim3(256), 0, s, c0, c1);
+      return launch_status("spv_dec_lse_grouped");
+    },
+    [&](int i) { return spv_dec_lse(&g[i].p, g[i].library, stream); });
 }
 
-template <bool TRAIN, typename GT, int CM, int KW>
-static void nb_launch_mode(const DecParams& p, hipStream_t s) {
-  const int ctiles = (p.Bp + NB_CELLS_PER_WG - 1) / NB_CELLS_PER_WG;
-  dim3 grid((ctiles + p.nb_cell_tiles - 1) / p.nb_cell_tiles, p.nb_splits);
-  if (p.logits_f32) hipLaunchKernelGGL((dec_nb_kernel<TRAIN, GT, float, CM, KW>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((dec_nb_kernel<TRAIN, GT, _Float16, CM, KW>), grid, dim3(256), 0, s, p);
-}
-template <bool TRAIN, typename GT, int KW>
-static void nb_launch_kw(const DecParams& p, hipStream_t s) {
-  if (!p.count_is_u16) return nb_launch_mode<TRAIN, GT, CNT_F32, KW>(p, s);
+// ---- the likelihood kernel: dec_nb_kernel for one group, dec_nb_pair_kernel for two in one grid (p1 != NULL) -----------------------------
+// count storage of a group: 16-bit counts are read four at a time when base, row pitch and column offset allow 8-byte loads
+static int nb_count_mode(const DecParams& p) {
+  if (!p.count_is_u16) return CNT_F32;
   const bool aligned = ((reinterpret_cast<uintptr_t>(p.X) & 7) == 0) && (p.ldx % 4 == 0) && (p.col_off % 4 == 0);
-  if (aligned) nb_launch_mode<TRAIN, GT, CNT_U16_ALIGNED, KW>(p, s);
-  else nb_launch_mode<TRAIN, GT, CNT_U16_ANY, KW>(p, s);
+  return aligned ? CNT_U16_ALIGNED : CNT_U16_ANY;
+}
+template <bool TRAIN, typename GT, typename LT, int CM, int KW>
+static void nb_launch_as(const DecParams& p0, const DecParams* p1, hipStream_t s) {
+  auto gx = [](const DecParams& p) { return ((p.Bp + NB_CELLS_PER_WG - 1) / NB_CELLS_PER_WG + p.nb_cell_tiles - 1) / p.nb_cell_tiles; };
+  if (!p1) hipLaunchKernelGGL((dec_nb_kernel<TRAIN, GT, LT, CM, KW>), dim3(gx(p0), p0.nb_splits), dim3(256), 0, s, p0);
+  else hipLaunchKernelGGL((dec_nb_pair_kernel<TRAIN, GT, LT, CM, KW>), dim3(max2(gx(p0), gx(*p1)), max2(p0.nb_splits, p1->nb_splits), 2), dim3(256), 0, s, p0, *p1);
+}
+// the kernel variant of p0 (a pair: of both groups, spv_dec_nb_fwd_grouped sees to it), resolved one template argument per step
+template <bool TRAIN, typename GT, int CM, int KW>
+static void nb_launch_lt(const DecParams& p0, const DecParams* p1, hipStream_t s) {
+  if (p0.logits_f32) nb_launch_as<TRAIN, GT, float, CM, KW>(p0, p1, s);
+  else nb_launch_as<TRAIN, GT, _Float16, CM, KW>(p0, p1, s);
+}
+template <bool TRAIN, typename GT, int CM>
+static void nb_launch_kw(const DecParams& p0, const DecParams* p1, int kw, hipStream_t s) {
+  if (kw == 2) nb_launch_lt<TRAIN, GT, CM, 2>(p0, p1, s);
+  else nb_launch_lt<TRAIN, GT, CM, 1>(p0, p1, s);
 }
 template <bool TRAIN, typename GT>
-static void nb_launch(const DecParams& p, int kw, hipStream_t s) {
-  if (kw == 2) nb_launch_kw<TRAIN, GT, 2>(p, s);
-  else nb_launch_kw<TRAIN, GT, 1>(p, s);
+static void nb_launch_cm(const DecParams& p0, const DecParams* p1, int kw, hipStream_t s) {
+  const int cm = nb_count_mode(p0);
+  if (cm == CNT_F32) nb_launch_kw<TRAIN, GT, CNT_F32>(p0, p1, kw, s);
+  else if (cm == CNT_U16_ALIGNED) nb_launch_kw<TRAIN, GT, CNT_U16_ALIGNED>(p0, p1, kw, s);
+  else nb_launch_kw<TRAIN, GT, CNT_U16_ANY>(p0, p1, kw, s);
+}
+static void nb_launch(const DecParams& p0, const DecParams* p1, int train, int kw, hipStream_t s) {
+  if (!train) nb_launch_cm<false, bf16_t>(p0, p1, kw, s);
+  else if (p0.grads_f32) nb_launch_cm<true, split_t>(p0, p1, kw, s);
+  else nb_launch_cm<true, bf16_t>(p0, p1, kw, s);
 }
 
 static int nb_prepare(const spv_dec_params* q, int32_t train, DecParams& p) {
@@ -673,65 +682,24 @@ extern "C" int spv_dec_nb_fwd(const spv_dec_params* q, int32_t train, void* stre
   DecParams p;
   int rc = nb_prepare(q, train, p);
   if (rc != SPV_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int kw = dec_kw(q);
-  if (train) {
-    if (p.grads_f32) nb_launch<true, split_t>(p, kw, s);
-    else nb_launch<true, bf16_t>(p, kw, s);
-  } else {
-    nb_launch<false, bf16_t>(p, kw, s);
-  }
+  nb_launch(p, nullptr, train, dec_kw(q), (hipStream_t)stream);
   return launch_status("spv_dec_nb_fwd");
-}
-static int nb_count_mode(const DecParams& p) {
-  if (!p.count_is_u16) return CNT_F32;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(p.X) & 7) == 0) && (p.ldx % 4 == 0) && (p.col_off % 4 == 0);
-  return aligned ? CNT_U16_ALIGNED : CNT_U16_ANY;
-}
-template <bool TRAIN, typename GT, int CM, int KW>
-static void nb_launch_pair_mode(const DecParams& p0, const DecParams& p1, hipStream_t s) {
-  auto gx = [](const DecParams& p) { return ((p.Bp + NB_CELLS_PER_WG - 1) / NB_CELLS_PER_WG + p.nb_cell_tiles - 1) / p.nb_cell_tiles; };
-  dim3 grid(gx(p0) > gx(p1) ? gx(p0) : gx(p1), p0.nb_splits > p1.nb_splits ? p0.nb_splits : p1.nb_splits, 2);
-  if (p0.logits_f32) hipLaunchKernelGGL((dec_nb_pair_kernel<TRAIN, GT, float, CM, KW>), grid, dim3(256), 0, s, p0, p1);
-  else hipLaunchKernelGGL((dec_nb_pair_kernel<TRAIN, GT, _Float16, CM, KW>), grid, dim3(256), 0, s, p0, p1);
-}
-template <bool TRAIN, typename GT, int KW>
-static void nb_launch_pair_kw(const DecParams& p0, const DecParams& p1, int cm, hipStream_t s) {
-  if (cm == CNT_F32) nb_launch_pair_mode<TRAIN, GT, CNT_F32, KW>(p0, p1, s);
-  else if (cm == CNT_U16_ALIGNED) nb_launch_pair_mode<TRAIN, GT, CNT_U16_ALIGNED, KW>(p0, p1, s);
-  else nb_launch_pair_mode<TRAIN, GT, CNT_U16_ANY, KW>(p0, p1, s);
-}
-template <bool TRAIN, typename GT>
-static void nb_launch_pair(const DecParams& p0, const DecParams& p1, int cm, int kw, hipStream_t s) {
-  if (kw == 2) nb_launch_pair_kw<TRAIN, GT, 2>(p0, p1, cm, s);
-  else nb_launch_pair_kw<TRAIN, GT, 1>(p0, p1, cm, s);
 }
 extern "C" int spv_dec_nb_fwd_grouped(const spv_dec_group* g, int32_t n, int32_t train, void* stream) {
   if (!g || n <= 0) return fail(SPV_ERR_ARG, "spv_dec_nb_fwd_grouped: bad arguments%s");
-  hipStream_t s = (hipStream_t)stream;
-  int i = 0;
-  for (; i + 1 < n; i += 2) {
-    DecParams p0, p1;
-    int rc = nb_prepare(&g[i].p, train, p0);
-    if (rc != SPV_OK) return rc;
-    rc = nb_prepare(&g[i + 1].p, train, p1);
-    if (rc != SPV_OK) return rc;
-    // one grid needs one kernel variant: count storage, logits type and gradient word type of both groups must agree
-    if (nb_count_mode(p0) != nb_count_mode(p1) || p0.logits_f32 != p1.logits_f32 || p0.grads_f32 != p1.grads_f32 || dec_kw(&g[i].p) != dec_kw(&g[i + 1].p)) break;
-    const int cm = nb_count_mode(p0), kw = dec_kw(&g[i].p);
-    if (train) {
-      if (p0.grads_f32) nb_launch_pair<true, split_t>(p0, p1, cm, kw, s);
-      else nb_launch_pair<true, bf16_t>(p0, p1, cm, kw, s);
-    } else {
-      nb_launch_pair<false, bf16_t>(p0, p1, cm, kw, s);
-    }
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_dec_nb_fwd_grouped");
-  }
-  for (; i < n; ++i) {
-    const int rc = spv_dec_nb_fwd(&g[i].p, train, stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n,
+    [&](int i) {
+      DecParams p0, p1;
+      int rc = nb_prepare(&g[i].p, train, p0);
+      if (rc != SPV_OK) return rc;
+      rc = nb_prepare(&g[i + 1].p, train, p1);
+      if (rc != SPV_OK) return rc;
+      // one grid needs one kernel variant: count storage, logits type and gradient word type of both groups must agree
+      if (nb_count_mode(p0) != nb_count_mode(p1) || p0.logits_f32 != p1.logits_f32 || p0.grads_f32 != p1.grads_f32 || dec_kw(&g[i].p) != dec_kw(&g[i + 1].p)) return NOT_A_PAIR;
+      nb_launch(p0, &p1, train, dec_kw(&g[i].p), (hipStream_t)stream);
+      return launch_status("spv_dec_nb_fwd_grouped");
+    },
+    [&](int i) { return spv_dec_nb_fwd(&g[i].p, train, stream); });
 }
 
 extern "C" int spv_dec_logits(const uint16_t* Am_hi, const uint16_t* Am_lo, const uint16_t* Wm_hi, const uint16_t* Wm_lo,
@@ -749,12 +717,9 @@ extern "C" int spv_dec_logits(const uint16_t* Am_hi, const uint16_t* Am_lo, cons
   p.epi = out_f32 ? EPI_TILED_F32 : EPI_TILED_F16;
   p.tiles_inner = Gp / 32;
   hipStream_t s = (hipStream_t)stream;
-  static const int logits_dma = getenv("SPV_LOGITS_DMA") ? atoi(getenv("SPV_LOGITS_DMA")) : 1;   // (A/B switch)
-  if (logits_dma && nsplit == 1 && !out_f32 && Gp % DL_BM == 0 && Bp % DL_BN == 0 && ((reinterpret_cast<uintptr_t>(Am_hi) | reinterpret_cast<uintptr_t>(Wm_hi)) & 15) == 0) {
+  if (nsplit == 1 && !out_f32 && Gp % DL_BM == 0 && Bp % DL_BN == 0 && aligned16(Am_hi, Wm_hi)) {
     // LDS-DMA kernel (spv_dec_gemm.h): 256 x 128 tiles, two workgroups per CU
-    static bool raised = false;
-    if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_logits_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS_BYTES); raised = true; }
-    hipLaunchKernelGGL(dec_logits_dma_kernel, dim3(Gp / DL_BM, Bp / DL_BN), dim3(512), DL_LDS_BYTES, s, (const bf16_t*)Wm_hi, (const bf16_t*)Am_hi, K, Gp / 32, (_Float16*)out);
+    launch_lds<dec_logits_dma_kernel>(dim3(Gp / DL_BM, Bp / DL_BN), dim3(512), DL_LDS_BYTES, s, (const bf16_t*)Wm_hi, (const bf16_t*)Am_hi, K, Gp / 32, (_Float16*)out);
     return launch_status("spv_dec_logits dma");
   }
   if (nsplit == 3) launch_gemm<GemmCfg<128, 128, 2, 2, false, false, SRC_PLAIN, SRC_PLAIN, unsigned short, 3, 32, 4>>(p, 1, s);
@@ -764,30 +729,24 @@ extern "C" int spv_dec_logits(const uint16_t* Am_hi, const uint16_t* Am_lo, cons
 }
 
 static bool logits_dma_ok(const spv_dec_group& a) {
-  static const int logits_dma = getenv("SPV_LOGITS_DMA") ? atoi(getenv("SPV_LOGITS_DMA")) : 1;
-  return logits_dma && a.Am_hi && a.Wm_hi && a.p.logits && a.nsplit == 1 && !a.p.logits_f32 && a.K > 0 && (a.K % 32) == 0 && a.p.Bp > 0 && a.p.Gp > 0 &&
-         a.p.Gp % DL_BM == 0 && a.p.Bp % DL_BN == 0 && ((reinterpret_cast<uintptr_t>(a.Am_hi) | reinterpret_cast<uintptr_t>(a.Wm_hi)) & 15) == 0;
+  return a.Am_hi && a.Wm_hi && a.p.logits && a.nsplit == 1 && !a.p.logits_f32 && a.K > 0 && (a.K % 32) == 0 && a.p.Bp > 0 && a.p.Gp > 0 &&
+         a.p.Gp % DL_BM == 0 && a.p.Bp % DL_BN == 0 && aligned16(a.Am_hi, a.Wm_hi);
 }
 extern "C" int spv_dec_logits_grouped(const spv_dec_group* g, int32_t n, void* stream) {
   if (!g || n <= 0) return fail(SPV_ERR_ARG, "spv_dec_logits_grouped: bad arguments%s");
-  int i = 0;
-  for (; i + 1 < n; i += 2) {
-    const spv_dec_group &a = g[i], &b = g[i + 1];
-    if (!(logits_dma_ok(a) && logits_dma_ok(b))) break;
-    static bool raised = false;
-    if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_logits_dma_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS_BYTES); raised = true; }
-    const LogitsArgs a0{(const bf16_t*)a.Wm_hi, (const bf16_t*)a.Am_hi, a.K, a.p.Gp / 32, a.p.Bp, (_Float16*)const_cast<void*>(a.p.logits)};
-    const LogitsArgs a1{(const bf16_t*)b.Wm_hi, (const bf16_t*)b.Am_hi, b.K, b.p.Gp / 32, b.p.Bp, (_Float16*)const_cast<void*>(b.p.logits)};
-    const int gp = a.p.Gp > b.p.Gp ? a.p.Gp : b.p.Gp, bp = a.p.Bp > b.p.Bp ? a.p.Bp : b.p.Bp;
-    hipLaunchKernelGGL(dec_logits_dma_pair_kernel, dim3(gp / DL_BM, bp / DL_BN, 2), dim3(512), DL_LDS_BYTES, (hipStream_t)stream, a0, a1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_dec_logits_grouped");
-  }
-  for (; i < n; ++i) {
-    const spv_dec_group& a = g[i];
-    const int rc = spv_dec_logits(a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.p.Bp, a.p.Gp, a.nsplit, const_cast<void*>(a.p.logits), a.p.logits_f32, stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n,
+    [&](int i) {
+      const spv_dec_group &a = g[i], &b = g[i + 1];
+      if (!(logits_dma_ok(a) && logits_dma_ok(b))) return NOT_A_PAIR;
+      const LogitsArgs a0{(const bf16_t*)a.Wm_hi, (const bf16_t*)a.Am_hi, a.K, a.p.Gp / 32, a.p.Bp, (_Float16*)const_cast<void*>(a.p.logits)};
+      const LogitsArgs a1{(const bf16_t*)b.Wm_hi, (const bf16_t*)b.Am_hi, b.K, b.p.Gp / 32, b.p.Bp, (_Float16*)const_cast<void*>(b.p.logits)};
+      launch_lds<dec_logits_dma_pair_kernel>(dim3(max2(a.p.Gp, b.p.Gp) / DL_BM, max2(a.p.Bp, b.p.Bp) / DL_BN, 2), dim3(512), DL_LDS_BYTES, (hipStream_t)stream, a0, a1);
+      return launch_status("spv_dec_logits_grouped");
+    },
+    [&](int i) {
+      const spv_dec_group& a = g[i];
+      return spv_dec_logits(a.Am_hi, a.Am_lo, a.Wm_hi, a.Wm_lo, a.K, a.p.Bp, a.p.Gp, a.nsplit, const_cast<void*>(a.p.logits), a.p.logits_f32, stream);
+    });
 }
 
 extern "C" int spv_dec_materialize(const spv_dec_params* q, float* scale_p, float* scale_s, float* rate_p, float* rate_s,
@@ -819,7 +778,7 @@ static int readout_prepare(const spv_dec_params* q, const char* who, const X* x,
   if (x->K <= 0 || (x->K % 32) || x->K > DX_KMAX) return fail(SPV_ERR_ARG, "%s: K must be a multiple of 32, at most 320", who);
   if (x->nsplit != 1 && x->nsplit != 3) return fail(SPV_ERR_ARG, "%s: nsplit must be 1 or 3", who);
   if (x->nsplit == 3 && (!x->Am_lo || !x->Wm_lo)) return fail(SPV_ERR_ARG, "%s: nsplit=3 needs lo images", who);
-  if ((reinterpret_cast<uintptr_t>(x->Am_hi) | reinterpret_cast<uintptr_t>(x->Wm_hi) | reinterpret_cast<uintptr_t>(x->Am_lo) | reinterpret_cast<uintptr_t>(x->Wm_lo)) & 15)
+  if (!aligned16(x->Am_hi, x->Wm_hi, x->Am_lo, x->Wm_lo))
     return fail(SPV_ERR_ARG, "%s: operand images must be 16-byte aligned", who);
   if (x->n_genes <= 0 || (!x->genes && x->n_genes > p.G)) return fail(SPV_ERR_ARG, "%s: n_genes must be positive (and at most G without a gene list)", who);
   // one workgroup per 32 cells and gene slice; each of its 4 waves walks every (4 gy)-th 32-gene tile.  ~8 workgroups per CU keep
@@ -1094,9 +1053,7 @@ extern "C" int spv_dec_heads_bwd(const spv_dec_params* q, const float* Tp, const
   if (rc != SPV_OK) return rc;
   dim3 grid(p.Bp / DEC_CELLS_PER_WG, p.gene_splits);
   if (p.grads_f32) {   // hi / lo planes of split-bf16 gradient words ("fp32" mode)
-    static bool raised = false;
-    if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_heads_bwd_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, HBS_LDS_BYTES); raised = true; }
-    hipLaunchKernelGGL(dec_heads_bwd_split_kernel, grid, dim3(256), HBS_LDS_BYTES, (hipStream_t)stream, p, Tp, Ts, dz_part, dw_part);
+    launch_lds<dec_heads_bwd_split_kernel>(grid, dim3(256), HBS_LDS_BYTES, (hipStream_t)stream, p, Tp, Ts, dz_part, dw_part);
     return launch_status("spv_dec_heads_bwd");
   }
   // (the partial slabs cover gene rows the splits do not reach only when genes_per_split * gene_splits < round_up(G, 32): the host sizes
@@ -1106,25 +1063,20 @@ extern "C" int spv_dec_heads_bwd(const spv_dec_params* q, const float* Tp, const
 }
 extern "C" int spv_dec_heads_bwd_grouped(const spv_dec_group* g, int32_t n, void* stream) {
   if (!g || n <= 0) return fail(SPV_ERR_ARG, "spv_dec_heads_bwd_grouped: bad arguments%s");
-  int i = 0;
-  for (; i + 1 < n; i += 2) {
-    HeadsBwdArgs a0, a1;
-    int rc = heads_bwd_prepare(&g[i].p, g[i].Tp, g[i].Ts, g[i].dz_part, g[i].dw_part, a0.p);
-    if (rc != SPV_OK) return rc;
-    rc = heads_bwd_prepare(&g[i + 1].p, g[i + 1].Tp, g[i + 1].Ts, g[i + 1].dz_part, g[i + 1].dw_part, a1.p);
-    if (rc != SPV_OK) return rc;
-    if (a0.p.grads_f32 || a1.p.grads_f32) break;   // (the split-word kernel takes a whole CU's LDS: no pair form)
-    a0.Tp = g[i].Tp; a0.Ts = g[i].Ts; a0.dz_part = g[i].dz_part; a0.dw_part = g[i].dw_part;
-    a1.Tp = g[i + 1].Tp; a1.Ts = g[i + 1].Ts; a1.dz_part = g[i + 1].dz_part; a1.dw_part = g[i + 1].dw_part;
-    const int bp = a0.p.Bp > a1.p.Bp ? a0.p.Bp : a1.p.Bp, gs = a0.p.gene_splits > a1.p.gene_splits ? a0.p.gene_splits : a1.p.gene_splits;
-    hipLaunchKernelGGL(dec_heads_bwd_pair_kernel, dim3(bp / DEC_CELLS_PER_WG, gs, 2), dim3(256), 0, (hipStream_t)stream, a0, a1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_dec_heads_bwd_grouped");
-  }
-  for (; i < n; ++i) {
-    const int rc = spv_dec_heads_bwd(&g[i].p, g[i].Tp, g[i].Ts, g[i].dz_part, g[i].dw_part, stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n,
+    [&](int i) {
+      HeadsBwdArgs a0, a1;
+      int rc = heads_bwd_prepare(&g[i].p, g[i].Tp, g[i].Ts, g[i].dz_part, g[i].dw_part, a0.p);
+      if (rc != SPV_OK) return rc;
+      rc = heads_bwd_prepare(&g[i + 1].p, g[i + 1].Tp, g[i + 1].Ts, g[i + 1].dz_part, g[i + 1].dw_part, a1.p);
+      if (rc != SPV_OK) return rc;
+      if (a0.p.grads_f32 || a1.p.grads_f32) return NOT_A_PAIR;   // (the split-word kernel takes a whole CU's LDS: no pair form)
+      a0.Tp = g[i].Tp; a0.Ts = g[i].Ts; a0.dz_part = g[i].dz_part; a0.dw_part = g[i].dw_part;
+      a1.Tp = g[i + 1].Tp; a1.Ts = g[i + 1].Ts; a1.dz_part = g[i + 1].dz_part; a1.dw_part = g[i + 1].dw_part;
+      hipLaunchKernelGGL(dec_heads_bwd_pair_kernel, dim3(max2(a0.p.Bp, a1.p.Bp) / DEC_CELLS_PER_WG, max2(a0.p.gene_splits, a1.p.gene_splits), 2), dim3(256), 0, (hipStream_t)stream, a0, a1);
+      return launch_status("spv_dec_heads_bwd_grouped");
+    },
+    [&](int i) { return spv_dec_heads_bwd(&g[i].p, g[i].Tp, g[i].Ts, g[i].dz_part, g[i].dw_part, stream); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1359,24 +1311,44 @@ extern "C" int spv_linear_fwd(const spv_linear_batch* a, void* stream) {
   hipLaunchKernelGGL(linear_fwd_kernel, dim3((rows + 63) / 64, (nmax + 63) / 64, a->nprob), dim3(256), 0, (hipStream_t)stream, *a);
   return launch_status("spv_linear_fwd");
 }
-extern "C" int spv_linear_dgrad(const spv_linear_batch* a, void* stream) {
-  int rc = check_linear(a, "spv_linear_dgrad");
+// the checks of an input-gradient batch (spv_linear_dgrad, the `d` batch of spv_linear_bwd)
+static int check_linear_dgrad(const spv_linear_batch* a, const char* who) {
+  int rc = check_linear(a, who);
   if (rc) return rc;
   for (int i = 0; i < a->nprob; ++i)
-    if (!a->p[i].dY || !a->p[i].dX || ((a->relu || a->drop_p > 0.f) && !a->p[i].Y)) return fail(SPV_ERR_ARG, "spv_linear_dgrad: null pointer%s");
+    if (!a->p[i].dY || !a->p[i].dX || ((a->relu || a->drop_p > 0.f) && !a->p[i].Y)) return fail(SPV_ERR_ARG, "%s: null pointer", who);
+  return SPV_OK;
+}
+// ... of a weight-gradient batch (spv_linear_wgrad, the `w` batch of spv_linear_bwd)
+static int check_linear_wgrad(const spv_linear_batch* a, const char* who) {
+  int rc = check_linear(a, who);
+  if (rc) return rc;
+  for (int i = 0; i < a->nprob; ++i)
+    if (!a->p[i].dY || !a->p[i].X || !a->p[i].dW || ((a->relu || a->drop_p > 0.f) && !a->p[i].Y)) return fail(SPV_ERR_ARG, "%s: null pointer", who);
+  return SPV_OK;
+}
+// ... and of that batch's partial-sum workspace; gives the batch's extents and prob_stride, the workspace elements per problem
+static int check_linear_wpart(const spv_linear_batch* a, const float* wpart, int64_t wpart_elems, const char* who, int& nmax, int& kmax, long& prob_stride) {
+  if (!wpart) return fail(SPV_ERR_ARG, "%s: workspace missing", who);
+  linear_extents(a, nmax, kmax);
+  prob_stride = (long)WG_SLICES * nmax * (kmax + 1);
+  if (wpart_elems < prob_stride * a->nprob) return fail(SPV_ERR_ARG, "%s: workspace too small", who);
+  return SPV_OK;
+}
+
+extern "C" int spv_linear_dgrad(const spv_linear_batch* a, void* stream) {
+  int rc = check_linear_dgrad(a, "spv_linear_dgrad");
+  if (rc) return rc;
   int nmax, kmax; linear_extents(a, nmax, kmax);
   hipLaunchKernelGGL(linear_dgrad_kernel, dim3((a->B + 63) / 64, (kmax + 63) / 64, a->nprob), dim3(256), 0, (hipStream_t)stream, *a);
   return launch_status("spv_linear_dgrad");
 }
 extern "C" int spv_linear_wgrad(const spv_linear_batch* a, float* wpart, int64_t wpart_elems, void* stream) {
-  int rc = check_linear(a, "spv_linear_wgrad");
+  int nmax, kmax;
+  long prob_stride;
+  int rc = check_linear_wgrad(a, "spv_linear_wgrad");
+  if (rc == SPV_OK) rc = check_linear_wpart(a, wpart, wpart_elems, "spv_linear_wgrad", nmax, kmax, prob_stride);
   if (rc) return rc;
-  for (int i = 0; i < a->nprob; ++i)
-    if (!a->p[i].dY || !a->p[i].X || !a->p[i].dW || ((a->relu || a->drop_p > 0.f) && !a->p[i].Y)) return fail(SPV_ERR_ARG, "spv_linear_wgrad: null pointer%s");
-  if (!wpart) return fail(SPV_ERR_ARG, "spv_linear_wgrad: workspace missing%s");
-  int nmax, kmax; linear_extents(a, nmax, kmax);
-  const long prob_stride = (long)WG_SLICES * nmax * (kmax + 1);
-  if (wpart_elems < prob_stride * a->nprob) return fail(SPV_ERR_ARG, "spv_linear_wgrad: workspace too small%s");
   hipStream_t s = (hipStream_t)stream;
   if (a->B <= WG_DIRECT_MAX_B) {   // one slice holds the whole minibatch: results straight into dW / db
     hipLaunchKernelGGL(linear_wgrad_direct_kernel, dim3((nmax + 31) / 32, (kmax + 31) / 32, a->nprob), dim3(256), 0, s, *a);
@@ -1418,24 +1390,19 @@ extern "C" int spv_linear_bwd(const spv_linear_batch* d, const spv_linear_batch*
   LinearBwdGrid g = {};
   long prob_stride = 0;
   if (d) {   // spv_linear_dgrad's checks and grid
-    int rc = check_linear(d, "spv_linear_bwd");
+    int rc = check_linear_dgrad(d, "spv_linear_bwd");
     if (rc) return rc;
-    for (int i = 0; i < d->nprob; ++i)
-      if (!d->p[i].dY || !d->p[i].dX || ((d->relu || d->drop_p > 0.f) && !d->p[i].Y)) return fail(SPV_ERR_ARG, "spv_linear_bwd: null pointer%s");
     int nmax, kmax; linear_extents(d, nmax, kmax);
     g.dgx = (d->B + 63) / 64; g.dgy = (kmax + 63) / 64;
     g.nd = g.dgx * g.dgy * d->nprob;
   }
   if (w) {   // spv_linear_wgrad's
-    int rc = check_linear(w, "spv_linear_bwd");
+    int nmax, kmax;
+    int rc = check_linear_wgrad(w, "spv_linear_bwd");
     if (rc) return rc;
-    for (int i = 0; i < w->nprob; ++i)
-      if (!w->p[i].dY || !w->p[i].X || !w->p[i].dW || ((w->relu || w->drop_p > 0.f) && !w->p[i].Y)) return fail(SPV_ERR_ARG, "spv_linear_bwd: null pointer%s");
     if (w->accumulate) return fail(SPV_ERR_ARG, "spv_linear_bwd: accumulate belongs to the input-gradient batch%s");
-    if (!wpart) return fail(SPV_ERR_ARG, "spv_linear_bwd: workspace missing%s");
-    int nmax, kmax; linear_extents(w, nmax, kmax);
-    prob_stride = (long)WG_SLICES * nmax * (kmax + 1);
-    if (wpart_elems < prob_stride * w->nprob) return fail(SPV_ERR_ARG, "spv_linear_bwd: workspace too small%s");
+    rc = check_linear_wpart(w, wpart, wpart_elems, "spv_linear_bwd", nmax, kmax, prob_stride);
+    if (rc) return rc;
     g.wgx = (nmax + 31) / 32; g.wgy = (kmax + 31) / 32;
     g.nw = g.wgx * g.wgy * w->nprob * (w->B <= WG_DIRECT_MAX_B ? 1 : WG_SLICES);
   }
@@ -1951,6 +1918,21 @@ static int fc1_finish_blocks(const Fc1PrepArgs& a) {
   const int nb_bias = (a.N1 + 63) / 64;
   return (a.img_lo == nullptr && a.nblk > nb_bias) ? a.nblk : nb_bias;
 }
+// (the arguments of spv_enc_fc1_bwd_prep)
+static Fc1PrepArgs fc1_prep_args(const float* dh1, const float* h1, int B, int N1, uint16_t* img_hi, uint16_t* img_lo, long ld_img, int Bp, float* part, float* db,
+                                 float* db2, int n_first, float* scale_ws) {
+  return Fc1PrepArgs{dh1, h1, B, N1, (bf16_t*)img_hi, (bf16_t*)img_lo, ld_img, part, Bp / 16, db, db2, n_first, scale_ws};
+}
+// the pair forms of spv_enc_fc1_bwd_grouped: 16-bit mode only, so the f16 image (no lo plane) whatever dh_lo says
+static Fc1PrepArgs fc1_prep_args(const spv_fc1_bwd_args& a) {
+  return fc1_prep_args(a.dh1, a.h1, a.B, a.N1, a.dh_hi, nullptr, a.ld_dh, a.Bp, a.part, a.db, a.db2, a.n_first, a.scale_ws);
+}
+// relu mask, image and bias gradients of both groups: one grid per kernel
+static void fc1_prep_pair_launch(const spv_fc1_bwd_args& a, const spv_fc1_bwd_args& b, hipStream_t s) {
+  const Fc1PrepArgs q0 = fc1_prep_args(a), q1 = fc1_prep_args(b);
+  hipLaunchKernelGGL(fc1_bwd_prep_pair_kernel, dim3(max2(q0.nblk, q1.nblk), 2), dim3(256), 0, s, q0, q1);
+  hipLaunchKernelGGL(fc1_bwd_finish_pair_kernel, dim3(max2(fc1_finish_blocks(q0), fc1_finish_blocks(q1)), 2), dim3(256), 0, s, q0, q1);
+}
 
 extern "C" int spv_enc_fc1_bwd_prep(const float* dh1, const float* h1, int32_t B, int32_t N1, uint16_t* img_hi, uint16_t* img_lo,
                                     int64_t ld_img, int32_t Bp, float* part, float* db, float* db2, int32_t n_first, float* scale_ws, void* stream) {
@@ -1959,7 +1941,7 @@ extern "C" int spv_enc_fc1_bwd_prep(const float* dh1, const float* h1, int32_t B
   if (!img_lo && !scale_ws) return fail(SPV_ERR_ARG, "spv_enc_fc1_bwd_prep: the f16 image (img_lo == NULL) needs scale_ws [2 + Bp / 16]%s");
   if (Bp / 16 > 65536) return fail(SPV_ERR_ARG, "spv_enc_fc1_bwd_prep: minibatch too large%s");
   hipStream_t s = (hipStream_t)stream;
-  const Fc1PrepArgs a{dh1, h1, B, N1, (bf16_t*)img_hi, (bf16_t*)img_lo, (long)ld_img, part, Bp / 16, db, db2, n_first, scale_ws};
+  const Fc1PrepArgs a = fc1_prep_args(dh1, h1, B, N1, img_hi, img_lo, ld_img, Bp, part, db, db2, n_first, scale_ws);
   hipLaunchKernelGGL(fc1_bwd_prep_kernel, dim3(a.nblk), dim3(256), 0, s, a);
   hipLaunchKernelGGL(fc1_bwd_finish_kernel, dim3(fc1_finish_blocks(a)), dim3(256), 0, s, a);
   return launch_status("spv_enc_fc1_bwd_prep");
@@ -1968,9 +1950,8 @@ extern "C" int spv_enc_fc1_bwd_prep(const float* dh1, const float* h1, int32_t B
 // ---- both groups of a step in one launch per kernel (csrc/spv_fc1.h: *_pair_kernel) ---------------------------------------------------
 static bool fc1_fwd_dma_ok(const spv_fc1_fwd_args& a) {
   return a.x && a.x->X && a.W1_hi && a.bias && a.slabs && a.h1 && a.library && a.xb_all && a.library_all && a.B > 0 && a.G > 0 && a.splits > 0 &&
-         spv_enc_fc1_fwd_uses_dma(a.B, a.G, a.N1, a.nsplit, 1, a.ldw, a.ld_xb) &&
-         ((reinterpret_cast<uintptr_t>(a.xb_all) | reinterpret_cast<uintptr_t>(a.W1_hi)) & 15) == 0 &&
-         (a.nsplit == 1 || (a.W1_lo && (reinterpret_cast<uintptr_t>(a.W1_lo) & 15) == 0));
+         spv_enc_fc1_fwd_uses_dma(a.B, a.G, a.N1, a.nsplit, 1, a.ldw, a.ld_xb) && aligned16(a.xb_all, a.W1_hi) &&
+         (a.nsplit == 1 || (a.W1_lo && aligned16(a.W1_lo)));
 }
 static GemmParams fc1_fwd_dma_params(const spv_fc1_fwd_args& a) {
   GemmParams p{};
@@ -1983,177 +1964,138 @@ static GemmParams fc1_fwd_dma_params(const spv_fc1_fwd_args& a) {
   return p;
 }
 
+// shapes the LDS-DMA kernel does not take, 16-bit mode on resident images, at most 128 output units (n_hidden <= 64): the register-staged
+// GEMM and its epilogue for both groups in one grid each (gemm_pair_kernel) -- at 128 cells per minibatch a launch is mostly fixed cost
+static bool fc1_fwd_plain_ok(const spv_fc1_fwd_args& a) {
+  return a.x && a.x->X && a.W1_hi && a.bias && a.slabs && a.rowsum_ws && a.h1 && a.library && a.xb_all && a.library_all && a.B > 0 && a.G > 0 && a.splits > 0 &&
+         a.nsplit == 1 && a.N1 > 32 && a.N1 <= 128 && (a.ldw % 32) == 0 && a.ldw >= ((a.G + 31) & ~31) && a.ld_xb >= ((a.G + 31) & ~31) && (a.ld_xb % 8) == 0 &&
+         (a.cov == nullptr) == (a.cov_idx == nullptr);
+}
+
 extern "C" int spv_enc_fc1_fwd_grouped(const spv_fc1_fwd_args* g, int32_t n_groups, void* stream) {
   if (!g || n_groups <= 0) return fail(SPV_ERR_ARG, "spv_enc_fc1_fwd_grouped: bad arguments%s");
   hipStream_t s = (hipStream_t)stream;
-  int i = 0;
-  for (; i + 1 < n_groups; i += 2) {
-    const spv_fc1_fwd_args &a = g[i], &b = g[i + 1];
-    if (!(fc1_fwd_dma_ok(a) && fc1_fwd_dma_ok(b) && a.N1 == b.N1 && a.nsplit == b.nsplit)) break;
-    const GemmParams p0 = fc1_fwd_dma_params(a), p1 = fc1_fwd_dma_params(b);
-    const int mt0 = (a.B + F1_BM - 1) / F1_BM, mt1 = (b.B + F1_BM - 1) / F1_BM;
-    static bool raised = false;
-    if (!raised) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fc1_fwd_dma_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F1_LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fc1_fwd_dma_split_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F1_LDS_BYTES);
-      raised = true;
-    }
-    const float acc_scale = (a.nsplit == 1) ? 1.0f / SPV_FC1_W_SCALE : 1.0f;
-    if (a.nsplit == 3) hipLaunchKernelGGL(fc1_fwd_dma_split_pair_kernel, dim3(mt0 * a.splits + mt1 * b.splits, a.N1 / F1_BN), dim3(512), F1_LDS_BYTES, s, p0, p1, mt0 * a.splits);
-    else hipLaunchKernelGGL(fc1_fwd_dma_pair_kernel, dim3(mt0 * a.splits + mt1 * b.splits, a.N1 / F1_BN), dim3(512), F1_LDS_BYTES, s, p0, p1, mt0 * a.splits);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_fwd_grouped gemm");
-    const long se0 = (long)mt0 * F1_BM * a.N1, se1 = (long)mt1 * F1_BM * b.N1;
-    const Fc1EpiArgs e0{a.slabs, a.splits, se0, a.B, a.N1, a.bias, a.bias2, a.n_first, a.h1, a.library, a.library_all, a.x->rows, acc_scale, a.cov, a.cov_idx};
-    const Fc1EpiArgs e1{b.slabs, b.splits, se1, b.B, b.N1, b.bias, b.bias2, b.n_first, b.h1, b.library, b.library_all, b.x->rows, acc_scale, b.cov, b.cov_idx};
-    const long sem = se0 > se1 ? se0 : se1;
-    hipLaunchKernelGGL(fc1_epilogue_tiled_pair_kernel, dim3((unsigned)((sem / 4 + 255) / 256), 2), dim3(256), 0, s, e0, e1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_fwd_grouped epilogue");
-  }
-  // shapes the LDS-DMA kernel does not take, 16-bit mode on resident images, at most 128 output units (n_hidden <= 64): the register-staged
-  // GEMM and its epilogue for both groups in one grid each (gemm_pair_kernel) -- at 128 cells per minibatch a launch is mostly fixed cost
-  typedef GemmCfg<64, 128, 2, 2, false, false, SRC_GATHER, SRC_PLAIN, unsigned short, 1, 32, 4, 1, true> PlainCfg;
-  auto plain_ok = [](const spv_fc1_fwd_args& a) {
-    return a.x && a.x->X && a.W1_hi && a.bias && a.slabs && a.rowsum_ws && a.h1 && a.library && a.xb_all && a.library_all && a.B > 0 && a.G > 0 && a.splits > 0 &&
-           a.nsplit == 1 && a.N1 > 32 && a.N1 <= 128 && (a.ldw % 32) == 0 && a.ldw >= ((a.G + 31) & ~31) && a.ld_xb >= ((a.G + 31) & ~31) && (a.ld_xb % 8) == 0 &&
-           (a.cov == nullptr) == (a.cov_idx == nullptr);
-  };
-  for (; i + 1 < n_groups; i += 2) {
-    const spv_fc1_fwd_args &a = g[i], &b = g[i + 1];
-    if (!(plain_ok(a) && plain_ok(b) && a.N1 == b.N1 && a.splits == b.splits)) break;
-    GemmParams p[2];
-    for (int k = 0; k < 2; ++k) {
-      const spv_fc1_fwd_args& c = k ? b : a;
-      GemmParams& w = p[k];
-      w = GemmParams{};
-      w.A = c.xb_all; w.lda = c.ld_xb; w.B = c.W1_hi; w.ldb = c.ldw;
-      w.rows = c.x->rows; w.counts_aligned = counts_aligned(c.x); w.col_off = c.x->col_off; w.n_cells = c.B; w.n_genes = c.G;
-      w.C = c.slabs; w.ldc = c.N1; w.slab_stride = (long)c.B * c.N1;
-      w.M = c.B; w.N = c.N1; w.K = c.G;
-      w.k_per_split = (((c.G + 31) / 32 + c.splits - 1) / c.splits) * 32;
-      w.epi = EPI_STORE;
-    }
-    if (launch_gemm_pair<PlainCfg>(p[0], p[1], a.splits, s) != SPV_OK) return launch_status("spv_enc_fc1_fwd_grouped gemm pair");
-    const float sc = 1.0f / SPV_FC1_W_SCALE;
-    const Fc1EpiPlainArgs e0{a.slabs, a.rowsum_ws, a.splits, a.B, a.N1, a.bias, a.bias2, a.n_first, a.h1, a.library, a.library_all, a.x->rows, sc, a.cov, a.cov_idx};
-    const Fc1EpiPlainArgs e1{b.slabs, b.rowsum_ws, b.splits, b.B, b.N1, b.bias, b.bias2, b.n_first, b.h1, b.library, b.library_all, b.x->rows, sc, b.cov, b.cov_idx};
-    const long tmax = (long)(a.B > b.B ? a.B : b.B) * a.N1;
-    hipLaunchKernelGGL(fc1_epilogue_pair_kernel, dim3((unsigned)((tmax + 255) / 256), 2), dim3(256), 0, s, e0, e1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_fwd_grouped epilogue pair");
-  }
-  for (; i < n_groups; ++i) {   // a leftover group, or shapes no pair form takes: the per-group entry point
-    const spv_fc1_fwd_args& a = g[i];
-    const int rc = spv_enc_fc1_fwd(a.x, a.B, a.G, a.W1_hi, a.W1_lo, a.ldw, a.N1, a.bias, a.bias2, a.n_first, a.nsplit, a.splits, a.slabs, a.rowsum_ws, a.h1,
-                                   a.library, a.xb_all, a.ld_xb, a.library_all, a.cov, a.cov_idx, stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n_groups,
+    [&](int i) {   // the LDS-DMA kernel
+      const spv_fc1_fwd_args &a = g[i], &b = g[i + 1];
+      if (!(fc1_fwd_dma_ok(a) && fc1_fwd_dma_ok(b) && a.N1 == b.N1 && a.nsplit == b.nsplit)) return NOT_A_PAIR;
+      const GemmParams p0 = fc1_fwd_dma_params(a), p1 = fc1_fwd_dma_params(b);
+      const int mt0 = (a.B + F1_BM - 1) / F1_BM, mt1 = (b.B + F1_BM - 1) / F1_BM;
+      const dim3 grid(mt0 * a.splits + mt1 * b.splits, a.N1 / F1_BN);
+      if (a.nsplit == 3) launch_lds<fc1_fwd_dma_split_pair_kernel>(grid, dim3(512), F1_LDS_BYTES, s, p0, p1, mt0 * a.splits);
+      else launch_lds<fc1_fwd_dma_pair_kernel>(grid, dim3(512), F1_LDS_BYTES, s, p0, p1, mt0 * a.splits);
+      if (int rc = launch_status("spv_enc_fc1_fwd_grouped gemm")) return rc;
+      const float acc_scale = (a.nsplit == 1) ? 1.0f / SPV_FC1_W_SCALE : 1.0f;
+      const long se0 = (long)mt0 * F1_BM * a.N1, se1 = (long)mt1 * F1_BM * b.N1;
+      const Fc1EpiArgs e0{a.slabs, a.splits, se0, a.B, a.N1, a.bias, a.bias2, a.n_first, a.h1, a.library, a.library_all, a.x->rows, acc_scale, a.cov, a.cov_idx};
+      const Fc1EpiArgs e1{b.slabs, b.splits, se1, b.B, b.N1, b.bias, b.bias2, b.n_first, b.h1, b.library, b.library_all, b.x->rows, acc_scale, b.cov, b.cov_idx};
+      const long sem = se0 > se1 ? se0 : se1;
+      hipLaunchKernelGGL(fc1_epilogue_tiled_pair_kernel, dim3((unsigned)((sem / 4 + 255) / 256), 2), dim3(256), 0, s, e0, e1);
+      return launch_status("spv_enc_fc1_fwd_grouped epilogue");
+    },
+    [&](int i) {   // the register-staged kernel
+      const spv_fc1_fwd_args &a = g[i], &b = g[i + 1];
+      if (!(fc1_fwd_plain_ok(a) && fc1_fwd_plain_ok(b) && a.N1 == b.N1 && a.splits == b.splits)) return NOT_A_PAIR;
+      typedef GemmCfg<64, 128, 2, 2, false, false, SRC_GATHER, SRC_PLAIN, unsigned short, 1, 32, 4, 1, true> PlainCfg;
+      if (launch_gemm_pair<PlainCfg>(fc1_fwd_params(a, 32), fc1_fwd_params(b, 32), a.splits, s) != SPV_OK) return launch_status("spv_enc_fc1_fwd_grouped gemm pair");
+      const float sc = 1.0f / SPV_FC1_W_SCALE;
+      const Fc1EpiPlainArgs e0{a.slabs, a.rowsum_ws, a.splits, a.B, a.N1, a.bias, a.bias2, a.n_first, a.h1, a.library, a.library_all, a.x->rows, sc, a.cov, a.cov_idx};
+      const Fc1EpiPlainArgs e1{b.slabs, b.rowsum_ws, b.splits, b.B, b.N1, b.bias, b.bias2, b.n_first, b.h1, b.library, b.library_all, b.x->rows, sc, b.cov, b.cov_idx};
+      const long tmax = (long)max2(a.B, b.B) * a.N1;
+      hipLaunchKernelGGL(fc1_epilogue_pair_kernel, dim3((unsigned)((tmax + 255) / 256), 2), dim3(256), 0, s, e0, e1);
+      return launch_status("spv_enc_fc1_fwd_grouped epilogue pair");
+    },
+    [&](int i) {   // a leftover group, or shapes no pair form takes: the per-group entry point
+      const spv_fc1_fwd_args& a = g[i];
+      return spv_enc_fc1_fwd(a.x, a.B, a.G, a.W1_hi, a.W1_lo, a.ldw, a.N1, a.bias, a.bias2, a.n_first, a.nsplit, a.splits, a.slabs, a.rowsum_ws, a.h1,
+                             a.library, a.xb_all, a.ld_xb, a.library_all, a.cov, a.cov_idx, stream);
+    });
 }
 
 static bool fc1_bwd_dma_ok(const spv_fc1_bwd_args& a) {
   if (!a.x || !a.x->X || !a.dh1 || !a.h1 || !a.dh_hi || !a.part || !a.db || !a.dW || !a.dW2 || !a.xb || !a.scale_ws || a.B <= 0 || a.G <= 0) return false;
   const int Kpad = (a.B + FW_BK - 1) / FW_BK * FW_BK;
   return a.nsplit == 1 && (a.N1 == FW_BM || a.N1 == 2 * FW_BM) && a.ld_dh == a.N1 && a.n_first == a.N1 / 2 && a.Bp >= Kpad && (a.Bp % 64) == 0 && a.ldc >= a.G &&
-         a.ld_xb >= ((a.G + 63) & ~63) && (a.ld_xb % 8) == 0 && fw_lds_bytes(96, Kpad) <= 160 * 1024 &&
-         ((reinterpret_cast<uintptr_t>(a.xb) | reinterpret_cast<uintptr_t>(a.dh_hi)) & 15) == 0;
+         a.ld_xb >= ((a.G + 63) & ~63) && (a.ld_xb % 8) == 0 && fw_lds_bytes(96, Kpad) <= 160 * 1024 && aligned16(a.xb, a.dh_hi);
+}
+
+// shapes the LDS-DMA kernel does not take (n_hidden <= 64), 16-bit mode on resident images: prep / finish and the register-staged weight-gradient
+// GEMM for both groups in one grid each
+static bool fc1_bwd_plain_ok(const spv_fc1_bwd_args& a) {
+  return a.x && a.x->X && a.dh1 && a.h1 && a.dh_hi && a.part && a.db && a.dW && a.xb && a.scale_ws && a.B > 0 && a.G > 0 && a.nsplit == 1 &&
+         a.N1 > 32 && a.N1 <= 128 && a.Bp >= a.B && (a.Bp % 64) == 0 && a.Bp / 16 <= 65536 && a.ld_dh >= ((a.N1 + 127) & ~127) && (a.ld_dh % 8) == 0 &&
+         a.ldc >= a.G && a.ld_xb >= ((a.G + 63) & ~63) && (a.ld_xb % 8) == 0;
 }
 
 extern "C" int spv_enc_fc1_bwd_grouped(const spv_fc1_bwd_args* g, int32_t n_groups, void* stream) {
   if (!g || n_groups <= 0) return fail(SPV_ERR_ARG, "spv_enc_fc1_bwd_grouped: bad arguments%s");
   hipStream_t s = (hipStream_t)stream;
-  int i = 0;
-  for (; i + 1 < n_groups; i += 2) {
-    const spv_fc1_bwd_args &a = g[i], &b = g[i + 1];
-    if (!(fc1_bwd_dma_ok(a) && fc1_bwd_dma_ok(b) && a.N1 == b.N1)) break;
-    const Fc1PrepArgs q0{a.dh1, a.h1, a.B, a.N1, (bf16_t*)a.dh_hi, nullptr, (long)a.ld_dh, a.part, a.Bp / 16, a.db, a.db2, a.n_first, a.scale_ws};
-    const Fc1PrepArgs q1{b.dh1, b.h1, b.B, b.N1, (bf16_t*)b.dh_hi, nullptr, (long)b.ld_dh, b.part, b.Bp / 16, b.db, b.db2, b.n_first, b.scale_ws};
-    const int nb = q0.nblk > q1.nblk ? q0.nblk : q1.nblk;
-    const int nf0 = fc1_finish_blocks(q0), nf1 = fc1_finish_blocks(q1);
-    hipLaunchKernelGGL(fc1_bwd_prep_pair_kernel, dim3(nb, 2), dim3(256), 0, s, q0, q1);
-    hipLaunchKernelGGL(fc1_bwd_finish_pair_kernel, dim3(nf0 > nf1 ? nf0 : nf1, 2), dim3(256), 0, s, q0, q1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_bwd_grouped prep");
-    GemmParams p[2];
-    for (int k = 0; k < 2; ++k) {
-      const spv_fc1_bwd_args& c = k ? b : a;
-      GemmParams& w = p[k];
-      w = GemmParams{};
-      w.A = c.dh_hi; w.lda = c.ld_dh; w.B = c.xb; w.ldb = c.ld_xb; w.rows = c.x->rows; w.n_cells = c.B; w.n_genes = c.G;
-      w.C = c.dW; w.ldc = c.ldc; w.C2 = c.dW2; w.c_split_row = c.n_first; w.M = c.N1; w.N = c.G; w.K = c.B;
-      w.out_scale = c.scale_ws + 1;
-    }
-    // tile: the one that gets BOTH groups into the fewest rounds of 256 one-per-CU workgroups (64-gene tiles are the faster ones alone)
-    const int n64 = (a.G + 63) / 64 + (b.G + 63) / 64, n96 = (a.G + 95) / 96 + (b.G + 95) / 96;
-    const int mth = a.N1 / FW_BM;   // 256-unit halves of the dh image (H = 256: one per encoder)
-    const bool use96 = (n96 * mth + 255) / 256 < (n64 * mth + 255) / 256;
-    const int Kp0 = (a.B + FW_BK - 1) / FW_BK * FW_BK, Kp1 = (b.B + FW_BK - 1) / FW_BK * FW_BK;
-    const int Kp = Kp0 > Kp1 ? Kp0 : Kp1;
-    // ... unless a WIDE tile (192 / 256 genes, fc1_wgrad_dma_wide_body) needs fewer ROUNDS of workgroups: a workgroup re-reads the dh image
-    // (512 B per cell) beside its 2 t bytes per cell of image rows, so a wide tile is the slower one per workgroup and the faster one only
-    // where the narrow tiles need a second round (rocprofv3, us per pair launch: C2 96: 77, 128: 83, 192: 112, 256: 114; G 20 000 96: 154,
-    // 192: 123, 256: 125)
-    const char* const force_env = getenv("SPV_FC1_WGRAD_TILE");   // (tuning / test switch, read per call: 64 / 96 / 128 / 192 / 256)
-    const int force_tile = force_env ? atoi(force_env) : 0;
-    int t = use96 ? 96 : 64;
-    auto model_us = [&](int tile) {   // every workgroup pulls its bytes at the ONE CU's fill rate, ~32 GB/s measured on every LDS-DMA kernel here, round after round
-      const long nwg = (long)((a.G + tile - 1) / tile + (b.G + tile - 1) / tile) * mth;
-      return (double)((nwg + 255) / 256) * (double)Kp * (512 + 2 * tile) / 32e3;
-    };
-    if (Kp >= 512) {
-      if (fww_lds_bytes(192, Kp) <= 160 * 1024 && model_us(192) < model_us(t)) t = 192;
-      if (fww_lds_bytes(256, Kp) <= 160 * 1024 && model_us(256) < model_us(t)) t = 256;
-    }
-    if (force_tile == 64 || force_tile == 96 || force_tile == 128 || force_tile == 192 || force_tile == 256) {
-      const int need = force_tile >= 192 ? fww_lds_bytes(force_tile, Kp) : fw_lds_bytes(force_tile, Kp);
-      if (need <= 160 * 1024) t = force_tile;
-    }
-    const int lds = t >= 192 ? fww_lds_bytes(t, Kp) : fw_lds_bytes(t, Kp);
-    void (*kfn)(GemmParams, GemmParams, int) = t == 256 ? fc1_wgrad_dma_wide_pair_kernel<256> : t == 192 ? fc1_wgrad_dma_wide_pair_kernel<192> :
-                                               t == 96 ? fc1_wgrad_dma_pair_kernel<96> : (t == 128 ? fc1_wgrad_dma_pair_kernel<128> : fc1_wgrad_dma_pair_kernel<64>);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const int nA = (a.G + t - 1) / t, nB = (b.G + t - 1) / t;
-    hipLaunchKernelGGL(kfn, dim3(nA + nB, mth), dim3(512), lds, s, p[0], p[1], nA);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_bwd_grouped wgrad");
-  }
-  // shapes the LDS-DMA kernel does not take (n_hidden <= 64), 16-bit mode on resident images: prep / finish and the register-staged weight-gradient
-  // GEMM for both groups in one grid each
-  auto plain_ok = [](const spv_fc1_bwd_args& a) {
-    return a.x && a.x->X && a.dh1 && a.h1 && a.dh_hi && a.part && a.db && a.dW && a.xb && a.scale_ws && a.B > 0 && a.G > 0 && a.nsplit == 1 &&
-           a.N1 > 32 && a.N1 <= 128 && a.Bp >= a.B && (a.Bp % 64) == 0 && a.Bp / 16 <= 65536 && a.ld_dh >= ((a.N1 + 127) & ~127) && (a.ld_dh % 8) == 0 &&
-           a.ldc >= a.G && a.ld_xb >= ((a.G + 63) & ~63) && (a.ld_xb % 8) == 0;
-  };
-  for (; i + 1 < n_groups; i += 2) {
-    const spv_fc1_bwd_args &a = g[i], &b = g[i + 1];
-    const bool t96a = a.ld_xb >= (a.G + 95) / 96 * 96, t96b = b.ld_xb >= (b.G + 95) / 96 * 96;
-    if (!(plain_ok(a) && plain_ok(b) && a.N1 == b.N1 && t96a == t96b)) break;
-    const Fc1PrepArgs q0{a.dh1, a.h1, a.B, a.N1, (bf16_t*)a.dh_hi, nullptr, (long)a.ld_dh, a.part, a.Bp / 16, a.db, a.db2, a.n_first, a.scale_ws};
-    const Fc1PrepArgs q1{b.dh1, b.h1, b.B, b.N1, (bf16_t*)b.dh_hi, nullptr, (long)b.ld_dh, b.part, b.Bp / 16, b.db, b.db2, b.n_first, b.scale_ws};
-    const int nb = q0.nblk > q1.nblk ? q0.nblk : q1.nblk;
-    const int nf0 = fc1_finish_blocks(q0), nf1 = fc1_finish_blocks(q1);
-    hipLaunchKernelGGL(fc1_bwd_prep_pair_kernel, dim3(nb, 2), dim3(256), 0, s, q0, q1);
-    hipLaunchKernelGGL(fc1_bwd_finish_pair_kernel, dim3(nf0 > nf1 ? nf0 : nf1, 2), dim3(256), 0, s, q0, q1);
-    if (hipGetLastError() != hipSuccess) return launch_status("spv_enc_fc1_bwd_grouped prep pair");
-    GemmParams p[2];
-    for (int k = 0; k < 2; ++k) {   // (as spv_enc_fc1_wgrad builds them for a resident f16 image)
-      const spv_fc1_bwd_args& c = k ? b : a;
-      GemmParams& w = p[k];
-      w = GemmParams{};
-      w.A = c.dh_hi; w.lda = c.ld_dh; w.B = c.xb; w.ldb = c.ld_xb;
-      w.rows = c.x->rows; w.counts_aligned = counts_aligned(c.x); w.col_off = c.x->col_off; w.n_cells = c.B; w.n_genes = c.G;
-      w.C = c.dW; w.ldc = c.ldc; w.C2 = c.dW2; w.c_split_row = c.n_first; w.out_scale = c.scale_ws + 1;
-      w.M = c.N1; w.N = c.G; w.K = c.B; w.k_per_split = (c.B + 63) & ~63; w.epi = EPI_STORE;
-    }
-    int rcg;
-    if (t96a) rcg = launch_gemm_pair<GemmCfg<128, 96, 4, 1, true, true, SRC_PLAIN, SRC_GATHER, unsigned short, 1, 64, 4, 1, true>>(p[0], p[1], 1, s);
-    else rcg = launch_gemm_pair<GemmCfg<128, 64, 4, 1, true, true, SRC_PLAIN, SRC_GATHER, unsigned short, 1, 64, 4, 1, true>>(p[0], p[1], 1, s);
-    if (rcg != SPV_OK) return launch_status("spv_enc_fc1_bwd_grouped wgrad pair");
-  }
-  for (; i < n_groups; ++i) {
-    const spv_fc1_bwd_args& a = g[i];
-    int rc = spv_enc_fc1_bwd_prep(a.dh1, a.h1, a.B, a.N1, a.dh_hi, a.dh_lo, a.ld_dh, a.Bp, a.part, a.db, a.db2, a.n_first, a.scale_ws, stream);
-    if (rc != SPV_OK) return rc;
-    rc = spv_enc_fc1_wgrad(a.x, a.B, a.G, a.dh_hi, a.dh_lo, a.ld_dh, a.N1, a.nsplit, a.dW, a.dW2, a.n_first, a.ldc, a.xb, a.ld_xb, a.scale_ws, stream);
-    if (rc != SPV_OK) return rc;
-  }
-  return SPV_OK;
+  return pairs_then_rest(n_groups,
+    [&](int i) {   // the LDS-DMA kernels
+      const spv_fc1_bwd_args &a = g[i], &b = g[i + 1];
+      if (!(fc1_bwd_dma_ok(a) && fc1_bwd_dma_ok(b) && a.N1 == b.N1)) return NOT_A_PAIR;
+      fc1_prep_pair_launch(a, b, s);
+      if (int rc = launch_status("spv_enc_fc1_bwd_grouped prep")) return rc;
+      GemmParams p[2];
+      for (int k = 0; k < 2; ++k) {
+        const spv_fc1_bwd_args& c = k ? b : a;
+        GemmParams& w = p[k];
+        w = GemmParams{};
+        w.A = c.dh_hi; w.lda = c.ld_dh; w.B = c.xb; w.ldb = c.ld_xb; w.rows = c.x->rows; w.n_cells = c.B; w.n_genes = c.G;
+        w.C = c.dW; w.ldc = c.ldc; w.C2 = c.dW2; w.c_split_row = c.n_first; w.M = c.N1; w.N = c.G; w.K = c.B;
+        w.out_scale = c.scale_ws + 1;
+      }
+      // tile: the one that gets BOTH groups into the fewest rounds of 256 one-per-CU workgroups (64-gene tiles are the faster ones alone)
+      const int n64 = (a.G + 63) / 64 + (b.G + 63) / 64, n96 = (a.G + 95) / 96 + (b.G + 95) / 96;
+      const int mth = a.N1 / FW_BM;   // 256-unit halves of the dh image (H = 256: one per encoder)
+      const bool use96 = (n96 * mth + 255) / 256 < (n64 * mth + 255) / 256;
+      const int Kp = max2((a.B + FW_BK - 1) / FW_BK * FW_BK, (b.B + FW_BK - 1) / FW_BK * FW_BK);
+      // ... unless a WIDE tile (192 / 256 genes, fc1_wgrad_dma_wide_body) needs fewer ROUNDS of workgroups: a workgroup re-reads the dh image
+      // (512 B per cell) beside its 2 t bytes per cell of image rows, so a wide tile is the slower one per workgroup and the faster one only
+      // where the narrow tiles need a second round (rocprofv3, us per pair launch: C2 96: 77, 128: 83, 192: 112, 256: 114; G 20 000 96: 154,
+      // 192: 123, 256: 125)
+      const char* const force_env = getenv("SPV_FC1_WGRAD_TILE");   // (tuning / test switch, read per call: 64 / 96 / 128 / 192 / 256)
+      const int force_tile = force_env ? atoi(force_env) : 0;
+      int t = use96 ? 96 : 64;
+      auto model_us = [&](int tile) {   // every workgroup pulls its bytes at the ONE CU's fill rate, ~32 GB/s measured on every LDS-DMA kernel here, round after round
+        const long nwg = (long)((a.G + tile - 1) / tile + (b.G + tile - 1) / tile) * mth;
+        return (double)((nwg + 255) / 256) * (double)Kp * (512 + 2 * tile) / 32e3;
+      };
+      if (Kp >= 512) {
+        if (fww_lds_bytes(192, Kp) <= 160 * 1024 && model_us(192) < model_us(t)) t = 192;
+        if (fww_lds_bytes(256, Kp) <= 160 * 1024 && model_us(256) < model_us(t)) t = 256;
+      }
+      if (force_tile == 64 || force_tile == 96 || force_tile == 128 || force_tile == 192 || force_tile == 256) {
+        const int need = force_tile >= 192 ? fww_lds_bytes(force_tile, Kp) : fw_lds_bytes(force_tile, Kp);
+        if (need <= 160 * 1024) t = force_tile;
+      }
+      const int lds = t >= 192 ? fww_lds_bytes(t, Kp) : fw_lds_bytes(t, Kp);
+      void (*kfn)(GemmParams, GemmParams, int) = t == 256 ? fc1_wgrad_dma_wide_pair_kernel<256> : t == 192 ? fc1_wgrad_dma_wide_pair_kernel<192> :
+                                                 t == 96 ? fc1_wgrad_dma_pair_kernel<96> : (t == 128 ? fc1_wgrad_dma_pair_kernel<128> : fc1_wgrad_dma_pair_kernel<64>);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      const int nA = (a.G + t - 1) / t, nB = (b.G + t - 1) / t;
+      hipLaunchKernelGGL(kfn, dim3(nA + nB, mth), dim3(512), lds, s, p[0], p[1], nA);
+      return launch_status("spv_enc_fc1_bwd_grouped wgrad");
+    },
+    [&](int i) {   // the register-staged kernel
+      const spv_fc1_bwd_args &a = g[i], &b = g[i + 1];
+      const bool t96a = a.ld_xb >= (a.G + 95) / 96 * 96, t96b = b.ld_xb >= (b.G + 95) / 96 * 96;
+      if (!(fc1_bwd_plain_ok(a) && fc1_bwd_plain_ok(b) && a.N1 == b.N1 && t96a == t96b)) return NOT_A_PAIR;
+      fc1_prep_pair_launch(a, b, s);
+      if (int rc = launch_status("spv_enc_fc1_bwd_grouped prep pair")) return rc;
+      const GemmParams p0 = fc1_wgrad_params(a.x, a.B, a.G, a.dh_hi, nullptr, a.ld_dh, a.N1, 1, a.dW, a.dW2, a.n_first, a.ldc, a.xb, a.ld_xb, a.scale_ws);
+      const GemmParams p1 = fc1_wgrad_params(b.x, b.B, b.G, b.dh_hi, nullptr, b.ld_dh, b.N1, 1, b.dW, b.dW2, b.n_first, b.ldc, b.xb, b.ld_xb, b.scale_ws);
+      int rcg;
+      if (t96a) rcg = launch_gemm_pair<GemmCfg<128, 96, 4, 1, true, true, SRC_PLAIN, SRC_GATHER, unsigned short, 1, 64, 4, 1, true>>(p0, p1, 1, s);
+      else rcg = launch_gemm_pair<GemmCfg<128, 64, 4, 1, true, true, SRC_PLAIN, SRC_GATHER, unsigned short, 1, 64, 4, 1, true>>(p0, p1, 1, s);
+      return rcg != SPV_OK ? launch_status("spv_enc_fc1_bwd_grouped wgrad pair") : SPV_OK;
+    },
+    [&](int i) {
+      const spv_fc1_bwd_args& a = g[i];
+      const int rc = spv_enc_fc1_bwd_prep(a.dh1, a.h1, a.B, a.N1, a.dh_hi, a.dh_lo, a.ld_dh, a.Bp, a.part, a.db, a.db2, a.n_first, a.scale_ws, stream);
+      if (rc != SPV_OK) return rc;
+      return spv_enc_fc1_wgrad(a.x, a.B, a.G, a.dh_hi, a.dh_lo, a.ld_dh, a.N1, a.nsplit, a.dW, a.dW2, a.n_first, a.ldc, a.xb, a.ld_xb, a.scale_ws, stream);
+    });
 }
 
 extern "C" int spv_plan_invmap(const int32_t* idx0, int32_t B0, const int32_t* idx1, int32_t B1, int32_t* inv0, int32_t n0, int32_t* inv1,

@@ -107,3 +107,45 @@ def test_fc1_plain_pair_launches_give_the_bits_of_the_per_group_calls(dev, B, G,
         W = (torch.cat([params[k][0], params[k][2]]) * 256.0).to(torch.float16).double() / 256.0
         ref = torch.relu(xr @ W.t() + torch.cat([params[k][1], params[k][3]]).double())
         torch.testing.assert_close(h1.detach().cpu().double(), ref, rtol=1e-4, atol=1e-4)
+
+
+def test_grouped_walker_leftover_group_and_refused_pair(dev):
+    """The two fall-through paths of the *_grouped entry points that a two-group step never takes, against the per-group entry points
+    bit for bit: three groups = one pair grid plus a leftover group (spv_dec_tables_grouped; G = 40, 300, 33: less than a block, more than
+    one block, odd), and a pair the pair kernel refuses -- the second Gp is no multiple of the LDS-DMA logits kernel's 256-gene tile -- so
+    that both groups go through spv_dec_logits in order (spv_dec_logits_grouped)."""
+    from spvipes_amd import _abi
+    from spvipes_amd._abi import NB_CMAX, ptr, round_up, stream_ptr
+    gen = torch.Generator().manual_seed(3)
+    # tables: a pair and a leftover
+    Gs = (40, 300, 33)
+    Gps = [round_up(G, 256) for G in Gs]
+    px_r = [(torch.randn(G, generator=gen) * 0.5).to(dev) for G in Gs]
+    new_tabs = lambda fill: [(torch.full((Gp, 4), fill, device=dev), torch.full((NB_CMAX, Gp, 2), fill, device=dev)) for Gp in Gps]
+    got, ref = new_tabs(float("nan")), new_tabs(-7.0)   # (different fills: an element neither call writes shows as a difference)
+    grp = (_abi.SpvDecGroup * 3)()
+    for k in range(3):
+        grp[k].px_r, grp[k].p.G, grp[k].p.Gp, grp[k].p.gene_tab, grp[k].p.cnt_tab = ptr(px_r[k]), Gs[k], Gps[k], ptr(got[k][0]), ptr(got[k][1])
+        _abi.call("spv_dec_tables", ptr(px_r[k]), Gs[k], Gps[k], ptr(ref[k][0]), ptr(ref[k][1]), stream_ptr())
+    _abi.call("spv_dec_tables_grouped", grp, 3, stream_ptr())
+    torch.cuda.synchronize()
+    for k in range(3):
+        for a, b in zip(got[k], ref[k]):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), k
+    # logits: a pair that is refused
+    Bp, K, Gps = 128, 64, (256, 384)
+    bf16_words = lambda *s: (torch.randn(*s, generator=gen) * 0.3).to(torch.bfloat16).view(torch.int16).to(dev)
+    Am = [bf16_words(Bp, K) for _ in Gps]
+    Wm = [bf16_words(Gp, K) for Gp in Gps]
+    got = [torch.ones((Bp, Gp), dtype=torch.float16, device=dev) for Gp in Gps]
+    ref = [torch.zeros((Bp, Gp), dtype=torch.float16, device=dev) for Gp in Gps]
+    grp = (_abi.SpvDecGroup * 2)()
+    for k in range(2):
+        g = grp[k]
+        g.Am_hi, g.Wm_hi, g.K, g.nsplit, g.p.Bp, g.p.Gp, g.p.logits, g.p.logits_f32 = ptr(Am[k]), ptr(Wm[k]), K, 1, Bp, Gps[k], ptr(got[k]), 0
+        _abi.call("spv_dec_logits", ptr(Am[k]), None, ptr(Wm[k]), None, K, Bp, Gps[k], 1, ptr(ref[k]), 0, stream_ptr())
+    _abi.call("spv_dec_logits_grouped", grp, 2, stream_ptr())
+    torch.cuda.synchronize()
+    for k in range(2):
+        assert torch.equal(got[k].view(torch.int16), ref[k].view(torch.int16)), k
+        assert got[k].float().abs().max() > 0
