@@ -429,7 +429,7 @@ class spVIPESmodule(nn.Module):
                   dropout_masks: Optional[dict] = None, **kwargs):
         """Runs the encoders and the PoE (spVIPESmodule.py:425-472).  ``noise`` optionally injects the
         standard-normal draws ("enc_{g}_private", "enc_{g}_shared", "poe_{g}") for parity tests."""
-        from .nn_ops import EncoderSpec, EncoderTails, PoELabel
+        from .nn_ops import DROPOUT_SET_STRIDE, EncoderSpec, EncoderTails, PoELabel
 
         noise = noise or {}
         private_stats, shared_stats, library = {}, {}, {}
@@ -543,14 +543,18 @@ class spVIPESmodule(nn.Module):
         # replace the kernels' counter-based draw.
         dm = dropout_masks or {}
         same_B = len({self._step_inputs[g][2] for g in groups_}) == 1
-        for gset in ([groups_[i:i + 2] for i in range(0, len(groups_), 2)] if same_B else [[g] for g in groups_]):   # (the batched kernels carry 8 problem slots: two groups)
+        gsets = [groups_[i:i + 2] for i in range(0, len(groups_), 2)] if same_B else [[g] for g in groups_]   # (the batched kernels carry 8 problem slots: two groups)
+        for k, gset in enumerate(gsets):
+            # every launch numbers its problems from 0 and the draw is keyed by (seed, problem, element): each launch after the first adds its own
+            # host base to the step counter, or group 2's encoders would get group 0's masks (launch 0 keeps the bare counter: two-group steps keep their bits)
+            seed = self._seed_dev if k == 0 else (k * DROPOUT_SET_STRIDE, self._seed_dev)
             specs, eps_list, masks = [], [], []
             for slot, g in enumerate(gset):
                 specs += [EncoderSpec(self.encoders[g]["private"], slot, 0), EncoderSpec(self.encoders[g]["shared"], slot, H)]
                 eps_list += [eps_enc[g][0], eps_enc[g][1]]
                 masks += [dm.get(f"enc_{g}_private"), dm.get(f"enc_{g}_shared")]
             flat = [p for s in specs for p in s.params()]
-            outs = EncoderTails.apply(specs, eps_list, self.training, float(self.dropout_rate), self._seed_dev,
+            outs = EncoderTails.apply(specs, eps_list, self.training, float(self.dropout_rate), seed,
                                       self._workspace(gset[0], h1s[gset[0]].device), masks if dropout_masks else None,
                                       *[h1s[g] for g in gset], *flat)
             for i, s in enumerate(specs):

@@ -19,10 +19,13 @@ from ._abi import SpvBnBatch, SpvLinearBatch, SpvLinearPending, SpvSampleBatch, 
 
 
 def _lin_batch(B: int, relu: bool = False, drop_p: float = 0.0, seed=0, accumulate: bool = False) -> SpvLinearBatch:
-    """``seed``: python int, or a device int64 tensor (read by the kernel at run time: hipGraph-safe)."""
+    """``seed``: python int, a device int64 tensor (read by the kernel at run time: hipGraph-safe), or a pair (host base, device tensor):
+    the kernel draws with base + *tensor (mod 2^64)."""
     b = SpvLinearBatch()
     b.nprob, b.B, b.relu, b.drop_p, b.accumulate = 0, B, int(relu), float(drop_p), int(accumulate)
-    if isinstance(seed, torch.Tensor):
+    if isinstance(seed, tuple):
+        b.seed, b.seed_ptr = int(seed[0]) & 0xFFFFFFFFFFFFFFFF, seed[1].data_ptr()
+    elif isinstance(seed, torch.Tensor):
         b.seed, b.seed_ptr = 0, seed.data_ptr()
     else:
         b.seed, b.seed_ptr = int(seed), None
@@ -112,6 +115,11 @@ class EncoderSpec:
 
 N_ENC_PARAMS = 10
 
+# The dropout draw is keyed by (seed, problem slot, element) and every EncoderTails launch numbers its problems from 0, so two launches of one
+# step must not share a seed: the k-th launch of a step (module.inference: one per pair of groups) draws with seed k * DROPOUT_SET_STRIDE +
+# step counter.  Odd and of the order of 2^63: no k * stride (k < 2^32) is within reach of the counter's +1 walk.  Launch 0 keeps the bare counter.
+DROPOUT_SET_STRIDE = 0x9E3779B97F4A7C15
+
 
 class EncoderTails(torch.autograd.Function):
     """All encoders' tails in 4 forward / 5 backward launches (fc2, heads, BatchNorm statistics, [finalise + normalise + sample + KL];
@@ -124,7 +132,8 @@ class EncoderTails(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, specs: Sequence[EncoderSpec], eps: Sequence[torch.Tensor], training: bool, drop_p: float, seed: int, ws, masks, *tensors):
-        """``masks``: None, or one optional [B, H] keep-mask (1 = keep) per encoder replacing the counter-based dropout draw."""
+        """``masks``: None, or one optional [B, H] keep-mask (1 = keep) per encoder replacing the counter-based dropout draw.
+        ``seed``: as ``_lin_batch``'s; only the forward draws -- the backward recovers the mask from the saved h2 > 0 and needs ``drop_p`` alone."""
         ctx.set_materialize_grads(False)  # outputs nobody differentiates (scale, unused loc/logvar) arrive as None, not as zero fills
         n_groups = max(s.h1_group for s in specs) + 1
         h1 = tensors[:n_groups]

@@ -82,9 +82,18 @@ def test_dropout_mask_is_reproducible_and_has_the_right_rate(dev):
     run = lambda seed: EncoderTails.apply(spec, eps, True, 0.25, seed, Workspace(dev), None, h1, *spec[0].params())
     a, b, c = run(7), run(7), run(8)
     assert torch.equal(a[3], b[3]) and not torch.equal(a[3], c[3])
-    # drop rate: compare kept fraction of the positive fc2 activations through a backward pass
-    a[3].sum().backward()
+    # drop rate: the kept fraction of the clearly positive fc2 activations (float64 pre-activation > 1e-3; the saved fc2 output h2 is nonzero
+    # exactly where such an element was kept) within 5 binomial sigma of 1 - p.  tests/test_gpu_dropout.py holds the draw to the rest of its law.
+    n_in = 1 + len(spec[0].params())
+    h2 = a[5].grad_fn.saved_tensors[n_in]   # EncoderTails.forward: save_for_backward(*inputs, *h2, ...)
+    assert h2.shape == (B, H)
+    a[3].sum().backward()   # (frees the saved tensors: h2 is read first)
     assert torch.isfinite(h1.grad).all()
+    live = (h1.detach()[:, :H].double() @ enc.fc2.weight.detach().double().T + enc.fc2.bias.detach().double()) > 1e-3
+    n = int(live.sum())
+    kept = int(((h2 != 0) & live).sum())
+    z = (kept / n - 0.75) / (0.25 * 0.75 / n) ** 0.5
+    assert n > B * H // 4 and abs(z) <= 5.0, (kept, n, z)
 
 
 def test_spv_randn_is_standard_normal_and_keyed_by_the_device_counter():
