@@ -375,6 +375,33 @@ typedef struct spv_dec_sample_args {
 } spv_dec_sample_args;
 int spv_dec_sample(const spv_dec_params* p, const spv_dec_sample_args* a, void* stream);
 
+/* Posterior-predictive check (posterior_predictive_check): spv_dec_sample's draws for one group and one minibatch, reduced inside the
+ * kernel instead of stored.  `p`, Am / Wm, K, nsplit, genes / n_genes, theta, cell_ids, key, sample: exactly as spv_dec_sample takes
+ * them (NegativeBinomialMixture of module/spVIPESmodule.py:751-759) -- x(b, genes[j]) is the integer that entry point would write.
+ *   seg: int32 device array [B] of segment codes in [0, n_seg), or NULL for everything in segment 0; a cell with a negative code
+ *        (and one with a code >= n_seg) is neither drawn nor counted.
+ *   stats: uint64 device array [n_seg][4][ld_stats], ld_stats >= n_genes; over the counted cells b of segment k
+ *        stats[k][0][j] += sum x      stats[k][1][j] += #(x > 0)      stats[k][2][j] += sum x^2 (modulo 2^64)
+ *        stats[k][3][j]  = max(stats[k][3][j], max x)
+ *   cell_total: uint64 device array [B] or NULL; cell_total[b] += sum_j x(b, genes[j]) for every counted cell.
+ * Everything ACCUMULATES: the caller zeroes the arrays once, and one table then collects every sample of every minibatch of a walk.
+ * The updates are 64-bit integer atomics, so the tables equal the reduction of spv_dec_sample's output bit for bit, in any order of
+ * calls, and two runs agree bit for bit.  Columns >= n_genes, rows of segments no counted cell belongs to and cell_total entries of
+ * cells that are not counted are never touched; a repeated gene of the selection fills its own column.  Nothing of size cells x
+ * genes is written.  Nothing is allocated; one launch on `stream`. */
+typedef struct spv_dec_sample_stats_args {
+  const uint16_t* Am_hi; const uint16_t* Am_lo; const uint16_t* Wm_hi; const uint16_t* Wm_lo;
+  int32_t K, nsplit;
+  const int32_t* genes; int32_t n_genes; int32_t n_seg;
+  const float* theta;
+  const int32_t* cell_ids;
+  uint64_t key; uint32_t sample;
+  const int32_t* seg;
+  uint64_t* stats; int64_t ld_stats;
+  uint64_t* cell_total;
+} spv_dec_sample_stats_args;
+int spv_dec_sample_stats(const spv_dec_params* p, const spv_dec_sample_stats_args* a, void* stream);
+
 /* The same sampler over given parameters (the law of module/spVIPESmodule.py:751-759 for anyone who holds its parameters):
  *   out[r * ld_out + g] ~ NBMix(rate_p[r * ld_in + g], rate_s[r * ld_in + g], theta[g], logit[r * ld_in + g]),  r < R, g < G
  * fp32 device inputs, int32 device output; ld_in, ld_out >= G.  key / sample / cell_ids (int32 [R] or NULL = the row number) mean

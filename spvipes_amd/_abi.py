@@ -236,6 +236,14 @@ class SpvDecSampleArgs(C.Structure):
                 ("key", C.c_uint64), ("sample", C.c_uint32), ("out", C.c_void_p), ("ld_out", C.c_int64)]
 
 
+class SpvDecSampleStatsArgs(C.Structure):
+    """the arguments of spv_dec_sample_stats (include/spvipes_hip.h: spv_dec_sample_stats_args)"""
+    _fields_ = [("Am_hi", C.c_void_p), ("Am_lo", C.c_void_p), ("Wm_hi", C.c_void_p), ("Wm_lo", C.c_void_p), ("K", C.c_int32), ("nsplit", C.c_int32),
+                ("genes", C.c_void_p), ("n_genes", C.c_int32), ("n_seg", C.c_int32), ("theta", C.c_void_p), ("cell_ids", C.c_void_p),
+                ("key", C.c_uint64), ("sample", C.c_uint32), ("seg", C.c_void_p), ("stats", C.c_void_p), ("ld_stats", C.c_int64),
+                ("cell_total", C.c_void_p)]
+
+
 class SpvDePairsArgs(C.Structure):
     """the arguments of spv_de_pairs (include/spvipes_hip.h: spv_de_pairs_args)"""
     _fields_ = [("bank1", C.c_void_p), ("bank2", C.c_void_p), ("ld1", C.c_int64), ("ld2", C.c_int64), ("rows1", C.c_void_p), ("rows2", C.c_void_p),
@@ -318,6 +326,7 @@ _SIGNATURES = {
     "spv_dec_materialize": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "spv_dec_expected": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecExpectedArgs), C.c_void_p]),
     "spv_dec_sample": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecSampleArgs), C.c_void_p]),
+    "spv_dec_sample_stats": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecSampleStatsArgs), C.c_void_p]),
     "spv_nbmix_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32,
                                    C.c_void_p, C.c_int64, C.c_void_p]),
     "spv_de_pairs": (C.c_int, [C.POINTER(SpvDePairsArgs), C.c_void_p]),

@@ -72,6 +72,73 @@ def _chunks(slabs: np.ndarray, limit: int):
     return out
 
 
+def count_square_sums(counts, rows: torch.Tensor, seg_sizes, genes: Optional[torch.Tensor] = None, row_totals: bool = False):
+    """Per segment and selected gene the sum of the SQUARED observed counts over listed cells -> device tensor [n_seg, n_sel]: int64
+    for uint16 counts (exact: 65535^2 * 2^31 < 2^63), fp64 for fp32 counts (squared and added in fp64, segment by segment in list
+    order).  ``rows`` / ``seg_sizes`` / ``genes``: as ``count_stats`` takes them (rows sorted by segment; checked the same way).
+    The second moment next to ``count_stats``' sum and non-zero tally: posterior_predictive_check's observed variance.  Not a
+    kernel of its own: ONE chunked torch reduction, ``COUNT_CHUNK_ROWS`` listed rows at a time -- a gather of the chunk's rows (a
+    CSR matrix is densified by spv_csr_gather first), a widening copy and a square, i.e. two temporaries of 8 bytes x chunk rows x
+    n_sel, and one read of every listed row.  A fourth row of spv_count_stats is the later home of this statistic.
+    ``row_totals``: also return each listed cell's total over the SELECTED genes (a repeated gene counts as often as it is listed),
+    fp64 [n] aligned with ``rows``, from the same pass -> (sums, totals)."""
+    fn = "count_square_sums"
+    _counts(counts, fn)
+    dev, G = counts.device, int(counts.G)
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous() or rows.device != dev:
+        raise _abi.SpvError(f"{fn}: rows must be a contiguous 1-d int32 tensor on the counts' device")
+    sizes = [int(s) for s in np.asarray(seg_sizes).ravel().tolist()]
+    n, n_seg = int(rows.numel()), len(sizes)
+    if n_seg < 1 or any(s < 0 for s in sizes) or sum(sizes) != n:
+        raise ValueError(f"{fn}: seg_sizes must be non-negative and add up to the number of listed rows ({n}), got {sizes!r}")
+    if genes is not None and (not isinstance(genes, torch.Tensor) or not genes.is_cuda or genes.device != dev or genes.dtype != torch.int32
+                              or genes.dim() != 1 or genes.numel() < 1 or not genes.is_contiguous()):
+        raise _abi.SpvError(f"{fn}: genes must be a non-empty contiguous 1-d int32 device tensor")
+    if n:
+        lo, hi = (int(v) for v in torch.aminmax(rows))
+        if lo < 0 or hi >= counts.n_cells:
+            raise ValueError(f"{fn}: rows must lie in [0, {counts.n_cells}), got values from {lo} to {hi}")
+    if genes is not None:
+        lo, hi = (int(v) for v in torch.aminmax(genes))
+        if lo < 0 or hi >= G:
+            raise ValueError(f"{fn}: genes must lie in [0, {G}), got values from {lo} to {hi}")
+    n_sel = G if genes is None else int(genes.numel())
+    is_f32 = counts.dtype == _abi.SPV_COUNT_F32
+    out = torch.zeros((n_seg, n_sel), dtype=torch.float64 if is_f32 else torch.int64, device=dev)
+    totals = torch.zeros((n,), dtype=torch.float64, device=dev) if row_totals else None
+    bounds = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    sparse = isinstance(counts, SparseGroupCounts)
+    if sparse and n:
+        ldx = round_up(G, 8)
+        buf = torch.empty((min(n, COUNT_CHUNK_ROWS), ldx), dtype=torch.float32 if is_f32 else torch.int16, device=dev)
+    for p0 in range(0, n, COUNT_CHUNK_ROWS):
+        p1 = min(p0 + COUNT_CHUNK_ROWS, n)
+        piece = rows[p0:p1]
+        if sparse:
+            g = (SpvCsrGatherArgs * 1)()
+            g[0].indptr, g[0].cols, g[0].vals, g[0].n_rows, g[0].G, g[0].dtype = ptr(counts.indptr), ptr(counts.cols), ptr(counts.vals), counts.n_cells, G, counts.dtype
+            g[0].B, g[0].rows, g[0].X, g[0].ldx = p1 - p0, ptr(piece), ptr(buf), ldx
+            g[0].xb, g[0].ld_xb, g[0].xb_split, g[0].library = None, 0, 0, None
+            _abi.call("spv_csr_gather", g, 1, stream_ptr())
+            x = buf[:p1 - p0, :G]
+        else:
+            x = counts.X.index_select(0, piece.long())[:, counts.col_off:counts.col_off + G]
+        if genes is not None:
+            x = x.index_select(1, genes.long())
+        if is_f32:
+            x = x.to(torch.float64)
+        else:   # uint16 bit patterns, whichever 16-bit integer dtype stores them
+            x = (x.view(torch.int16) if x.dtype != torch.int16 else x).to(torch.int64) & 0xFFFF
+        if row_totals:
+            totals[p0:p1] = x.sum(1).to(torch.float64)
+        x = x * x
+        for k in range(n_seg):   # the segments this chunk touches
+            a, b = max(int(bounds[k]), p0), min(int(bounds[k + 1]), p1)
+            if a < b:
+                out[k] += x[a - p0:b - p0].sum(0)
+    return (out, totals) if row_totals else out
+
+
 def count_stats(counts, rows: torch.Tensor, seg_sizes, w: Optional[torch.Tensor] = None, genes: Optional[torch.Tensor] = None,
                 ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per segment and selected gene the statistics of the observed counts over LISTED cells -> fp64 device tensor [n_seg, 3, n_sel]

@@ -7,6 +7,7 @@
 #include "spv_decoder.h"
 #include "spv_dec_expected.h"
 #include "spv_dec_sample.h"
+#include "spv_dec_sample_stats.h"
 #include "spv_de.h"
 #include "spv_de_median.h"
 #include "spv_count_stats.h"
@@ -826,6 +827,32 @@ extern "C" int spv_dec_sample(const spv_dec_params* q, const spv_dec_sample_args
   else if (wide) hipLaunchKernelGGL((dec_sample_kernel<1, 2>), grid, dim3(256), 0, s, p, a);
   else hipLaunchKernelGGL((dec_sample_kernel<1, 1>), grid, dim3(256), 0, s, p, a);
   return launch_status("spv_dec_sample");
+}
+
+extern "C" int spv_dec_sample_stats(const spv_dec_params* q, const spv_dec_sample_stats_args* x, void* stream) {
+  DecParams p;
+  dim3 grid;
+  // readout_prepare checks the fields the read-outs share under spv_dec_sample's names: the table stands in for its `out`
+  spv_dec_sample_args y{};
+  if (x) {
+    y.Am_hi = x->Am_hi; y.Am_lo = x->Am_lo; y.Wm_hi = x->Wm_hi; y.Wm_lo = x->Wm_lo; y.K = x->K; y.nsplit = x->nsplit;
+    y.genes = x->genes; y.n_genes = x->n_genes; y.out = reinterpret_cast<int32_t*>(x->stats);
+  }
+  int rc = readout_prepare(q, "spv_dec_sample_stats", x ? &y : nullptr, p, grid);
+  if (rc != SPV_OK) return rc;
+  if (!x->theta) return fail(SPV_ERR_ARG, "spv_dec_sample_stats: null pointer%s");
+  if (x->n_seg < 1) return fail(SPV_ERR_ARG, "spv_dec_sample_stats: n_seg < 1%s");
+  if (x->ld_stats < x->n_genes) return fail(SPV_ERR_ARG, "spv_dec_sample_stats: ld_stats < n_genes%s");
+  const DecSampleStatsArgs a{(const bf16_t*)x->Am_hi, (const bf16_t*)x->Am_lo, (const bf16_t*)x->Wm_hi, (const bf16_t*)x->Wm_lo, x->K,
+                             x->genes, x->n_genes, x->theta, x->cell_ids, (unsigned long long)x->key, x->sample, x->seg, x->n_seg,
+                             (unsigned long long*)x->stats, (long)x->ld_stats, (unsigned long long*)x->cell_total};
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = dec_kw(q) == 2;
+  if (x->nsplit == 3 && wide) hipLaunchKernelGGL((dec_sample_stats_kernel<3, 2>), grid, dim3(256), 0, s, p, a);
+  else if (x->nsplit == 3) hipLaunchKernelGGL((dec_sample_stats_kernel<3, 1>), grid, dim3(256), 0, s, p, a);
+  else if (wide) hipLaunchKernelGGL((dec_sample_stats_kernel<1, 2>), grid, dim3(256), 0, s, p, a);
+  else hipLaunchKernelGGL((dec_sample_stats_kernel<1, 1>), grid, dim3(256), 0, s, p, a);
+  return launch_status("spv_dec_sample_stats");
 }
 
 extern "C" int spv_nbmix_sample(const float* rate_p, const float* rate_s, const float* logit, int64_t ld_in, const float* theta, int32_t R, int32_t G,

@@ -607,3 +607,119 @@ def count_table(own, n_own: int, other, n_other: int) -> dict:
     n1, n2 = float(int(n_own)), float(int(n_other))
     return {"raw_mean1": a[0] / n1, "raw_mean2": b[0] / n2, "non_zeros_proportion1": a[1] / n1, "non_zeros_proportion2": b[1] / n2,
             "raw_normalized_mean1": a[2] / n1, "raw_normalized_mean2": b[2] / n2}
+
+
+# ---- posterior-predictive check (model.posterior_predictive_check): segment codes of a walk and the result table -----------------
+PPC_STATS = ("mean", "var", "cv", "zero_fraction", "max")   # the columns ppc_table derives from a table of spv_dec_sample_stats
+
+
+def check_ppc_library(library_size):
+    """``library_size`` of posterior_predictive_check: "observed" -> "observed"; else what posterior_predictive_sample takes ("latent"
+    or a positive finite number), returned unchanged after the same check"""
+    if isinstance(library_size, str) and library_size == "observed":
+        return library_size
+    try:
+        expression_log_library(library_size)
+    except ValueError:
+        raise ValueError(f"library_size must be 'latent', 'observed' or a positive number, got {library_size!r}") from None
+    return library_size
+
+
+def ppc_segments(cell_labels, labels=None, n_cells: Optional[int] = None, positions=None):
+    """The populations of posterior_predictive_check as segment codes of a minibatch walk -> (names, sizes, seg).
+    ``cell_labels``: one label per cell of the group, entry i = the cell at position i of ``group_indices_list[group]`` (row i of the
+    group's read-out); None = one population "all" over ``n_cells`` cells.  ``labels``: the wanted labels, in the order the result
+    lists them (an unknown label is a KeyError, a repeated one a ValueError); None = ``np.unique(cell_labels)`` (sorted).
+      names  the populations, in order          sizes  how many of the group's cells each one holds
+      seg    int32 code per entry of ``positions`` (walk positions: the concatenation of a group's per-step rows; None = every cell
+             once, 0 .. n - 1): the place of the cell's label in ``names``, -1 for a cell of any other label, and -1 for every
+             position at or beyond the group's size -- the replayed rows a read-out cuts off (``_eval_minibatches``), which would
+             otherwise be counted twice."""
+    if cell_labels is None:
+        if labels is not None:
+            raise ValueError("labels goes with groupby")
+        if isinstance(n_cells, bool) or not isinstance(n_cells, (int, np.integer)) or int(n_cells) < 1:
+            raise ValueError(f"n_cells must be a positive integer, got {n_cells!r}")
+        n, names = int(n_cells), ["all"]
+        code = np.zeros(n, dtype=np.int32)
+    else:
+        lab = np.asarray(cell_labels).ravel()
+        n = int(lab.size)
+        if n == 0:
+            raise ValueError("groupby: the group has no cells")
+        if n_cells is not None and int(n_cells) != n:
+            raise ValueError(f"groupby: one label per cell of the group ({int(n_cells)}) is needed, got {n}")
+        uniq, inv = np.unique(lab, return_inverse=True)
+        known = uniq.tolist()
+        names = known if labels is None else np.asarray(labels).ravel().tolist()
+        if not names:
+            raise ValueError("labels is empty: name at least one label")
+        if len(set(names)) != len(names):
+            raise ValueError(f"labels names a label more than once: {names!r}")
+        where = {v: k for k, v in enumerate(known)}
+        place = np.full(len(known), -1, dtype=np.int32)
+        for k, v in enumerate(names):
+            if v not in where:
+                raise KeyError(f"labels: {v!r} is not among the labels {known!r}")
+            place[where[v]] = k
+        code = place[inv.ravel()]
+    sizes = np.bincount(code[code >= 0], minlength=len(names)).astype(np.int64).tolist()
+    if positions is None:
+        return names, sizes, code
+    pos = np.asarray(positions, dtype=np.int64).ravel()
+    if pos.size and pos.min() < 0:
+        raise ValueError("positions must not be negative")
+    seg = np.full(pos.size, -1, dtype=np.int32)
+    inside = pos < n
+    seg[inside] = code[pos[inside]]
+    return names, sizes, seg
+
+
+def ppc_table(stats, counts, prefix: str = "ppc_"):
+    """The per-(segment, gene) columns of posterior_predictive_check from a table of spv_dec_sample_stats -> pandas DataFrame, one row
+    per (segment, column) in segment-major order, with the columns ``segment``, ``column`` and ``<prefix>`` + PPC_STATS.
+    ``stats``: uint64 [n_seg, 4, n_sel] (int64 storage is read as the same bits): S = sum of x, NZ = number of x > 0, Q = sum of x^2
+    modulo 2^64, M = max of x.  ``counts``: N_k = how many values segment k's entries were reduced over (cells x samples).
+        mean = S / N      var = (N Q - S^2) / (N (N - 1)), NaN for N < 2      zero_fraction = (N - NZ) / N = 1 - NZ / N
+        cv = sqrt(var) / mean, NaN at mean 0          (every column NaN for N < 1)
+    Numerators and denominators are formed as exact Python integers and divided ONCE, so mean, var and zero_fraction are the
+    correctly rounded fp64 values of the exact rationals (no cancellation between N Q and S^2 however large the counts).
+    Overflow rule: where N * M^2 >= 2^64 the square sum may have wrapped; ``var`` and ``cv`` of that (segment, gene) are NaN and one
+    RuntimeWarning says how many there are.  Below that bound Q < 2^64 holds, the table is exact."""
+    import warnings
+
+    import pandas as pd
+
+    t = np.asarray(stats)
+    if t.dtype == np.int64:
+        t = t.view(np.uint64)
+    if t.dtype != np.uint64 or t.ndim != 3 or t.shape[1] != 4:
+        raise ValueError(f"stats must be a uint64 array [n_seg, 4, n_sel], got {t.dtype} {t.shape}")
+    n_seg, _, n_sel = t.shape
+    cnt = [int(c) for c in np.asarray(counts).ravel().tolist()]
+    if len(cnt) != n_seg or any(c < 0 for c in cnt):
+        raise ValueError(f"counts must hold one non-negative count per segment ({n_seg}), got {cnt!r}")
+    col = {k: np.full((n_seg, n_sel), np.nan) for k in PPC_STATS}
+    wrapped = 0
+    for k, N in enumerate(cnt):
+        if N < 1:
+            continue
+        S, NZ, Q, M = (t[k, j].astype(object) for j in range(4))   # Python integers from here on
+        col["mean"][k] = np.asarray(S / N, dtype=np.float64)
+        col["zero_fraction"][k] = np.asarray((N - NZ) / N, dtype=np.float64)
+        col["max"][k] = t[k, 3].astype(np.float64)
+        if N >= 2:
+            safe = np.asarray(N * M * M < (1 << 64), dtype=bool)
+            wrapped += int(n_sel - safe.sum())
+            var = np.full(n_sel, np.nan)
+            if safe.any():
+                var[safe] = np.asarray((N * Q[safe] - S[safe] * S[safe]) / (N * (N - 1)), dtype=np.float64)
+            col["var"][k] = var
+            with np.errstate(divide="ignore", invalid="ignore"):
+                col["cv"][k] = np.where(col["mean"][k] > 0, np.sqrt(var) / col["mean"][k], np.nan)
+    if wrapped:
+        warnings.warn(f"ppc_table: the sum of squares of {wrapped} (segment, gene) entries may have wrapped past 2^64 "
+                      "(N * max^2 >= 2^64); their var and cv are NaN", RuntimeWarning, stacklevel=2)
+    frame = {"segment": np.repeat(np.arange(n_seg), n_sel), "column": np.tile(np.arange(n_sel), n_seg)}
+    frame.update({prefix + k: col[k].ravel() for k in PPC_STATS})
+    return pd.DataFrame(frame)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecSampleArgs, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
+from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecSampleArgs, SpvDecSampleStatsArgs, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
                    ptr, round_up, stream_ptr)
 from .nn_ops import _add_lin, _fptr, _lin_batch, _linear_bwd, _reduce_pending, _wgrad, grad_out
 from . import ops as _ops
@@ -914,13 +914,22 @@ def _gene_selection(genes, G: int, dev, who: str):
     return gidx, n
 
 
-def _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, who: str):
-    """the shared prelude of expected_expression / sample_counts: ``library_size`` override of the library, operand preparation
-    without the tiled logits, gene selection -> (_DecOperands, gene ids or None, n_genes)"""
+def _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, who: str,
+                      log_library: Optional[torch.Tensor] = None):
+    """the shared prelude of expected_expression / sample_counts / sample_count_stats: ``library_size`` override of the library,
+    operand preparation without the tiled logits, gene selection -> (_DecOperands, gene ids or None, n_genes).  ``log_library``: a
+    per-cell fp32 device vector [B] of LOG library sizes that wins over ``library_size`` (-inf: a cell whose rates are all 0)."""
     from .data import expression_log_library
 
     logL = expression_log_library(library_size)
-    lib = library if logL is None else torch.full((private_log_z.shape[0],), logL, dtype=torch.float32, device=private_log_z.device)
+    B = private_log_z.shape[0]
+    if log_library is not None:
+        if (not isinstance(log_library, torch.Tensor) or not log_library.is_cuda or log_library.dtype != torch.float32 or log_library.dim() != 1
+                or log_library.numel() != B or not log_library.is_contiguous()):
+            raise _abi.SpvError(f"{who}: the library override must be a contiguous fp32 device vector with one log library size per cell ({B})")
+        lib = log_library
+    else:
+        lib = library if logL is None else torch.full((B,), logL, dtype=torch.float32, device=private_log_z.device)
     o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
     return (o, *_gene_selection(genes, o.G, private_log_z.device, who))
 
@@ -970,6 +979,20 @@ def sample_key(seed: int) -> int:
     return ((0x53504C43 << 32) | (int(seed) & 0xFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
 
 
+def _check_stream(key, sample, who: str) -> None:
+    """``key`` / ``sample`` of the count sampler's entry points: integers in [0, 2^64) / [0, 2^32), else ValueError"""
+    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 64:
+        raise ValueError(f"{who}: key must be an integer in [0, 2^64), got {key!r}")
+    if isinstance(sample, bool) or not isinstance(sample, (int, np.integer)) or not 0 <= int(sample) < 1 << 32:
+        raise ValueError(f"{who}: sample must be an integer in [0, 2^32), got {sample!r}")
+
+
+def _check_cell_ids(cell_ids, B: int, who: str) -> None:
+    if cell_ids is not None and (not isinstance(cell_ids, torch.Tensor) or not cell_ids.is_cuda or cell_ids.dtype != torch.int32 or cell_ids.dim() != 1
+                                 or cell_ids.numel() < B or not cell_ids.is_contiguous()):
+        raise _abi.SpvError(f"{who}: cell_ids must be a contiguous int32 device tensor of at least {B} entries")
+
+
 @torch.no_grad()
 def sample_counts(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
                   training: bool, nsplit: int, ws: Workspace, par=None, *, genes=None, library_size="latent", key: int = 0, sample: int = 0,
@@ -982,15 +1005,10 @@ def sample_counts(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_
     ``sample`` (0 .. 2^32 - 1) the draw, ``key`` (0 .. 2^64 - 1) the stream.  ``out``: int32 device tensor to write into, either
     [>= B, >= n_genes] with unit column stride or [>= B, >= n_genes, S] viewed at one sample (``out3[:, :, s]``: column stride S);
     rows >= B, columns >= n_genes and the other samples' elements stay untouched."""
-    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 64:
-        raise ValueError(f"sample_counts: key must be an integer in [0, 2^64), got {key!r}")
-    if isinstance(sample, bool) or not isinstance(sample, (int, np.integer)) or not 0 <= int(sample) < 1 << 32:
-        raise ValueError(f"sample_counts: sample must be an integer in [0, 2^32), got {sample!r}")
+    _check_stream(key, sample, "sample_counts")
     o, gidx, n = _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, "sample_counts")
     B, dev = o.B, private_log_z.device
-    if cell_ids is not None and (not isinstance(cell_ids, torch.Tensor) or not cell_ids.is_cuda or cell_ids.dtype != torch.int32 or cell_ids.dim() != 1
-                                 or cell_ids.numel() < B or not cell_ids.is_contiguous()):
-        raise _abi.SpvError(f"sample_counts: cell_ids must be a contiguous int32 device tensor of at least {B} entries")
+    _check_cell_ids(cell_ids, B, "sample_counts")
     if out is None:
         out = torch.empty((B, n), dtype=torch.int32, device=dev)
     elif (not out.is_cuda or out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] < B or out.shape[1] < n
@@ -1005,6 +1023,63 @@ def sample_counts(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_
     a.out, a.ld_out = ptr(out), (out.stride(0) if out.shape[0] > 1 else (n - 1) * ld_gene + 1)
     _abi.call("spv_dec_sample", C.byref(o.p), C.byref(a), stream_ptr())
     return out[:B, :n]
+
+
+SAMPLE_STATS = ("sum", "non_zeros", "sum_squares", "max")   # the rows of spv_dec_sample_stats' table
+_U64 = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)   # 64-bit integer storage of either signedness
+
+
+def check_sample_stats_tables(B: int, n: int, seg, n_seg, stats, cell_total, who: str = "sample_count_stats") -> int:
+    """The dtype / shape / contiguity checks of ``sample_count_stats``' tables for a minibatch of ``B`` cells and ``n`` selected genes
+    -> n_seg.  Pure host code: it looks at tensor metadata only."""
+    if isinstance(n_seg, bool) or not isinstance(n_seg, (int, np.integer)) or int(n_seg) < 1:
+        raise ValueError(f"{who}: n_seg must be a positive integer, got {n_seg!r}")
+    n_seg = int(n_seg)
+    if seg is not None and (not isinstance(seg, torch.Tensor) or not seg.is_cuda or seg.dtype != torch.int32 or seg.dim() != 1 or seg.numel() < B
+                            or not seg.is_contiguous()):
+        raise _abi.SpvError(f"{who}: seg must be a contiguous int32 device tensor of at least {B} segment codes")
+    if (not isinstance(stats, torch.Tensor) or not stats.is_cuda or stats.dtype not in _U64 or stats.dim() != 3 or stats.shape[0] != n_seg
+            or stats.shape[1] != len(SAMPLE_STATS) or stats.shape[2] < n or not stats.is_contiguous()):
+        raise _abi.SpvError(f"{who}: stats must be a contiguous 64-bit integer device tensor [{n_seg}, {len(SAMPLE_STATS)}, >= {n}]")
+    if cell_total is not None and (not isinstance(cell_total, torch.Tensor) or not cell_total.is_cuda or cell_total.dtype not in _U64
+                                   or cell_total.dim() != 1 or cell_total.numel() < B or not cell_total.is_contiguous()):
+        raise _abi.SpvError(f"{who}: cell_total must be a contiguous 64-bit integer device tensor of at least {B} entries")
+    return n_seg
+
+
+@torch.no_grad()
+def sample_count_stats(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
+                       training: bool, nsplit: int, ws: Workspace, par=None, *, genes=None, library_size="latent", log_library=None,
+                       key: int = 0, sample: int = 0, cell_ids: Optional[torch.Tensor] = None, seg: Optional[torch.Tensor] = None,
+                       n_seg: int = 1, stats: torch.Tensor, cell_total: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sample_counts``' draws for ONE group's minibatch, reduced inside the kernel instead of stored (spv_dec_sample_stats;
+    module/spVIPESmodule.py:751-759): with x[b, j] the integer ``sample_counts`` returns for the same operands, ``genes``,
+    ``library_size``, ``key``, ``sample`` and ``cell_ids``,
+
+        stats[k, 0, j] += sum x    stats[k, 1, j] += #(x > 0)    stats[k, 2, j] += sum x^2 (modulo 2^64)    stats[k, 3, j] = max(., max x)
+
+    over the cells b with ``seg[b] == k``, and ``cell_total[b] += sum_j x[b, j]``.  ``seg``: int32 device tensor [>= B] of codes in
+    [0, n_seg), None = every cell in segment 0; a cell with a negative code (or one >= n_seg) is neither drawn nor counted.
+    ``stats``: 64-bit integer device tensor [n_seg, 4, >= n_genes] (torch.int64 holds the same bits as uint64: view it on the
+    host), ``cell_total``: [>= B] or None.  Everything ACCUMULATES with integer atomics: zero the tables once, then one table
+    collects every sample of every minibatch, equal bit for bit to the reduction of the stored draws; columns >= n_genes, rows of
+    segments without a counted cell and totals of cells that are not counted stay untouched.  ``log_library``: a per-cell fp32
+    device vector [B] of log library sizes that wins over ``library_size``.  One launch; nothing of size cells x genes is written.
+    Returns ``stats``."""
+    who = "sample_count_stats"
+    _check_stream(key, sample, who)
+    o, gidx, n = _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, who,
+                                   log_library=log_library)
+    B = o.B
+    _check_cell_ids(cell_ids, B, who)
+    n_seg = check_sample_stats_tables(B, n, seg, n_seg, stats, cell_total, who)
+    theta = _theta(o.par)
+    a = SpvDecSampleStatsArgs()
+    _fill_readout(a, o, nsplit, gidx, n)
+    a.theta, a.cell_ids, a.key, a.sample = ptr(theta), ptr(cell_ids), int(key), int(sample)
+    a.seg, a.n_seg, a.stats, a.ld_stats, a.cell_total = ptr(seg), n_seg, ptr(stats), stats.stride(1), ptr(cell_total)
+    _abi.call("spv_dec_sample_stats", C.byref(o.p), C.byref(a), stream_ptr())
+    return stats
 
 
 @torch.no_grad()

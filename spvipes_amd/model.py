@@ -570,6 +570,118 @@ class spVIPES:
             frames.append(df)
         return pd.concat(frames)
 
+    @torch.no_grad()
+    def posterior_predictive_check(self, group_indices_list: List[List[int]], group: int, n_samples: int = 25, groupby=None, labels=None,
+                                   gene_list=None, library_size="latent", seed: int = 0, batch_size: Optional[int] = None, _noise=None):
+        """A posterior-predictive check of ONE group's count model that never leaves the device (scvi-tools'
+        ``criticism.PosteriorPredictiveCheck``: per-gene mean, variance / CV and zero fraction of sampled against observed counts):
+        a pandas DataFrame with one row per (population, selected gene) and the columns
+
+            population, gene, n_cells, n_samples
+            obs_mean, obs_var, obs_cv, obs_zero_fraction                  the OBSERVED counts of the population's cells
+            ppc_mean, ppc_var, ppc_cv, ppc_zero_fraction, ppc_max         the n_cells * n_samples counts DRAWN for them
+
+        (var: the unbiased sample variance, NaN for fewer than two values; cv = sqrt(var) / mean, NaN at mean 0.)
+        ``attrs["cell_totals"]`` holds a frame with ``obs_total`` and ``ppc_total_mean`` (the cell's drawn total averaged over the
+        samples) per cell of ``group_indices_list[group]``, in ``get_latent_representation``'s row order, indexed by the adata row
+        numbers; a cell outside every population has NaN in both.  Sampled totals run over the SELECTED genes (a repeated gene counts as
+        often as it is listed), and the observed totals run over the same selection here -- unlike ``count_statistics``, whose
+        normalisation weight always uses the total over all of the group's genes.
+
+        The drawn counts are those of ``posterior_predictive_sample(group_indices_list, n_samples, gene_list, library_size, seed,
+        batch_size)`` for this group, integer for integer (same minibatch walk, ``draw = step * n_samples + sample``, same key and cell
+        ids), but the [n_cells, n_sel, n_samples] cube is never stored: one fused HIP kernel (spv_dec_sample_stats) decodes, draws and
+        adds every minibatch into one 64-bit integer table per (population, gene) and one total per cell; only those leave the device.
+        ``groupby``: None -- one population "all" -- or the name of an ``adata.obs`` column or an array with one label per cell of
+        ``group_indices_list[group]``: each label is a population, in ``labels`` order (default: the sorted unique labels; an unknown
+        label is a KeyError); cells of other labels are left out.  ``gene_list``: None or this group's selection, as
+        ``differential_expression`` takes it.  ``library_size``: "latent" and a positive number mean what they mean for
+        ``posterior_predictive_sample``; "observed" gives each cell the log of its observed total over ALL of the group's genes as its
+        library, so its draws are on the raw-count scale of that cell (a cell without counts gets rate 0 and draws 0).
+        The sampled columns are exact: integer sums, divided once (``data.ppc_table``, which also states the overflow rule for the
+        sum of squares).  The observed second moment is one chunked pass over the resident counts (``count_ops.count_square_sums``).
+        Dense and CSR ``counts_storage`` give the same frame.  ``_noise`` (tests only): as ``posterior_predictive_sample`` takes it."""
+        import pandas as pd
+
+        from .count_ops import count_square_sums, count_stats, count_totals
+        from .data import check_ppc_library, ppc_segments, ppc_table
+        from .dec_ops import sample_key
+
+        library_size = check_ppc_library(library_size)
+        observed = isinstance(library_size, str) and library_size == "observed"
+        n_samples, seed, _log_l = check_sample_args(n_samples, seed, "latent" if observed else library_size)
+        if group not in (0, 1):
+            raise ValueError(f"group must be 0 or 1, got {group!r}")
+        g = int(group)
+        cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
+        n_g = len(cells)
+        if groupby is None:
+            cell_labels = None
+        elif isinstance(groupby, str):
+            if groupby not in self.adata.obs:
+                raise KeyError(f"groupby: adata.obs has no column {groupby!r}")
+            cell_labels = np.asarray(self.adata.obs[groupby])[cells]
+        else:
+            cell_labels = np.asarray(groupby).ravel()
+            if cell_labels.shape[0] != n_g:
+                raise ValueError(f"groupby: an array must hold one label per cell of group_indices_list[{g}] ({n_g}), got {cell_labels.shape[0]}")
+        names, sizes, code = ppc_segments(cell_labels, labels, n_cells=n_g)
+        n_seg = len(names)
+        _sel, dev_sel, n_sel, index = self._de_genes(g, gene_list)
+        obs_ids = torch.as_tensor(np.asarray(self.obs_idx[g]), dtype=torch.int32, device=self.device)
+        key = sample_key(seed)
+        stats = torch.zeros((n_seg, 4, n_sel), dtype=torch.int64, device=self.device)   # (uint64 bits)
+        totals = torch.zeros((n_g + (batch_size or 128),), dtype=torch.int64, device=self.device)   # walk positions; the tail is never counted
+        obs_all = count_totals(self.counts[g]) if observed else None
+        off = 0
+        for step, tensors, B in self._eval_minibatches(group_indices_list, batch_size, None):
+            Bg = B[g]
+            cpos = off + np.arange(Bg)
+            off += Bg
+            seg = ppc_segments(cell_labels, labels, n_cells=n_g, positions=cpos)[2]
+            if not (seg >= 0).any():
+                continue   # nothing of this step is counted (eval mode: steps are independent of each other)
+            rows = tensors[g]["rows"].long()
+            ids = obs_ids[rows].contiguous()
+            seg_d = torch.as_tensor(seg, dtype=torch.int32, device=self.device)
+            lib = torch.log(obs_all.index_select(0, rows)).to(torch.float32).contiguous() if observed else None
+            for smp in range(n_samples):
+                out = self._infer(tensors, _noise, step * n_samples + smp, B[0], B[1])
+                self.module.sample_count_stats(out, g, genes=dev_sel, library_size="latent" if observed else library_size, library=lib, key=key,
+                                               sample=smp, cell_ids=ids, seg=seg_d, n_seg=n_seg, stats=stats, cell_total=totals[off - Bg:off])
+        table = stats.cpu().numpy().view(np.uint64)
+        ppc = ppc_table(table, [sizes[k] * n_samples for k in range(n_seg)], prefix="ppc_")
+        # the observed side: the populations' cells sorted by population, one segmented reduction + one chunked pass for the squares
+        kept = np.nonzero(code >= 0)[0]
+        order = kept[np.argsort(code[kept], kind="stable")]
+        rows = torch.as_tensor(self._local_rows(g, cells[order]).astype(np.int32), device=self.device)
+        sums = count_stats(self.counts[g], rows, sizes, genes=dev_sel).cpu().numpy()
+        sq, tot = count_square_sums(self.counts[g], rows, sizes, genes=dev_sel, row_totals=True)
+        sq = sq.cpu().numpy()
+        if sq.dtype == np.int64 or (np.all(sums[:, :2] == np.floor(sums[:, :2])) and np.all(sq == np.floor(sq)) and (sq.size == 0 or sq.max() < 2.0 ** 53)):
+            exact = np.zeros((n_seg, 4, n_sel), dtype=np.uint64)   # whole numbers below 2^53: the exact route (no modular sum here: max row 0)
+            exact[:, 0], exact[:, 1], exact[:, 2] = sums[:, 0].astype(np.uint64), sums[:, 1].astype(np.uint64), sq.astype(np.uint64)
+            obs = ppc_table(exact, sizes, prefix="obs_")
+        else:   # fractional fp32 counts: fp64 throughout
+            N = np.asarray(sizes, dtype=np.float64)[:, None]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                mean = np.where(N > 0, sums[:, 0] / N, np.nan)
+                var = np.where(N > 1, (N * sq - sums[:, 0] ** 2) / (N * (N - 1)), np.nan)
+                obs = pd.DataFrame({"obs_mean": mean.ravel(), "obs_var": var.ravel(),
+                                    "obs_cv": np.where(mean > 0, np.sqrt(var) / mean, np.nan).ravel(),
+                                    "obs_zero_fraction": np.where(N > 0, (N - sums[:, 1]) / N, np.nan).ravel()})
+        frame = pd.DataFrame({"population": np.repeat(np.asarray(names, dtype=object), n_sel), "gene": np.tile(np.asarray(index), n_seg),
+                              "n_cells": np.repeat(np.asarray(sizes, dtype=np.int64), n_sel), "n_samples": n_samples})
+        for c in ("obs_mean", "obs_var", "obs_cv", "obs_zero_fraction"):
+            frame[c] = obs[c].to_numpy()
+        for c in ("ppc_mean", "ppc_var", "ppc_cv", "ppc_zero_fraction", "ppc_max"):
+            frame[c] = ppc[c].to_numpy()
+        obs_total, ppc_total = np.full(n_g, np.nan), np.full(n_g, np.nan)
+        obs_total[order] = tot.cpu().numpy()
+        ppc_total[kept] = totals[:n_g].cpu().numpy().view(np.uint64)[kept].astype(np.float64) / n_samples
+        frame.attrs["cell_totals"] = pd.DataFrame({"obs_total": obs_total, "ppc_total_mean": ppc_total}, index=cells)
+        return frame
+
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}
         with the reference's column names ``Z_private_{n}`` / ``Z_shared_{n}`` and the group's own var_names as the index

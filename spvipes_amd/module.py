@@ -752,6 +752,22 @@ class spVIPESmodule(nn.Module):
                              self._workspace(group, lib.device), par=par, genes=genes, library_size=library_size, key=key, sample=sample,
                              cell_ids=cell_ids, out=out)
 
+    @torch.no_grad()
+    def sample_count_stats(self, inference_outputs, group: int, *, genes=None, library_size="latent", library=None, use_mean: bool = False,
+                           key: int = 0, sample: int = 0, cell_ids=None, seg=None, n_seg: int = 1, stats, cell_total=None) -> torch.Tensor:
+        """``sample_counts``' draws for one group of the minibatch ``inference_outputs`` describes, reduced on the device instead of
+        stored: per segment and selected gene the sum, the non-zero tally, the sum of squares and the max of the drawn counts are
+        ACCUMULATED into ``stats`` (64-bit integers [n_seg, 4, >= n_genes]) and per cell the total into ``cell_total`` -- equal bit for
+        bit to reducing what ``sample_counts`` returns for the same arguments.  ``library``: a per-cell fp32 device vector of LOG
+        library sizes that wins over ``library_size``.  ``seg`` / ``n_seg`` / ``stats`` / ``cell_total``: dec_ops.sample_count_stats
+        (one fused HIP kernel, spv_dec_sample_stats; no [B, n_genes] array is written)."""
+        from .dec_ops import sample_count_stats
+
+        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
+        return sample_count_stats(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
+                                  self._workspace(group, lib.device), par=par, genes=genes, library_size=library_size, log_library=library,
+                                  key=key, sample=sample, cell_ids=cell_ids, seg=seg, n_seg=n_seg, stats=stats, cell_total=cell_total)
+
     def loss(self, tensors_by_group, inference_outputs, generative_outputs, kl_weight: float = 1.0):
         """spVIPESmodule.py:809-899."""
         from .dec_ops import DecoderFused, decoder_params
