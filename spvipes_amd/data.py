@@ -253,6 +253,32 @@ def latent_steps(local: Sequence[Sequence[int]], batch_size: int, drop_last: boo
     return steps
 
 
+def walk_positions(steps, g: int, n_g: int):
+    """The eval walk ``steps`` ((step, tensors, (B0, B1)), as ``_eval_minibatches`` yields them) with group g's bookkeeping -> (step, tensors, (B0, B1),
+    off, pos): the step's rows are rows off .. off + B_g - 1 of the group's concatenated read-out, ``pos`` (int64) those positions, with -1 for every
+    one at or beyond ``n_g`` -- the replayed rows, which a read-out cuts off and a reduction must not count twice."""
+    off = 0
+    for step, tensors, B in steps:
+        pos = off + np.arange(B[g], dtype=np.int64)
+        yield step, tensors, B, off, np.where(pos < n_g, pos, -1)
+        off += B[g]
+
+
+class RowBlocks:
+    """Per-step blocks of a two-group read-out, copied to the host as they complete or kept on the device; ``result``: concatenated, cut at the sizes ``n``"""
+
+    def __init__(self, n: Sequence[int], return_numpy: bool):
+        self.n, self.return_numpy, self.blocks = n, return_numpy, ([], [])
+
+    def add(self, per_group) -> None:
+        for g, block in enumerate(per_group):
+            self.blocks[g].append(block.cpu().numpy() if self.return_numpy else block)
+
+    def result(self) -> dict:
+        cat = np.concatenate if self.return_numpy else torch.cat
+        return {g: cat(self.blocks[g])[:self.n[g]] for g in range(2)}
+
+
 def format_latent_results(private0, private1, shared0, shared1, indices1, n0: int, n1: int) -> dict:
     """model/spvipes.py:628-650: per-step arrays concatenated, truncated to the group sizes; the ``*_reordered`` entries sort
     GROUP 1 ONLY by its 'indices' column (group 0 is returned as is)."""
@@ -404,6 +430,37 @@ def check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells=None):
     if max_cells is not None and (isinstance(max_cells, bool) or not isinstance(max_cells, (int, np.integer)) or int(max_cells) < 1):
         raise ValueError(f"max_cells must be None or a positive integer, got {max_cells!r}")
     return int(n_pairs), delta, pseudocount, fdr_target, (None if max_cells is None else int(max_cells))
+
+
+def check_group(group) -> int:
+    """``group`` of the one-group read-outs: 0 or 1, else ValueError"""
+    if group not in (0, 1):
+        raise ValueError(f"group must be 0 or 1, got {group!r}")
+    return int(group)
+
+
+def group_cell_labels(obs, groupby, cells: np.ndarray, g: int, unique: bool = False) -> np.ndarray:
+    """``groupby`` -> one label per cell of ``cells`` (= ``group_indices_list[g]``, adata row numbers): the name of a column of ``obs``
+    (KeyError for an unknown one) or an array of that length (else ValueError).  ``unique``: then, ValueError for a cell listed twice."""
+    if isinstance(groupby, str):
+        if groupby not in obs:
+            raise KeyError(f"groupby: adata.obs has no column {groupby!r}")
+        cell_labels = np.asarray(obs[groupby])[cells]
+    else:
+        cell_labels = np.asarray(groupby).ravel()
+        if cell_labels.shape[0] != len(cells):
+            raise ValueError(f"groupby: an array must hold one label per cell of group_indices_list[{g}] ({len(cells)}), got {cell_labels.shape[0]}")
+    if unique and len(np.unique(cells)) != len(cells):
+        raise ValueError(f"group_indices_list[{g}] lists a cell more than once")
+    return cell_labels
+
+
+def vs_rest_frames(tables, index):
+    """The frame of a one-vs-rest read-out: ``tables`` = (label, column -> array) per compared label, in order -> their frames over
+    ``index`` with ``comparison`` ("<label> vs Rest"), ``group1`` (the label) and ``group2`` ("Rest") appended, concatenated."""
+    import pandas as pd
+
+    return pd.concat([pd.DataFrame(table, index=index).assign(comparison=f"{name} vs Rest", group1=name, group2="Rest") for name, table in tables])
 
 
 def de_populations(group_indices, idx1, idx2=None, group: int = 0):
@@ -723,3 +780,42 @@ def ppc_table(stats, counts, prefix: str = "ppc_"):
     frame = {"segment": np.repeat(np.arange(n_seg), n_sel), "column": np.tile(np.arange(n_sel), n_seg)}
     frame.update({prefix + k: col[k].ravel() for k in PPC_STATS})
     return pd.DataFrame(frame)
+
+
+def ppc_observed_columns(sums, sq, sizes):
+    """The observed columns of posterior_predictive_check -> DataFrame with ``obs_`` + mean / var / cv / zero_fraction, one row per (population,
+    gene), population-major, NaN where ``ppc_table`` has it.  ``sums``: fp64 [n_seg, 3, n_sel] of ``count_ops.count_stats``, ``sq``: [n_seg, n_sel] of
+    ``count_ops.count_square_sums``, ``sizes``: cells per population.  Integer or whole-number sums below 2^53 go through ``ppc_table`` (exact)."""
+    import pandas as pd
+
+    n_seg, n_sel = sq.shape
+    if sq.dtype == np.int64 or (np.all(sums[:, :2] == np.floor(sums[:, :2])) and np.all(sq == np.floor(sq)) and (sq.size == 0 or sq.max() < 2.0 ** 53)):
+        exact = np.zeros((n_seg, 4, n_sel), dtype=np.uint64)   # whole numbers below 2^53: the exact route (no modular sum here: max row 0)
+        exact[:, 0], exact[:, 1], exact[:, 2] = sums[:, 0].astype(np.uint64), sums[:, 1].astype(np.uint64), sq.astype(np.uint64)
+        return ppc_table(exact, sizes, prefix="obs_")
+    N = np.asarray(sizes, dtype=np.float64)[:, None]   # fractional fp32 counts: fp64 throughout
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(N > 0, sums[:, 0] / N, np.nan)
+        var = np.where(N > 1, (N * sq - sums[:, 0] ** 2) / (N * (N - 1)), np.nan)
+        return pd.DataFrame({"obs_mean": mean.ravel(), "obs_var": var.ravel(),
+                             "obs_cv": np.where(mean > 0, np.sqrt(var) / mean, np.nan).ravel(),
+                             "obs_zero_fraction": np.where(N > 0, (N - sums[:, 1]) / N, np.nan).ravel()})
+
+
+def ppc_frame(names, sizes, index, obs, ppc, n_samples: int, cells, order, kept, obs_totals, ppc_totals):
+    """The frame posterior_predictive_check returns: one row per (population of ``names`` / ``sizes``, gene of ``index``), population-major, with the
+    columns of ``obs`` (``ppc_observed_columns``) and ``ppc`` (``ppc_table``).  ``attrs["cell_totals"]``: ``obs_total`` / ``ppc_total_mean`` per cell of
+    ``cells`` (adata row numbers, the index), NaN outside every population.  ``kept``: the positions in ``cells`` of the populations' cells, ascending;
+    ``order``: the same sorted by population, as ``obs_totals`` is; ``ppc_totals``: uint64 per position, summed over the ``n_samples`` samples."""
+    import pandas as pd
+
+    n_seg, n_sel = len(names), len(index)
+    frame = pd.DataFrame({"population": np.repeat(np.asarray(names, dtype=object), n_sel), "gene": np.tile(np.asarray(index), n_seg),
+                          "n_cells": np.repeat(np.asarray(sizes, dtype=np.int64), n_sel), "n_samples": n_samples})
+    for table, prefix, stats in ((obs, "obs_", PPC_STATS[:4]), (ppc, "ppc_", PPC_STATS)):
+        for c in stats:
+            frame[prefix + c] = table[prefix + c].to_numpy()
+    totals = np.full((2, len(cells)), np.nan)
+    totals[0, order], totals[1, kept] = obs_totals, np.asarray(ppc_totals)[kept].astype(np.float64) / n_samples
+    frame.attrs["cell_totals"] = pd.DataFrame({"obs_total": totals[0], "ppc_total_mean": totals[1]}, index=cells)
+    return frame

@@ -20,9 +20,9 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, check_de_args, check_expression_args, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays, csr_to_dense, de_bank_rows, de_label_populations,
-                   de_pair_rows, de_populations, de_subsample, de_table, format_latent_results, group_var_names, is_sparse, latent_loader_mode, latent_steps, resolve_gene_list,
-                   to_group_counts, to_sparse_group_counts)
+from .data import (MinibatchSampler, RowBlocks, check_de_args, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
+                   csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, format_latent_results, group_cell_labels, group_var_names, is_sparse,
+                   latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions)
 from .module import spVIPESmodule
 from .train import Trainer, default_max_epochs
 
@@ -246,6 +246,25 @@ class spVIPES:
         kw = {} if _noise is None else {"noise": _noise(draw, B0, B1)}
         return self.module.inference(**self.module._get_inference_input(tensors), **kw)
 
+    def _draws(self, step: int, tensors, B, n_samples: int, _noise):
+        """(sample, inference outputs) for the ``n_samples`` draws of one step of the walk.  The draw index ``step * n_samples + sample``
+        is what ``_noise`` is asked for: every read-out walking the same minibatches sees the same latents draw for draw."""
+        for smp in range(n_samples):
+            yield smp, self._infer(tensors, _noise, step * n_samples + smp, B[0], B[1])
+
+    def _genes(self, g: int, gene_list, own: bool = False):
+        """-> (positions or None, their device copy or None, how many, the index of a result table) for group g's part of a gene
+        selection.  ``gene_list``: one entry per group as ``resolve_gene_list`` takes it, or with ``own`` group g's entry alone."""
+        if own and gene_list is not None:
+            gene_list = [gene_list if k == g else None for k in range(2)]
+        n_genes = [int(self.module.input_dims[k]) for k in range(2)]
+        names = group_var_names(self.adata)
+        sel = resolve_gene_list(gene_list, n_genes, names)[g]
+        dev_sel = None if sel is None else torch.as_tensor(sel, dtype=torch.int32, device=self.device)
+        n_sel = n_genes[g] if sel is None else len(sel)
+        index = (np.arange(n_sel) if sel is None else np.asarray(sel)) if names[g] is None else (np.asarray(names[g]) if sel is None else np.asarray(names[g])[sel])
+        return sel, dev_sel, n_sel, index
+
     @torch.no_grad()
     def get_normalized_expression(self, group_indices_list: List[List[int]], gene_list=None, library_size="latent", component: str = "mixture",
                                   n_samples: int = 1, use_mean: bool = True, batch_size: Optional[int] = None, return_numpy: bool = True,
@@ -270,21 +289,16 @@ class spVIPES:
         Each cell is decoded with its own batch covariate.  ``_noise`` (tests only): callable (draw, B0, B1) -> injected standard-normal
         draws for module.inference, draw = step * n_samples + sample."""
         _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
-        n = [len(g) for g in group_indices_list]
-        sel = resolve_gene_list(gene_list, [int(self.module.input_dims[g]) for g in range(2)], group_var_names(self.adata))
-        dev_sel = [None if s is None else torch.as_tensor(s, dtype=torch.int32, device=self.device) for s in sel]
-        blocks = {0: [], 1: []}
-        for step, tensors, (B0, B1) in self._eval_minibatches(group_indices_list, batch_size, None):
+        blocks = RowBlocks([len(g) for g in group_indices_list], return_numpy)
+        dev_sel = [self._genes(g, gene_list)[1] for g in range(2)]
+        for step, tensors, B in self._eval_minibatches(group_indices_list, batch_size, None):
             blk = [None, None]
-            for smp in range(n_samples):
-                out = self._infer(tensors, _noise, step * n_samples + smp, B0, B1)
+            for smp, out in self._draws(step, tensors, B, n_samples, _noise):
                 for g in range(2):
                     blk[g] = self.module.expected_expression(out, g, genes=dev_sel[g], what=component, library_size=library_size, use_mean=use_mean,
                                                              out=blk[g], alpha=1.0 / n_samples, accumulate=smp > 0)
-            for g in range(2):
-                blocks[g].append(blk[g].cpu().numpy() if return_numpy else blk[g])
-        cat = np.concatenate if return_numpy else torch.cat
-        return {g: cat(blocks[g])[:n[g]] for g in range(2)}
+            blocks.add(blk)
+        return blocks.result()
 
     @torch.no_grad()
     def posterior_predictive_sample(self, group_indices_list: List[List[int]], n_samples: int = 1, gene_list=None, library_size="latent", seed: int = 0,
@@ -308,26 +322,19 @@ class spVIPES:
         from .dec_ops import sample_key
 
         n_samples, seed, _log_l = check_sample_args(n_samples, seed, library_size)
-        n = [len(g) for g in group_indices_list]
-        sel = resolve_gene_list(gene_list, [int(self.module.input_dims[g]) for g in range(2)], group_var_names(self.adata))
-        dev_sel = [None if s is None else torch.as_tensor(s, dtype=torch.int32, device=self.device) for s in sel]
-        n_sel = [int(self.module.input_dims[g]) if sel[g] is None else int(sel[g].size) for g in range(2)]
+        blocks = RowBlocks([len(g) for g in group_indices_list], return_numpy)
+        _sel, dev_sel, n_sel, _index = zip(*[self._genes(g, gene_list) for g in range(2)])
         obs = [torch.as_tensor(np.asarray(self.obs_idx[g]), dtype=torch.int32, device=self.device) for g in range(2)]
         key = sample_key(seed)
-        blocks = {0: [], 1: []}
         for step, tensors, B in self._eval_minibatches(group_indices_list, batch_size, None):
             blk = [torch.empty((B[g], n_sel[g], n_samples), dtype=torch.int32, device=self.device) for g in range(2)]
             ids = [obs[g][tensors[g]["rows"].long()].contiguous() for g in range(2)]
-            for smp in range(n_samples):
-                out = self._infer(tensors, _noise, step * n_samples + smp, B[0], B[1])
+            for smp, out in self._draws(step, tensors, B, n_samples, _noise):
                 for g in range(2):
                     self.module.sample_counts(out, g, genes=dev_sel[g], library_size=library_size, key=key, sample=smp, cell_ids=ids[g],
                                               out=blk[g][:, :, smp])
-            for g in range(2):
-                b = blk[g] if n_samples > 1 else blk[g][:, :, 0]
-                blocks[g].append(b.cpu().numpy() if return_numpy else b)
-        cat = np.concatenate if return_numpy else torch.cat
-        return {g: cat(blocks[g])[:n[g]] for g in range(2)}
+            blocks.add(blk if n_samples > 1 else [b[:, :, 0] for b in blk])
+        return blocks.result()
 
     @torch.no_grad()
     def differential_expression(self, group_indices_list: List[List[int]], group: int, idx1, idx2=None, gene_list=None, component: str = "mixture",
@@ -356,8 +363,8 @@ class spVIPES:
         device.  Bank memory is (n_1 + n_2) * n_samples * n_sel * 4 bytes; ``max_cells`` caps each population by a seeded subsample
         before the walk.  ``use_mean=True`` (needs ``n_samples == 1``) compares decoded posterior means and is deterministic.
         ``_noise`` (tests only): as in ``get_normalized_expression``; ``_pair_rows`` (tests only): (r1, r2) bank rows instead of drawn ones."""
-        return self._differential_expression(group_indices_list, group, idx1, idx2, gene_list, component, library_size, n_samples, use_mean, n_pairs,
-                                             delta, pseudocount, fdr_target, max_cells, seed, batch_size, _noise, _pair_rows, lfc_median=False)
+        return self.differential_expression_median(group_indices_list, group, idx1, idx2, gene_list, component, library_size, n_samples, use_mean, n_pairs,
+                                                   delta, pseudocount, fdr_target, max_cells, seed, batch_size, False, _noise, _pair_rows)
 
     @torch.no_grad()
     def differential_expression_median(self, group_indices_list: List[List[int]], group: int, idx1, idx2=None, gene_list=None, component: str = "mixture",
@@ -369,50 +376,40 @@ class spVIPES:
         the two middle order statistics in float64.  They come from a second HIP kernel (spv_de_median, a radix select in four gather
         passes) on the banks the first one read; ``lfc_min <= lfc_median <= lfc_max`` holds exactly.  ``lfc_median=False`` launches
         nothing more and returns ``differential_expression``'s frame."""
-        return self._differential_expression(group_indices_list, group, idx1, idx2, gene_list, component, library_size, n_samples, use_mean, n_pairs,
-                                             delta, pseudocount, fdr_target, max_cells, seed, batch_size, _noise, _pair_rows, lfc_median=bool(lfc_median))
+        import pandas as pd
 
-    def _de_genes(self, g: int, gene_list):
-        """-> (positions or None, their device copy or None, how many, the index of the result table) for a selection of group g's genes"""
-        gl = [None, None]
-        gl[g] = gene_list
-        sel = resolve_gene_list(None if gene_list is None else gl, [int(self.module.input_dims[k]) for k in range(2)], group_var_names(self.adata))[g]
-        dev_sel = None if sel is None else torch.as_tensor(sel, dtype=torch.int32, device=self.device)
-        n_sel = int(self.module.input_dims[g]) if sel is None else len(sel)
-        names = group_var_names(self.adata)[g]
-        index = (np.arange(n_sel) if sel is None else np.asarray(sel)) if names is None else (np.asarray(names) if sel is None else np.asarray(names)[sel])
-        return sel, dev_sel, n_sel, index
+        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
+        n_pairs, delta, pseudocount, fdr_target, max_cells = check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells)
+        g = check_group(group)
+        _sel, dev_sel, n_sel, index = self._genes(g, gene_list, own=True)
+        pops = de_populations(group_indices_list[g], idx1, idx2, group=g)
+        pops = [de_subsample(p, max_cells, seed + 1 + k) for k, p in enumerate(pops)]
+        banks = self._de_banks(group_indices_list, g, pops, dev_sel, n_sel, component, library_size, n_samples, use_mean, batch_size, _noise)
+        r1, r2 = de_pair_rows(banks[0].shape[0], banks[1].shape[0], n_pairs, seed) if _pair_rows is None else (np.asarray(r).astype(np.int32) for r in _pair_rows)
+        return pd.DataFrame(self._de_compare(banks[0], banks[1], r1, r2, delta, pseudocount, fdr_target, bool(lfc_median)), index=index)
 
     def _de_banks(self, group_indices_list, g: int, pops, dev_sel, n_sel: int, component, library_size, n_samples: int, use_mean: bool, batch_size, _noise):
         """One device-resident fp32 bank [len(p) * n_samples, n_sel] per population p of ``pops`` (positions within
         ``group_indices_list[g]``): row draw * len(p) + i holds draw ``draw`` of the decoded expression of the population's i-th cell.
         ONE walk of the eval minibatches fills them all; steps without a population cell are skipped."""
         n_g = len(group_indices_list[g])
-        slot, banks = [], []
-        for p in pops:   # position within group_indices_list[g] -> the cell's place in its population (-1: not in it)
-            s = np.full(n_g, -1, dtype=np.int64)
+        slot = [np.full(n_g, -1, dtype=np.int64) for _ in pops]   # position within group_indices_list[g] -> the cell's place in its population (-1: not in it)
+        for s, p in zip(slot, pops):
             s[p] = np.arange(len(p))
-            slot.append(s)
-            banks.append(torch.empty((len(p) * n_samples, n_sel), dtype=torch.float32, device=self.device))
-        off, blk = 0, None
-        for step, tensors, (B0, B1) in self._eval_minibatches(group_indices_list, batch_size, None):
-            Bg = (B0, B1)[g]
-            cpos = off + np.arange(Bg)   # the rows this step contributes to the group's concatenated read-out, which is cut at n_g
-            off += Bg
-            keep = cpos < n_g
+        banks = [torch.empty((len(p) * n_samples, n_sel), dtype=torch.float32, device=self.device) for p in pops]
+        blk = None
+        for step, tensors, B, _off, pos in walk_positions(self._eval_minibatches(group_indices_list, batch_size, None), g, n_g):
             moves = []
             for k in range(len(pops)):
-                sl = np.full(Bg, -1, dtype=np.int64)
-                sl[keep] = slot[k][cpos[keep]]
+                sl = np.where(pos >= 0, slot[k][pos], -1)   # a cut row (pos -1) belongs to no population
                 src = np.nonzero(sl >= 0)[0]
                 if src.size:
                     moves.append((k, torch.as_tensor(src, device=self.device), torch.as_tensor(sl[src], device=self.device)))
             if not moves:
                 continue   # eval mode: steps are independent of each other
-            for smp in range(n_samples):
-                out = self._infer(tensors, _noise, step * n_samples + smp, B0, B1)
-                if blk is None or blk.shape[0] < Bg:
-                    blk = torch.empty((Bg, n_sel), dtype=torch.float32, device=self.device)
+            for smp, out in self._draws(step, tensors, B, n_samples, _noise):
+                if blk is None or blk.shape[0] < B[g]:
+                    blk = torch.empty((B[g], n_sel), dtype=torch.float32, device=self.device)
                 rows = self.module.expected_expression(out, g, genes=dev_sel, what=component, library_size=library_size, use_mean=use_mean, out=blk)
                 for k, src, dst in moves:
                     banks[k].index_copy_(0, dst + smp * len(pops[k]), rows.index_select(0, src))
@@ -428,25 +425,6 @@ class spVIPES:
             mid = de_median(bank1, bank2, t1, t2, eps=pseudocount)
             stats["lfc_median"] = 0.5 * (mid["mid_lo"].cpu().numpy().astype(np.float64) + mid["mid_hi"].cpu().numpy().astype(np.float64))
         return de_table(stats, len(r1), fdr_target)
-
-    def _differential_expression(self, group_indices_list, group, idx1, idx2, gene_list, component, library_size, n_samples, use_mean, n_pairs, delta,
-                                 pseudocount, fdr_target, max_cells, seed, batch_size, _noise, _pair_rows, lfc_median: bool):
-        import pandas as pd
-
-        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
-        n_pairs, delta, pseudocount, fdr_target, max_cells = check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells)
-        if group not in (0, 1):
-            raise ValueError(f"group must be 0 or 1, got {group!r}")
-        g = int(group)
-        _sel, dev_sel, n_sel, index = self._de_genes(g, gene_list)
-        pops = de_populations(group_indices_list[g], idx1, idx2, group=g)
-        pops = [de_subsample(p, max_cells, seed + 1 + k) for k, p in enumerate(pops)]
-        banks = self._de_banks(group_indices_list, g, pops, dev_sel, n_sel, component, library_size, n_samples, use_mean, batch_size, _noise)
-        if _pair_rows is None:
-            r1, r2 = de_pair_rows(banks[0].shape[0], banks[1].shape[0], n_pairs, seed)
-        else:
-            r1, r2 = (np.asarray(r).astype(np.int32) for r in _pair_rows)
-        return pd.DataFrame(self._de_compare(banks[0], banks[1], r1, r2, delta, pseudocount, fdr_target, lfc_median), index=index)
 
     @torch.no_grad()
     def differential_expression_by(self, group_indices_list: List[List[int]], group: int, groupby, labels=None, gene_list=None, component: str = "mixture",
@@ -469,36 +447,20 @@ class spVIPES:
         ``differential_expression_median(group_indices_list, group, idx1=<the label's cells in position order>, idx2=None,
         seed=seed + k, ...)`` bit for bit, which decodes the whole group again for every label.  The other arguments are
         ``differential_expression``'s."""
-        import pandas as pd
-
         _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
         n_pairs, delta, pseudocount, fdr_target, max_cells = check_de_args(n_pairs, delta, pseudocount, fdr_target, max_cells)
-        if group not in (0, 1):
-            raise ValueError(f"group must be 0 or 1, got {group!r}")
-        g = int(group)
+        g = check_group(group)
         cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
-        if isinstance(groupby, str):
-            if groupby not in self.adata.obs:
-                raise KeyError(f"groupby: adata.obs has no column {groupby!r}")
-            cell_labels = np.asarray(self.adata.obs[groupby])[cells]
-        else:
-            cell_labels = np.asarray(groupby).ravel()
-            if cell_labels.shape[0] != len(cells):
-                raise ValueError(f"groupby: an array must hold one label per cell of group_indices_list[{g}] ({len(cells)}), got {cell_labels.shape[0]}")
-        if len(np.unique(cells)) != len(cells):
-            raise ValueError(f"group_indices_list[{g}] lists a cell more than once")
+        cell_labels = group_cell_labels(self.adata.obs, groupby, cells, g, unique=True)
         names, compared, kept, places = de_label_populations(cell_labels, labels, max_cells, seed)
-        _sel, dev_sel, n_sel, index = self._de_genes(g, gene_list)
+        _sel, dev_sel, n_sel, index = self._genes(g, gene_list, own=True)
         bank, = self._de_banks(group_indices_list, g, [kept], dev_sel, n_sel, component, library_size, n_samples, use_mean, batch_size, _noise)
-        frames = []
+        tables = []
         for k in compared:
             p1, p2 = places[k]
             r1, r2 = de_pair_rows(len(p1) * n_samples, len(p2) * n_samples, n_pairs, seed + k)
-            table = self._de_compare(bank, bank, de_bank_rows(r1, p1, len(kept)), de_bank_rows(r2, p2, len(kept)), delta, pseudocount, fdr_target, bool(lfc_median))
-            df = pd.DataFrame(table, index=index)
-            df["comparison"], df["group1"], df["group2"] = f"{names[k]} vs Rest", names[k], "Rest"
-            frames.append(df)
-        return pd.concat(frames)
+            tables.append((names[k], self._de_compare(bank, bank, de_bank_rows(r1, p1, len(kept)), de_bank_rows(r2, p2, len(kept)), delta, pseudocount, fdr_target, bool(lfc_median))))
+        return vs_rest_frames(tables, index)
 
     @torch.no_grad()
     def count_statistics(self, group_indices_list: List[List[int]], group: int, idx1=None, idx2=None, groupby=None, labels=None, gene_list=None,
@@ -531,9 +493,7 @@ class spVIPES:
         target_sum = check_target_sum(target_sum)
         if (idx1 is None) == (groupby is None):
             raise ValueError("count_statistics: give exactly one of idx1 (two populations) and groupby (every label against the rest)")
-        if group not in (0, 1):
-            raise ValueError(f"group must be 0 or 1, got {group!r}")
-        g = int(group)
+        g = check_group(group)
         cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
         if groupby is None:
             if labels is not None:
@@ -543,32 +503,19 @@ class spVIPES:
         else:
             if idx2 is not None:
                 raise ValueError("count_statistics: idx2 goes with idx1")
-            if isinstance(groupby, str):
-                if groupby not in self.adata.obs:
-                    raise KeyError(f"groupby: adata.obs has no column {groupby!r}")
-                cell_labels = np.asarray(self.adata.obs[groupby])[cells]
-            else:
-                cell_labels = np.asarray(groupby).ravel()
-                if cell_labels.shape[0] != len(cells):
-                    raise ValueError(f"groupby: an array must hold one label per cell of group_indices_list[{g}] ({len(cells)}), got {cell_labels.shape[0]}")
-            if len(np.unique(cells)) != len(cells):
-                raise ValueError(f"group_indices_list[{g}] lists a cell more than once")
+            cell_labels = group_cell_labels(self.adata.obs, groupby, cells, g, unique=True)
             names, compared, _kept, _places = de_label_populations(cell_labels, labels, None, 0)
             code = np.unique(cell_labels, return_inverse=True)[1].ravel()
             order, sizes = np.argsort(code, kind="stable"), np.bincount(code, minlength=len(names)).tolist()
-        _sel, dev_sel, _n_sel, index = self._de_genes(g, gene_list)
+        _sel, dev_sel, _n_sel, index = self._genes(g, gene_list, own=True)
         rows = torch.as_tensor(self._local_rows(g, cells[order]).astype(np.int32), device=self.device)
         total = count_totals(self.counts[g]).index_select(0, rows.long())
         w = torch.where(total > 0, target_sum / total, torch.zeros_like(total))
         sums = count_stats(self.counts[g], rows, sizes, w=w, genes=dev_sel).cpu().numpy()
         if groupby is None:
             return pd.DataFrame(count_table(sums[0], sizes[0], sums[1], sizes[1]), index=index)
-        rest, n_all, frames = count_rest(sums), int(sum(sizes)), []
-        for k in compared:
-            df = pd.DataFrame(count_table(sums[k], sizes[k], rest[k], n_all - sizes[k]), index=index)
-            df["comparison"], df["group1"], df["group2"] = f"{names[k]} vs Rest", names[k], "Rest"
-            frames.append(df)
-        return pd.concat(frames)
+        rest, n_all = count_rest(sums), int(sum(sizes))
+        return vs_rest_frames(((names[k], count_table(sums[k], sizes[k], rest[k], n_all - sizes[k])) for k in compared), index)
 
     @torch.no_grad()
     def posterior_predictive_check(self, group_indices_list: List[List[int]], group: int, n_samples: int = 25, groupby=None, labels=None,
@@ -601,86 +548,44 @@ class spVIPES:
         The sampled columns are exact: integer sums, divided once (``data.ppc_table``, which also states the overflow rule for the
         sum of squares).  The observed second moment is one chunked pass over the resident counts (``count_ops.count_square_sums``).
         Dense and CSR ``counts_storage`` give the same frame.  ``_noise`` (tests only): as ``posterior_predictive_sample`` takes it."""
-        import pandas as pd
-
         from .count_ops import count_square_sums, count_stats, count_totals
-        from .data import check_ppc_library, ppc_segments, ppc_table
         from .dec_ops import sample_key
 
         library_size = check_ppc_library(library_size)
         observed = isinstance(library_size, str) and library_size == "observed"
         n_samples, seed, _log_l = check_sample_args(n_samples, seed, "latent" if observed else library_size)
-        if group not in (0, 1):
-            raise ValueError(f"group must be 0 or 1, got {group!r}")
-        g = int(group)
+        g = check_group(group)
         cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
         n_g = len(cells)
-        if groupby is None:
-            cell_labels = None
-        elif isinstance(groupby, str):
-            if groupby not in self.adata.obs:
-                raise KeyError(f"groupby: adata.obs has no column {groupby!r}")
-            cell_labels = np.asarray(self.adata.obs[groupby])[cells]
-        else:
-            cell_labels = np.asarray(groupby).ravel()
-            if cell_labels.shape[0] != n_g:
-                raise ValueError(f"groupby: an array must hold one label per cell of group_indices_list[{g}] ({n_g}), got {cell_labels.shape[0]}")
+        cell_labels = None if groupby is None else group_cell_labels(self.adata.obs, groupby, cells, g)
         names, sizes, code = ppc_segments(cell_labels, labels, n_cells=n_g)
         n_seg = len(names)
-        _sel, dev_sel, n_sel, index = self._de_genes(g, gene_list)
+        _sel, dev_sel, n_sel, index = self._genes(g, gene_list, own=True)
         obs_ids = torch.as_tensor(np.asarray(self.obs_idx[g]), dtype=torch.int32, device=self.device)
         key = sample_key(seed)
         stats = torch.zeros((n_seg, 4, n_sel), dtype=torch.int64, device=self.device)   # (uint64 bits)
         totals = torch.zeros((n_g + (batch_size or 128),), dtype=torch.int64, device=self.device)   # walk positions; the tail is never counted
         obs_all = count_totals(self.counts[g]) if observed else None
-        off = 0
-        for step, tensors, B in self._eval_minibatches(group_indices_list, batch_size, None):
-            Bg = B[g]
-            cpos = off + np.arange(Bg)
-            off += Bg
-            seg = ppc_segments(cell_labels, labels, n_cells=n_g, positions=cpos)[2]
+        for step, tensors, B, off, pos in walk_positions(self._eval_minibatches(group_indices_list, batch_size, None), g, n_g):
+            seg = np.where(pos >= 0, code[pos], -1)   # a cut row (pos -1) is in no population
             if not (seg >= 0).any():
                 continue   # nothing of this step is counted (eval mode: steps are independent of each other)
             rows = tensors[g]["rows"].long()
             ids = obs_ids[rows].contiguous()
             seg_d = torch.as_tensor(seg, dtype=torch.int32, device=self.device)
             lib = torch.log(obs_all.index_select(0, rows)).to(torch.float32).contiguous() if observed else None
-            for smp in range(n_samples):
-                out = self._infer(tensors, _noise, step * n_samples + smp, B[0], B[1])
+            for smp, out in self._draws(step, tensors, B, n_samples, _noise):
                 self.module.sample_count_stats(out, g, genes=dev_sel, library_size="latent" if observed else library_size, library=lib, key=key,
-                                               sample=smp, cell_ids=ids, seg=seg_d, n_seg=n_seg, stats=stats, cell_total=totals[off - Bg:off])
-        table = stats.cpu().numpy().view(np.uint64)
-        ppc = ppc_table(table, [sizes[k] * n_samples for k in range(n_seg)], prefix="ppc_")
+                                               sample=smp, cell_ids=ids, seg=seg_d, n_seg=n_seg, stats=stats, cell_total=totals[off:off + B[g]])
+        ppc = ppc_table(stats.cpu().numpy().view(np.uint64), [sizes[k] * n_samples for k in range(n_seg)], prefix="ppc_")
         # the observed side: the populations' cells sorted by population, one segmented reduction + one chunked pass for the squares
         kept = np.nonzero(code >= 0)[0]
         order = kept[np.argsort(code[kept], kind="stable")]
         rows = torch.as_tensor(self._local_rows(g, cells[order]).astype(np.int32), device=self.device)
         sums = count_stats(self.counts[g], rows, sizes, genes=dev_sel).cpu().numpy()
         sq, tot = count_square_sums(self.counts[g], rows, sizes, genes=dev_sel, row_totals=True)
-        sq = sq.cpu().numpy()
-        if sq.dtype == np.int64 or (np.all(sums[:, :2] == np.floor(sums[:, :2])) and np.all(sq == np.floor(sq)) and (sq.size == 0 or sq.max() < 2.0 ** 53)):
-            exact = np.zeros((n_seg, 4, n_sel), dtype=np.uint64)   # whole numbers below 2^53: the exact route (no modular sum here: max row 0)
-            exact[:, 0], exact[:, 1], exact[:, 2] = sums[:, 0].astype(np.uint64), sums[:, 1].astype(np.uint64), sq.astype(np.uint64)
-            obs = ppc_table(exact, sizes, prefix="obs_")
-        else:   # fractional fp32 counts: fp64 throughout
-            N = np.asarray(sizes, dtype=np.float64)[:, None]
-            with np.errstate(divide="ignore", invalid="ignore"):
-                mean = np.where(N > 0, sums[:, 0] / N, np.nan)
-                var = np.where(N > 1, (N * sq - sums[:, 0] ** 2) / (N * (N - 1)), np.nan)
-                obs = pd.DataFrame({"obs_mean": mean.ravel(), "obs_var": var.ravel(),
-                                    "obs_cv": np.where(mean > 0, np.sqrt(var) / mean, np.nan).ravel(),
-                                    "obs_zero_fraction": np.where(N > 0, (N - sums[:, 1]) / N, np.nan).ravel()})
-        frame = pd.DataFrame({"population": np.repeat(np.asarray(names, dtype=object), n_sel), "gene": np.tile(np.asarray(index), n_seg),
-                              "n_cells": np.repeat(np.asarray(sizes, dtype=np.int64), n_sel), "n_samples": n_samples})
-        for c in ("obs_mean", "obs_var", "obs_cv", "obs_zero_fraction"):
-            frame[c] = obs[c].to_numpy()
-        for c in ("ppc_mean", "ppc_var", "ppc_cv", "ppc_zero_fraction", "ppc_max"):
-            frame[c] = ppc[c].to_numpy()
-        obs_total, ppc_total = np.full(n_g, np.nan), np.full(n_g, np.nan)
-        obs_total[order] = tot.cpu().numpy()
-        ppc_total[kept] = totals[:n_g].cpu().numpy().view(np.uint64)[kept].astype(np.float64) / n_samples
-        frame.attrs["cell_totals"] = pd.DataFrame({"obs_total": obs_total, "ppc_total_mean": ppc_total}, index=cells)
-        return frame
+        obs = ppc_observed_columns(sums, sq.cpu().numpy(), sizes)
+        return ppc_frame(names, sizes, index, obs, ppc, n_samples, cells, order, kept, tot.cpu().numpy(), totals[:n_g].cpu().numpy().view(np.uint64))
 
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}

@@ -716,6 +716,13 @@ class spVIPESmodule(nn.Module):
         pl, ql = (ps["logtheta_loc"], qs["logtheta_loc"]) if use_mean else (ps["log_z"], qs["logtheta_log_z"])
         return (*self._decoder_operands(group, pl.detach(), ql.detach()), inference_outputs["library"][group].detach())
 
+    def _readout(self, op: str, inference_outputs, group: int, use_mean: bool, **kw):
+        """dec_ops' read-out function ``op`` on one group of ``inference_outputs``: its operands, the module's mode and the group's workspace, then ``kw``"""
+        from . import dec_ops
+
+        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
+        return getattr(dec_ops, op)(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit, self._workspace(group, lib.device), par=par, **kw)
+
     @torch.no_grad()
     def expected_expression(self, inference_outputs, group: int, *, genes=None, what="mixture", library_size="latent", use_mean: bool = False,
                             out=None, alpha: float = 1.0, accumulate: bool = False) -> torch.Tensor:
@@ -728,12 +735,8 @@ class spVIPESmodule(nn.Module):
         encoder's library) or a positive number.  Honours ``self.training`` as ``generative`` does: batch statistics in training mode
         without touching the running statistics, running statistics in eval mode.  ``out`` / ``alpha`` / ``accumulate``:
         dec_ops.expected_expression (one fused HIP kernel, spv_dec_expected; no [B, G] intermediate is written)."""
-        from .dec_ops import expected_expression
-
-        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
-        return expected_expression(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
-                                   self._workspace(group, lib.device), par=par, genes=genes, what=what, library_size=library_size,
-                                   out=out, alpha=alpha, accumulate=accumulate)
+        return self._readout("expected_expression", inference_outputs, group, use_mean, genes=genes, what=what, library_size=library_size,
+                             out=out, alpha=alpha, accumulate=accumulate)
 
     @torch.no_grad()
     def sample_counts(self, inference_outputs, group: int, *, genes=None, library_size="latent", use_mean: bool = False, key: int = 0,
@@ -745,11 +748,7 @@ class spVIPESmodule(nn.Module):
         latents or, with ``use_mean``, the posterior means; ``genes`` / ``library_size`` and the handling of ``self.training`` are
         ``expected_expression``'s.  ``key`` / ``sample`` / ``cell_ids`` / ``out``: dec_ops.sample_counts (one fused HIP kernel,
         spv_dec_sample; neither the rates nor the logits are written anywhere)."""
-        from .dec_ops import sample_counts
-
-        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
-        return sample_counts(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
-                             self._workspace(group, lib.device), par=par, genes=genes, library_size=library_size, key=key, sample=sample,
+        return self._readout("sample_counts", inference_outputs, group, use_mean, genes=genes, library_size=library_size, key=key, sample=sample,
                              cell_ids=cell_ids, out=out)
 
     @torch.no_grad()
@@ -761,12 +760,8 @@ class spVIPESmodule(nn.Module):
         bit to reducing what ``sample_counts`` returns for the same arguments.  ``library``: a per-cell fp32 device vector of LOG
         library sizes that wins over ``library_size``.  ``seg`` / ``n_seg`` / ``stats`` / ``cell_total``: dec_ops.sample_count_stats
         (one fused HIP kernel, spv_dec_sample_stats; no [B, n_genes] array is written)."""
-        from .dec_ops import sample_count_stats
-
-        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
-        return sample_count_stats(self.decoders[group], self.px_r[group], first, second, lib, self.training, self.nsplit,
-                                  self._workspace(group, lib.device), par=par, genes=genes, library_size=library_size, log_library=library,
-                                  key=key, sample=sample, cell_ids=cell_ids, seg=seg, n_seg=n_seg, stats=stats, cell_total=cell_total)
+        return self._readout("sample_count_stats", inference_outputs, group, use_mean, genes=genes, library_size=library_size, log_library=library,
+                             key=key, sample=sample, cell_ids=cell_ids, seg=seg, n_seg=n_seg, stats=stats, cell_total=cell_total)
 
     def loss(self, tensors_by_group, inference_outputs, generative_outputs, kl_weight: float = 1.0):
         """spVIPESmodule.py:809-899."""
