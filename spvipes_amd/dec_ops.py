@@ -20,7 +20,7 @@ import torch
 from . import _abi
 from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecSampleArgs, SpvDecSampleStatsArgs, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
                    ptr, round_up, stream_ptr)
-from .nn_ops import _add_lin, _fptr, _lin_batch, _linear_bwd, _reduce_pending, _wgrad, grad_out
+from .nn_ops import _add_lin, _first_ws, _fptr, _lin_batch, _linear_bwd, _reduce_pending, _wgrad, grad_out
 from . import ops as _ops
 from .ops import N_HIDDEN_MIX, GroupCounts, Workspace, _bf16_image, _gemm_slabs, _gene_splits, _nb_cell_tiles, _nb_splits, _pack, fork, group_streams, join
 
@@ -66,15 +66,134 @@ def _add_red(b: SpvReduceBatch, src: torch.Tensor, nslabs: int, slab_stride: int
     b.nprob += 1
 
 
-def _add_wide_bc(red: SpvReduceBatch, slabs, nslabs: int, G: int, dWp: torch.Tensor, dWs: torch.Tensor, sl, alpha) -> None:
-    """wide layout: the 32-column slabs of d [W'_p | c_p] and d [W'_s | c_s] (_DecoderBwd.gemm_bc) into dWp [G][KP] / dWs [G][KS]"""
-    for slab, n, hd, c0 in slabs:
-        _add_red(red, slab, nslabs, G * n, n, G, n, (dWp, dWs)[hd], (sl.KP, sl.KS)[hd], dst_col=c0, alpha=alpha)
+def _add_heads_red(red: SpvReduceBatch, st: "_DecoderBwd", slabs, dWp: torch.Tensor, dWs: torch.Tensor, sl, alpha) -> None:
+    """one group's regressor weight-gradient slabs d [W'_p | c_p], d [W'_s | c_s] (``st.gemm_bc()``) into dWp [G][KP] / dWs [G][KS]"""
+    G, KP, KS, KPS = st.G, sl.KP, sl.KS, sl.KPS
+    if sl.kslots:   # wide: [(slab, columns, head, first column of the head)] of 32-column problems
+        for slab, n, hd, c0 in slabs:
+            _add_red(red, slab, st.csp_n, G * n, n, G, n, (dWp, dWs)[hd], (KP, KS)[hd], dst_col=c0, alpha=alpha)
+    elif st.fused_heads:   # spv_dec_heads_bwd's slabs: [Gp][48] for both heads, private columns first
+        _add_red(red, slabs[0], st.csp_n, st.Gp * KPS, KPS, G, KP, dWp, KP, alpha=alpha)
+        _add_red(red, slabs[1], st.csp_n, st.Gp * KPS, KPS, G, KS, dWs, KS, col_off=KP, alpha=alpha)
+    else:   # the GEMM slabs [G][16] / [G][32]
+        _add_red(red, slabs[0], st.csp_n, G * KP, KP, G, KP, dWp, KP, alpha=alpha)
+        _add_red(red, slabs[1], st.csp_n, G * KS, KS, G, KS, dWs, KS, alpha=alpha)
 
 
 def _run_red(b: SpvReduceBatch) -> None:
     if b.nprob:
         _abi.call("spv_reduce_slabs", C.byref(b), stream_ptr())
+
+
+# ---- one function per argument block: every site that launches with a block gets it from here and sets no field of it itself ----
+def _check_latent_sizes(sl, n_p: int, n_s: int, n_m: int) -> None:
+    if n_p + 1 > sl.KP or n_s + 1 > sl.KS:
+        raise _abi.SpvError(f"decoder kernels support n_private <= {sl.KP - 1} and n_shared <= {sl.KS - 1}")
+    if n_m + n_p + n_s + 1 > KMP:
+        raise _abi.SpvError("mixture input wider than 320 columns is not supported")
+
+
+def _zsplit_args(B: int, Bp: int, n_p: int, n_s: int, n_m: int, sl, lat, zcat, Am_img=None, Aps_img=None) -> SpvZsplitArgs:
+    """spv_zsplit_fwd's block: per group ``lat`` = (private, poe) latents (contiguous fp32: the caller holds them) into ``zcat``; with the
+    (hi, lo) operand images given, the same launch packs them"""
+    za = SpvZsplitArgs()
+    za.B, za.n_p, za.n_s, za.ngroups, za.kslots = B, n_p, n_s, len(lat), sl.kslots
+    za.ld_am, za.am_col, za.am_cols, za.Bp = KMP, n_m, KMP - n_m, Bp
+    for g, (pz, qz) in enumerate(lat):
+        za.priv[g], za.poe[g], za.zcat[g] = ptr(pz), ptr(qz), ptr(zcat[g])
+        if Am_img is not None:
+            za.am_hi[g], za.am_lo[g], za.aps_hi[g], za.aps_lo[g] = ptr(Am_img[g][0]), ptr(Am_img[g][1]), ptr(Aps_img[g][0]), ptr(Aps_img[g][1])
+    return za
+
+
+def _zstats_batch(B: int, n_p: int, n_s: int, zcat, zsum, zz, trunk=None):
+    """the z statistics of the BatchNorm fold as spv_linear_wgrad problems: per group the column sums ``zsum[g][k]`` and z^T z ``zz[g][k]`` of
+    the private / shared columns of ``zcat[g]``; ``trunk`` = (zsum_t, zz_t): also those of all its columns (spv_trunk_fold_fwd)"""
+    nt = n_p + n_s
+    b = _lin_batch(B)
+    for g, z in enumerate(zcat):
+        for k, (off, n) in enumerate(((0, n_p), (n_p, n_s))):
+            _add_lin(b, N=n, K=n, W=ptr(zz[g][k]), X=_fptr(z, off), ldx=nt, dY=_fptr(z, off), lddy=nt, dW=ptr(zz[g][k]), db=ptr(zsum[g][k]))
+        if trunk is not None:
+            _add_lin(b, N=nt, K=nt, W=ptr(trunk[1][g]), X=ptr(z), ldx=nt, dY=ptr(z), lddy=nt, dW=ptr(trunk[1][g]), db=ptr(trunk[0][g]))
+    return b
+
+
+def _fold_batch(B: int, training: bool, momentum: float, sl) -> SpvFoldBatch:
+    fb = SpvFoldBatch()
+    fb.nprob, fb.B, fb.training, fb.eps, fb.momentum, fb.kslots = 0, B, int(training), 1e-3, momentum, sl.kslots
+    return fb
+
+
+def _add_fold(fb: SpvFoldBatch, decoder, par, n_p: int, n_s: int, zcat, zsum, zz, fstat, Wps, G: int, Gp: int, sl) -> None:
+    """the two regressors of one decoder as problems of spv_bn_fold_fwd: private into columns 0.. of the (hi, lo) image ``Wps``, shared into KP.."""
+    for k, (reg, W, gam, bet, off, slot, n, zoff) in enumerate(((decoder.factor_regressor_private, par[0], par[1], par[2], 0, sl.KP, n_p, 0),
+                                                                (decoder.factor_regressor_shared, par[3], par[4], par[5], sl.KP, sl.KS, n_s, n_p))):
+        q = fb.p[fb.nprob]
+        q.W, q.gamma, q.beta, q.running_mean, q.running_var = ptr(W), ptr(gam), ptr(bet), ptr(reg.bn.running_mean), ptr(reg.bn.running_var)
+        q.zsum, q.zz, q.z, q.ldz, q.stat = ptr(zsum[k]), ptr(zz[k]), _fptr(zcat, zoff), n_p + n_s, ptr(fstat[k])
+        q.img_hi, q.img_lo, q.ld_img, q.col_off, q.slot = ptr(Wps[0]), ptr(Wps[1]), sl.KPS, off, slot
+        q.G, q.Gp, q.K = G, Gp, n
+        fb.nprob += 1
+
+
+def _trunk_bn_batch(B: int, training: bool, momentum: float, decoders, par, pre_a, m, tstat, parts, n_m: int, Am_img=None, Bp: int = 0,
+                    grads=None) -> SpvBnBatch:
+    """the mixing trunks' BatchNorm + rectifier (spv_bn_fwd / spv_bn_bwd), one problem per decoder.  ``Am_img``: per group the (hi, lo) logits
+    operand image m is also written into; ``grads`` = (dY, dX, dgamma, dbeta) per-group lists: the backward's fields"""
+    bn = SpvBnBatch()
+    bn.nprob, bn.B, bn.training, bn.relu, bn.eps, bn.momentum = len(decoders), B, int(training), 1, 1e-3, momentum
+    for g, dec in enumerate(decoders):
+        tb = dec.sigmoid_decoder.bn
+        q = bn.p[g]
+        q.X, q.ldx, q.Y, q.ldy, q.gamma, q.beta = ptr(pre_a[g]), n_m, ptr(m[g]), n_m, ptr(par[g][8]), ptr(par[g][9])
+        q.running_mean, q.running_var, q.stats, q.N = ptr(tb.running_mean), ptr(tb.running_var), ptr(tstat[g]), n_m
+        q.part = ptr(parts[g])
+        if Am_img is not None:  # m straight into the logits operand image
+            q.img_hi, q.img_lo, q.ld_img, q.img_rows = ptr(Am_img[g][0]), ptr(Am_img[g][1]), KMP, Bp
+        if grads is not None:
+            q.dY, q.lddy, q.dX, q.lddx, q.dgamma, q.dbeta = ptr(grads[0][g]), n_m, ptr(grads[1][g]), n_m, ptr(grads[2][g]), ptr(grads[3][g])
+    return bn
+
+
+def _trunk_batch(B: int, training: bool, decoders, Wa, par, zsum_t, zz_t, Wf, cf, tstat, n_m: int, nt: int, bwd=None) -> SpvTrunkBatch:
+    """spv_trunk_fold_fwd's block, one problem per decoder (``Wa``: its contiguous trunk weights, held by the caller); ``bwd``: per group
+    (dWf, dcf, dW, dbias, dgamma, dbeta, dred, z, dz), the further fields of spv_trunk_fold_bwd"""
+    tb_ = SpvTrunkBatch()
+    tb_.nprob, tb_.B, tb_.training, tb_.eps, tb_.momentum = len(decoders), B, int(training), 1e-3, 0.01
+    for g, dec in enumerate(decoders):
+        bnm = dec.sigmoid_decoder.bn
+        q = tb_.p[g]
+        q.W, q.bias, q.gamma, q.beta = ptr(Wa[g]), ptr(par[g][7]), ptr(par[g][8]), ptr(par[g][9])
+        q.running_mean, q.running_var = ptr(bnm.running_mean), ptr(bnm.running_var)
+        q.zsum, q.zz, q.Wf, q.cf, q.stat, q.N, q.K = ptr(zsum_t[g]), ptr(zz_t[g]), ptr(Wf[g]), ptr(cf[g]), ptr(tstat[g]), n_m, nt
+        if bwd is not None:
+            q.dWf, q.dcf, q.dW, q.dbias, q.dgamma, q.dbeta, q.dred, q.z, q.dz = (ptr(t) for t in bwd[g])
+            q.ldz, q.lddz = nt, nt
+    return tb_
+
+
+def _dec_params(wsg: Workspace, pre: str, B: int, G: int, Bp: int, Gp: int, mlo: bool, sl, logits, Wps, Aps, *, cst=None, tabs=(None, None),
+                w_row=None, nb=None, grads=None, grads_f32: bool = False) -> SpvDecParams:
+    """one group's spv_dec_params over the workspace arrays named ``pre`` + ...; the read-outs pass none of ``cst`` (the counts), ``tabs``
+    (gene_tab, cnt_tab), ``w_row``, ``nb`` = (nb_splits, nb_genes_per_split, nb_cell_tiles: the likelihood kernel's partial rows) and
+    ``grads`` = (dtheta_part, dL, tP, tS)"""
+    splits, per = _gene_splits(Bp, Gp)
+    nbs, nbper, nbtiles = nb if nb is not None else (1, 32, 0)
+    vec = lambda nme: ptr(wsg.get(pre + nme, (Bp,), torch.float32))
+    part = lambda nme: ptr(wsg.get(pre + nme, (splits, Bp), torch.float32))
+    nbpart = lambda nme: ptr(wsg.get(pre + nme, (nbs, Bp), torch.float32)) if nb is not None else None
+    dth, dL, tP, tS = grads if grads is not None else (None,) * 4
+    counts = dict(X=cst.X, ldx=cst.ld, rows=cst.rows, col_off=cst.col_off, count_is_u16=int(cst.dtype == _abi.SPV_COUNT_U16)) if cst is not None else {}
+    return SpvDecParams(
+        B=B, G=G, Bp=Bp, Gp=Gp, logits=ptr(logits), n_gene_tiles=Gp // 32, logits_f32=int(mlo),
+        Wps_hi=ptr(Wps[0]), Wps_lo=ptr(Wps[1]), Aps_hi=ptr(Aps[0]), Aps_lo=ptr(Aps[1]), gene_tab=ptr(tabs[0]), cnt_tab=ptr(tabs[1]),
+        lse_p=vec("lse_p"), lse_s=vec("lse_s"), a_p=vec("a_p"), a_s=vec("a_s"), w_row=ptr(w_row), gene_splits=splits, genes_per_split=per,
+        part_max_p=part("pmp"), part_sum_p=part("psp"), part_max_s=part("pms"), part_sum_s=part("pss"),
+        rec_part=nbpart("rec"), tp_part=nbpart("tp"), ts_part=nbpart("ts"),
+        dtheta_part=ptr(dth), dL=ptr(dL), tP=ptr(tP), tS=ptr(tS), grads_f32=int(grads_f32), nb_splits=nbs, nb_genes_per_split=nbper,
+        nb_cell_tiles=nbtiles, kslots=sl.kslots, **counts,
+    )
 
 
 class _DecoderBwd:
@@ -259,12 +378,9 @@ class DecoderFused(torch.autograd.Function):
         DEC_KP, DEC_KS, DEC_KPS = sl.KP, sl.KS, sl.KPS
         if any(dec_slots(d) != sl for d in decoders):
             raise _abi.SpvError("DecoderFused: the decoders of one call must share their operand layout")
-        if n_p + 1 > DEC_KP or n_s + 1 > DEC_KS:
-            raise _abi.SpvError(f"decoder kernels support n_private <= {DEC_KP - 1} and n_shared <= {DEC_KS - 1}")
         n_m = par[0][6].shape[0]
         KM = n_m + nt + 1
-        if KM > KMP:
-            raise _abi.SpvError("mixture input wider than 320 columns is not supported")
+        _check_latent_sizes(sl, n_p, n_s, n_m)
         need_grad = any(ctx.needs_input_grad)  # (grad mode is off inside Function.forward)
         Bp = round_up(B, DEC_CELLS_PER_WG)
         Gs = [c.G for c in counts]
@@ -273,20 +389,13 @@ class DecoderFused(torch.autograd.Function):
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         # ---- 1. latent slicing: zcat = [z_private | z_shared] --------------------------------------
         zcat = [new(B, nt) for _ in range(NG)]
-        za = SpvZsplitArgs()
-        za.B, za.n_p, za.n_s, za.ngroups, za.kslots = B, n_p, n_s, NG, sl.kslots
-        keep = []
         # ... and, from the same call, the decoder's packed bf16 operand images of these latents
         Am_img = [_bf16_image(ws[g], "dec_Am", Bp, KMP, mlo) for g in range(NG)]
         Aps_img = [_bf16_image(ws[g], "dec_Aps", Bp, DEC_KPS, True) for g in range(NG)]
         fused_pack = bool(_ops.FUSED_PACK)
-        za.ld_am, za.am_col, za.am_cols, za.Bp = KMP, n_m, KMP - n_m, Bp
-        for g in range(NG):
-            pz, qz = _cont(lat[g][0]), _cont(lat[g][1])
-            keep += [pz, qz]
-            za.priv[g], za.poe[g], za.zcat[g] = ptr(pz), ptr(qz), ptr(zcat[g])
-            if fused_pack:
-                za.am_hi[g], za.am_lo[g], za.aps_hi[g], za.aps_lo[g] = ptr(Am_img[g][0]), ptr(Am_img[g][1]), ptr(Aps_img[g][0]), ptr(Aps_img[g][1])
+        lat = [(_cont(pz), _cont(qz)) for pz, qz in lat]
+        keep = [t for pq in lat for t in pq]
+        za = _zsplit_args(B, Bp, n_p, n_s, n_m, sl, lat, zcat, *((Am_img, Aps_img) if fused_pack else ()))
         _abi.call("spv_zsplit_fwd", C.byref(za), stream_ptr())
         # ---- 2. batch statistics of z (column sums and z^T z) for the BatchNorm fold ---------------
         zsum = [[new(n_p), new(n_s)] for _ in range(NG)]
@@ -296,28 +405,13 @@ class DecoderFused(torch.autograd.Function):
         zsum_t = [new(nt) for _ in range(NG)] if trunk_fold else None
         zz_t = [new(nt, nt) for _ in range(NG)] if trunk_fold else None
         if training:
-            b = _lin_batch(B)
-            for g in range(NG):
-                for k, (off, n) in enumerate(((0, n_p), (n_p, n_s))):
-                    _add_lin(b, N=n, K=n, W=ptr(zz[g][k]), X=_fptr(zcat[g], off), ldx=nt, dY=_fptr(zcat[g], off), lddy=nt, dW=ptr(zz[g][k]), db=ptr(zsum[g][k]))
-                if trunk_fold:
-                    _add_lin(b, N=nt, K=nt, W=ptr(zz_t[g]), X=ptr(zcat[g]), ldx=nt, dY=ptr(zcat[g]), lddy=nt, dW=ptr(zz_t[g]), db=ptr(zsum_t[g]))
-            _wgrad(b, ws if not isinstance(ws, (list, tuple)) else ws[0])
+            _wgrad(_zstats_batch(B, n_p, n_s, zcat, zsum, zz, (zsum_t, zz_t) if trunk_fold else None), _first_ws(ws))
         # ---- 3. fold the regressors' BatchNorm into the packed [Gp][48] operand image ---------------
         Wps = [_bf16_image(ws[g], "dec_Wps", Gps[g], DEC_KPS, True) for g in range(NG)]
         fstat = [[new(Gs[g], 2), new(Gs[g], 2)] for g in range(NG)]
-        fb = SpvFoldBatch()
-        fb.nprob, fb.B, fb.training, fb.eps, fb.momentum, fb.kslots = 0, B, int(training), 1e-3, 0.01, sl.kslots
+        fb = _fold_batch(B, training, 0.01, sl)
         for g in range(NG):
-            fp, fs = decoders[g].factor_regressor_private, decoders[g].factor_regressor_shared
-            for k, (reg, W, gam, bet, off, slot, n, zoff) in enumerate(((fp, par[g][0], par[g][1], par[g][2], 0, DEC_KP, n_p, 0),
-                                                                        (fs, par[g][3], par[g][4], par[g][5], DEC_KP, DEC_KS, n_s, n_p))):
-                q = fb.p[fb.nprob]
-                q.W, q.gamma, q.beta, q.running_mean, q.running_var = ptr(W), ptr(gam), ptr(bet), ptr(reg.bn.running_mean), ptr(reg.bn.running_var)
-                q.zsum, q.zz, q.z, q.ldz, q.stat = ptr(zsum[g][k]), ptr(zz[g][k]), _fptr(zcat[g], zoff), nt, ptr(fstat[g][k])
-                q.img_hi, q.img_lo, q.ld_img, q.col_off, q.slot = ptr(Wps[g][0]), ptr(Wps[g][1]), DEC_KPS, off, slot
-                q.G, q.Gp, q.K = Gs[g], Gps[g], n
-                fb.nprob += 1
+            _add_fold(fb, decoders[g], par[g], n_p, n_s, zcat[g], zsum[g], zz[g], fstat[g], Wps[g], Gs[g], Gps[g], sl)
         pair = _ops.dec_pair_for(B, NG)   # both groups' per-group launches as one grid per kernel (ops.DEC_PAIR)
         # The fold, the mixture-weight images and the (count, gene) tables depend on nothing the trunk (step 4) computes:
         # they run beside it on a side stream and are joined before the per-group section.
@@ -347,18 +441,13 @@ class DecoderFused(torch.autograd.Function):
         m = [new(B, n_m) for _ in range(NG)]
         tstat = [new(n_m, 2) for _ in range(NG)]
         Wf = cf = pre_a = None
+        decs = [decoders[g] for g in range(NG)]
         if trunk_fold:
             # the BatchNorm folded into the layer (batch mean / variance of a linear map of z from zbar and cov(z)): one affine map + rectifier,
             # written by spv_linear_fwd straight into m AND into the logits operand image -- no statistics / finalise / normalise launches
             Wf, cf = [new(n_m, nt) for _ in range(NG)], [new(n_m) for _ in range(NG)]
-            tb_ = SpvTrunkBatch()
-            tb_.nprob, tb_.B, tb_.training, tb_.eps, tb_.momentum = NG, B, int(training), 1e-3, 0.01
-            for g in range(NG):
-                bnm = decoders[g].sigmoid_decoder.bn
-                q = tb_.p[g]
-                q.W, q.bias, q.gamma, q.beta = ptr(_cont(par[g][6])), ptr(par[g][7]), ptr(par[g][8]), ptr(par[g][9])
-                q.running_mean, q.running_var = ptr(bnm.running_mean), ptr(bnm.running_var)
-                q.zsum, q.zz, q.Wf, q.cf, q.stat, q.N, q.K = ptr(zsum_t[g]), ptr(zz_t[g]), ptr(Wf[g]), ptr(cf[g]), ptr(tstat[g]), n_m, nt
+            wa_c = [_cont(par[g][6]) for g in range(NG)]
+            tb_ = _trunk_batch(B, training, decs, wa_c, par, zsum_t, zz_t, Wf, cf, tstat, n_m, nt)
             _abi.call("spv_trunk_fold_fwd", C.byref(tb_), stream_ptr())
             b = _lin_batch(B, relu=True)
             for g in range(NG):
@@ -374,16 +463,8 @@ class DecoderFused(torch.autograd.Function):
                 _add_lin(b, N=n_m, K=nt, W=ptr(par[g][6]), bias=ptr(par[g][7]), X=ptr(zcat[g]), ldx=nt, Y=ptr(pre_a[g]), ldy=n_m)
             _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
             nblk = -(-B // _abi.BN_ROWS)
-            bn = SpvBnBatch()
-            bn.nprob, bn.B, bn.training, bn.relu, bn.eps, bn.momentum = NG, B, int(training), 1, 1e-3, 0.01
-            for g in range(NG):
-                tb = decoders[g].sigmoid_decoder.bn
-                q = bn.p[g]
-                q.X, q.ldx, q.Y, q.ldy, q.gamma, q.beta = ptr(pre_a[g]), n_m, ptr(m[g]), n_m, ptr(par[g][8]), ptr(par[g][9])
-                q.running_mean, q.running_var, q.stats, q.N = ptr(tb.running_mean), ptr(tb.running_var), ptr(tstat[g]), n_m
-                q.part = ptr(ws[g].get("trunk_bn_part", (nblk, n_m, 2), torch.float32))
-                if fused_pack:  # m straight into the logits operand image
-                    q.img_hi, q.img_lo, q.ld_img, q.img_rows = ptr(Am_img[g][0]), ptr(Am_img[g][1]), KMP, Bp
+            parts = [ws[g].get("trunk_bn_part", (nblk, n_m, 2), torch.float32) for g in range(NG)]
+            bn = _trunk_bn_batch(B, training, 0.01, decs, par, pre_a, m, tstat, parts, n_m, Am_img if fused_pack else None, Bp)
             _abi.call("spv_bn_fwd", C.byref(bn), stream_ptr())
         # ---- 5. per group: operand images, tables, logits GEMM, softmax statistics, likelihood ------
         if w_pad.numel() < Bp or w_pad.dtype != torch.float32 or not w_pad.is_contiguous():
@@ -405,7 +486,7 @@ class DecoderFused(torch.autograd.Function):
         for g in range(NG):
           with torch.cuda.stream(streams[g]):
               G, Gp, wsg = Gs[g], Gps[g], ws[g]
-              (Wm_hi, Wm_lo), (gene_tab, cnt_tab) = Wm_img[g], tabs[g]
+              Wm_hi, Wm_lo = Wm_img[g]
               (Am_hi, Am_lo), (Aps_hi, Aps_lo) = Am_img[g], Aps_img[g]
               if not fused_pack:
                   _pack(m[g], Am_hi, Am_lo, dst_col_off=0, cslot=n_m)
@@ -414,12 +495,10 @@ class DecoderFused(torch.autograd.Function):
                   _pack(zcat[g][:, n_p:], Aps_hi, Aps_lo, extra_one=True, dst_col_off=DEC_KP, cslot=DEC_KS)
               logits = wsg.get("dec_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
               lse_first = bool(_ops.STAGGER and g % 2 == 1)  # group 1 runs its (VALU-bound) softmax statistics beside group 0's logits GEMM
+              run_logits = lambda: _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(logits), int(mlo), stream_ptr())
               if not lse_first and not pair:
-                  _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(logits), int(mlo), stream_ptr())
-              splits, per = _gene_splits(Bp, Gp)
+                  run_logits()
               nbs, nbper = _nb_splits(Gp, Bp)
-              vec = lambda nme: wsg.get(nme, (Bp,), torch.float32)
-              part = lambda nme: wsg.get(nme, (splits, Bp), torch.float32)
               nbpart = lambda nme: wsg.get(nme, (nbs, Bp), torch.float32)
               if need_grad:
                   dL = wsg.get("dec_dL_" + gname, (gplanes * Bp, Gp), gdt, zero=True)
@@ -429,19 +508,8 @@ class DecoderFused(torch.autograd.Function):
                   Tp, Ts = wsg.get("dec_Tp", (Bp,), torch.float32), wsg.get("dec_Ts", (Bp,), torch.float32)
               else:
                   dL = tP = tS = dth = Tp = Ts = None
-              lse_p, lse_s, a_p, a_s = vec("dec_lse_p"), vec("dec_lse_s"), vec("dec_a_p"), vec("dec_a_s")
-              cst = counts[g].c_struct(rows[g])
-              p = SpvDecParams(
-                  X=cst.X, ldx=cst.ld, rows=cst.rows, col_off=cst.col_off, count_is_u16=int(cst.dtype == _abi.SPV_COUNT_U16),
-                  B=B, G=G, Bp=Bp, Gp=Gp, logits=ptr(logits), n_gene_tiles=Gp // 32, logits_f32=int(mlo),
-                  Wps_hi=ptr(Wps[g][0]), Wps_lo=ptr(Wps[g][1]), Aps_hi=ptr(Aps_hi), Aps_lo=ptr(Aps_lo),
-                  gene_tab=ptr(gene_tab), cnt_tab=ptr(cnt_tab), a_p=ptr(a_p), a_s=ptr(a_s), lse_p=ptr(lse_p), lse_s=ptr(lse_s),
-                  w_row=ptr(w_pad), gene_splits=splits, genes_per_split=per,
-                  part_max_p=ptr(part("dec_pmp")), part_sum_p=ptr(part("dec_psp")), part_max_s=ptr(part("dec_pms")), part_sum_s=ptr(part("dec_pss")),
-                  rec_part=ptr(nbpart("dec_rec")), tp_part=ptr(nbpart("dec_tp")), ts_part=ptr(nbpart("dec_ts")),
-                  dtheta_part=ptr(dth), dL=ptr(dL), tP=ptr(tP), tS=ptr(tS), grads_f32=int(grads_f32), nb_splits=nbs, nb_genes_per_split=nbper,
-                  nb_cell_tiles=_nb_cell_tiles(Bp, Gp), kslots=sl.kslots,
-              )
+              p = _dec_params(wsg, "dec_", B, G, Bp, Gp, mlo, sl, logits, Wps[g], Aps_img[g], cst=counts[g].c_struct(rows[g]), tabs=tabs[g], w_row=w_pad,
+                              nb=(nbs, nbper, _nb_cell_tiles(Bp, Gp)), grads=(dth, dL, tP, tS), grads_f32=grads_f32)
               if pair:
                   lib_keep.append(_cont(library[g].flatten()))
                   q = dgrp[g]
@@ -450,7 +518,7 @@ class DecoderFused(torch.autograd.Function):
               else:
                   _abi.call("spv_dec_lse", C.byref(p), ptr(_cont(library[g].flatten())), stream_ptr())
                   if lse_first:
-                      _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(logits), int(mlo), stream_ptr())
+                      run_logits()
                   _abi.call("spv_dec_nb_fwd", C.byref(p), int(need_grad), stream_ptr())
               r = rec[g]
               _add_red(red, nbpart("dec_rec"), nbs, Bp, Bp, 1, B, r, B)
@@ -594,14 +662,7 @@ class DecoderFused(torch.autograd.Function):
         for g in range(NG):
             st, G, Gp = stages[g], Gs[g], Gps[g]
             if bc_slabs[g] is not None:
-                if sl.kslots:
-                    _add_wide_bc(red, bc_slabs[g], st.csp_n, G, dWp[g], dWs[g], sl, al)
-                elif st.fused_heads:
-                    _add_red(red, bc_slabs[g][0], st.csp_n, st.Gp * DEC_KPS, DEC_KPS, G, DEC_KP, dWp[g], DEC_KP, alpha=al)                  # d [W'_p | c_p]
-                    _add_red(red, bc_slabs[g][1], st.csp_n, st.Gp * DEC_KPS, DEC_KPS, G, DEC_KS, dWs[g], DEC_KS, col_off=DEC_KP, alpha=al)  # d [W'_s | c_s]
-                else:
-                    _add_red(red, bc_slabs[g][0], st.csp_n, G * DEC_KP, DEC_KP, G, DEC_KP, dWp[g], DEC_KP, alpha=al)      # d [W'_p | c_p]
-                    _add_red(red, bc_slabs[g][1], st.csp_n, G * DEC_KS, DEC_KS, G, DEC_KS, dWs[g], DEC_KS, alpha=al)      # d [W'_s | c_s]
+                _add_heads_red(red, st, bc_slabs[g], dWp[g], dWs[g], sl, al)
             if d_slabs[g] is not None:   # (else: the GEMM summed its slabs itself, straight into dAm / d_zcat -- spv_gemm_bf16_fix)
                 _add_red(red, d_slabs[g], st.ksp_m, B * KMP, KMP, B, n_m, dAm[g], n_m, alpha=al)                          # d m (trunk output)
                 # gradient reaching zcat directly: through the logits GEMM (columns n_m..) and the two regressors
@@ -635,20 +696,10 @@ class DecoderFused(torch.autograd.Function):
                 red_bc = SpvReduceBatch()
                 red_bc.nprob = 0
                 for g in range(NG):
-                    st, G = stages[g], Gs[g]
+                    st = stages[g]
                     if split_fix:
                         st.softmax_fix()
-                    if sl.kslots:
-                        _add_wide_bc(red_bc, st.gemm_bc(), st.csp_n, G, dWp[g], dWs[g], sl, g_loss)
-                        continue
-                    b_, c = st.gemm_bc()
-                    # (spv_dec_heads_bwd's slabs are [Gp][32] for both heads; the GEMM slabs [G][16] / [G][32])
-                    if st.fused_heads:   # spv_dec_heads_bwd's slabs: [Gp][48], private columns first
-                        _add_red(red_bc, b_, st.csp_n, st.Gp * DEC_KPS, DEC_KPS, G, DEC_KP, dWp[g], DEC_KP, alpha=g_loss)
-                        _add_red(red_bc, c, st.csp_n, st.Gp * DEC_KPS, DEC_KPS, G, DEC_KS, dWs[g], DEC_KS, col_off=DEC_KP, alpha=g_loss)
-                    else:
-                        _add_red(red_bc, b_, st.csp_n, G * DEC_KP, DEC_KP, G, DEC_KP, dWp[g], DEC_KP, alpha=g_loss)
-                        _add_red(red_bc, c, st.csp_n, G * DEC_KS, DEC_KS, G, DEC_KS, dWs[g], DEC_KS, alpha=g_loss)
+                    _add_heads_red(red_bc, st, st.gemm_bc(), dWp[g], dWs[g], sl, g_loss)
                 _run_red(red_bc)
                 if side is not cur:
                     bc_done = torch.cuda.Event()
@@ -682,6 +733,7 @@ class DecoderFused(torch.autograd.Function):
         # ---- trunk backward (BatchNorm + relu, Linear) ----------------------------------------------
         dWa, dba = [pg[g][6][0] for g in range(NG)], [pg[g][7][0] for g in range(NG)]
         d_gam_a, d_bet_a = [pg[g][8][0] for g in range(NG)], [pg[g][9][0] for g in range(NG)]
+        decs = [ctx.decoders[g] for g in range(NG)]
         if ctx.trunk is not None:
             # folded trunk (spv_trunk_fold_fwd): the layer is relu(zcat W'^T + c'); its input gradient and the gradients of (W', c') come from the
             # rectifier-masked linear kernels, spv_trunk_fold_bwd takes (d W', d c') back to W_a / gamma / beta and adds the part of d zcat that
@@ -694,43 +746,28 @@ class DecoderFused(torch.autograd.Function):
                 _add_lin(bw, N=n_m, K=nt, W=ptr(Wf[g]), X=ptr(zcat[g]), ldx=nt, Y=ptr(m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dW=ptr(dWf[g]), db=ptr(dcf[g]))
                 _add_lin(bd, N=n_m, K=nt, W=ptr(Wf[g]), Y=ptr(m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
             if _ops.LINEAR_BWD:   # one launch; spv_trunk_fold_bwd reads the summed d W', so the slice sum stays on the chain
-                _reduce_pending(_linear_bwd(bd, bw, ws if not isinstance(ws, (list, tuple)) else ws[0], "wgrad_part_trunk"))
+                _reduce_pending(_linear_bwd(bd, bw, _first_ws(ws), "wgrad_part_trunk"))
             else:
                 _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
-                _wgrad(bw, ws if not isinstance(ws, (list, tuple)) else ws[0])
-            tb_ = SpvTrunkBatch()
-            tb_.nprob, tb_.B, tb_.training, tb_.eps, tb_.momentum = NG, B, int(training), 1e-3, 0.01
+                _wgrad(bw, _first_ws(ws))
             wa_c = [par[g][6] if par[g][6].is_contiguous() else par[g][6].contiguous() for g in range(NG)]
-            for g in range(NG):
-                bnm = ctx.decoders[g].sigmoid_decoder.bn
-                q = tb_.p[g]
-                q.W, q.bias, q.gamma, q.beta = ptr(wa_c[g]), ptr(par[g][7]), ptr(par[g][8]), ptr(par[g][9])
-                q.running_mean, q.running_var = ptr(bnm.running_mean), ptr(bnm.running_var)
-                q.zsum, q.zz, q.Wf, q.cf, q.stat, q.N, q.K = ptr(zsum_t[g]), ptr(zz_t[g]), ptr(Wf[g]), ptr(cf[g]), ptr(tstat[g]), n_m, nt
-                q.dWf, q.dcf, q.dW, q.dbias, q.dgamma, q.dbeta = ptr(dWf[g]), ptr(dcf[g]), ptr(dWa[g]), ptr(dba[g]), ptr(d_gam_a[g]), ptr(d_bet_a[g])
-                q.dred, q.z, q.ldz, q.dz, q.lddz = ptr(dred[g]), ptr(zcat[g]), nt, ptr(d_zcat[g]), nt
+            tb_ = _trunk_batch(B, training, decs, wa_c, par, zsum_t, zz_t, Wf, cf, tstat, n_m, nt,
+                               bwd=list(zip(dWf, dcf, dWa, dba, d_gam_a, d_bet_a, dred, zcat, d_zcat)))
             _abi.call("spv_trunk_fold_bwd", C.byref(tb_), stream_ptr())
         else:
             nblk = -(-B // _abi.BN_ROWS)
             d_pre = [new(B, n_m) for _ in range(NG)]
-            bn = SpvBnBatch()
-            bn.nprob, bn.B, bn.training, bn.relu, bn.eps, bn.momentum = NG, B, int(training), 1, 1e-3, 0.01
-            for g in range(NG):
-                tb = ctx.decoders[g].sigmoid_decoder.bn
-                q = bn.p[g]
-                q.X, q.ldx, q.Y, q.ldy, q.gamma, q.beta = ptr(pre_a[g]), n_m, ptr(m[g]), n_m, ptr(par[g][8]), ptr(par[g][9])
-                q.running_mean, q.running_var, q.stats, q.N = ptr(tb.running_mean), ptr(tb.running_var), ptr(tstat[g]), n_m
-                q.part = ptr(ws[g].get("trunk_bn_part", (nblk, n_m, 2), torch.float32))
-                q.dY, q.lddy, q.dX, q.lddx, q.dgamma, q.dbeta = ptr(dAm[g]), n_m, ptr(d_pre[g]), n_m, ptr(d_gam_a[g]), ptr(d_bet_a[g])
+            parts = [ws[g].get("trunk_bn_part", (nblk, n_m, 2), torch.float32) for g in range(NG)]
+            bn = _trunk_bn_batch(B, training, 0.01, decs, par, pre_a, m, tstat, parts, n_m, grads=(dAm, d_pre, d_gam_a, d_bet_a))
             _abi.call("spv_bn_bwd", C.byref(bn), stream_ptr())
             bw, bd = _lin_batch(B), _lin_batch(B, accumulate=True)
             for g in range(NG):
                 _add_lin(bw, N=n_m, K=nt, W=ptr(par[g][6]), X=ptr(zcat[g]), ldx=nt, dY=ptr(d_pre[g]), lddy=n_m, dW=ptr(dWa[g]), db=ptr(dba[g]))
                 _add_lin(bd, N=n_m, K=nt, W=ptr(par[g][6]), dY=ptr(d_pre[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
             if _ops.LINEAR_BWD:
-                _reduce_pending(_linear_bwd(bd, bw, ws if not isinstance(ws, (list, tuple)) else ws[0], "wgrad_part_trunk"))
+                _reduce_pending(_linear_bwd(bd, bw, _first_ws(ws), "wgrad_part_trunk"))
             else:
-                _wgrad(bw, ws if not isinstance(ws, (list, tuple)) else ws[0])
+                _wgrad(bw, _first_ws(ws))
                 _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
         # ---- BatchNorm-fold backward (+ the z statistics it used) ------------------------------------
         fb = ctx.fb   # (kslots set by the forward pass)
@@ -793,44 +830,24 @@ def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, p
     B, n_p, n_s = pz.shape[0], pz.shape[1], qz.shape[1]
     nt = n_p + n_s
     sl = dec_slots(decoder)
-    DEC_KP, DEC_KS, DEC_KPS = sl.KP, sl.KS, sl.KPS
-    if n_p + 1 > DEC_KP or n_s + 1 > DEC_KS:
-        raise _abi.SpvError(f"decoder kernels support n_private <= {DEC_KP - 1} and n_shared <= {DEC_KS - 1}")
     n_m = par[6].shape[0]
-    if n_m + nt + 1 > KMP:
-        raise _abi.SpvError("mixture input wider than 320 columns is not supported")
+    _check_latent_sizes(sl, n_p, n_s, n_m)
     G = par[0].shape[0]
     Bp, Gp = round_up(B, DEC_CELLS_PER_WG), round_up(G, 256)
     mlo = nsplit == 3
     new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     zcat = new(B, nt)
-    Am_hi, Am_lo = _bf16_image(ws, "mat_Am", Bp, KMP, mlo)
-    Aps_hi, Aps_lo = _bf16_image(ws, "mat_Aps", Bp, DEC_KPS, True)
-    za = SpvZsplitArgs()
-    za.B, za.n_p, za.n_s, za.ngroups, za.kslots = B, n_p, n_s, 1, sl.kslots
-    za.ld_am, za.am_col, za.am_cols, za.Bp = KMP, n_m, KMP - n_m, Bp
-    za.priv[0], za.poe[0], za.zcat[0] = ptr(pz), ptr(qz), ptr(zcat)
-    za.am_hi[0], za.am_lo[0], za.aps_hi[0], za.aps_lo[0] = ptr(Am_hi), ptr(Am_lo), ptr(Aps_hi), ptr(Aps_lo)
+    Am = Am_hi, Am_lo = _bf16_image(ws, "mat_Am", Bp, KMP, mlo)
+    Aps = _bf16_image(ws, "mat_Aps", Bp, sl.KPS, True)
+    za = _zsplit_args(B, Bp, n_p, n_s, n_m, sl, [(pz, qz)], [zcat], [Am], [Aps])
     _abi.call("spv_zsplit_fwd", C.byref(za), stream_ptr())
     zsum, zz = [new(n_p), new(n_s)], [new(n_p, n_p), new(n_s, n_s)]
     if training:
-        b = _lin_batch(B)
-        for k, (off, n) in enumerate(((0, n_p), (n_p, n_s))):
-            _add_lin(b, N=n, K=n, W=ptr(zz[k]), X=_fptr(zcat, off), ldx=nt, dY=_fptr(zcat, off), lddy=nt, dW=ptr(zz[k]), db=ptr(zsum[k]))
-        _wgrad(b, ws)
-    Wps_hi, Wps_lo = _bf16_image(ws, "mat_Wps", Gp, DEC_KPS, True)
+        _wgrad(_zstats_batch(B, n_p, n_s, [zcat], [zsum], [zz]), ws)
+    Wps = _bf16_image(ws, "mat_Wps", Gp, sl.KPS, True)
     fstat = [new(G, 2), new(G, 2)]
-    fb = SpvFoldBatch()
-    fb.nprob, fb.B, fb.training, fb.eps, fb.momentum, fb.kslots = 0, B, int(training), 1e-3, 0.0, sl.kslots   # momentum 0: running statistics untouched
-    fp, fs = decoder.factor_regressor_private, decoder.factor_regressor_shared
-    for k, (reg, W, gam, bet, off, slot, n, zoff) in enumerate(((fp, par[0], par[1], par[2], 0, DEC_KP, n_p, 0),
-                                                                (fs, par[3], par[4], par[5], DEC_KP, DEC_KS, n_s, n_p))):
-        q = fb.p[fb.nprob]
-        q.W, q.gamma, q.beta, q.running_mean, q.running_var = ptr(W), ptr(gam), ptr(bet), ptr(reg.bn.running_mean), ptr(reg.bn.running_var)
-        q.zsum, q.zz, q.z, q.ldz, q.stat = ptr(zsum[k]), ptr(zz[k]), _fptr(zcat, zoff), nt, ptr(fstat[k])
-        q.img_hi, q.img_lo, q.ld_img, q.col_off, q.slot = ptr(Wps_hi), ptr(Wps_lo), DEC_KPS, off, slot
-        q.G, q.Gp, q.K = G, Gp, n
-        fb.nprob += 1
+    fb = _fold_batch(B, training, 0.0, sl)   # momentum 0: running statistics untouched
+    _add_fold(fb, decoder, par, n_p, n_s, zcat, zsum, zz, fstat, Wps, G, Gp, sl)
     _abi.call("spv_bn_fold_fwd", C.byref(fb), stream_ptr())
     Wm_hi, Wm_lo = _bf16_image(ws, "mat_Wm", Gp, KMP, mlo)
     _pack(_cont(par[10]), Wm_hi, Wm_lo, extra_col=_cont(par[11]))
@@ -840,31 +857,13 @@ def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, p
     _add_lin(b, N=n_m, K=nt, W=ptr(par[6]), bias=ptr(par[7]), X=ptr(zcat), ldx=nt, Y=ptr(pre_a), ldy=n_m)
     _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
     nblk = -(-B // _abi.BN_ROWS)
-    bn = SpvBnBatch()
-    bn.nprob, bn.B, bn.training, bn.relu, bn.eps, bn.momentum = 1, B, int(training), 1, 1e-3, 0.0
-    tb = decoder.sigmoid_decoder.bn
-    q = bn.p[0]
-    q.X, q.ldx, q.Y, q.ldy, q.gamma, q.beta = ptr(pre_a), n_m, ptr(m), n_m, ptr(par[8]), ptr(par[9])
-    q.running_mean, q.running_var, q.stats, q.N = ptr(tb.running_mean), ptr(tb.running_var), ptr(tstat), n_m
-    q.part = ptr(ws.get("mat_bn_part", (nblk, n_m, 2), torch.float32))
-    q.img_hi, q.img_lo, q.ld_img, q.img_rows = ptr(Am_hi), ptr(Am_lo), KMP, Bp
+    bn = _trunk_bn_batch(B, training, 0.0, [decoder], [par], [pre_a], [m], [tstat], [ws.get("mat_bn_part", (nblk, n_m, 2), torch.float32)], n_m, [Am], Bp)
     _abi.call("spv_bn_fwd", C.byref(bn), stream_ptr())
     tiled = None
     if logits:
         tiled = ws.get("mat_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
         _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(tiled), int(mlo), stream_ptr())
-    splits, per = _gene_splits(Bp, Gp)
-    vec = lambda nme: ws.get(nme, (Bp,), torch.float32)
-    part = lambda nme: ws.get(nme, (splits, Bp), torch.float32)
-    lse_p, lse_s, a_p, a_s = vec("mat_lse_p"), vec("mat_lse_s"), vec("mat_a_p"), vec("mat_a_s")
-    p = SpvDecParams(
-        X=None, ldx=0, rows=None, col_off=0, count_is_u16=0, B=B, G=G, Bp=Bp, Gp=Gp, logits=ptr(tiled), n_gene_tiles=Gp // 32, logits_f32=int(mlo),
-        Wps_hi=ptr(Wps_hi), Wps_lo=ptr(Wps_lo), Aps_hi=ptr(Aps_hi), Aps_lo=ptr(Aps_lo), gene_tab=None, cnt_tab=None,
-        a_p=ptr(a_p), a_s=ptr(a_s), lse_p=ptr(lse_p), lse_s=ptr(lse_s), w_row=None, gene_splits=splits, genes_per_split=per,
-        part_max_p=ptr(part("mat_pmp")), part_sum_p=ptr(part("mat_psp")), part_max_s=ptr(part("mat_pms")), part_sum_s=ptr(part("mat_pss")),
-        rec_part=None, tp_part=None, ts_part=None, dtheta_part=None, dL=None, tP=None, tS=None, grads_f32=0, nb_splits=1, nb_genes_per_split=32,
-        kslots=sl.kslots,
-    )
+    p = _dec_params(ws, "mat_", B, G, Bp, Gp, mlo, sl, tiled, Wps, Aps)
     lib = _cont(library.flatten())
     if lib.numel() != B:
         raise _abi.SpvError("decoder: the library vector must hold one value per cell")

@@ -588,16 +588,23 @@ class spVIPESmodule(nn.Module):
                 pre_stream = None
             o = PoELabel.apply([labels[0], labels[1]], e, self._workspace(0, dev), label_pre, shared_stats[0]["logtheta_loc"], shared_stats[0]["logtheta_logvar"],
                                shared_stats[1]["logtheta_loc"], shared_stats[1]["logtheta_logvar"])
-            poe_stats = {}
-            for g in (0, 1):
-                loc, logvar, scale, log_z, theta, kl = o[6 * g: 6 * g + 6]
-                poe_stats[g] = OrderedDict([("logtheta_loc", loc), ("logtheta_logvar", logvar), ("logtheta_scale", scale),
-                                            ("logtheta_qz", torch.distributions.Normal(loc, scale, validate_args=False)),
-                                            ("logtheta_log_z", log_z), ("logtheta_theta", theta)])
-                self._kl_poe[g] = kl
+            poe_stats = self._poe_stats(o, 6, (0, 1))
         else:
             poe_stats = self._supervised_poe(shared_stats, global_indices, processed_labels, labels, noise)
         return {"private_stats": private_stats, "shared_stats": shared_stats, "poe_stats": poe_stats, "library": library}
+
+    def _poe_stats(self, o, stride: int, groups):
+        """the ``poe_stats`` of ``inference`` from a PoE op's flat outputs, ``stride`` per group: (loc, logvar, scale, log_z, theta, kl[, the scale
+        of ``qz``: else ``scale`` itself]); stores each group's KL vector for ``loss``"""
+        out = {}
+        for i, g in enumerate(groups):
+            loc, logvar, scale, log_z, theta, kl = o[stride * i: stride * i + 6]
+            qscale = o[stride * i + 6] if stride > 6 else scale
+            out[g] = OrderedDict([("logtheta_loc", loc), ("logtheta_logvar", logvar), ("logtheta_scale", scale),
+                                  ("logtheta_qz", torch.distributions.Normal(loc, qscale, validate_args=False)),
+                                  ("logtheta_log_z", log_z), ("logtheta_theta", theta)])
+            self._kl_poe[g] = kl
+        return out
 
     def _supervised_poe(self, shared_stats, global_indices, processed_labels, labels, noise):
         """Dispatch of spVIPESmodule.py:484-509 (same priorities and errors); label-based PoE, first in that order, has
@@ -632,14 +639,7 @@ class spVIPESmodule(nn.Module):
         o = PoEPaired.apply(self.sparse_plan(dev), [global_indices[0], global_indices[1]], e, self._workspace(0, dev),
                             shared_stats[0]["logtheta_loc"], shared_stats[0]["logtheta_logvar"],
                             shared_stats[1]["logtheta_loc"], shared_stats[1]["logtheta_logvar"])
-        out = {}
-        for g in (0, 1):
-            loc, logvar, scale, log_z, theta, kl, qscale = o[7 * g: 7 * g + 7]
-            out[g] = OrderedDict([("logtheta_loc", loc), ("logtheta_logvar", logvar), ("logtheta_scale", scale),
-                                  ("logtheta_qz", torch.distributions.Normal(loc, qscale, validate_args=False)),
-                                  ("logtheta_log_z", log_z), ("logtheta_theta", theta)])
-            self._kl_poe[g] = kl
-        return out
+        return self._poe_stats(o, 7, (0, 1))
 
     def _cluster_poe_hip(self, shared_stats, global_indices, processed_labels, noise):
         """spVIPESmodule.py:184-280 on the sparse plan: plan-weighted component experts + _poe2 fusion in HIP."""
@@ -653,14 +653,7 @@ class spVIPESmodule(nn.Module):
         o = PoECluster.apply(self.sparse_plan(dev), [global_indices[0], global_indices[1]], [processed_labels[0], processed_labels[1]], e,
                              self._workspace(0, dev), shared_stats[0]["logtheta_loc"], shared_stats[0]["logtheta_logvar"],
                              shared_stats[1]["logtheta_loc"], shared_stats[1]["logtheta_logvar"])
-        out = {}
-        for g in (0, 1):
-            loc, logvar, scale, log_z, theta, kl, qscale = o[7 * g: 7 * g + 7]
-            out[g] = OrderedDict([("logtheta_loc", loc), ("logtheta_logvar", logvar), ("logtheta_scale", scale),
-                                  ("logtheta_qz", torch.distributions.Normal(loc, qscale, validate_args=False)),
-                                  ("logtheta_log_z", log_z), ("logtheta_theta", theta)])
-            self._kl_poe[g] = kl
-        return out
+        return self._poe_stats(o, 7, (0, 1))
 
     def _components_poe_hip(self, shared_stats, components, noise):
         """N-group cluster-matched PoE with component-mean experts (csrc/spv_poe_n.h): this build's extension for more than
@@ -677,14 +670,7 @@ class spVIPESmodule(nn.Module):
             raise ValueError("n_components must be given to the module for more than two groups")
         flat = [t for g in gs for t in (shared_stats[g]["logtheta_loc"], shared_stats[g]["logtheta_logvar"])]
         o = PoEComponents.apply([components[g] for g in gs], int(self.n_components), e, self._workspace(gs[0], dev), *flat)
-        out = {}
-        for i, g in enumerate(gs):
-            loc, logvar, scale, log_z, theta, kl, qscale = o[7 * i: 7 * i + 7]
-            out[g] = OrderedDict([("logtheta_loc", loc), ("logtheta_logvar", logvar), ("logtheta_scale", scale),
-                                  ("logtheta_qz", torch.distributions.Normal(loc, qscale, validate_args=False)),
-                                  ("logtheta_log_z", log_z), ("logtheta_theta", theta)])
-            self._kl_poe[g] = kl
-        return out
+        return self._poe_stats(o, 7, gs)
 
     def generative(self, private_stats, shared_stats, poe_stats, library, groups, batch_index):
         """spVIPESmodule.py:720-771: latent concatenation + slicing quirk; the decoder itself is

@@ -100,6 +100,16 @@ def _fptr(t: torch.Tensor, col: int = 0) -> int:
     return t.data_ptr() + 4 * col
 
 
+def _cont(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """``t`` itself if it is contiguous, else such a copy; None (a gradient nobody sent) stays None"""
+    return None if t is None else t.contiguous()
+
+
+def _first_ws(ws):
+    """the workspace the small batched launches share: ``ws`` itself, or the first of a per-group list"""
+    return ws[0] if isinstance(ws, (list, tuple)) else ws
+
+
 class EncoderSpec:
     """Parameters and buffers of one reference ``Encoder`` (nn/networks.py:47-83) after fc1."""
 
@@ -119,6 +129,27 @@ N_ENC_PARAMS = 10
 # step must not share a seed: the k-th launch of a step (module.inference: one per pair of groups) draws with seed k * DROPOUT_SET_STRIDE +
 # step counter.  Odd and of the order of 2^63: no k * stride (k < 2^32) is within reach of the counter's +1 walk.  Launch 0 keeps the bare counter.
 DROPOUT_SET_STRIDE = 0x9E3779B97F4A7C15
+
+
+def _tail_bn_batch(B: int, training: bool, specs, par, pre, post, stats, ws, grads=None) -> SpvBnBatch:
+    """the BatchNorm1d of every encoder's mu and logvar heads (torch defaults eps 1e-5, momentum 0.1: nn/networks.py:76,82), two problems
+    per encoder on the column halves of ``pre`` / ``post``; ``grads`` = (d_post, d_pre, d_gb [d gamma_mu, d beta_mu, d gamma_lv, d beta_lv])
+    per encoder: the backward's fields"""
+    nblk = -(-B // _abi.BN_ROWS)
+    bn = SpvBnBatch()
+    bn.nprob, bn.B, bn.training, bn.relu, bn.eps, bn.momentum = 0, B, int(training), 0, 1e-5, 0.1
+    for i, (s, p) in enumerate(zip(specs, par)):
+        for half, (g, be, mod) in enumerate(((p[6], p[7], s.enc.mu_encoder[1]), (p[8], p[9], s.enc.lvar_encoder[1]))):
+            q = bn.p[bn.nprob]
+            q.X, q.ldx, q.Y, q.ldy = _fptr(pre[i], half * s.n), 2 * s.n, _fptr(post[i], half * s.n), 2 * s.n
+            q.gamma, q.beta, q.running_mean, q.running_var = ptr(g), ptr(be), ptr(mod.running_mean), ptr(mod.running_var)
+            q.stats, q.part, q.N = ptr(stats[i][half]), ptr(ws.get(f"tail_bn_part_{bn.nprob}", (nblk, s.n, 2), torch.float32)), s.n
+            if grads is not None:
+                d_post, d_pre, d_gb = grads
+                q.dY, q.lddy, q.dX, q.lddx = _fptr(d_post[i], half * s.n), 2 * s.n, _fptr(d_pre[i], half * s.n), 2 * s.n
+                q.dgamma, q.dbeta = ptr(d_gb[i][2 * half]), ptr(d_gb[i][2 * half + 1])
+            bn.nprob += 1
+    return bn
 
 
 class EncoderTails(torch.autograd.Function):
@@ -148,7 +179,6 @@ class EncoderTails(torch.autograd.Function):
         pre = [new(B, 2 * s.n) for s in specs]
         post = [new(B, 2 * s.n) for s in specs]
         stats = [new(2, s.n, 2) for s in specs]
-        nblk = -(-B // _abi.BN_ROWS)
         dp = float(drop_p) if training else 0.0
         # 1. fc2 + relu (+ dropout)
         b = _lin_batch(B, relu=True, drop_p=dp, seed=seed)
@@ -168,19 +198,8 @@ class EncoderTails(torch.autograd.Function):
             _add_lin(b, N=s.n, K=H, W=ptr(p[2]), bias=ptr(p[3]), X=ptr(x), ldx=H, Y=_fptr(y, 0), ldy=2 * s.n)
             _add_lin(b, N=s.n, K=H, W=ptr(p[4]), bias=ptr(p[5]), X=ptr(x), ldx=H, Y=_fptr(y, s.n), ldy=2 * s.n)
         _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
-        # 3. BatchNorm1d (torch defaults eps 1e-5, momentum 0.1: nn/networks.py:76,82)
-        bn = SpvBnBatch()
-        bn.nprob, bn.B, bn.training, bn.relu, bn.eps, bn.momentum = 0, B, int(training), 0, 1e-5, 0.1
-        parts = []
-        for s, p, x, y, st in zip(specs, par, pre, post, stats):
-            for half, (g, be, mod) in enumerate(((p[6], p[7], s.enc.mu_encoder[1]), (p[8], p[9], s.enc.lvar_encoder[1]))):
-                part = ws.get(f"tail_bn_part_{len(parts)}", (nblk, s.n, 2), torch.float32)
-                parts.append(part)
-                q = bn.p[bn.nprob]
-                q.X, q.ldx, q.Y, q.ldy = _fptr(x, half * s.n), 2 * s.n, _fptr(y, half * s.n), 2 * s.n
-                q.gamma, q.beta, q.running_mean, q.running_var = ptr(g), ptr(be), ptr(mod.running_mean), ptr(mod.running_var)
-                q.stats, q.part, q.N = ptr(st[half]), ptr(part), s.n
-                bn.nprob += 1
+        # 3. BatchNorm1d
+        bn = _tail_bn_batch(B, training, specs, par, pre, post, stats, ws)
         # 4. scale, reparameterised draw, softmax, KL -- in the same launch as the BatchNorm apply (spv_enc_heads_fwd: batch statistics,
         #    then ONE kernel that finalises them, normalises, samples and forms the KL)
         scale = [new(B, s.n) for s in specs]
@@ -214,7 +233,6 @@ class EncoderTails(torch.autograd.Function):
         h2, pre, post, stats, scale = (saved[n_in + k * E: n_in + (k + 1) * E] for k in range(5))
         dev = h1[0].device
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        cont = lambda t: None if t is None else t.contiguous()
         # 1. sampling / KL backward -> d_post
         d_post = [new(B, 2 * s.n) for s in specs]
         sb = SpvSampleBatch()
@@ -228,8 +246,8 @@ class EncoderTails(torch.autograd.Function):
             if strided and all(t is None or (t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) == strided[0].stride(0)) for t in (gl, gv)):
                 g_ld = strided[0].stride(0)
             else:
-                gl, gv = cont(gl), cont(gv)
-            gs, gz, gk = cont(gs), cont(gz), cont(gk)
+                gl, gv = _cont(gl), _cont(gv)
+            gs, gz, gk = _cont(gs), _cont(gz), _cont(gk)
             keep += [gl, gv, gs, gz, gk]
             q = sb.p[i]
             q.post, q.n, q.eps, q.scale = ptr(post[i]), s.n, ptr(ctx.eps[i]), ptr(scale[i])
@@ -242,20 +260,7 @@ class EncoderTails(torch.autograd.Function):
         # parameter gradients: (write target, autograd return value) per parameter of each encoder
         pg = [[grad_out(par[i][j]) for j in range(N_ENC_PARAMS)] for i in range(E)]
         d_gb = [[pg[i][6][0], pg[i][7][0], pg[i][8][0], pg[i][9][0]] for i in range(E)]  # d gamma_mu, d beta_mu, d gamma_lv, d beta_lv
-        nblk = -(-B // _abi.BN_ROWS)
-        bn = SpvBnBatch()
-        bn.nprob, bn.B, bn.training, bn.relu, bn.eps, bn.momentum = 0, B, int(ctx.training), 0, 1e-5, 0.1
-        k = 0
-        for i, (s, p) in enumerate(zip(specs, par)):
-            for half, (gam, be, mod) in enumerate(((p[6], p[7], s.enc.mu_encoder[1]), (p[8], p[9], s.enc.lvar_encoder[1]))):
-                q = bn.p[bn.nprob]
-                q.X, q.ldx, q.Y, q.ldy = _fptr(pre[i], half * s.n), 2 * s.n, _fptr(post[i], half * s.n), 2 * s.n
-                q.gamma, q.beta, q.running_mean, q.running_var = ptr(gam), ptr(be), ptr(mod.running_mean), ptr(mod.running_var)
-                q.stats, q.part, q.N = ptr(stats[i][half]), ptr(ws.get(f"tail_bn_part_{k}", (nblk, s.n, 2), torch.float32)), s.n
-                q.dY, q.lddy, q.dX, q.lddx = _fptr(d_post[i], half * s.n), 2 * s.n, _fptr(d_pre[i], half * s.n), 2 * s.n
-                q.dgamma, q.dbeta = ptr(d_gb[i][2 * half]), ptr(d_gb[i][2 * half + 1])
-                bn.nprob += 1
-                k += 1
+        bn = _tail_bn_batch(B, ctx.training, specs, par, pre, post, stats, ws, grads=(d_post, d_pre, d_gb))
         if fused:
             _abi.call("spv_enc_heads_bwd", C.byref(bn), C.byref(sb), stream_ptr())
         else:
@@ -267,7 +272,7 @@ class EncoderTails(torch.autograd.Function):
             _add_lin(bwh, N=s.n, K=H, W=ptr(par[i][2]), X=ptr(h2[i]), ldx=H, dY=_fptr(d_pre[i], 0), lddy=2 * s.n, dW=ptr(dWmu[i]), db=ptr(dbmu[i]))
             _add_lin(bwh, N=s.n, K=H, W=ptr(par[i][4]), X=ptr(h2[i]), ldx=H, dY=_fptr(d_pre[i], s.n), lddy=2 * s.n, dW=ptr(dWlv[i]), db=ptr(dblv[i]))
         from . import ops as _ops
-        wsw = ws if not isinstance(ws, (list, tuple)) else ws[0]
+        wsw = _first_ws(ws)
         one_launch = _ops.LINEAR_BWD   # (spv_linear_bwd: nothing a launch writes is read by its other part -- d h2 / h2, d h1 / h1 are distinct buffers)
         if not one_launch:
             _wgrad(bwh, wsw)
@@ -338,6 +343,59 @@ def label_partners(labels: Sequence[torch.Tensor], ws):
     return partner, mode, lab, order, rank, tables
 
 
+# The per-group fields of spv_poe_args, one function per kind.  They go by attribute name, so PoEComponents fills the fields of the same
+# names in spv_poe_comp_args with them.
+_POE_OUT = ("loc", "logvar", "scale", "logz", "theta")
+
+
+def _poe_args(n: int, clamp_scale: int = 0, lone_passthrough: int = 0):
+    a = _abi.SpvPoeArgs()
+    a.n, a.clamp_scale, a.lone_passthrough = n, clamp_scale, lone_passthrough
+    return a
+
+
+def _poe_common(a, k: int, block, eps: torch.Tensor, B: int, partner=None, mode=None) -> None:
+    """group ``k``'s inputs: ``block`` = _loc_logvar_block's (holder, base pointer, row pitch) of the encoder statistics, the noise, the
+    pairing (spv_poe_args only)"""
+    a.stats[k], a.ld[k], a.eps[k], a.B[k] = block[1], block[2], ptr(eps), B
+    if partner is not None:
+        a.partner[k], a.mode[k] = ptr(partner), ptr(mode)
+
+
+def _poe_outputs(a, Bs: Sequence[int], n: int, dev):
+    """allocates every group's five outputs [B][n] and its KL vector [B] and sets their pointers -> ({name: per group}, kl per group)"""
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    out = {k: [new(B, n) for B in Bs] for k in _POE_OUT}
+    kl = [new(B) for B in Bs]
+    for g in range(len(Bs)):
+        a.loc[g], a.logvar[g], a.scale[g], a.logz[g], a.theta[g] = (ptr(out[k][g]) for k in _POE_OUT)
+        a.kl[g] = ptr(kl[g])
+    return out, kl
+
+
+def _poe_grads(a, k: int, g, loc: torch.Tensor, scale: torch.Tensor) -> list:
+    """group ``k``'s backward inputs: ``g`` = the gradients of (loc, logvar, scale, log_z, theta, kl), theta's unused, and the saved outputs;
+    returns the contiguous gradients the launch reads (the caller holds them until it is queued)"""
+    gl, gv, gs, gz, _gt, gk = g
+    keep = [_cont(t) for t in (gl, gv, gs, gz, gk)]
+    a.g_loc[k], a.g_logvar[k], a.g_scale[k], a.g_logz[k], a.g_kl[k] = (ptr(t) for t in keep)
+    a.loc[k], a.scale[k] = ptr(loc), ptr(scale)
+    return keep
+
+
+def _poe_result(ctx, out, kl, qscale: bool) -> tuple:
+    """per group (loc*, logvar*, scale*, log_z, theta, kl[, qscale = scale*.clamp(min = 1e-6)]); theta and qscale not differentiable"""
+    res = []
+    for g in range(len(kl)):
+        res += [out[k][g] for k in _POE_OUT] + [kl[g]]
+        nd = [out["theta"][g]]
+        if qscale:
+            nd.append(out["scale"][g].clamp(min=1e-6))
+            res.append(nd[1])
+        ctx.mark_non_differentiable(*nd)
+    return tuple(res)
+
+
 class PoELabel(torch.autograd.Function):
     """Both groups' label-based PoE in 2 forward launches (ranking; lookup + fusion / draw / KL) and 2 backward launches (fill, scatter).
     inputs : loc0, logvar0, loc1, logvar1 (shared-encoder statistics); outputs per group
@@ -346,59 +404,40 @@ class PoELabel(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, labels: Sequence[torch.Tensor], eps: Sequence[torch.Tensor], ws, pre, loc0, logvar0, loc1, logvar1):
-        from ._abi import SpvPoeArgs
         ctx.set_materialize_grads(False)
-        dev = loc0.device
         n = loc0.shape[1]
         Bs = [loc0.shape[0], loc1.shape[0]]
         partner, mode, lab, order, rank, tables = pre if pre is not None else label_partners(labels, ws)
         blocks = [_loc_logvar_block(loc0, logvar0), _loc_logvar_block(loc1, logvar1)]
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        out = {k: [new(Bs[g], n) for g in range(2)] for k in ("loc", "logvar", "scale", "logz", "theta")}
-        kl = [new(Bs[g]) for g in range(2)]
+        a = _poe_args(n)
+        out, kl = _poe_outputs(a, Bs, n, loc0.device)
         eps = [e.contiguous() for e in eps]
-        a = SpvPoeArgs()
-        a.n = n
         for g in range(2):
-            a.stats[g], a.ld[g], a.partner[g], a.mode[g], a.eps[g], a.B[g] = blocks[g][1], blocks[g][2], ptr(partner[g]), ptr(mode[g]), ptr(eps[g]), Bs[g]
-            a.loc[g], a.logvar[g], a.scale[g], a.logz[g], a.theta[g] = (ptr(out[k][g]) for k in ("loc", "logvar", "scale", "logz", "theta"))
-            a.kl[g] = ptr(kl[g])
+            _poe_common(a, g, blocks[g], eps[g], Bs[g], partner[g], mode[g])
             a.lab[g], a.order[g], a.rank[g] = ptr(lab[g]), ptr(order[g]), ptr(rank[g])   # the fusion kernel looks the partners up itself
         a.tables = ptr(tables)
         _abi.call("spv_poe_fuse_fwd", C.byref(a), stream_ptr())
         ctx.blocks, ctx.eps, ctx.partner, ctx.mode, ctx.n, ctx.Bs = blocks, eps, partner, mode, n, Bs
         ctx.lab = lab
         ctx.save_for_backward(out["loc"][0], out["loc"][1], out["scale"][0], out["scale"][1])
-        res = []
-        for g in range(2):
-            res += [out["loc"][g], out["logvar"][g], out["scale"][g], out["logz"][g], out["theta"][g], kl[g]]
-            ctx.mark_non_differentiable(out["theta"][g])
-        return tuple(res)
+        return _poe_result(ctx, out, kl, qscale=False)
 
     @staticmethod
     def backward(ctx, *g):
-        from ._abi import SpvPoeArgs
         loc = ctx.saved_tensors[0:2]
         scale = ctx.saved_tensors[2:4]
         n, Bs = ctx.n, ctx.Bs
-        dev = loc[0].device
-        cont = lambda t: None if t is None else t.contiguous()
-        a = SpvPoeArgs()
-        a.n = n
+        a = _poe_args(n)
         # both groups' gradient blocks in ONE allocation: spv_poe_fuse_bwd then zeroes them with a single memset
         lds = [ctx.blocks[k][2] for k in range(2)]
-        dbuf = torch.empty(Bs[0] * lds[0] + Bs[1] * lds[1], dtype=torch.float32, device=dev)
+        dbuf = torch.empty(Bs[0] * lds[0] + Bs[1] * lds[1], dtype=torch.float32, device=loc[0].device)
         d = [dbuf[:Bs[0] * lds[0]].view(Bs[0], lds[0]), dbuf[Bs[0] * lds[0]:].view(Bs[1], lds[1])]
         keep = []
         for k in range(2):
-            gl, gv, gs, gz, _gt, gk = (cont(t) for t in g[6 * k: 6 * k + 6])
-            keep += [gl, gv, gs, gz, gk]
-            a.stats[k], a.ld[k], a.partner[k], a.mode[k], a.eps[k], a.B[k] = ctx.blocks[k][1], ctx.blocks[k][2], ptr(ctx.partner[k]), ptr(ctx.mode[k]), ptr(ctx.eps[k]), Bs[k]
-            a.loc[k], a.scale[k] = ptr(loc[k]), ptr(scale[k])
-            a.g_loc[k], a.g_logvar[k], a.g_scale[k], a.g_logz[k], a.g_kl[k] = ptr(gl), ptr(gv), ptr(gs), ptr(gz), ptr(gk)
+            keep += _poe_grads(a, k, g[6 * k: 6 * k + 6], loc[k], scale[k])
+            _poe_common(a, k, ctx.blocks[k], ctx.eps[k], Bs[k], ctx.partner[k], ctx.mode[k])
             a.lab[k] = ptr(ctx.lab[k])   # (a flag for the backward kernel: label pairs are one to one)
-        for k in range(2):  # (d_stats uses the same pitch as stats, which may be views of a wider buffer)
-            a.d_stats[k] = ptr(d[k])
+            a.d_stats[k] = ptr(d[k])     # (the same pitch as stats, which may be views of a wider buffer)
         _abi.call("spv_poe_fuse_bwd", C.byref(a), stream_ptr())
         return (None, None, None, None, d[0][:, :n], d[0][:, n:2 * n], d[1][:, :n], d[1][:, n:2 * n])
 
@@ -411,7 +450,6 @@ class PoEPaired(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, idx: Sequence[torch.Tensor], eps: Sequence[torch.Tensor], ws, loc0, logvar0, loc1, logvar1):
-        from ._abi import SpvPoeArgs
         ctx.set_materialize_grads(False)
         dev = loc0.device
         n = loc0.shape[1]
@@ -426,43 +464,26 @@ class PoEPaired(torch.autograd.Function):
         _abi.call("spv_plan_argmax", C.byref(ps), ptr(idx[0]), ptr(idx[1]), ptr(plan.inv0), ptr(plan.inv1), Bs[0], Bs[1], ptr(partner[0]),
                   ptr(partner[1]), stream_ptr())
         blocks = [_loc_logvar_block(loc0, logvar0), _loc_logvar_block(loc1, logvar1)]
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        out = {k: [new(Bs[g], n) for g in range(2)] for k in ("loc", "logvar", "scale", "logz", "theta")}
-        kl = [new(Bs[g]) for g in range(2)]
+        a = _poe_args(n, clamp_scale=1, lone_passthrough=0)
+        out, kl = _poe_outputs(a, Bs, n, dev)
         eps = [e.contiguous() for e in eps]
-        a = SpvPoeArgs()
-        a.n, a.clamp_scale, a.lone_passthrough = n, 1, 0
         for g in range(2):
-            a.stats[g], a.ld[g], a.partner[g], a.mode[g], a.eps[g], a.B[g] = blocks[g][1], blocks[g][2], ptr(partner[g]), ptr(mode[g]), ptr(eps[g]), Bs[g]
-            a.loc[g], a.logvar[g], a.scale[g], a.logz[g], a.theta[g] = (ptr(out[k][g]) for k in ("loc", "logvar", "scale", "logz", "theta"))
-            a.kl[g] = ptr(kl[g])
+            _poe_common(a, g, blocks[g], eps[g], Bs[g], partner[g], mode[g])
         _abi.call("spv_poe_fuse_fwd", C.byref(a), stream_ptr())
         ctx.blocks, ctx.eps, ctx.partner, ctx.mode, ctx.n, ctx.Bs = blocks, eps, partner, mode, n, Bs
         ctx.save_for_backward(out["loc"][0], out["loc"][1], out["scale"][0], out["scale"][1])
-        res = []
-        for g in range(2):
-            qscale = out["scale"][g].clamp(min=1e-6)
-            res += [out["loc"][g], out["logvar"][g], out["scale"][g], out["logz"][g], out["theta"][g], kl[g], qscale]
-            ctx.mark_non_differentiable(out["theta"][g], qscale)
-        return tuple(res)
+        return _poe_result(ctx, out, kl, qscale=True)
 
     @staticmethod
     def backward(ctx, *g):
-        from ._abi import SpvPoeArgs
         loc, scale = ctx.saved_tensors[0:2], ctx.saved_tensors[2:4]
         n, Bs = ctx.n, ctx.Bs
-        dev = loc[0].device
-        cont = lambda t: None if t is None else t.contiguous()
-        a = SpvPoeArgs()
-        a.n, a.clamp_scale, a.lone_passthrough = n, 1, 0
+        a = _poe_args(n, clamp_scale=1, lone_passthrough=0)
         keep, d = [], []
         for k in range(2):
-            gl, gv, gs, gz, _gt, gk, _gq = (cont(t) for t in g[7 * k: 7 * k + 7])
-            keep += [gl, gv, gs, gz, gk]
-            a.stats[k], a.ld[k], a.partner[k], a.mode[k], a.eps[k], a.B[k] = ctx.blocks[k][1], ctx.blocks[k][2], ptr(ctx.partner[k]), ptr(ctx.mode[k]), ptr(ctx.eps[k]), Bs[k]
-            a.loc[k], a.scale[k] = ptr(loc[k]), ptr(scale[k])
-            a.g_loc[k], a.g_logvar[k], a.g_scale[k], a.g_logz[k], a.g_kl[k] = ptr(gl), ptr(gv), ptr(gs), ptr(gz), ptr(gk)
-            d.append(torch.empty(Bs[k], ctx.blocks[k][2], dtype=torch.float32, device=dev))  # zeroed by spv_poe_fuse_bwd
+            keep += _poe_grads(a, k, g[7 * k: 7 * k + 6], loc[k], scale[k])
+            _poe_common(a, k, ctx.blocks[k], ctx.eps[k], Bs[k], ctx.partner[k], ctx.mode[k])
+            d.append(torch.empty(Bs[k], ctx.blocks[k][2], dtype=torch.float32, device=loc[0].device))  # zeroed by spv_poe_fuse_bwd
             a.d_stats[k] = ptr(d[k])
         _abi.call("spv_poe_fuse_bwd", C.byref(a), stream_ptr())
         return (None, None, None, None, d[0][:, :n], d[0][:, n:2 * n], d[1][:, :n], d[1][:, n:2 * n])
@@ -476,7 +497,7 @@ class PoECluster(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, idx: Sequence[torch.Tensor], comps: Sequence[torch.Tensor], eps: Sequence[torch.Tensor], ws, loc0, logvar0, loc1, logvar1):
-        from ._abi import SpvPlanExpertArgs, SpvPoeArgs
+        from ._abi import SpvPlanExpertArgs
         ctx.set_materialize_grads(False)
         dev = loc0.device
         n = loc0.shape[1]
@@ -507,16 +528,12 @@ class PoECluster(torch.autograd.Function):
             ea.idx[g], ea.inv[g], ea.comp[g], ea.stats[g], ea.ld[g] = ptr(idx[g]), ptr(inv[g]), ptr(comp[g]), blocks[g][1], blocks[g][2]
             ea.expert[g], ea.ld_expert[g], ea.rowsum[g] = ptr(expert[g]), 2 * n, ptr(rowsum[g])
         _abi.call("spv_plan_expert_fwd", C.byref(ea), stream_ptr())
-        out = {k: [new(B, n) for g in range(2)] for k in ("loc", "logvar", "scale", "logz", "theta")}
-        kl = [new(B) for g in range(2)]
+        a = _poe_args(n, clamp_scale=1, lone_passthrough=1)
+        out, kl = _poe_outputs(a, Bs, n, dev)
         eps = [e.contiguous() for e in eps]
-        a = SpvPoeArgs()
-        a.n, a.clamp_scale, a.lone_passthrough = n, 1, 1
         for g in range(2):
-            a.stats[g], a.ld[g], a.partner[g], a.mode[g], a.eps[g], a.B[g] = blocks[g][1], blocks[g][2], ptr(partner[g]), ptr(mode[g]), ptr(eps[g]), B
+            _poe_common(a, g, blocks[g], eps[g], B, partner[g], mode[g])
             a.expert[g], a.ld_expert[g] = ptr(expert[g]), 2 * n
-            a.loc[g], a.logvar[g], a.scale[g], a.logz[g], a.theta[g] = (ptr(out[k][g]) for k in ("loc", "logvar", "scale", "logz", "theta"))
-            a.kl[g] = ptr(kl[g])
         _abi.call("spv_poe_fuse_fwd", C.byref(a), stream_ptr())
         # the inverse maps of the plan are rebuilt by the next minibatch: keep what the backward needs of them
         # (copied by a kernel: a tensor .clone() would put a memcpy node into the captured step, DESIGN.md §4 "memset node")
@@ -526,30 +543,20 @@ class PoECluster(torch.autograd.Function):
         ctx.blocks, ctx.eps, ctx.partner, ctx.mode, ctx.n, ctx.B = blocks, eps, partner, mode, n, B
         ctx.expert, ctx.rowsum = expert, rowsum
         ctx.save_for_backward(out["loc"][0], out["loc"][1], out["scale"][0], out["scale"][1])
-        res = []
-        for g in range(2):
-            qscale = out["scale"][g].clamp(min=1e-6)
-            res += [out["loc"][g], out["logvar"][g], out["scale"][g], out["logz"][g], out["theta"][g], kl[g], qscale]
-            ctx.mark_non_differentiable(out["theta"][g], qscale)
-        return tuple(res)
+        return _poe_result(ctx, out, kl, qscale=True)
 
     @staticmethod
     def backward(ctx, *g):
-        from ._abi import SpvPlanExpertArgs, SpvPoeArgs
+        from ._abi import SpvPlanExpertArgs
         loc, scale = ctx.saved_tensors[0:2], ctx.saved_tensors[2:4]
         n, B = ctx.n, ctx.B
         dev = loc[0].device
-        cont = lambda t: None if t is None else t.contiguous()
-        a = SpvPoeArgs()
-        a.n, a.clamp_scale, a.lone_passthrough = n, 1, 1
+        a = _poe_args(n, clamp_scale=1, lone_passthrough=1)
         keep, d, de = [], [], []
         for k in range(2):
-            gl, gv, gs, gz, _gt, gk, _gq = (cont(t) for t in g[7 * k: 7 * k + 7])
-            keep += [gl, gv, gs, gz, gk]
-            a.stats[k], a.ld[k], a.partner[k], a.mode[k], a.eps[k], a.B[k] = ctx.blocks[k][1], ctx.blocks[k][2], ptr(ctx.partner[k]), ptr(ctx.mode[k]), ptr(ctx.eps[k]), B
+            keep += _poe_grads(a, k, g[7 * k: 7 * k + 6], loc[k], scale[k])
+            _poe_common(a, k, ctx.blocks[k], ctx.eps[k], B, ctx.partner[k], ctx.mode[k])
             a.expert[k], a.ld_expert[k] = ptr(ctx.expert[k]), 2 * n
-            a.loc[k], a.scale[k] = ptr(loc[k]), ptr(scale[k])
-            a.g_loc[k], a.g_logvar[k], a.g_scale[k], a.g_logz[k], a.g_kl[k] = ptr(gl), ptr(gv), ptr(gs), ptr(gz), ptr(gk)
             d.append(torch.empty(B, ctx.blocks[k][2], dtype=torch.float32, device=dev))   # both zeroed by spv_poe_fuse_bwd
             de.append(torch.empty(B, 2 * n, dtype=torch.float32, device=dev))
             a.d_stats[k], a.d_expert[k] = ptr(d[k]), ptr(de[k])
@@ -564,15 +571,25 @@ class PoECluster(torch.autograd.Function):
         return (None, None, None, None, None, d[0][:, :n], d[0][:, n:2 * n], d[1][:, :n], d[1][:, n:2 * n])
 
 
-
 class PoEComponents(torch.autograd.Function):
     """N-group cluster-matched PoE (csrc/spv_poe_n.h; BASELINE config 4, throughput only: the reference stops at two groups).
     inputs : per group (loc_g, logvar_g) of the shared encoders; ``comp``: per-group component codes [B] (fp32, integral in
     [0, n_comp)); outputs per group (loc*, logvar*, scale*, log_z, theta, kl, qscale) -- theta and qscale not differentiable."""
 
     @staticmethod
+    def _args(NG: int, n: int, n_comp: int, ws, mean=None):
+        """spv_poe_comp_args' header: the per-component partial sums (workspace) and means (the forward's are new) -> (block, means)"""
+        from ._abi import POE_COMP_SEG, SpvPoeCompArgs
+        a = SpvPoeCompArgs()
+        part = ws.get("poen_part", (NG, POE_COMP_SEG, n_comp, 2 * n + 1), torch.float32)
+        if mean is None:
+            mean = torch.empty(NG, n_comp, 2 * n + 1, dtype=torch.float32, device=part.device)
+        a.ngroups, a.n, a.ncomp, a.part, a.mean = NG, n, n_comp, ptr(part), ptr(mean)
+        return a, mean
+
+    @staticmethod
     def forward(ctx, comp: Sequence[torch.Tensor], n_comp: int, eps: Sequence[torch.Tensor], ws, *stats):
-        from ._abi import POE_COMP_CMAX, POE_COMP_SEG, SPV_POE_MAXG, SpvPoeCompArgs
+        from ._abi import POE_COMP_CMAX, SPV_POE_MAXG
         ctx.set_materialize_grads(False)
         NG = len(comp)
         if not (2 <= NG <= SPV_POE_MAXG) or len(stats) != 2 * NG:
@@ -585,52 +602,35 @@ class PoEComponents(torch.autograd.Function):
         blocks = [_loc_logvar_block(stats[2 * g], stats[2 * g + 1]) for g in range(NG)]
         comp = [c.flatten().contiguous().float() for c in comp]
         eps = [e.contiguous() for e in eps]
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        W = 2 * n + 1
-        part = ws.get("poen_part", (NG, POE_COMP_SEG, n_comp, W), torch.float32)
-        mean = new(NG, n_comp, W)
-        out = {k: [new(Bs[g], n) for g in range(NG)] for k in ("loc", "logvar", "scale", "logz", "theta")}
-        kl = [new(Bs[g]) for g in range(NG)]
-        a = SpvPoeCompArgs()
-        a.ngroups, a.n, a.ncomp, a.part, a.mean = NG, n, n_comp, ptr(part), ptr(mean)
+        a, mean = PoEComponents._args(NG, n, n_comp, ws)
+        out, kl = _poe_outputs(a, Bs, n, dev)
         for g in range(NG):
-            a.B[g], a.stats[g], a.ld[g], a.comp[g], a.eps[g] = Bs[g], blocks[g][1], blocks[g][2], ptr(comp[g]), ptr(eps[g])
-            a.loc[g], a.logvar[g], a.scale[g], a.logz[g], a.theta[g] = (ptr(out[k][g]) for k in ("loc", "logvar", "scale", "logz", "theta"))
-            a.kl[g] = ptr(kl[g])
+            _poe_common(a, g, blocks[g], eps[g], Bs[g])
+            a.comp[g] = ptr(comp[g])
         _abi.call("spv_poe_comp_fwd", C.byref(a), stream_ptr())
         ctx.blocks, ctx.comp, ctx.eps, ctx.n, ctx.Bs, ctx.NG, ctx.n_comp, ctx.ws, ctx.mean = blocks, comp, eps, n, Bs, NG, n_comp, ws, mean
         ctx.save_for_backward(*out["loc"], *out["scale"])
-        res = []
-        for g in range(NG):
-            qscale = out["scale"][g].clamp(min=1e-6)
-            res += [out["loc"][g], out["logvar"][g], out["scale"][g], out["logz"][g], out["theta"][g], kl[g], qscale]
-            ctx.mark_non_differentiable(out["theta"][g], qscale)
-        return tuple(res)
+        return _poe_result(ctx, out, kl, qscale=True)
 
     @staticmethod
     def backward(ctx, *g):
-        from ._abi import POE_COMP_SEG, SpvPoeCompArgs
         NG, n, Bs = ctx.NG, ctx.n, ctx.Bs
         loc, scale = ctx.saved_tensors[:NG], ctx.saved_tensors[NG:2 * NG]
         dev = loc[0].device
-        cont = lambda t: None if t is None else t.contiguous()
-        a = SpvPoeCompArgs()
-        W = 2 * n + 1
-        part = ctx.ws.get("poen_part", (NG, POE_COMP_SEG, ctx.n_comp, W), torch.float32)
-        a.ngroups, a.n, a.ncomp, a.part, a.mean = NG, n, ctx.n_comp, ptr(part), ptr(ctx.mean)
+        a, _mean = PoEComponents._args(NG, n, ctx.n_comp, ctx.ws, ctx.mean)
         keep, d = [], []
         for k in range(NG):
-            gl, gv, gs, gz, _gt, gk, _gq = (cont(t) for t in g[7 * k: 7 * k + 7])
+            keep += _poe_grads(a, k, g[7 * k: 7 * k + 6], loc[k], scale[k])
             dk = torch.empty((Bs[k], ctx.blocks[k][2]), dtype=torch.float32, device=dev)
             dpn = torch.empty((Bs[k], 2 * n), dtype=torch.float32, device=dev)
-            keep += [gl, gv, gs, gz, gk, dpn]
+            keep.append(dpn)
             d.append(dk)
-            a.B[k], a.stats[k], a.ld[k], a.comp[k], a.eps[k] = Bs[k], ctx.blocks[k][1], ctx.blocks[k][2], ptr(ctx.comp[k]), ptr(ctx.eps[k])
-            a.loc[k], a.scale[k] = ptr(loc[k]), ptr(scale[k])
-            a.g_loc[k], a.g_logvar[k], a.g_scale[k], a.g_logz[k], a.g_kl[k] = ptr(gl), ptr(gv), ptr(gs), ptr(gz), ptr(gk)
-            a.dpn[k], a.d_stats[k] = ptr(dpn), ptr(dk)
+            _poe_common(a, k, ctx.blocks[k], ctx.eps[k], Bs[k])
+            a.comp[k], a.dpn[k], a.d_stats[k] = ptr(ctx.comp[k]), ptr(dpn), ptr(dk)
         _abi.call("spv_poe_comp_bwd", C.byref(a), stream_ptr())
         grads = []
         for k in range(NG):
             grads += [d[k][:, :n], d[k][:, n:2 * n]]
         return (None, None, None, None, *grads)
+
+
