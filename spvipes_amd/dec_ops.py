@@ -214,7 +214,7 @@ class _DecoderBwd:
         # the wide layout (sl.kslots = 1) runs the in-place softmax fix and the split-K GEMMs: the fused one-pass backward kernels are
         # built for the narrow layout only
         wide = sl.kslots != 0
-        self.fused_dz = bool(_ops.FUSED_DZ and (not grads_f32 or _ops.FUSED_DZ_F32) and not wide)
+        self.fused_dz = bool(_ops.FUSED_DZ and not wide)
         self.dz_part = wsg.get("dec_dz_part", (P.gene_splits, Bp, sl.KPS), torch.float32) if self.fused_dz else None
         self.T = T = Gp // 32
         bt = Bp // 32
@@ -224,25 +224,24 @@ class _DecoderBwd:
         self.ksp_m, self.ksp_n = max(1, min(T // 8, -(-256 // max(Bp // 64, 1)))), max(1, min(T // 8, -(-512 // max(Bp // 128, 1))))
         self.csp_m, self.csp_n = max(1, min(bt // 8, -(-256 // max(Gp // 64, 1)))), max(1, min(bt // 8, -(-512 // max(Gp // 128, 1))))
         # bf16 mode: one streaming kernel for both regressor weight gradients (csrc/spv_dec_gemm.h)
-        self.heads_dma = bool(_ops.HEADS_DMA and nsplit == 1 and not grads_f32 and Bp % 64 == 0 and not wide)
+        self.heads_dma = bool(nsplit == 1 and not grads_f32 and Bp % 64 == 0 and not wide)
         if self.heads_dma:
             mt, kt = -(-G // 128), Bp // 64   # 128-gene workgroup tiles, two workgroups per CU
             self.csp_n = max(1, min(512 // mt if mt <= 512 else 1, max(kt // 4, 1)))
         # bf16 mode: the regressor weight gradients come out of the softmax-fix pass itself (spv_dec_heads_bwd), one partial slab per
         # 128-cell workgroup row
-        self.fused_heads = bool(_ops.FUSED_HEADS and not _ops.DZ_ONLY and self.fused_dz and self.heads_dma and Bp % DEC_CELLS_PER_WG == 0)
+        self.fused_heads = bool(self.fused_dz and self.heads_dma and Bp % DEC_CELLS_PER_WG == 0)
         # "fp32" mode (split-bf16 gradient words, round 4): the same one-pass kernel on the hi / lo planes -- no in-place fix of the four
         # planes and no register-staged weight-gradient GEMMs re-reading them
-        if _ops.FUSED_HEADS_F32 and grads_f32 and nsplit == 3 and not _ops.DZ_ONLY and self.fused_dz and Bp % DEC_CELLS_PER_WG == 0:
+        if grads_f32 and nsplit == 3 and self.fused_dz and Bp % DEC_CELLS_PER_WG == 0:
             self.fused_heads = True
         if self.fused_heads:
             self.csp_n = Bp // DEC_CELLS_PER_WG
             self.dw_part = wsg.get("dec_dW48", (self.csp_n, Gp, sl.KPS), torch.float32)   # [d W'_p | d W'_s] rows over the padded genes
         # bf16 mode: the two 320-column GEMMs run the LDS-DMA 128 x 320 kernels, which want their own split counts
-        # (d A_m of the two groups run side by side on the group streams; d W_m one after the other on the side stream)
-        self.ksp_m = self._splits(False, B, G, self.ksp_m, 128 if (pair and _ops.DEC_PAIR_SPLITS) else 256)
-        # the d A_m GEMM may sum its split-K slabs inside the launch (LDS-DMA kernels only)
-        self.can_fix_d = bool((_ops.DA_FIXUP == "1" or (_ops.DA_FIXUP == "fp32" and nsplit == 3)) and _abi.load().spv_gemm_bf16_uses_dma(0, B, KMP, G, nsplit, self.T, KMP))
+        # (d A_m of the two groups of a ``pair`` run side by side, K splits sized so that they share one round of workgroups; d W_m one
+        # after the other on the side stream)
+        self.ksp_m = self._splits(False, B, G, self.ksp_m, 128 if pair else 256)
         self.csp_m = self._splits(True, G, Bp, self.csp_m)
 
     def _operand(self, key: str):
@@ -257,14 +256,6 @@ class _DecoderBwd:
             _abi.call("spv_dec_heads_bwd", C.byref(self.P), ptr(self.S["Tp"]), ptr(self.S["Ts"]), ptr(self.dz_part), ptr(self.dw_part), stream_ptr())
             return
         _abi.call("spv_dec_softmax_bwd", C.byref(self.P), ptr(self.S["Tp"]), ptr(self.S["Ts"]), ptr(self.dz_part), stream_ptr())
-
-    def dz_only(self):
-        """read-only pass: the latent gradient of the rate heads (into dz_part), tP / tS left uncorrected"""
-        _abi.call("spv_dec_dz", C.byref(self.P), ptr(self.S["Tp"]), ptr(self.S["Ts"]), ptr(self.dz_part), stream_ptr())
-
-    def softmax_fix(self):
-        """the in-place correction of tP / tS alone (what gemm_bc consumes)"""
-        _abi.call("spv_dec_softmax_bwd", C.byref(self.P), ptr(self.S["Tp"]), ptr(self.S["Ts"]), None, stream_ptr())
 
     @staticmethod
     def _dma_splits(M: int, K: int, cus: int = 256) -> int:
@@ -286,21 +277,8 @@ class _DecoderBwd:
             return self._dma_splits(M, K, cus)
         return default
 
-    def gemm_d(self, fix=None):
-        """``fix``: (alpha, dAm [B][n_m], d_zcat [B][nt], n_m, nt) -- the slabs are summed inside the launch (spv_gemm_bf16_fix) straight into the
-        two consumers of d A_m; returns None then (nothing is left for spv_reduce_slabs)"""
+    def gemm_d(self):
         (Wm_hi, Wm_lo), (dL_hi, dL_lo) = self.S["Wm"], self._operand("dL")
-        if fix is not None and self.can_fix_d:
-            alpha, dAm, d_zcat, n_m, nt = fix
-            M, N, K = self.B, KMP, self.G
-            out = self.wsg.get("dec_dAm", (self.ksp_m, M, N), torch.float32)
-            fx = _abi.SpvGemmFixup()
-            fx.counters = ptr(self.wsg.get("dec_dAm_cnt", (-(-M // 128),), torch.int32, zero=True))
-            fx.alpha, fx.dst0, fx.ld0, fx.n0 = ptr(alpha), ptr(dAm), n_m, n_m
-            fx.dst1, fx.ld1, fx.c1, fx.n1 = ptr(d_zcat), nt, n_m, nt
-            _abi.call("spv_gemm_bf16_fix", 0, ptr(dL_hi), ptr(dL_lo), self.Gp, ptr(Wm_hi), ptr(Wm_lo) if Wm_lo is not None else None, KMP, ptr(out), N, M, N, K,
-                      self.nsplit, self.ksp_m, M * N, self.T, C.byref(fx), stream_ptr())
-            return None
         return _gemm_slabs(False, dL_hi, dL_lo, self.Gp, Wm_hi, Wm_lo, KMP, self.B, KMP, self.G, self.nsplit,
                            self.ksp_m, self.wsg, "dec_dAm", a_tiles=self.T)
 
@@ -375,7 +353,7 @@ class DecoderFused(torch.autograd.Function):
         n_p, n_s = lat[0][0].shape[1], lat[0][1].shape[1]
         nt = n_p + n_s
         sl = dec_slots(decoders[0])
-        DEC_KP, DEC_KS, DEC_KPS = sl.KP, sl.KS, sl.KPS
+        DEC_KPS = sl.KPS
         if any(dec_slots(d) != sl for d in decoders):
             raise _abi.SpvError("DecoderFused: the decoders of one call must share their operand layout")
         n_m = par[0][6].shape[0]
@@ -392,10 +370,9 @@ class DecoderFused(torch.autograd.Function):
         # ... and, from the same call, the decoder's packed bf16 operand images of these latents
         Am_img = [_bf16_image(ws[g], "dec_Am", Bp, KMP, mlo) for g in range(NG)]
         Aps_img = [_bf16_image(ws[g], "dec_Aps", Bp, DEC_KPS, True) for g in range(NG)]
-        fused_pack = bool(_ops.FUSED_PACK)
         lat = [(_cont(pz), _cont(qz)) for pz, qz in lat]
         keep = [t for pq in lat for t in pq]
-        za = _zsplit_args(B, Bp, n_p, n_s, n_m, sl, lat, zcat, *((Am_img, Aps_img) if fused_pack else ()))
+        za = _zsplit_args(B, Bp, n_p, n_s, n_m, sl, lat, zcat, Am_img, Aps_img)
         _abi.call("spv_zsplit_fwd", C.byref(za), stream_ptr())
         # ---- 2. batch statistics of z (column sums and z^T z) for the BatchNorm fold ---------------
         zsum = [[new(n_p), new(n_s)] for _ in range(NG)]
@@ -412,12 +389,14 @@ class DecoderFused(torch.autograd.Function):
         fb = _fold_batch(B, training, 0.01, sl)
         for g in range(NG):
             _add_fold(fb, decoders[g], par[g], n_p, n_s, zcat[g], zsum[g], zz[g], fstat[g], Wps[g], Gs[g], Gps[g], sl)
-        pair = _ops.dec_pair_for(B, NG)   # both groups' per-group launches as one grid per kernel (ops.DEC_PAIR)
+        # the schedule of this call AND of its backward pass (ops.DecSchedule): decided here, once
+        grads_f32 = bool(need_grad and mlo)
+        sched = _ops.dec_schedule(B, Gs, NG, grads_f32)
+        pair = sched.pair   # both groups' per-group launches as one grid per kernel (ops.DEC_PAIR)
         # The fold, the mixture-weight images and the (count, gene) tables depend on nothing the trunk (step 4) computes:
         # they run beside it on a side stream and are joined before the per-group section.
-        side = group_streams(dev, 3)[2] if _ops.OVERLAP_SMALL else torch.cuda.current_stream(dev)
-        if _ops.OVERLAP_SMALL:
-            side.wait_stream(torch.cuda.current_stream(dev))
+        side = group_streams(dev, 3, sched.serial)[2]
+        side.wait_stream(torch.cuda.current_stream(dev))
         Wm_img, tabs = [], []
         with torch.cuda.stream(side):
             _abi.call("spv_bn_fold_fwd", C.byref(fb), stream_ptr())
@@ -452,9 +431,8 @@ class DecoderFused(torch.autograd.Function):
             b = _lin_batch(B, relu=True)
             for g in range(NG):
                 _add_lin(b, N=n_m, K=nt, W=ptr(Wf[g]), bias=ptr(cf[g]), X=ptr(zcat[g]), ldx=nt, Y=ptr(m[g]), ldy=n_m)
-                if fused_pack:  # m straight into the logits operand image
-                    q = b.p[g]
-                    q.img_hi, q.img_lo, q.ld_img, q.img_rows = ptr(Am_img[g][0]), ptr(Am_img[g][1]), KMP, Bp
+                q = b.p[g]   # m straight into the logits operand image
+                q.img_hi, q.img_lo, q.ld_img, q.img_rows = ptr(Am_img[g][0]), ptr(Am_img[g][1]), KMP, Bp
             _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
         else:
             pre_a = [new(B, n_m) for _ in range(NG)]
@@ -464,12 +442,11 @@ class DecoderFused(torch.autograd.Function):
             _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
             nblk = -(-B // _abi.BN_ROWS)
             parts = [ws[g].get("trunk_bn_part", (nblk, n_m, 2), torch.float32) for g in range(NG)]
-            bn = _trunk_bn_batch(B, training, 0.01, decs, par, pre_a, m, tstat, parts, n_m, Am_img if fused_pack else None, Bp)
+            bn = _trunk_bn_batch(B, training, 0.01, decs, par, pre_a, m, tstat, parts, n_m, Am_img, Bp)
             _abi.call("spv_bn_fwd", C.byref(bn), stream_ptr())
         # ---- 5. per group: operand images, tables, logits GEMM, softmax statistics, likelihood ------
         if w_pad.numel() < Bp or w_pad.dtype != torch.float32 or not w_pad.is_contiguous():
             raise _abi.SpvError("DecoderFused: w_pad must be contiguous fp32 of length >= round_up(B, 128)")
-        grads_f32 = bool(need_grad and mlo)
         # bf16 mode: one bf16 array per gradient; fp32 mode: a bf16 hi plane followed by a bf16 lo plane ([2 Bp][Gp] rows):
         # the two operand images the split-bf16 GEMMs consume, written directly by the likelihood kernel
         gdt, gname, gplanes = (torch.int16, "split", 2) if grads_f32 else (torch.int16, "bf16", 1)
@@ -477,9 +454,8 @@ class DecoderFused(torch.autograd.Function):
         rec = [new(B) for _ in range(NG)]  # (allocated before the fork: every temporary belongs to the main stream)
         red = SpvReduceBatch()
         red.nprob = 0
-        if _ops.OVERLAP_SMALL:
-            torch.cuda.current_stream(dev).wait_stream(side)
-        streams = group_streams(dev, NG) if (_ops.FWD_GROUP_STREAMS and not pair) else [torch.cuda.current_stream(dev)] * NG
+        torch.cuda.current_stream(dev).wait_stream(side)
+        streams = group_streams(dev, NG, sched.serial) if not pair else [torch.cuda.current_stream(dev)] * NG
         fork(streams)
         dgrp = (SpvDecGroup * NG)() if pair else None
         lib_keep = []
@@ -488,13 +464,8 @@ class DecoderFused(torch.autograd.Function):
               G, Gp, wsg = Gs[g], Gps[g], ws[g]
               Wm_hi, Wm_lo = Wm_img[g]
               (Am_hi, Am_lo), (Aps_hi, Aps_lo) = Am_img[g], Aps_img[g]
-              if not fused_pack:
-                  _pack(m[g], Am_hi, Am_lo, dst_col_off=0, cslot=n_m)
-                  _pack(zcat[g], Am_hi, Am_lo, extra_one=True, dst_col_off=n_m, cslot=KMP - n_m)
-                  _pack(zcat[g][:, :n_p], Aps_hi, Aps_lo, extra_one=True, dst_col_off=0, cslot=DEC_KP)
-                  _pack(zcat[g][:, n_p:], Aps_hi, Aps_lo, extra_one=True, dst_col_off=DEC_KP, cslot=DEC_KS)
               logits = wsg.get("dec_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
-              lse_first = bool(_ops.STAGGER and g % 2 == 1)  # group 1 runs its (VALU-bound) softmax statistics beside group 0's logits GEMM
+              lse_first = g % 2 == 1  # group 1 runs its (VALU-bound) softmax statistics beside group 0's logits GEMM
               run_logits = lambda: _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(logits), int(mlo), stream_ptr())
               if not lse_first and not pair:
                   run_logits()
@@ -546,7 +517,7 @@ class DecoderFused(torch.autograd.Function):
             ctx.small = (zcat, zsum, zz, fstat, pre_a, m, tstat)
             ctx.trunk = (Wf, cf, zsum_t, zz_t) if trunk_fold else None
             ctx.gkl, ctx.n_kl = gkl, n_kl
-            ctx.sl = sl
+            ctx.sl, ctx.sched = sl, sched
             ctx.save_for_backward(*tensors[:2 * NG + NG * N_DEC_PARAMS])
         ctx.mark_non_differentiable(rec_sum, *rec)
         return (loss, rec_sum, *rec)
@@ -576,29 +547,26 @@ class DecoderFused(torch.autograd.Function):
         dWp, dWs = [new(Gs[g], DEC_KP) for g in range(NG)], [new(Gs[g], DEC_KS) for g in range(NG)]
         dAm, d_zcat = [new(B, n_m) for _ in range(NG)], [new(B, nt) for _ in range(NG)]
         # ---- schedule ---------------------------------------------------------------------------------------------
-        # group g's softmax fix and d A_m GEMM on group stream g; the regressor weight-gradient GEMMs (first needed by the
-        # BatchNorm-fold backward, which sits behind the ~15 small launches of the trunk backward) and then the
-        # mixture-weight GEMMs (which feed only the optimiser) on the side stream, beside the trunk / PoE / encoder-tail
-        # backward chain; the side stream is joined at the end of the backward pass (train.Trainer, DEFER_JOIN) or before
-        # returning.  Same-box A/B: SPV_DEFER_BC 1.90 -> 1.82 ms.  (Measured and left out: running the softmax fix BESIDE
-        # the d A_m GEMM + trunk backward instead of ahead of them, +0.01 ms.)
+        # The d A_m GEMMs go first, group g's on group stream g: the critical chain (trunk / fold / PoE / encoder backward) needs only
+        # d A_m up to the point where the latent gradient of the rate heads joins (red2).  The HBM-bound one-pass softmax / heads
+        # kernels run on the side stream, then the regressor weight-gradient reductions (first needed by the BatchNorm-fold backward,
+        # which sits behind the ~15 small launches of the trunk backward) and the mixture-weight GEMMs (which feed only the
+        # optimiser), beside the trunk / PoE / encoder-tail backward chain; the side stream is joined at the end of the backward
+        # pass (train.Trainer, DEFER_JOIN) or before returning.  Everything the switches and the step shape decide was fixed by
+        # the forward pass (ctx.sched): nothing here asks ops for it again.
+        sched = ctx.sched
         cur = torch.cuda.current_stream(dev)
-        streams = group_streams(dev, NG) if _ops.BWD_GROUP_STREAMS else [cur] * NG
-        side = group_streams(dev, 3)[2] if _ops.DEFER_WM else cur
-        stages = [_DecoderBwd(g, ctx.P[g], ctx.saved_g[g], ctx.Wps[g], ws[g], B, Bp, Gs[g], Gps[g], nsplit, ctx.grads_f32, pair=(NG == 2 and _ops.BWD_GROUP_STREAMS), sl=sl) for g in range(NG)]
-        d_slabs, bc_slabs, ef_slabs = [None] * NG, [None] * NG, [None] * NG
-        # bf16 mode with the regressor GEMMs deferred to the side stream: the critical chain only needs the latent gradient, which
-        # the READ-ONLY pass spv_dec_dz gives (168 MB read per group instead of 336 MB read + written); the in-place fix of
-        # tP / tS runs on the side stream right before the GEMMs that consume it
-        split_fix = bool(_ops.DZ_ONLY and _ops.DEFER_BC and _ops.DEFER_WM and all(st.fused_dz for st in stages))
-        # DA_FIRST: the critical chain (trunk / fold / PoE / encoder backward) only needs d A_m up to the point where the latent
-        # gradient of the rate heads joins (red2) -- so the two d A_m GEMMs go first and the HBM-bound softmax fixes move to the
-        # side stream, ahead of the regressor and mixture weight-gradient GEMMs they feed
-        da_first = int(_ops.DA_FIRST) if (_ops.DEFER_BC and _ops.DEFER_WM and side is not cur and not split_fix and all(st.fused_dz for st in stages)) else 0
+        streams = group_streams(dev, NG, sched.serial)
+        side = group_streams(dev, 3, sched.serial)[2]
+        stages = [_DecoderBwd(g, ctx.P[g], ctx.saved_g[g], ctx.Wps[g], ws[g], B, Bp, Gs[g], Gps[g], nsplit, ctx.grads_f32, pair=(NG == 2), sl=sl) for g in range(NG)]
+        d_slabs, ef_slabs = [None] * NG, [None] * NG
+        # without a second stream, or where the softmax fix does not yield the latent gradient (wide layout, ops.FUSED_DZ off), the
+        # softmax kernels stay ahead of the d A_m GEMMs on the group streams
+        da_first = side is not cur and all(st.fused_dz for st in stages)
         sm_done = None
-        wm_late = bool(_ops.wm_late_for(max(Gs), bool(ctx.grads_f32)) and side is not cur)
-        # ops.DEC_PAIR: the default schedule's per-group launches (d A_m GEMMs, one-pass backward, d W_m GEMMs) as one grid per kernel
-        pair = bool(_ops.dec_pair_for(B, NG) and da_first in (0, 1) and not split_fix and _ops.DEFER_BC and all(st.fused_heads and not st.grads_f32 for st in stages))
+        wm_late = bool(sched.wm_late and side is not cur)
+        # ops.DEC_PAIR: the per-group launches (d A_m GEMMs, one-pass backward, d W_m GEMMs) as one grid per kernel
+        pair = bool(sched.pair and all(st.fused_heads and not st.grads_f32 for st in stages))
 
         def pair_gemm(which):
             ga = (SpvGemmArgs * NG)()
@@ -618,55 +586,32 @@ class DecoderFused(torch.autograd.Function):
             if not da_first:   # (single stream: the one-pass backward first, as the per-group schedule orders it)
                 pair_heads_bwd()
             d_slabs = pair_gemm("d")
-        if da_first == 2:
-            side.wait_stream(cur)
         fork(streams)
-        for g in range(NG):
-            if pair:
-                continue
-            if da_first:
-                with torch.cuda.stream(streams[g]):
-                    d_slabs[g] = stages[g].gemm_d(fix=(g_loss, dAm[g], d_zcat[g], n_m, nt))
-                continue
+        for g in range(0 if pair else NG):
             with torch.cuda.stream(streams[g]):
-                # group 1 issues its (MFMA / LDS-bound) d A_m GEMM BEFORE its (HBM-bound) softmax fix, group 0 the other way round: the two
-                # streams then pair a bandwidth-bound kernel with a compute-bound one instead of two of a kind (ops.STAGGER_BWD)
-                gemm_first = bool(_ops.STAGGER_BWD and g % 2 == 1)
-                if gemm_first:
-                    d_slabs[g] = stages[g].gemm_d()
-                if split_fix:
-                    stages[g].dz_only()
-                else:
+                if not da_first:
                     stages[g].softmax()
-                if not gemm_first:
-                    d_slabs[g] = stages[g].gemm_d()
-                if not _ops.DEFER_BC:
-                    bc_slabs[g] = stages[g].gemm_bc()
+                d_slabs[g] = stages[g].gemm_d()
                 if not stages[g].fused_dz:
                     ef_slabs[g] = stages[g].gemm_ef()
         join(streams)
-        if _ops.DEFER_WM and da_first != 2:
-            side.wait_stream(cur)   # (before the reductions: the side work needs none of them)
+        side.wait_stream(cur)   # (before the reductions: the side work needs none of them)
         if da_first:
             with torch.cuda.stream(side):
                 if pair:
                     pair_heads_bwd()
-                for g in range(NG):
-                    if pair:
-                        break
-                    stages[g].softmax()
+                else:
+                    for st in stages:
+                        st.softmax()
                 sm_done = torch.cuda.Event()
                 sm_done.record(side)
         # slab sums, scaled by the upstream gradient, straight into their consumers' buffers
         al = g_loss
         for g in range(NG):
             st, G, Gp = stages[g], Gs[g], Gps[g]
-            if bc_slabs[g] is not None:
-                _add_heads_red(red, st, bc_slabs[g], dWp[g], dWs[g], sl, al)
-            if d_slabs[g] is not None:   # (else: the GEMM summed its slabs itself, straight into dAm / d_zcat -- spv_gemm_bf16_fix)
-                _add_red(red, d_slabs[g], st.ksp_m, B * KMP, KMP, B, n_m, dAm[g], n_m, alpha=al)                          # d m (trunk output)
-                # gradient reaching zcat directly: through the logits GEMM (columns n_m..) and the two regressors
-                _add_red(red, d_slabs[g], st.ksp_m, B * KMP, KMP, B, nt, d_zcat[g], nt, col_off=n_m, alpha=al)
+            _add_red(red, d_slabs[g], st.ksp_m, B * KMP, KMP, B, n_m, dAm[g], n_m, alpha=al)                          # d m (trunk output)
+            # gradient reaching zcat directly: through the logits GEMM (columns n_m..) and the two regressors
+            _add_red(red, d_slabs[g], st.ksp_m, B * KMP, KMP, B, nt, d_zcat[g], nt, col_off=n_m, alpha=al)
             if st.fused_dz:
                 _add_red(red2, st.dz_part, st.P.gene_splits, Bp * DEC_KPS, DEC_KPS, B, n_p, d_zcat[g], nt, accumulate=True, alpha=al)
                 _add_red(red2, st.dz_part, st.P.gene_splits, Bp * DEC_KPS, DEC_KPS, B, n_s, d_zcat[g], nt, col_off=DEC_KP, dst_col=n_p, accumulate=True, alpha=al)
@@ -692,18 +637,14 @@ class DecoderFused(torch.autograd.Function):
         # pass, which feed nothing but the optimiser)
         bc_done = None
         with torch.cuda.stream(side):
-            if _ops.DEFER_BC:
-                red_bc = SpvReduceBatch()
-                red_bc.nprob = 0
-                for g in range(NG):
-                    st = stages[g]
-                    if split_fix:
-                        st.softmax_fix()
-                    _add_heads_red(red_bc, st, st.gemm_bc(), dWp[g], dWs[g], sl, g_loss)
-                _run_red(red_bc)
-                if side is not cur:
-                    bc_done = torch.cuda.Event()
-                    bc_done.record(side)
+            red_bc = SpvReduceBatch()
+            red_bc.nprob = 0
+            for g in range(NG):
+                _add_heads_red(red_bc, stages[g], stages[g].gemm_bc(), dWp[g], dWs[g], sl, g_loss)
+            _run_red(red_bc)
+            if side is not cur:
+                bc_done = torch.cuda.Event()
+                bc_done.record(side)
 
         def issue_wm(after=None):
             with torch.cuda.stream(side):
@@ -718,9 +659,7 @@ class DecoderFused(torch.autograd.Function):
                     _add_red(red3, a, st.csp_m, G * KMP, KMP, G, KM - 1, pg[g][10][0], KM - 1, alpha=g_loss)                 # d W_m
                     _add_red(red3, a, st.csp_m, G * KMP, KMP, G, 1, pg[g][11][0], 1, col_off=KM - 1, alpha=g_loss)           # d b_m
                 _run_red(red3)
-            if not _ops.DEFER_WM:
-                pass
-            elif _ops.DEFER_JOIN:
+            if _ops.DEFER_JOIN:
                 _ops.defer(side, [g_loss])
             else:
                 cur.wait_stream(side)

@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -262,14 +262,15 @@ def serial_streams() -> bool:
     return SERIAL_STREAMS or (SERIAL_AUTO and _SMALL_STEP and DEC_PAIR != "0")
 
 
-def group_streams(device, n: int = 2):
+def group_streams(device, n: int = 2, serial: Optional[bool] = None):
     """[current stream, side stream, ...]: the two groups' launch chains are independent for long stretches of the step
     (fc1, operand packing, logits / lse / likelihood, the backward GEMMs) and most of those kernels leave CUs idle on
     their own, so group 1 runs on a side stream: fork with ``fork(streams)``, join with ``join(streams)``.  Under
-    hipGraph capture the fork/join become parallel branches of the graph."""
+    hipGraph capture the fork/join become parallel branches of the graph.  ``serial``: a decision taken earlier
+    (DecSchedule.serial) instead of ``serial_streams()`` now."""
     dev = torch.device(device)
     out = [torch.cuda.current_stream(dev)]
-    if serial_streams():  # every chain on the caller's stream: kernels run one at a time (per-kernel timing, debugging; small steps)
+    if serial_streams() if serial is None else serial:  # every chain on the caller's stream: kernels run one at a time (per-kernel timing, debugging; small steps)
         return out * n
     for i in range(1, n):
         key = (dev.index, i)
@@ -294,10 +295,12 @@ def join(streams) -> None:
 # possible.  With DEFER_JOIN False the join happens before DecoderFused.backward returns (any caller may then read .grad);
 # train.Trainer sets it True around its backward pass and joins with ``join_pending`` right after it.
 DEFER_JOIN = False
-OVERLAP_SMALL = os.environ.get("SPV_OVERLAP_SMALL", "1") != "0"  # side-stream overlap of independent small-kernel groups
-STAGGER = os.environ.get("SPV_STAGGER", "1") != "0"  # group 1 orders its independent kernels differently from group 0
-STAGGER_BWD = os.environ.get("SPV_STAGGER_BWD", "0") != "0"  # backward: group 1 runs its d A_m GEMM ahead of its softmax fix (A/B on MI355X: 1.703 vs 1.693 ms, noise -> off)
-DA_FIRST = int(os.environ.get("SPV_DA_FIRST", "1"))  # backward: d A_m GEMMs first, softmax fixes on the side stream (1: side starts after them, 2: with them); A/B with the half-chip d A_m launches: -9 / -3 us on two boxes
+# Settled by same-box A/B and no longer switches (the variants and their numbers: docs/lab_notes.md, "Schedule variants tried and
+# retired").  Forward: the fold / weight images / tables run beside the trunk on the side stream; the two groups' chains run on the group
+# streams, group 1 with its softmax statistics ahead of its logits GEMM; the latent and trunk kernels write the decoder's operand images.
+# Backward: the d A_m GEMMs go first (K splits sized so that a pair of groups shares one round of workgroups), the one-pass softmax /
+# heads kernels, the regressor and the mixture weight-gradient GEMMs follow on the side stream; split-K slabs are summed by spv_reduce_slabs.
+
 # mixture-weight GEMMs held back until the BatchNorm-fold backward (beside the tiny-kernel tail) instead of beside the trunk backward, which they
 # slow down.  Same box, ms/step, held back / not: C3 (G 20 000) 2.118 2.122 / 2.157 2.152; C2 1.307 1.316 1.318 1.343 1.313 1.320 / 1.323 1.314
 # 1.312 1.317 1.313 1.316; C5 4.941 4.965 4.946 5.022 5.003 / 4.981 4.904 4.921 5.005 5.001; C2 split words 2.125 2.133 / 2.122 2.115; C4 3.618
@@ -339,42 +342,31 @@ def dec_pair_for(B: int, n_groups: int) -> bool:
     return True if DEC_PAIR == "1" else _SMALL_STEP
 
 
+class DecSchedule(NamedTuple):
+    """What one DecoderFused call's schedule takes from the switches and the step shape.  Decided ONCE, in forward, and carried on
+    ``ctx``: a forward pass of another shape between a step's forward and its backward must not change the backward's launches."""
+
+    serial: bool    # every chain on the caller's stream (group_streams(..., serial=...))
+    pair: bool      # one grid per decoder kernel for the two groups
+    wm_late: bool   # mixture-weight GEMMs held back until the BatchNorm-fold backward
+
+
+def dec_schedule(B: int, Gs: Sequence[int], n_groups: int, grads_f32: bool) -> DecSchedule:
+    """the schedule of a DecoderFused call over ``n_groups`` groups of ``Gs`` genes, as the switches and set_step_shape stand now"""
+    return DecSchedule(bool(serial_streams()), bool(dec_pair_for(B, n_groups)), bool(wm_late_for(max(Gs), grads_f32)))
+
+
 FC1_PAIR_SPLITS = os.environ.get("SPV_FC1_PAIR_SPLITS", "1") != "0"  # grouped fc1 forward: K splits sized for the pair's shared grid
-DEC_PAIR_SPLITS = os.environ.get("SPV_DEC_PAIR_SPLITS", "1") != "0"  # d A_m GEMMs of the two groups: K splits sized so that the pair shares one round
-HEADS_DMA = os.environ.get("SPV_HEADS_DMA", "1") != "0"  # both regressor weight gradients in one LDS-DMA pass (spv_dec_heads_wgrad)
-# bf16 mode: the softmax fix, the latent gradient AND the regressor weight gradients from ONE read-only pass over t_P / t_S
-# (spv_dec_heads_bwd): no write-back of the corrected arrays, no second pass over them
-FUSED_HEADS = os.environ.get("SPV_FUSED_HEADS", "1") != "0"
 # workgroups the softmax-statistics / softmax-fix kernels are split into (cell blocks x gene splits).  512 = ONE round of two workgroups per CU, and half the
 # per-split partials (statistics, latent gradient) to write and re-read.  Same-box A/B 1024 / 768 / 512 / 384 / 256 at C2: 1.440 / 1.438 / 1.412 / 1.417 / 1.426 ms;
 # C3 2.39 -> 2.36, C4 3.90 -> 3.88, C5 8.29 -> 8.18, C1 unchanged
 GSPLIT_WANT = int(os.environ.get("SPV_GSPLIT_WANT", "512"))
-FUSED_HEADS_F32 = os.environ.get("SPV_FUSED_HEADS_F32", "1") != "0"   # ... and in "fp32" mode on the hi / lo planes of the split gradient words (spv_dec_heads_bwd, grads_f32)
-FUSED_DZ = os.environ.get("SPV_FUSED_DZ", "1") != "0"  # softmax fix also produces the latent gradient of the rate heads
-FUSED_DZ_F32 = os.environ.get("SPV_FUSED_DZ_F32", "1") != "0"   # "fp32" mode: the latent gradient of the rate heads comes out of the softmax-fix pass too (split-bf16 contraction)
-# d A_m GEMM sums its split-K slabs inside the launch (spv_gemm_bf16_fix: the last-arriving tile of a row block adds the slabs) instead of
-# a reduction launch on the critical chain.  Measured and NOT the default: the finisher of a 128 x 320 tile re-reads splits x 160 KB
-# (600 KB at c2) at the tail of a short launch while the other CUs are already idle, and that costs more than the 1.5 us boundary plus the
-# chip-wide reduction it replaces.  Same box, ms/step, with / without: c2 bf16 1.3268 1.3029 1.3165 / 1.2873 1.2840 1.2979;
-# c2 split words 2.214 2.203 2.208 / 2.193 2.184 2.172; c5 5.018 5.016 / 5.031 5.019 (first box: 5.032 / 5.100); c4 3.761 3.789 /
-# 3.797 3.793.  "1" = on wherever the LDS-DMA kernels run, "fp32" = split-word mode only.  (tests/test_gpu_gemm_fixup.py keeps the
-# entry point bit-exact against the slab sum.)
-DA_FIXUP = os.environ.get("SPV_DA_FIXUP", "0")
+# the softmax fix also yields the latent gradient of the rate heads (both precisions); off: the in-place fix plus the gemm_ef GEMMs
+FUSED_DZ = os.environ.get("SPV_FUSED_DZ", "1") != "0"
 # a small layer's input and weight gradients as ONE launch (spv_linear_bwd; the slice sum of the weight gradient rides in the next such launch or runs
 # alone) instead of dgrad, wgrad and wgrad-reduce launches one after the other; "0": the separate launches.  Same kernel bodies, same bits.
 LINEAR_BWD = os.environ.get("SPV_LINEAR_BWD", "1") != "0"
 TRUNK_FOLD = os.environ.get("SPV_TRUNK_FOLD", "1") != "0"  # the mixing trunk's BatchNorm folded into its Linear (spv_trunk_fold_fwd / _bwd)
-FUSED_PACK = os.environ.get("SPV_FUSED_PACK", "1") != "0"  # latent / trunk kernels also write the decoder's bf16 operand images
-DEFER_WM = os.environ.get("SPV_DEFER_WM", "1") != "0"  # mixture-weight gradient GEMMs on the late side stream
-DEFER_BC = os.environ.get("SPV_DEFER_BC", "1") != "0"  # regressor weight-gradient GEMMs beside the trunk backward (side stream)
-# critical chain runs the read-only latent-gradient pass (spv_dec_dz), the in-place softmax fix moves beside it on the side stream.
-# Measured at C2, same box, alternating (round 2): OFF 1.690 / 1.690 ms per step, ON 1.745 / 1.737 ms -- the second pass over the two
-# gradient arrays (2 x 168 MB more HBM reads per step) costs more than the shorter critical chain gains.  Kept as a switch, off.
-DZ_ONLY = os.environ.get("SPV_DZ_ONLY", "0") != "0"
-# the two groups' decoder-forward chains (logits GEMM, softmax statistics, likelihood) / d A_m GEMMs on two streams (parallel graph
-# branches) or one after the other on the caller's stream (every fork / join of graph branches leaves the GPU idle for >= 10 us)
-FWD_GROUP_STREAMS = os.environ.get("SPV_FWD_GROUP_STREAMS", "1") != "0"
-BWD_GROUP_STREAMS = os.environ.get("SPV_BWD_GROUP_STREAMS", "1") != "0"
 _PENDING: list = []
 _PENDING_KEEP: list = []
 
