@@ -402,6 +402,38 @@ typedef struct spv_dec_sample_stats_args {
 } spv_dec_sample_stats_args;
 int spv_dec_sample_stats(const spv_dec_params* p, const spv_dec_sample_stats_args* a, void* stream);
 
+/* Expected-expression statistics (expression_statistics): spv_dec_expected's values for one group and one minibatch (the NB mixture
+ * of nn/networks.py:314-325 and module/spVIPESmodule.py:751-759), reduced over the cells of each segment instead of stored.
+ * `p`, Am / Wm, K, nsplit, genes / n_genes: exactly as spv_dec_expected takes them; with
+ * v_w(b, j) the fp32 value that entry point writes for what = w (0 mixture mean, 1 private part, 2 shared part, 3 mixing weight) at
+ * alpha = 1, bit for bit,
+ *   stats[k][w][j] += sum of v_w(b, genes[j])        stats[k][4 + w][j] += sum of v_w(b, genes[j])^2        (w = 0 .. 3)
+ * over the counted cells b of segment k.  stats: fp64 device array [n_seg][8][ld_stats], ld_stats >= n_genes.  Every value is widened
+ * to fp64 before it is added and its square is formed in fp64 (exact).
+ * The cells arrive arranged by segment, in tiles of 32 consecutive operand rows:
+ *   tile_seg: int32 device array [Bp / 32]: the segment of tile t; a negative code or a code >= n_seg skips the whole tile.
+ *   tile_n:   int32 device array [Bp / 32]: the first tile_n[t] rows of tile t count (values above 32 mean 32, values <= 0 skip the
+ *             tile); the other rows of the tile and rows >= B are padding and are never counted.  Entries of tiles that lie wholly at
+ *             or beyond row B are not read.
+ *   ws:       fp64 device scratch of spv_dec_expected_stats_ws_bytes(n_genes, Bp / 32) bytes = [Bp / 32][8][n_genes]: a workgroup
+ *             per counted tile writes the tile's eight partial sums per gene, a second kernel of the same call adds them onto `stats`
+ *             tile after tile in ascending order (one writer per table element).
+ * Everything ACCUMULATES: the caller zeroes `stats` once, and one table collects a whole walk.  There are no floating-point atomics
+ * and the order of every addition is fixed by (B, tile_seg, tile_n): two calls agree bit for bit.  Columns >= n_genes, rows of
+ * segments no counted tile belongs to and everything beyond ws_bytes are never touched; a repeated gene of the selection fills its
+ * own column.  Nothing is allocated; two launches on `stream`. */
+typedef struct spv_dec_expected_stats_args {
+  const uint16_t* Am_hi; const uint16_t* Am_lo; const uint16_t* Wm_hi; const uint16_t* Wm_lo;
+  int32_t K, nsplit;
+  const int32_t* genes; int32_t n_genes; int32_t n_seg;
+  const int32_t* tile_seg;
+  const int32_t* tile_n;
+  double* stats; int64_t ld_stats;
+  double* ws;
+} spv_dec_expected_stats_args;
+int spv_dec_expected_stats(const spv_dec_params* p, const spv_dec_expected_stats_args* a, void* stream);
+int64_t spv_dec_expected_stats_ws_bytes(int32_t n_genes, int32_t n_cell_tiles);
+
 /* The same sampler over given parameters (the law of module/spVIPESmodule.py:751-759 for anyone who holds its parameters):
  *   out[r * ld_out + g] ~ NBMix(rate_p[r * ld_in + g], rate_s[r * ld_in + g], theta[g], logit[r * ld_in + g]),  r < R, g < G
  * fp32 device inputs, int32 device output; ld_in, ld_out >= G.  key / sample / cell_ids (int32 [R] or NULL = the row number) mean

@@ -244,6 +244,13 @@ class SpvDecSampleStatsArgs(C.Structure):
                 ("cell_total", C.c_void_p)]
 
 
+class SpvDecExpectedStatsArgs(C.Structure):
+    """the arguments of spv_dec_expected_stats (include/spvipes_hip.h: spv_dec_expected_stats_args)"""
+    _fields_ = [("Am_hi", C.c_void_p), ("Am_lo", C.c_void_p), ("Wm_hi", C.c_void_p), ("Wm_lo", C.c_void_p), ("K", C.c_int32), ("nsplit", C.c_int32),
+                ("genes", C.c_void_p), ("n_genes", C.c_int32), ("n_seg", C.c_int32), ("tile_seg", C.c_void_p), ("tile_n", C.c_void_p),
+                ("stats", C.c_void_p), ("ld_stats", C.c_int64), ("ws", C.c_void_p)]
+
+
 class SpvDePairsArgs(C.Structure):
     """the arguments of spv_de_pairs (include/spvipes_hip.h: spv_de_pairs_args)"""
     _fields_ = [("bank1", C.c_void_p), ("bank2", C.c_void_p), ("ld1", C.c_int64), ("ld2", C.c_int64), ("rows1", C.c_void_p), ("rows2", C.c_void_p),
@@ -327,6 +334,8 @@ _SIGNATURES = {
     "spv_dec_expected": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecExpectedArgs), C.c_void_p]),
     "spv_dec_sample": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecSampleArgs), C.c_void_p]),
     "spv_dec_sample_stats": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecSampleStatsArgs), C.c_void_p]),
+    "spv_dec_expected_stats": (C.c_int, [C.POINTER(SpvDecParams), C.POINTER(SpvDecExpectedStatsArgs), C.c_void_p]),
+    "spv_dec_expected_stats_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "spv_nbmix_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32,
                                    C.c_void_p, C.c_int64, C.c_void_p]),
     "spv_de_pairs": (C.c_int, [C.POINTER(SpvDePairsArgs), C.c_void_p]),

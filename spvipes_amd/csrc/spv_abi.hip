@@ -8,6 +8,7 @@
 #include "spv_dec_expected.h"
 #include "spv_dec_sample.h"
 #include "spv_dec_sample_stats.h"
+#include "spv_dec_expected_stats.h"
 #include "spv_de.h"
 #include "spv_de_median.h"
 #include "spv_count_stats.h"
@@ -853,6 +854,43 @@ extern "C" int spv_dec_sample_stats(const spv_dec_params* q, const spv_dec_sampl
   else if (wide) hipLaunchKernelGGL((dec_sample_stats_kernel<1, 2>), grid, dim3(256), 0, s, p, a);
   else hipLaunchKernelGGL((dec_sample_stats_kernel<1, 1>), grid, dim3(256), 0, s, p, a);
   return launch_status("spv_dec_sample_stats");
+}
+
+extern "C" int64_t spv_dec_expected_stats_ws_bytes(int32_t n_genes, int32_t n_cell_tiles) {
+  if (n_genes <= 0 || n_cell_tiles <= 0) return 0;
+  return (int64_t)n_cell_tiles * DXS_ROWS * n_genes * (int64_t)sizeof(double);
+}
+
+extern "C" int spv_dec_expected_stats(const spv_dec_params* q, const spv_dec_expected_stats_args* x, void* stream) {
+  DecParams p;
+  dim3 grid;
+  // readout_prepare checks the fields the read-outs share under spv_dec_expected's names: the table stands in for its `out`
+  spv_dec_expected_args y{};
+  if (x) {
+    y.Am_hi = x->Am_hi; y.Am_lo = x->Am_lo; y.Wm_hi = x->Wm_hi; y.Wm_lo = x->Wm_lo; y.K = x->K; y.nsplit = x->nsplit;
+    y.genes = x->genes; y.n_genes = x->n_genes; y.out = reinterpret_cast<float*>(x->stats);
+  }
+  int rc = readout_prepare(q, "spv_dec_expected_stats", x ? &y : nullptr, p, grid);
+  if (rc != SPV_OK) return rc;
+  if (!x->ws) return fail(SPV_ERR_ARG, "spv_dec_expected_stats: null workspace%s");
+  if (!x->tile_seg) return fail(SPV_ERR_ARG, "spv_dec_expected_stats: null tile_seg%s");
+  if (!x->tile_n) return fail(SPV_ERR_ARG, "spv_dec_expected_stats: null tile_n%s");
+  if (x->n_seg < 1) return fail(SPV_ERR_ARG, "spv_dec_expected_stats: n_seg < 1%s");
+  if (x->ld_stats < x->n_genes) return fail(SPV_ERR_ARG, "spv_dec_expected_stats: ld_stats < n_genes%s");
+  const DecExpStatsArgs a{(const bf16_t*)x->Am_hi, (const bf16_t*)x->Am_lo, (const bf16_t*)x->Wm_hi, (const bf16_t*)x->Wm_lo, x->K,
+                          x->genes, x->n_genes, x->n_seg, x->tile_seg, x->tile_n, x->ws};
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = dec_kw(q) == 2;
+  if (x->nsplit == 3 && wide) hipLaunchKernelGGL((dec_expected_stats_kernel<3, 2>), grid, dim3(256), 0, s, p, a);
+  else if (x->nsplit == 3) hipLaunchKernelGGL((dec_expected_stats_kernel<3, 1>), grid, dim3(256), 0, s, p, a);
+  else if (wide) hipLaunchKernelGGL((dec_expected_stats_kernel<1, 2>), grid, dim3(256), 0, s, p, a);
+  else hipLaunchKernelGGL((dec_expected_stats_kernel<1, 1>), grid, dim3(256), 0, s, p, a);
+  rc = launch_status("spv_dec_expected_stats");
+  if (rc != SPV_OK) return rc;
+  // the tiles' partial sums -> the table: one thread per (row, gene), the cell tiles in ascending order
+  hipLaunchKernelGGL(dec_expected_stats_merge_kernel, dim3((x->n_genes + 255) / 256, DXS_ROWS), dim3(256), 0, s, x->tile_seg, x->tile_n,
+                     p.Bp / DX_CELLS, x->n_seg, p.B, x->n_genes, (const double*)x->ws, x->stats, (long)x->ld_stats);
+  return launch_status("spv_dec_expected_stats");
 }
 
 extern "C" int spv_nbmix_sample(const float* rate_p, const float* rate_s, const float* logit, int64_t ld_in, const float* theta, int32_t R, int32_t G,

@@ -819,3 +819,85 @@ def ppc_frame(names, sizes, index, obs, ppc, n_samples: int, cells, order, kept,
     totals[0, order], totals[1, kept] = obs_totals, np.asarray(ppc_totals)[kept].astype(np.float64) / n_samples
     frame.attrs["cell_totals"] = pd.DataFrame({"obs_total": totals[0], "ppc_total_mean": totals[1]}, index=cells)
     return frame
+
+
+# ---- expected-expression statistics (model.expression_statistics): the tile plan of a step and the result table ---------------------
+EXPRESSION_STATS = ("mean", "mean_private", "mean_shared", "mixing", "private_fraction", "var", "var_private", "var_shared", "var_mixing")
+
+
+def expression_tile_plan(seg, n_seg: int, tile: int = 32):
+    """One minibatch's per-cell segment codes -> (perm, tile_seg, tile_n), the arrangement spv_dec_expected_stats reduces in a fixed order.
+    ``seg``: one code per row of the step; a code of -1 (any negative one) or >= ``n_seg`` means the cell is not counted.
+      perm      int64 row numbers, a multiple of ``tile`` long: for each segment present, in ascending order, its rows in walk order,
+                the run padded to a multiple of ``tile`` by repeating the run's first row; rows that are not counted do not appear
+      tile_seg  int32, one per ``tile`` rows of ``perm``: the tile's segment
+      tile_n    int32, one per tile: how many of its leading rows count (``tile`` everywhere but in a run's last tile)
+    A step without a counted cell gives three empty arrays: the caller skips it."""
+    if isinstance(n_seg, bool) or not isinstance(n_seg, (int, np.integer)) or int(n_seg) < 1:
+        raise ValueError(f"n_seg must be a positive integer, got {n_seg!r}")
+    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or int(tile) < 1:
+        raise ValueError(f"tile must be a positive integer, got {tile!r}")
+    code = np.asarray(seg).ravel()
+    if code.size and not np.issubdtype(code.dtype, np.integer):
+        raise TypeError("seg must hold integer segment codes")
+    code, tile = code.astype(np.int64), int(tile)
+    counted = (code >= 0) & (code < int(n_seg))
+    perm, tile_seg, tile_n = [], [], []
+    for k in np.unique(code[counted]).tolist():   # ascending
+        rows = np.nonzero(code == k)[0]           # walk order
+        n_tiles = -(-rows.size // tile)
+        run = np.full(n_tiles * tile, rows[0], dtype=np.int64)
+        run[:rows.size] = rows
+        perm.append(run)
+        tile_seg += [k] * n_tiles
+        tile_n += [tile] * (n_tiles - 1) + [rows.size - (n_tiles - 1) * tile]
+    perm = np.concatenate(perm) if perm else np.zeros(0, dtype=np.int64)
+    return perm, np.asarray(tile_seg, dtype=np.int32), np.asarray(tile_n, dtype=np.int32)
+
+
+def expression_stats_table(stats, counts):
+    """The per-(segment, gene) columns of expression_statistics from a table of spv_dec_expected_stats -> pandas DataFrame, one row per
+    (segment, column) in segment-major order, with the columns ``segment``, ``column`` and EXPRESSION_STATS, all float64.
+    ``stats``: fp64 [n_seg, 8, n_sel]: rows 0..3 the sums S of the mixture mean, its private part, its shared part and the mixing
+    weight, rows 4..7 the sums Q of their squares.  ``counts``: n_k = how many values segment k's entries were summed over
+    (cells x samples).
+        mean* / mixing = S / n, NaN for n < 1        var* = max(0, (Q - S^2 / n) / (n - 1)), NaN for n < 2
+        private_fraction = S_private / S_mixture, NaN where S_mixture is 0 (and for n < 1)
+    (the unbiased sample variance; the clamp removes the small negative values cancellation leaves for a constant column)."""
+    import pandas as pd
+
+    t = np.asarray(stats)
+    if t.dtype != np.float64 or t.ndim != 3 or t.shape[1] != 8:
+        raise ValueError(f"stats must be a float64 array [n_seg, 8, n_sel], got {t.dtype} {t.shape}")
+    n_seg, _, n_sel = t.shape
+    cnt = np.asarray(counts).ravel()
+    if cnt.size != n_seg or (cnt.size and (not np.issubdtype(cnt.dtype, np.integer) or cnt.min() < 0)):
+        raise ValueError(f"counts must hold one non-negative integer per segment ({n_seg}), got {cnt.tolist()!r}")
+    n = cnt.astype(np.float64)[:, None]
+    names = ("", "_private", "_shared", "_mixing")
+    col = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for w, suffix in enumerate(names):
+            S, Q = t[:, w], t[:, 4 + w]
+            col["mixing" if w == 3 else "mean" + suffix] = np.where(n >= 1, S / n, np.nan)
+            col["var" + suffix] = np.where(n >= 2, np.maximum((Q - S * S / n) / (n - 1), 0.0), np.nan)
+        col["private_fraction"] = np.where((n >= 1) & (t[:, 0] != 0), t[:, 1] / t[:, 0], np.nan)
+    frame = {"segment": np.repeat(np.arange(n_seg), n_sel), "column": np.tile(np.arange(n_sel), n_seg)}
+    frame.update({k: col[k].ravel() for k in EXPRESSION_STATS})
+    return pd.DataFrame(frame)
+
+
+def expression_stats_frame(names, sizes, index, table, n_samples: int, sums=None):
+    """The frame expression_statistics returns: one row per (population of ``names`` / ``sizes``, gene of ``index``), population-major, with
+    ``population``, ``gene``, ``n_cells``, ``n_samples`` and the EXPRESSION_STATS columns of ``table`` (``expression_stats_table``).
+    ``sums``: the fp64 table [n_seg, 8, n_sel] the columns were derived from, kept as ``attrs["sums"]``."""
+    import pandas as pd
+
+    n_seg, n_sel = len(names), len(index)
+    frame = pd.DataFrame({"population": np.repeat(np.asarray(names, dtype=object), n_sel), "gene": np.tile(np.asarray(index), n_seg),
+                          "n_cells": np.repeat(np.asarray(sizes, dtype=np.int64), n_sel), "n_samples": n_samples})
+    for c in EXPRESSION_STATS:
+        frame[c] = table[c].to_numpy()
+    if sums is not None:
+        frame.attrs["sums"] = np.asarray(sums)
+    return frame

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecGroup, SpvDecSampleArgs, SpvDecSampleStatsArgs, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
+from ._abi import (DEC_CELLS_PER_WG, DEC_NARROW, NB_CMAX, TRUNK_KMAX, SpvBnBatch, SpvDecExpectedArgs, SpvDecExpectedStatsArgs, SpvDecGroup, SpvDecSampleArgs, SpvDecSampleStatsArgs, SpvDecParams, SpvFoldBatch, SpvGemmArgs, SpvReduceBatch, SpvTrunkBatch, SpvZsplitArgs,
                    ptr, round_up, stream_ptr)
 from .nn_ops import _add_lin, _first_ws, _fptr, _lin_batch, _linear_bwd, _reduce_pending, _wgrad, grad_out
 from . import ops as _ops
@@ -174,11 +174,13 @@ def _trunk_batch(B: int, training: bool, decoders, Wa, par, zsum_t, zz_t, Wf, cf
 
 
 def _dec_params(wsg: Workspace, pre: str, B: int, G: int, Bp: int, Gp: int, mlo: bool, sl, logits, Wps, Aps, *, cst=None, tabs=(None, None),
-                w_row=None, nb=None, grads=None, grads_f32: bool = False) -> SpvDecParams:
+                w_row=None, nb=None, grads=None, grads_f32: bool = False, split_Bp: Optional[int] = None) -> SpvDecParams:
     """one group's spv_dec_params over the workspace arrays named ``pre`` + ...; the read-outs pass none of ``cst`` (the counts), ``tabs``
     (gene_tab, cnt_tab), ``w_row``, ``nb`` = (nb_splits, nb_genes_per_split, nb_cell_tiles: the likelihood kernel's partial rows) and
-    ``grads`` = (dtheta_part, dL, tP, tS)"""
-    splits, per = _gene_splits(Bp, Gp)
+    ``grads`` = (dtheta_part, dL, tP, tS).  ``split_Bp``: the padded row count whose gene split the softmax statistics take (default: ``Bp``'s
+    own) -- the split fixes the order in which spv_dec_lse adds up a row's denominator, so rows gathered out of a minibatch of another
+    size keep that minibatch's values bit for bit"""
+    splits, per = _gene_splits(split_Bp or Bp, Gp)
     nbs, nbper, nbtiles = nb if nb is not None else (1, 32, 0)
     vec = lambda nme: ptr(wsg.get(pre + nme, (Bp,), torch.float32))
     part = lambda nme: ptr(wsg.get(pre + nme, (splits, Bp), torch.float32))
@@ -758,11 +760,12 @@ class _DecOperands:
 
 @torch.no_grad()
 def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
-                     training: bool, nsplit: int, ws: Workspace, par=None, *, logits: bool) -> _DecOperands:
+                     training: bool, nsplit: int, ws: Workspace, par=None, *, logits: bool, split_rows: Optional[int] = None) -> _DecOperands:
     """The operand preparation of ``DecoderFused.forward`` for ONE group, outside autograd -- latent slicing quirk, BatchNorm fold
     (batch statistics in training mode, WITHOUT touching the running statistics: momentum 0), mixing trunk, the Wm / Am operand
     images, the tiled logits GEMM (``logits``: only spv_dec_materialize reads that array) and the softmax statistics over all G
-    genes (spv_dec_lse).  Shared by ``materialize_decoder`` and ``expected_expression``."""
+    genes (spv_dec_lse).  Shared by ``materialize_decoder`` and ``expected_expression``.  ``split_rows``: the size of the minibatch
+    whose gene split spv_dec_lse takes (``_dec_params``: ``split_Bp``); None = this call's own row count."""
     dev = private_log_z.device
     par = list(par) if par is not None else decoder_params(decoder, px_r)   # (``par``: spVIPESmodule._decoder_operands' covariate-extended set)
     pz, qz = _cont(private_log_z), _cont(poe_log_z)
@@ -802,7 +805,7 @@ def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, p
     if logits:
         tiled = ws.get("mat_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
         _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(tiled), int(mlo), stream_ptr())
-    p = _dec_params(ws, "mat_", B, G, Bp, Gp, mlo, sl, tiled, Wps, Aps)
+    p = _dec_params(ws, "mat_", B, G, Bp, Gp, mlo, sl, tiled, Wps, Aps, split_Bp=None if split_rows is None else round_up(int(split_rows), DEC_CELLS_PER_WG))
     lib = _cont(library.flatten())
     if lib.numel() != B:
         raise _abi.SpvError("decoder: the library vector must hold one value per cell")
@@ -853,7 +856,7 @@ def _gene_selection(genes, G: int, dev, who: str):
 
 
 def _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, who: str,
-                      log_library: Optional[torch.Tensor] = None):
+                      log_library: Optional[torch.Tensor] = None, split_rows: Optional[int] = None):
     """the shared prelude of expected_expression / sample_counts / sample_count_stats: ``library_size`` override of the library,
     operand preparation without the tiled logits, gene selection -> (_DecOperands, gene ids or None, n_genes).  ``log_library``: a
     per-cell fp32 device vector [B] of LOG library sizes that wins over ``library_size`` (-inf: a cell whose rates are all 0)."""
@@ -868,7 +871,7 @@ def _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training
         lib = log_library
     else:
         lib = library if logL is None else torch.full((B,), logL, dtype=torch.float32, device=private_log_z.device)
-    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False)
+    o = _prepare_decoder(decoder, px_r, private_log_z, poe_log_z, lib, training, nsplit, ws, par, logits=False, split_rows=split_rows)
     return (o, *_gene_selection(genes, o.G, private_log_z.device, who))
 
 
@@ -1017,6 +1020,68 @@ def sample_count_stats(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor,
     a.theta, a.cell_ids, a.key, a.sample = ptr(theta), ptr(cell_ids), int(key), int(sample)
     a.seg, a.n_seg, a.stats, a.ld_stats, a.cell_total = ptr(seg), n_seg, ptr(stats), stats.stride(1), ptr(cell_total)
     _abi.call("spv_dec_sample_stats", C.byref(o.p), C.byref(a), stream_ptr())
+    return stats
+
+
+EXPECTED_STATS = ("sum_mixture", "sum_private", "sum_shared", "sum_mixing", "sq_mixture", "sq_private", "sq_shared", "sq_mixing")   # the rows of spv_dec_expected_stats' table
+EXPRESSION_TILE = 32   # cells per tile of spv_dec_expected_stats' tile arrays (one workgroup)
+
+
+def check_expected_stats_tables(B: int, n: int, tile_seg, tile_n, n_seg, stats, who: str = "expected_expression_stats") -> int:
+    """The dtype / device / shape / contiguity checks of ``expected_expression_stats``' tables for ``B`` operand rows and ``n`` selected
+    genes -> n_seg.  Pure host code: it looks at tensor metadata only."""
+    if isinstance(n_seg, bool) or not isinstance(n_seg, (int, np.integer)) or int(n_seg) < 1:
+        raise ValueError(f"{who}: n_seg must be a positive integer, got {n_seg!r}")
+    n_seg, n_tiles = int(n_seg), -(-B // EXPRESSION_TILE)
+    for name, t in (("tile_seg", tile_seg), ("tile_n", tile_n)):
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or t.numel() < n_tiles or not t.is_contiguous()):
+            raise _abi.SpvError(f"{who}: {name} must be a contiguous int32 device tensor with one entry per {EXPRESSION_TILE}-row tile ({n_tiles})")
+    if (not isinstance(stats, torch.Tensor) or not stats.is_cuda or stats.dtype != torch.float64 or stats.dim() != 3 or stats.shape[0] != n_seg
+            or stats.shape[1] != len(EXPECTED_STATS) or stats.shape[2] < n or not stats.is_contiguous()):
+        raise _abi.SpvError(f"{who}: stats must be a contiguous fp64 device tensor [{n_seg}, {len(EXPECTED_STATS)}, >= {n}]")
+    if tile_seg.device != stats.device or tile_n.device != stats.device:
+        raise _abi.SpvError(f"{who}: tile_seg, tile_n and stats must live on one device")
+    return n_seg
+
+
+@torch.no_grad()
+def expected_expression_stats(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
+                              training: bool, nsplit: int, ws: Workspace, par=None, *, genes=None, library_size="latent", log_library=None,
+                              tile_seg: torch.Tensor, tile_n: torch.Tensor, n_seg: int, stats: torch.Tensor, batch_rows: Optional[int] = None) -> torch.Tensor:
+    """``expected_expression``'s four values for ONE group's minibatch, reduced per segment inside the entry point instead of stored
+    (spv_dec_expected_stats): with v_w[b, j] the fp32 value ``expected_expression(..., what=w)`` returns for the same operands,
+    ``genes`` and ``library_size`` (w = mixture, private, shared, mixing),
+
+        stats[k, w, j] += sum v_w[b, j]        stats[k, 4 + w, j] += sum v_w[b, j] ** 2
+
+    over the counted rows b of segment k, every term widened to fp64 first.  The rows arrive ARRANGED BY SEGMENT (``data.
+    expression_tile_plan``): ``tile_seg`` / ``tile_n`` are int32 device tensors with one entry per 32-row tile of the operands --
+    tile t belongs to segment ``tile_seg[t]`` (a negative code or one >= n_seg skips the tile) and its first ``tile_n[t]`` rows count;
+    the rest are padding.  ``stats``: fp64 device tensor [n_seg, 8, >= n_genes].  Everything ACCUMULATES in a fixed order without
+    floating-point atomics: zero the table once, then one table collects a whole walk, and two identical sequences of calls agree bit
+    for bit; columns >= n_genes and rows of segments without a counted tile stay untouched.  The per-tile partial sums live in the
+    group's ``Workspace`` ([tiles, 8, n_genes] fp64).  ``log_library``: a per-cell fp32 device vector [B] of log library sizes that
+    wins over ``library_size``.  ``batch_rows``: the size of the minibatch the rows were gathered from (None: this call's own row
+    count).  The softmax denominators over all G genes are added up in gene splits whose number follows the padded row count; with
+    ``batch_rows`` they take the split of that minibatch, so every value equals ``expected_expression``'s on the ungathered minibatch
+    bit for bit however many padding rows the arrangement added.  Eval mode only: padding rows would enter the batch statistics of
+    training mode, and the tile layout assumes that every row is its own computation.  Nothing of size cells x genes is written.
+    Returns ``stats``."""
+    who = "expected_expression_stats"
+    if training:
+        raise _abi.SpvError(f"{who}: eval mode only (in training mode the padding rows would enter the BatchNorm batch statistics)")
+    if batch_rows is not None and (isinstance(batch_rows, bool) or not isinstance(batch_rows, (int, np.integer)) or int(batch_rows) < 1):
+        raise ValueError(f"{who}: batch_rows must be a positive integer, got {batch_rows!r}")
+    o, gidx, n = _readout_operands(decoder, px_r, private_log_z, poe_log_z, library, training, nsplit, ws, par, genes, library_size, who,
+                                   log_library=log_library, split_rows=batch_rows)
+    n_seg = check_expected_stats_tables(o.B, n, tile_seg, tile_n, n_seg, stats, who)
+    n_tiles = o.Bp // EXPRESSION_TILE
+    need = int(_abi.load().spv_dec_expected_stats_ws_bytes(n, n_tiles))
+    part = ws.get("mat_xstats", (1 << max(need // 8 - 1, 0).bit_length(),), torch.float64)   # a power of two: the tile count changes from step to step
+    a = SpvDecExpectedStatsArgs()
+    _fill_readout(a, o, nsplit, gidx, n)
+    a.n_seg, a.tile_seg, a.tile_n, a.stats, a.ld_stats, a.ws = n_seg, ptr(tile_seg), ptr(tile_n), ptr(stats), stats.stride(1), ptr(part)
+    _abi.call("spv_dec_expected_stats", C.byref(o.p), C.byref(a), stream_ptr())
     return stats
 
 

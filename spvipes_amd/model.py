@@ -21,7 +21,7 @@ import torch
 
 from . import _abi
 from .data import (MinibatchSampler, RowBlocks, check_de_args, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
-                   csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, format_latent_results, group_cell_labels, group_var_names, is_sparse,
+                   csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
                    latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions)
 from .module import spVIPESmodule
 from .train import Trainer, default_max_epochs
@@ -586,6 +586,70 @@ class spVIPES:
         sq, tot = count_square_sums(self.counts[g], rows, sizes, genes=dev_sel, row_totals=True)
         obs = ppc_observed_columns(sums, sq.cpu().numpy(), sizes)
         return ppc_frame(names, sizes, index, obs, ppc, n_samples, cells, order, kept, tot.cpu().numpy(), totals[:n_g].cpu().numpy().view(np.uint64))
+
+    @torch.no_grad()
+    def expression_statistics(self, group_indices_list: List[List[int]], group: int, groupby=None, labels=None, gene_list=None, library_size="latent",
+                              n_samples: int = 1, use_mean: bool = True, batch_size: Optional[int] = None, _noise=None):
+        """What the model EXPECTS per population and gene of ONE group, split into its private and its shared part (the third read-out
+        next to ``count_statistics``, what was observed, and ``posterior_predictive_check``, what the model draws): a pandas DataFrame
+        with one row per (population, selected gene) and the columns
+
+            population, gene, n_cells, n_samples
+            mean, mean_private, mean_shared, mixing      the means over the population's cells of the four ``component`` values of
+                                                         ``get_normalized_expression``: the NB mixture's mean pi * rate_private +
+                                                         (1 - pi) * rate_shared, its two terms, and pi itself
+            private_fraction                             sum of the private part / sum of the mixture mean (NaN where that is 0)
+            var, var_private, var_shared, var_mixing     their unbiased sample variances over the same values (NaN for fewer than two)
+
+        ``attrs["sums"]`` holds the fp64 table [populations, 8, n_sel] the columns are derived from (``data.expression_stats_table``):
+        the sums of the four values and the sums of their squares.
+
+        The summed values are the very fp32 numbers ``get_normalized_expression(group_indices_list, gene_list, library_size, component,
+        n_samples=1, use_mean, batch_size)`` returns for those cells (same minibatch walk, same kernel front end), but no [n_cells,
+        n_sel] matrix is stored or copied: one fused HIP entry point (spv_dec_expected_stats) decodes every minibatch and adds it into
+        ONE fp64 table [populations, 8, n_sel]; only that table leaves the device.
+        ``groupby`` / ``labels``: ``posterior_predictive_check``'s rules and errors -- None is one population "all", else the name of
+        an ``adata.obs`` column or one label per cell of ``group_indices_list[group]``; the populations come in ``labels`` order
+        (default: sorted unique labels; an unknown label is a KeyError); a cell outside every population is left out.
+        ``gene_list``: None or this group's selection, as ``differential_expression`` takes it.
+        ``library_size``: "latent" or a positive number, as ``get_normalized_expression`` means them, or "observed", as
+        ``posterior_predictive_check`` means it: each cell decodes at the log of its observed total over ALL of the group's genes, so
+        ``mean`` is on the raw-count scale of ``count_statistics``' ``raw_mean``.
+        ``use_mean`` / ``n_samples``: ``get_normalized_expression``'s rules.  With sampled latents every draw adds its values to the
+        table (``draw = step * n_samples + sample``): the statistics then run over n_cells * n_samples values.
+        Cost of the arrangement: within a step the cells are sorted by population and each population's run is padded to a multiple of
+        32 rows, so up to 31 padded rows are decoded per population present in a step; a ``batch_size`` well above 32 x the number of
+        labels keeps that overhead small.
+        Reproducibility: there are no floating-point atomics and every order of addition is fixed, so two calls with the same arguments
+        agree bit for bit.  A different ``batch_size`` changes the order of summation (last bits) and, under a label PoE, which
+        minibatch mates a cell is fused with (its values).  ``_noise`` (tests only): as ``get_normalized_expression`` takes it."""
+        from .count_ops import count_totals
+
+        library_size = check_ppc_library(library_size)
+        observed = isinstance(library_size, str) and library_size == "observed"
+        _what, _log_l, n_samples = check_expression_args("mixture", "latent" if observed else library_size, n_samples, use_mean)
+        g = check_group(group)
+        cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
+        n_g = len(cells)
+        cell_labels = None if groupby is None else group_cell_labels(self.adata.obs, groupby, cells, g)
+        names, sizes, code = ppc_segments(cell_labels, labels, n_cells=n_g)
+        n_seg = len(names)
+        _sel, dev_sel, n_sel, index = self._genes(g, gene_list, own=True)
+        stats = torch.zeros((n_seg, 8, n_sel), dtype=torch.float64, device=self.device)
+        obs_all = count_totals(self.counts[g]) if observed else None
+        for step, tensors, B, _off, pos in walk_positions(self._eval_minibatches(group_indices_list, batch_size, None), g, n_g):
+            seg = np.where(pos >= 0, code[pos], -1)   # a cut row (pos -1) is in no population
+            perm, tile_seg, tile_n = expression_tile_plan(seg, n_seg)
+            if not perm.size:
+                continue   # nothing of this step is counted (eval mode: steps are independent of each other)
+            plan = [torch.as_tensor(t, device=self.device) for t in (perm, tile_seg, tile_n)]
+            lib = torch.log(obs_all.index_select(0, tensors[g]["rows"].long())).to(torch.float32).contiguous() if observed else None
+            for _smp, out in self._draws(step, tensors, B, n_samples, _noise):
+                self.module.expression_stats(out, g, genes=dev_sel, library_size="latent" if observed else library_size, library=lib, use_mean=use_mean,
+                                             perm=plan[0], tile_seg=plan[1], tile_n=plan[2], n_seg=n_seg, stats=stats)
+        sums = stats.cpu().numpy()
+        table = expression_stats_table(sums, [sizes[k] * n_samples for k in range(n_seg)])
+        return expression_stats_frame(names, sizes, index, table, n_samples, sums=sums)
 
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}

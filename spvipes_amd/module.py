@@ -749,6 +749,32 @@ class spVIPESmodule(nn.Module):
         return self._readout("sample_count_stats", inference_outputs, group, use_mean, genes=genes, library_size=library_size, log_library=library,
                              key=key, sample=sample, cell_ids=cell_ids, seg=seg, n_seg=n_seg, stats=stats, cell_total=cell_total)
 
+    @torch.no_grad()
+    def expression_stats(self, inference_outputs, group: int, *, genes=None, library_size="latent", library=None, use_mean: bool = False,
+                         perm, tile_seg, tile_n, n_seg: int, stats) -> torch.Tensor:
+        """``expected_expression``'s four values ("mixture", "private", "shared", "mixing") for one group of the minibatch
+        ``inference_outputs`` describes, reduced on the device instead of stored: per segment and selected gene their sums and the sums
+        of their squares are ACCUMULATED into ``stats`` (fp64 [n_seg, 8, >= n_genes]) in a fixed order.  ``perm`` (int64 device tensor
+        of minibatch row numbers), ``tile_seg`` and ``tile_n`` are a ``data.expression_tile_plan`` of the step: the operand rows -- the
+        two latents, already extended by the cells' batch covariates, and the library -- are gathered by ``perm`` so that every 32-row
+        tile holds cells of one segment; the softmax statistics keep the gene split of the minibatch's own size (``batch_rows``), so the
+        values are ``expected_expression``'s for the same minibatch bit for bit.  ``library``: a per-cell fp32 device vector of LOG
+        library sizes (minibatch order) that wins over ``library_size``.  Eval mode only.  ``n_seg`` / ``stats``:
+        dec_ops.expected_expression_stats (spv_dec_expected_stats; no [B, n_genes] array is written)."""
+        from . import dec_ops
+
+        if self.training:
+            raise RuntimeError("expression_stats: eval mode only (in training mode the padding rows would enter the BatchNorm batch statistics)")
+        first, second, par, lib = self._readout_operands(inference_outputs, group, use_mean)
+        if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int64 or perm.dim() != 1 or perm.device != first.device:
+            raise TypeError("expression_stats: perm must be a 1-d int64 tensor of minibatch rows on the module's device")
+        take = lambda t: t.index_select(0, perm).contiguous()
+        log_library = None if library is None else take(library)
+        return dec_ops.expected_expression_stats(self.decoders[group], self.px_r[group], take(first), take(second), take(lib.flatten()), False, self.nsplit,
+                                                 self._workspace(group, lib.device), par=par, genes=genes, library_size=library_size,
+                                                 log_library=log_library, tile_seg=tile_seg, tile_n=tile_n, n_seg=n_seg, stats=stats,
+                                                 batch_rows=int(first.shape[0]))
+
     def loss(self, tensors_by_group, inference_outputs, generative_outputs, kl_weight: float = 1.0):
         """spVIPESmodule.py:809-899."""
         from .dec_ops import DecoderFused, decoder_params
