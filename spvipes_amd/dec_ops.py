@@ -86,23 +86,15 @@ def _run_red(b: SpvReduceBatch) -> None:
 
 
 # ---- one function per argument block: every site that launches with a block gets it from here and sets no field of it itself ----
-def _check_latent_sizes(sl, n_p: int, n_s: int, n_m: int) -> None:
-    if n_p + 1 > sl.KP or n_s + 1 > sl.KS:
-        raise _abi.SpvError(f"decoder kernels support n_private <= {sl.KP - 1} and n_shared <= {sl.KS - 1}")
-    if n_m + n_p + n_s + 1 > KMP:
-        raise _abi.SpvError("mixture input wider than 320 columns is not supported")
-
-
-def _zsplit_args(B: int, Bp: int, n_p: int, n_s: int, n_m: int, sl, lat, zcat, Am_img=None, Aps_img=None) -> SpvZsplitArgs:
-    """spv_zsplit_fwd's block: per group ``lat`` = (private, poe) latents (contiguous fp32: the caller holds them) into ``zcat``; with the
-    (hi, lo) operand images given, the same launch packs them"""
+def _zsplit_args(B: int, Bp: int, n_p: int, n_s: int, n_m: int, sl, lat, zcat, Am_img, Aps_img) -> SpvZsplitArgs:
+    """spv_zsplit_fwd's block: per group ``lat`` = (private, poe) latents (contiguous fp32: the caller holds them) into ``zcat`` and, packed
+    by the same launch, into the (hi, lo) operand images"""
     za = SpvZsplitArgs()
     za.B, za.n_p, za.n_s, za.ngroups, za.kslots = B, n_p, n_s, len(lat), sl.kslots
     za.ld_am, za.am_col, za.am_cols, za.Bp = KMP, n_m, KMP - n_m, Bp
     for g, (pz, qz) in enumerate(lat):
         za.priv[g], za.poe[g], za.zcat[g] = ptr(pz), ptr(qz), ptr(zcat[g])
-        if Am_img is not None:
-            za.am_hi[g], za.am_lo[g], za.aps_hi[g], za.aps_lo[g] = ptr(Am_img[g][0]), ptr(Am_img[g][1]), ptr(Aps_img[g][0]), ptr(Aps_img[g][1])
+        za.am_hi[g], za.am_lo[g], za.aps_hi[g], za.aps_lo[g] = ptr(Am_img[g][0]), ptr(Am_img[g][1]), ptr(Aps_img[g][0]), ptr(Aps_img[g][1])
     return za
 
 
@@ -196,6 +188,106 @@ def _dec_params(wsg: Workspace, pre: str, B: int, G: int, Bp: int, Gp: int, mlo:
         dtheta_part=ptr(dth), dL=ptr(dL), tP=ptr(tP), tS=ptr(tS), grads_f32=int(grads_f32), nb_splits=nbs, nb_genes_per_split=nbper,
         nb_cell_tiles=nbtiles, kslots=sl.kslots, **counts,
     )
+
+
+class _DecOperands:
+    """one group's decoder operand set as ``spv_dec_lse`` leaves it (the inputs of spv_dec_materialize and spv_dec_expected)"""
+    __slots__ = ("p", "B", "G", "Bp", "Gp", "Am", "Wm", "par", "keep")
+
+
+class _DecFront:
+    """What the decoder's front end (the ``_front_*`` stages below) leaves for one call over NG groups: one or two in
+    ``DecoderFused.forward``, whose backward reads it by name, one in a read-out.  Everything after the sizes is a per-group list."""
+    __slots__ = ("dev", "B", "Bp", "Gs", "Gps", "n_p", "n_s", "n_m", "sl", "mlo",   # sizes, K-slot layout, lo planes (fp32 mode)
+                 "lat", "zcat", "Am", "Aps",       # contiguous (private, poe) latents; [z_private | z_shared]; (hi, lo) logits / regressor operand images
+                 "zsum", "zz", "zsum_t", "zz_t",   # z statistics per head [private, shared]; of all of zcat's columns (folded trunk only, else None)
+                 "Wps", "fstat", "fb", "Wm",       # folded regressor image (hi, lo), its statistics per head, the spv_fold_batch; [W_m | b_m] image (hi, lo)
+                 "m", "tstat", "pre_a", "Wf", "cf")   # trunk output and statistics; pre-activation (unfolded trunk) or folded weights (folded), else None
+
+    def __init__(self, dev, B: int, Gs, n_p: int, n_s: int, n_m: int, sl, mlo: bool):
+        if n_p + 1 > sl.KP or n_s + 1 > sl.KS:
+            raise _abi.SpvError(f"decoder kernels support n_private <= {sl.KP - 1} and n_shared <= {sl.KS - 1}")
+        if n_m + n_p + n_s + 1 > KMP:
+            raise _abi.SpvError("mixture input wider than 320 columns is not supported")
+        self.dev, self.B, self.Gs, self.n_p, self.n_s, self.n_m, self.sl, self.mlo = dev, B, list(Gs), n_p, n_s, n_m, sl, mlo
+        self.Bp, self.Gps = round_up(B, DEC_CELLS_PER_WG), [round_up(G, 256) for G in Gs]   # 256: the logits GEMM runs 256-gene workgroup tiles
+        self.zsum_t = self.zz_t = self.pre_a = self.Wf = self.cf = None   # (what a call does not make stays None)
+
+    def new(self, *shape) -> torch.Tensor:
+        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
+
+
+# ---- the front end's stages over per-group lists (``ws``: one workspace per group), on the caller's current stream.  DecoderFused.forward
+# names its workspace arrays "dec_", _prepare_decoder "mat_": a read-out may run between a step's forward and its backward, which reads them ----
+def _front_latents(r: _DecFront, lat, ws, pre: str) -> None:
+    """latent slicing: zcat = [z_private | z_shared] and, from the same launch, the packed operand images of these latents"""
+    NG, nt = len(lat), r.n_p + r.n_s
+    r.zcat = [r.new(r.B, nt) for _ in range(NG)]
+    r.Am, r.Aps = [_bf16_image(ws[g], pre + "Am", r.Bp, KMP, r.mlo) for g in range(NG)], [_bf16_image(ws[g], pre + "Aps", r.Bp, r.sl.KPS, True) for g in range(NG)]
+    r.lat = [(_cont(pz), _cont(qz)) for pz, qz in lat]
+    za = _zsplit_args(r.B, r.Bp, r.n_p, r.n_s, r.n_m, r.sl, r.lat, r.zcat, r.Am, r.Aps)
+    _abi.call("spv_zsplit_fwd", C.byref(za), stream_ptr())
+
+
+def _front_zstats(r: _DecFront, training: bool, trunk_fold: bool, ws) -> None:
+    """batch statistics of z (column sums and z^T z) for the BatchNorm fold; ``trunk_fold``: the mixing trunk's BatchNorm is folded too
+    (spv_trunk_fold_fwd) and needs those of ALL of zcat's columns, cross terms included.  Launched in training mode only"""
+    NG, n_p, n_s, nt = len(r.zcat), r.n_p, r.n_s, r.n_p + r.n_s
+    r.zsum, r.zz = [[r.new(n_p), r.new(n_s)] for _ in range(NG)], [[r.new(n_p, n_p), r.new(n_s, n_s)] for _ in range(NG)]
+    if trunk_fold:
+        r.zsum_t, r.zz_t = [r.new(nt) for _ in range(NG)], [r.new(nt, nt) for _ in range(NG)]
+    if training:
+        _wgrad(_zstats_batch(r.B, n_p, n_s, r.zcat, r.zsum, r.zz, (r.zsum_t, r.zz_t) if trunk_fold else None), _first_ws(ws))
+
+
+def _front_fold(r: _DecFront, decoders, par, training: bool, momentum: float, ws, pre: str) -> None:
+    """the regressors' BatchNorm folded into the packed [Gp][KPS] operand image: builds the block (kept as ``r.fb``: the backward completes it);
+    ``_run_fold`` launches it where the caller says.  ``momentum`` 0 leaves the running statistics alone"""
+    NG = len(r.zcat)
+    r.Wps = [_bf16_image(ws[g], pre + "Wps", r.Gps[g], r.sl.KPS, True) for g in range(NG)]
+    r.fstat, r.fb = [[r.new(r.Gs[g], 2), r.new(r.Gs[g], 2)] for g in range(NG)], _fold_batch(r.B, training, momentum, r.sl)
+    for g in range(NG):
+        _add_fold(r.fb, decoders[g], par[g], r.n_p, r.n_s, r.zcat[g], r.zsum[g], r.zz[g], r.fstat[g], r.Wps[g], r.Gs[g], r.Gps[g], r.sl)
+
+
+def _run_fold(r: _DecFront) -> None:
+    _abi.call("spv_bn_fold_fwd", C.byref(r.fb), stream_ptr())
+
+
+def _front_wm(r: _DecFront, g: int, par_g, wsg: Workspace, pre: str, reuse: bool):
+    """group ``g``'s [W_m | b_m] logits operand image -> (hi, lo), for ``r.Wm`` (per group: the step packs it between the group's other
+    side-stream launches).  ``reuse``: skip the pack where the workspace holds the image of these very parameters (Adam has just rewritten it)"""
+    Wm_hi, Wm_lo = _bf16_image(wsg, pre + "Wm", r.Gps[g], KMP, r.mlo)
+    if not reuse or Wm_lo is not None or wsg.fresh.get(pre + "Wm") != _ops.image_token(par_g[10], par_g[11]):
+        _pack(_cont(par_g[10]), Wm_hi, Wm_lo, extra_col=_cont(par_g[11]))
+    return Wm_hi, Wm_lo
+
+
+def _front_trunk(r: _DecFront, decoders, par, training: bool, trunk_fold: bool, momentum: float, ws, part_name: str) -> None:
+    """mixing trunk: m = relu(BN(zcat Wa^T + ba)) into ``r.m`` / ``r.tstat`` (the caller's allocations, as is ``r.pre_a`` where it wants that
+    ahead of them) AND into the logits operand image.  ``trunk_fold``: the BatchNorm folded into the layer (batch mean / variance of a linear
+    map of z from zbar and cov(z)): one affine map + rectifier, no statistics / finalise / normalise launches -- the same mathematics with
+    other roundings, so a caller stays with its form.  ``momentum``, ``part_name`` (the BatchNorm partials' workspace array): the unfolded form's"""
+    NG, B, n_m, nt = len(r.zcat), r.B, r.n_m, r.n_p + r.n_s
+    if trunk_fold:
+        r.Wf, r.cf = [r.new(n_m, nt) for _ in range(NG)], [r.new(n_m) for _ in range(NG)]
+        wa_c = [_cont(par[g][6]) for g in range(NG)]
+        tb_ = _trunk_batch(B, training, decoders, wa_c, par, r.zsum_t, r.zz_t, r.Wf, r.cf, r.tstat, n_m, nt)
+        _abi.call("spv_trunk_fold_fwd", C.byref(tb_), stream_ptr())
+        b = _lin_batch(B, relu=True)
+        for g in range(NG):
+            _add_lin(b, N=n_m, K=nt, W=ptr(r.Wf[g]), bias=ptr(r.cf[g]), X=ptr(r.zcat[g]), ldx=nt, Y=ptr(r.m[g]), ldy=n_m,
+                     img=(ptr(r.Am[g][0]), ptr(r.Am[g][1]), KMP, r.Bp))
+        _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
+        return
+    r.pre_a = r.pre_a or [r.new(B, n_m) for _ in range(NG)]
+    b = _lin_batch(B)
+    for g in range(NG):
+        _add_lin(b, N=n_m, K=nt, W=ptr(par[g][6]), bias=ptr(par[g][7]), X=ptr(r.zcat[g]), ldx=nt, Y=ptr(r.pre_a[g]), ldy=n_m)
+    _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
+    parts = [ws[g].get(part_name, (-(-B // _abi.BN_ROWS), n_m, 2), torch.float32) for g in range(NG)]
+    bn = _trunk_bn_batch(B, training, momentum, decoders, par, r.pre_a, r.m, r.tstat, parts, n_m, r.Am, r.Bp)
+    _abi.call("spv_bn_fwd", C.byref(bn), stream_ptr())
 
 
 class _DecoderBwd:
@@ -332,6 +424,73 @@ class _DecoderBwd:
         return e, f
 
 
+def _trunk_bwd(r: _DecFront, decoders, par, training: bool, ws, pg, dAm, d_zcat):
+    """DecoderFused.backward's trunk tail (BatchNorm + relu, Linear) from ``dAm`` = d m, in the form the forward took.  ``pg``: per group and
+    parameter (kernel target, autograd return); ``d_zcat``: per group the gradient reaching zcat so far, which both tails add to.  Returns
+    its temporaries: the caller holds them to the end of the pass, so that no later array of the pass takes their memory"""
+    NG, B, n_m, nt, new = len(r.zcat), r.B, r.n_m, r.n_p + r.n_s, r.new
+    dWa, dba, d_gam_a, d_bet_a = ([pg[g][j][0] for g in range(NG)] for j in (6, 7, 8, 9))
+    if r.Wf is not None:
+        # folded trunk (spv_trunk_fold_fwd): the layer is relu(zcat W'^T + c'); its input gradient and the gradients of (W', c') come from the
+        # rectifier-masked linear kernels, spv_trunk_fold_bwd takes (d W', d c') back to W_a / gamma / beta and adds the part of d zcat that
+        # flows through the batch statistics -- the three BatchNorm-backward launches are gone from this chain
+        dWf, dcf = [new(n_m, nt) for _ in range(NG)], [new(n_m) for _ in range(NG)]
+        dred = [new(-(-n_m // 64), nt + nt * nt) for _ in range(NG)]
+        bw, bd = _lin_batch(B, relu=True), _lin_batch(B, relu=True, accumulate=True)
+        for g in range(NG):
+            _add_lin(bw, N=n_m, K=nt, W=ptr(r.Wf[g]), X=ptr(r.zcat[g]), ldx=nt, Y=ptr(r.m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dW=ptr(dWf[g]), db=ptr(dcf[g]))
+            _add_lin(bd, N=n_m, K=nt, W=ptr(r.Wf[g]), Y=ptr(r.m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
+        if _ops.LINEAR_BWD:   # one launch; spv_trunk_fold_bwd reads the summed d W', so the slice sum stays on the chain
+            _reduce_pending(_linear_bwd(bd, bw, _first_ws(ws), "wgrad_part_trunk"))
+        else:
+            _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
+            _wgrad(bw, _first_ws(ws))
+        wa_c = [par[g][6] if par[g][6].is_contiguous() else par[g][6].contiguous() for g in range(NG)]
+        tb_ = _trunk_batch(B, training, decoders, wa_c, par, r.zsum_t, r.zz_t, r.Wf, r.cf, r.tstat, n_m, nt,
+                           bwd=list(zip(dWf, dcf, dWa, dba, d_gam_a, d_bet_a, dred, r.zcat, d_zcat)))
+        _abi.call("spv_trunk_fold_bwd", C.byref(tb_), stream_ptr())
+        return dWf, dcf, dred, wa_c
+    d_pre = [new(B, n_m) for _ in range(NG)]
+    parts = [ws[g].get("trunk_bn_part", (-(-B // _abi.BN_ROWS), n_m, 2), torch.float32) for g in range(NG)]
+    bn = _trunk_bn_batch(B, training, 0.01, decoders, par, r.pre_a, r.m, r.tstat, parts, n_m, grads=(dAm, d_pre, d_gam_a, d_bet_a))
+    _abi.call("spv_bn_bwd", C.byref(bn), stream_ptr())
+    bw, bd = _lin_batch(B), _lin_batch(B, accumulate=True)
+    for g in range(NG):
+        _add_lin(bw, N=n_m, K=nt, W=ptr(par[g][6]), X=ptr(r.zcat[g]), ldx=nt, dY=ptr(d_pre[g]), lddy=n_m, dW=ptr(dWa[g]), db=ptr(dba[g]))
+        _add_lin(bd, N=n_m, K=nt, W=ptr(par[g][6]), dY=ptr(d_pre[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
+    if _ops.LINEAR_BWD:
+        _reduce_pending(_linear_bwd(bd, bw, _first_ws(ws), "wgrad_part_trunk"))
+    else:
+        _wgrad(bw, _first_ws(ws))
+        _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
+    return d_pre
+
+
+def _fold_bwd(r: _DecFront, training: bool, ws, pg, dWp, dWs, d_zcat, joins):
+    """BatchNorm-fold backward (+ the z statistics it used) from the folded weights' gradients ``dWp`` / ``dWs``, then the latent slicing
+    backward -> (d private, d poe) per group.  It completes the block the forward built and kept (``r.fb``), so that the two launches
+    cannot disagree on the forward's half; ``joins()`` runs once the block is complete, ahead of the launch (the schedule's waits)"""
+    NG, B, n_p, n_s, nt, sl = len(r.zcat), r.B, r.n_p, r.n_s, r.n_p + r.n_s, r.sl
+    d_priv, d_poe = [r.new(B, n_p) for _ in range(NG)], [r.new(B, n_s) for _ in range(NG)]
+    for g in range(NG):
+        for k, (dweff, ld, n, zoff) in enumerate(((dWp[g], sl.KP, n_p, 0), (dWs[g], sl.KS, n_s, n_p))):
+            q = r.fb.p[2 * g + k]   # (_add_fold's order)
+            q.dWeff, q.ld_dw, q.dz, q.lddz = ptr(dweff), ld, _fptr(d_zcat[g], zoff), nt
+            q.dW, q.dgamma, q.dbeta = (ptr(pg[g][3 * k + j][0]) for j in range(3))   # parameters 0-2: private W, gamma, beta; 3-5: shared
+            q.red_part = ptr(ws[g].get(f"fold_red_{k}", (-(-r.Gs[g] // 256) + 1, n + n * n), torch.float32))
+            if training:   # the latent-slicing backward rides in the same kernel (spv_fold_prob.out_priv)
+                q.zcol, q.out_priv, q.out_poe, q.n_p, q.n_s = zoff, ptr(d_priv[g]), ptr(d_poe[g]), n_p, n_s
+    joins()
+    _abi.call("spv_bn_fold_bwd", C.byref(r.fb), stream_ptr())
+    if not training:   # (training: already done by the z-statistics kernel of spv_bn_fold_bwd)
+        za = SpvZsplitArgs()
+        za.B, za.n_p, za.n_s, za.ngroups = B, n_p, n_s, NG
+        for g in range(NG):
+            za.d_zcat[g], za.d_priv[g], za.d_poe[g] = ptr(d_zcat[g]), ptr(d_priv[g]), ptr(d_poe[g])
+        _abi.call("spv_zsplit_bwd", C.byref(za), stream_ptr())
+    return d_priv, d_poe
+
+
 class DecoderFused(torch.autograd.Function):
     """inputs : per group (private_log_z [B,n_p], poe_log_z [B,n_s]), per group its 13 parameters, then n_kl KL
              vectors [B] (module/spVIPESmodule.py:841-868) that the loss adds with weight kl_weight / B
@@ -352,45 +511,18 @@ class DecoderFused(torch.autograd.Function):
         if len(kls) != n_kl or n_kl > 4:
             raise _abi.SpvError("DecoderFused: expected n_kl <= 4 KL vectors after the parameters")
         dev = lat[0][0].device
-        n_p, n_s = lat[0][0].shape[1], lat[0][1].shape[1]
-        nt = n_p + n_s
+        n_p, n_s, n_m, mlo = lat[0][0].shape[1], lat[0][1].shape[1], par[0][6].shape[0], nsplit == 3
         sl = dec_slots(decoders[0])
-        DEC_KPS = sl.KPS
         if any(dec_slots(d) != sl for d in decoders):
             raise _abi.SpvError("DecoderFused: the decoders of one call must share their operand layout")
-        n_m = par[0][6].shape[0]
-        KM = n_m + nt + 1
-        _check_latent_sizes(sl, n_p, n_s, n_m)
         need_grad = any(ctx.needs_input_grad)  # (grad mode is off inside Function.forward)
-        Bp = round_up(B, DEC_CELLS_PER_WG)
-        Gs = [c.G for c in counts]
-        Gps = [round_up(G, 256) for G in Gs]  # 256: the logits GEMM runs 256-gene workgroup tiles
-        mlo = nsplit == 3
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        # ---- 1. latent slicing: zcat = [z_private | z_shared] --------------------------------------
-        zcat = [new(B, nt) for _ in range(NG)]
-        # ... and, from the same call, the decoder's packed bf16 operand images of these latents
-        Am_img = [_bf16_image(ws[g], "dec_Am", Bp, KMP, mlo) for g in range(NG)]
-        Aps_img = [_bf16_image(ws[g], "dec_Aps", Bp, DEC_KPS, True) for g in range(NG)]
-        lat = [(_cont(pz), _cont(qz)) for pz, qz in lat]
-        keep = [t for pq in lat for t in pq]
-        za = _zsplit_args(B, Bp, n_p, n_s, n_m, sl, lat, zcat, Am_img, Aps_img)
-        _abi.call("spv_zsplit_fwd", C.byref(za), stream_ptr())
-        # ---- 2. batch statistics of z (column sums and z^T z) for the BatchNorm fold ---------------
-        zsum = [[new(n_p), new(n_s)] for _ in range(NG)]
-        zz = [[new(n_p, n_p), new(n_s, n_s)] for _ in range(NG)]
-        # the mixing trunk's BatchNorm is folded too (spv_trunk_fold_fwd): it needs the statistics of ALL of zcat's columns, cross terms included
-        trunk_fold = bool(_ops.TRUNK_FOLD and nt <= TRUNK_KMAX and n_m <= 256)
-        zsum_t = [new(nt) for _ in range(NG)] if trunk_fold else None
-        zz_t = [new(nt, nt) for _ in range(NG)] if trunk_fold else None
-        if training:
-            _wgrad(_zstats_batch(B, n_p, n_s, zcat, zsum, zz, (zsum_t, zz_t) if trunk_fold else None), _first_ws(ws))
-        # ---- 3. fold the regressors' BatchNorm into the packed [Gp][48] operand image ---------------
-        Wps = [_bf16_image(ws[g], "dec_Wps", Gps[g], DEC_KPS, True) for g in range(NG)]
-        fstat = [[new(Gs[g], 2), new(Gs[g], 2)] for g in range(NG)]
-        fb = _fold_batch(B, training, 0.01, sl)
-        for g in range(NG):
-            _add_fold(fb, decoders[g], par[g], n_p, n_s, zcat[g], zsum[g], zz[g], fstat[g], Wps[g], Gs[g], Gps[g], sl)
+        r = _DecFront(dev, B, [c.G for c in counts], n_p, n_s, n_m, sl, mlo)
+        Bp, Gs, Gps, new = r.Bp, r.Gs, r.Gps, r.new
+        # ---- 1.-3. latent slicing, the z statistics, the regressors' BatchNorm fold (built here, launched on the side stream below) ----
+        _front_latents(r, lat, ws, "dec_")
+        trunk_fold = bool(_ops.TRUNK_FOLD and n_p + n_s <= TRUNK_KMAX and n_m <= 256)
+        _front_zstats(r, training, trunk_fold, ws)
+        _front_fold(r, decoders, par, training, 0.01, ws, "dec_")
         # the schedule of this call AND of its backward pass (ops.DecSchedule): decided here, once
         grads_f32 = bool(need_grad and mlo)
         sched = _ops.dec_schedule(B, Gs, NG, grads_f32)
@@ -399,18 +531,15 @@ class DecoderFused(torch.autograd.Function):
         # they run beside it on a side stream and are joined before the per-group section.
         side = group_streams(dev, 3, sched.serial)[2]
         side.wait_stream(torch.cuda.current_stream(dev))
-        Wm_img, tabs = [], []
+        r.Wm, tabs = [], []
         with torch.cuda.stream(side):
-            _abi.call("spv_bn_fold_fwd", C.byref(fb), stream_ptr())
+            _run_fold(r)
             for g in range(NG):
-                Wm_hi, Wm_lo = _bf16_image(ws[g], "dec_Wm", Gps[g], KMP, mlo)
-                if Wm_lo is not None or ws[g].fresh.get("dec_Wm") != _ops.image_token(par[g][10], par[g][11]):   # (else: Adam has just rewritten it)
-                    _pack(_cont(par[g][10]), Wm_hi, Wm_lo, extra_col=_cont(par[g][11]))
+                r.Wm.append(_front_wm(r, g, par[g], ws[g], "dec_", reuse=True))
                 gene_tab = ws[g].get("dec_gene_tab", (Gps[g], 4), torch.float32)
                 cnt_tab = ws[g].get("dec_cnt_tab", (NB_CMAX, Gps[g], 2), torch.float32)
                 if not pair:
                     _abi.call("spv_dec_tables", ptr(_cont(par[g][12])), Gs[g], Gps[g], ptr(gene_tab), ptr(cnt_tab), stream_ptr())
-                Wm_img.append((Wm_hi, Wm_lo))
                 tabs.append((gene_tab, cnt_tab))
             if pair:   # one grid for both groups' tables
                 tg = (SpvDecGroup * NG)()
@@ -419,33 +548,8 @@ class DecoderFused(torch.autograd.Function):
                     tg[g].px_r, tg[g].p.G, tg[g].p.Gp, tg[g].p.gene_tab, tg[g].p.cnt_tab = ptr(px_keep[g]), Gs[g], Gps[g], ptr(tabs[g][0]), ptr(tabs[g][1])
                 _abi.call("spv_dec_tables_grouped", tg, NG, stream_ptr())
         # ---- 4. mixing trunk: m = relu(BN(zcat Wa^T + ba)) -------------------------------------------
-        m = [new(B, n_m) for _ in range(NG)]
-        tstat = [new(n_m, 2) for _ in range(NG)]
-        Wf = cf = pre_a = None
-        decs = [decoders[g] for g in range(NG)]
-        if trunk_fold:
-            # the BatchNorm folded into the layer (batch mean / variance of a linear map of z from zbar and cov(z)): one affine map + rectifier,
-            # written by spv_linear_fwd straight into m AND into the logits operand image -- no statistics / finalise / normalise launches
-            Wf, cf = [new(n_m, nt) for _ in range(NG)], [new(n_m) for _ in range(NG)]
-            wa_c = [_cont(par[g][6]) for g in range(NG)]
-            tb_ = _trunk_batch(B, training, decs, wa_c, par, zsum_t, zz_t, Wf, cf, tstat, n_m, nt)
-            _abi.call("spv_trunk_fold_fwd", C.byref(tb_), stream_ptr())
-            b = _lin_batch(B, relu=True)
-            for g in range(NG):
-                _add_lin(b, N=n_m, K=nt, W=ptr(Wf[g]), bias=ptr(cf[g]), X=ptr(zcat[g]), ldx=nt, Y=ptr(m[g]), ldy=n_m)
-                q = b.p[g]   # m straight into the logits operand image
-                q.img_hi, q.img_lo, q.ld_img, q.img_rows = ptr(Am_img[g][0]), ptr(Am_img[g][1]), KMP, Bp
-            _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
-        else:
-            pre_a = [new(B, n_m) for _ in range(NG)]
-            b = _lin_batch(B)
-            for g in range(NG):
-                _add_lin(b, N=n_m, K=nt, W=ptr(par[g][6]), bias=ptr(par[g][7]), X=ptr(zcat[g]), ldx=nt, Y=ptr(pre_a[g]), ldy=n_m)
-            _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
-            nblk = -(-B // _abi.BN_ROWS)
-            parts = [ws[g].get("trunk_bn_part", (nblk, n_m, 2), torch.float32) for g in range(NG)]
-            bn = _trunk_bn_batch(B, training, 0.01, decs, par, pre_a, m, tstat, parts, n_m, Am_img, Bp)
-            _abi.call("spv_bn_fwd", C.byref(bn), stream_ptr())
+        r.m, r.tstat = [new(B, n_m) for _ in range(NG)], [new(n_m, 2) for _ in range(NG)]
+        _front_trunk(r, [decoders[g] for g in range(NG)], par, training, trunk_fold, 0.01, ws, "trunk_bn_part")
         # ---- 5. per group: operand images, tables, logits GEMM, softmax statistics, likelihood ------
         if w_pad.numel() < Bp or w_pad.dtype != torch.float32 or not w_pad.is_contiguous():
             raise _abi.SpvError("DecoderFused: w_pad must be contiguous fp32 of length >= round_up(B, 128)")
@@ -464,8 +568,8 @@ class DecoderFused(torch.autograd.Function):
         for g in range(NG):
           with torch.cuda.stream(streams[g]):
               G, Gp, wsg = Gs[g], Gps[g], ws[g]
-              Wm_hi, Wm_lo = Wm_img[g]
-              (Am_hi, Am_lo), (Aps_hi, Aps_lo) = Am_img[g], Aps_img[g]
+              Wm_hi, Wm_lo = r.Wm[g]
+              (Am_hi, Am_lo), (Aps_hi, Aps_lo) = r.Am[g], r.Aps[g]
               logits = wsg.get("dec_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
               lse_first = g % 2 == 1  # group 1 runs its (VALU-bound) softmax statistics beside group 0's logits GEMM
               run_logits = lambda: _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(logits), int(mlo), stream_ptr())
@@ -481,7 +585,7 @@ class DecoderFused(torch.autograd.Function):
                   Tp, Ts = wsg.get("dec_Tp", (Bp,), torch.float32), wsg.get("dec_Ts", (Bp,), torch.float32)
               else:
                   dL = tP = tS = dth = Tp = Ts = None
-              p = _dec_params(wsg, "dec_", B, G, Bp, Gp, mlo, sl, logits, Wps[g], Aps_img[g], cst=counts[g].c_struct(rows[g]), tabs=tabs[g], w_row=w_pad,
+              p = _dec_params(wsg, "dec_", B, G, Bp, Gp, mlo, sl, logits, r.Wps[g], r.Aps[g], cst=counts[g].c_struct(rows[g]), tabs=tabs[g], w_row=w_pad,
                               nb=(nbs, nbper, _nb_cell_tiles(Bp, Gp)), grads=(dth, dL, tP, tS), grads_f32=grads_f32)
               if pair:
                   lib_keep.append(_cont(library[g].flatten()))
@@ -493,8 +597,7 @@ class DecoderFused(torch.autograd.Function):
                   if lse_first:
                       run_logits()
                   _abi.call("spv_dec_nb_fwd", C.byref(p), int(need_grad), stream_ptr())
-              r = rec[g]
-              _add_red(red, nbpart("dec_rec"), nbs, Bp, Bp, 1, B, r, B)
+              _add_red(red, nbpart("dec_rec"), nbs, Bp, Bp, 1, B, rec[g], B)
               if need_grad:
                   _add_red(red, nbpart("dec_tp"), nbs, Bp, Bp, 1, Bp, Tp, Bp)
                   _add_red(red, nbpart("dec_ts"), nbs, Bp, Bp, 1, Bp, Ts, Bp)
@@ -512,14 +615,8 @@ class DecoderFused(torch.autograd.Function):
         _abi.call("spv_loss_assemble", ptr(rec[0]), ptr(rec[1]) if NG > 1 else None, ptr(w_pad), klp, n_kl, B, ptr(klw), ptr(loss), ptr(rec_sum), ptr(gkl), stream_ptr())
         if need_grad:
             ctx.P, ctx.saved_g, ctx.ws, ctx.decoders, ctx.training, ctx.nsplit = P, saved_g, ws, decoders, training, nsplit
-            ctx.dims = (B, Bp, Gs, Gps, n_p, n_s, n_m, KM)
-            ctx.NG = NG
-            ctx.grads_f32, ctx.done, ctx.keep = grads_f32, False, keep
-            ctx.Wps, ctx.fb = Wps, fb
-            ctx.small = (zcat, zsum, zz, fstat, pre_a, m, tstat)
-            ctx.trunk = (Wf, cf, zsum_t, zz_t) if trunk_fold else None
-            ctx.gkl, ctx.n_kl = gkl, n_kl
-            ctx.sl, ctx.sched = sl, sched
+            ctx.NG, ctx.front, ctx.sched = NG, r, sched
+            ctx.grads_f32, ctx.done, ctx.gkl, ctx.n_kl = grads_f32, False, gkl, n_kl
             ctx.save_for_backward(*tensors[:2 * NG + NG * N_DEC_PARAMS])
         ctx.mark_non_differentiable(rec_sum, *rec)
         return (loss, rec_sum, *rec)
@@ -529,22 +626,17 @@ class DecoderFused(torch.autograd.Function):
         if ctx.done:
             raise _abi.SpvError("DecoderFused.backward may run once per forward (gradient buffers are consumed in place)")
         ctx.done = True
-        NG = ctx.NG
-        tensors = ctx.saved_tensors
+        NG, tensors = ctx.NG, ctx.saved_tensors
         par = [tensors[2 * NG + g * N_DEC_PARAMS: 2 * NG + (g + 1) * N_DEC_PARAMS] for g in range(NG)]
-        B, Bp, Gs, Gps, n_p, n_s, n_m, KM = ctx.dims
-        nt = n_p + n_s
-        ws, nsplit, training = ctx.ws, ctx.nsplit, ctx.training
-        zcat, zsum, zz, fstat, pre_a, m, tstat = ctx.small
-        dev = zcat[0].device
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        r, ws, nsplit, training = ctx.front, ctx.ws, ctx.nsplit, ctx.training
+        B, Bp, Gs, Gps, n_p, n_s, n_m, sl, dev, new = r.B, r.Bp, r.Gs, r.Gps, r.n_p, r.n_s, r.n_m, r.sl, r.dev, r.new
+        nt, KM = n_p + n_s, n_m + n_p + n_s + 1
         if g_loss is None:
             raise _abi.SpvError("DecoderFused.backward: the loss output received no gradient")
         g_loss = g_loss if (g_loss.dtype == torch.float32 and g_loss.is_contiguous()) else g_loss.float().contiguous()
         pg = [[grad_out(par[g][j]) for j in range(N_DEC_PARAMS)] for g in range(NG)]  # (kernel target, autograd return) per parameter
         red, red2 = SpvReduceBatch(), SpvReduceBatch()
         red.nprob = red2.nprob = 0
-        sl = ctx.sl
         DEC_KP, DEC_KS, DEC_KPS = sl.KP, sl.KS, sl.KPS
         dWp, dWs = [new(Gs[g], DEC_KP) for g in range(NG)], [new(Gs[g], DEC_KS) for g in range(NG)]
         dAm, d_zcat = [new(B, n_m) for _ in range(NG)], [new(B, nt) for _ in range(NG)]
@@ -560,7 +652,7 @@ class DecoderFused(torch.autograd.Function):
         cur = torch.cuda.current_stream(dev)
         streams = group_streams(dev, NG, sched.serial)
         side = group_streams(dev, 3, sched.serial)[2]
-        stages = [_DecoderBwd(g, ctx.P[g], ctx.saved_g[g], ctx.Wps[g], ws[g], B, Bp, Gs[g], Gps[g], nsplit, ctx.grads_f32, pair=(NG == 2), sl=sl) for g in range(NG)]
+        stages = [_DecoderBwd(g, ctx.P[g], ctx.saved_g[g], r.Wps[g], ws[g], B, Bp, Gs[g], Gps[g], nsplit, ctx.grads_f32, pair=(NG == 2), sl=sl) for g in range(NG)]
         d_slabs, ef_slabs = [None] * NG, [None] * NG
         # without a second stream, or where the softmax fix does not yield the latent gradient (wide layout, ops.FUSED_DZ off), the
         # softmax kernels stay ahead of the d A_m GEMMs on the group streams
@@ -671,148 +763,56 @@ class DecoderFused(torch.autograd.Function):
         # trunk backward, which they slow down
         if not wm_late:
             issue_wm()
-        # ---- trunk backward (BatchNorm + relu, Linear) ----------------------------------------------
-        dWa, dba = [pg[g][6][0] for g in range(NG)], [pg[g][7][0] for g in range(NG)]
-        d_gam_a, d_bet_a = [pg[g][8][0] for g in range(NG)], [pg[g][9][0] for g in range(NG)]
-        decs = [ctx.decoders[g] for g in range(NG)]
-        if ctx.trunk is not None:
-            # folded trunk (spv_trunk_fold_fwd): the layer is relu(zcat W'^T + c'); its input gradient and the gradients of (W', c') come from the
-            # rectifier-masked linear kernels, spv_trunk_fold_bwd takes (d W', d c') back to W_a / gamma / beta and adds the part of d zcat that
-            # flows through the batch statistics -- the three BatchNorm-backward launches are gone from this chain
-            Wf, cf, zsum_t, zz_t = ctx.trunk
-            dWf, dcf = [new(n_m, nt) for _ in range(NG)], [new(n_m) for _ in range(NG)]
-            dred = [new(-(-n_m // 64), nt + nt * nt) for _ in range(NG)]
-            bw, bd = _lin_batch(B, relu=True), _lin_batch(B, relu=True, accumulate=True)
-            for g in range(NG):
-                _add_lin(bw, N=n_m, K=nt, W=ptr(Wf[g]), X=ptr(zcat[g]), ldx=nt, Y=ptr(m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dW=ptr(dWf[g]), db=ptr(dcf[g]))
-                _add_lin(bd, N=n_m, K=nt, W=ptr(Wf[g]), Y=ptr(m[g]), ldy=n_m, dY=ptr(dAm[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
-            if _ops.LINEAR_BWD:   # one launch; spv_trunk_fold_bwd reads the summed d W', so the slice sum stays on the chain
-                _reduce_pending(_linear_bwd(bd, bw, _first_ws(ws), "wgrad_part_trunk"))
-            else:
-                _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
-                _wgrad(bw, _first_ws(ws))
-            wa_c = [par[g][6] if par[g][6].is_contiguous() else par[g][6].contiguous() for g in range(NG)]
-            tb_ = _trunk_batch(B, training, decs, wa_c, par, zsum_t, zz_t, Wf, cf, tstat, n_m, nt,
-                               bwd=list(zip(dWf, dcf, dWa, dba, d_gam_a, d_bet_a, dred, zcat, d_zcat)))
-            _abi.call("spv_trunk_fold_bwd", C.byref(tb_), stream_ptr())
-        else:
-            nblk = -(-B // _abi.BN_ROWS)
-            d_pre = [new(B, n_m) for _ in range(NG)]
-            parts = [ws[g].get("trunk_bn_part", (nblk, n_m, 2), torch.float32) for g in range(NG)]
-            bn = _trunk_bn_batch(B, training, 0.01, decs, par, pre_a, m, tstat, parts, n_m, grads=(dAm, d_pre, d_gam_a, d_bet_a))
-            _abi.call("spv_bn_bwd", C.byref(bn), stream_ptr())
-            bw, bd = _lin_batch(B), _lin_batch(B, accumulate=True)
-            for g in range(NG):
-                _add_lin(bw, N=n_m, K=nt, W=ptr(par[g][6]), X=ptr(zcat[g]), ldx=nt, dY=ptr(d_pre[g]), lddy=n_m, dW=ptr(dWa[g]), db=ptr(dba[g]))
-                _add_lin(bd, N=n_m, K=nt, W=ptr(par[g][6]), dY=ptr(d_pre[g]), lddy=n_m, dX=ptr(d_zcat[g]), lddx=nt)
-            if _ops.LINEAR_BWD:
-                _reduce_pending(_linear_bwd(bd, bw, _first_ws(ws), "wgrad_part_trunk"))
-            else:
-                _wgrad(bw, _first_ws(ws))
-                _abi.call("spv_linear_dgrad", C.byref(bd), stream_ptr())
-        # ---- BatchNorm-fold backward (+ the z statistics it used) ------------------------------------
-        fb = ctx.fb   # (kslots set by the forward pass)
-        d_priv, d_poe = [new(B, n_p) for _ in range(NG)], [new(B, n_s) for _ in range(NG)]
-        dWraw = [[pg[g][0][0], pg[g][3][0]] for g in range(NG)]
-        dgam = [[pg[g][1][0], pg[g][4][0]] for g in range(NG)]
-        dbet = [[pg[g][2][0], pg[g][5][0]] for g in range(NG)]
-        i = 0
-        for g in range(NG):
-            for k, (dweff, ld, n, zoff) in enumerate(((dWp[g], DEC_KP, n_p, 0), (dWs[g], DEC_KS, n_s, n_p))):
-                q = fb.p[i]
-                q.dWeff, q.ld_dw, q.dW, q.dgamma, q.dbeta = ptr(dweff), ld, ptr(dWraw[g][k]), ptr(dgam[g][k]), ptr(dbet[g][k])
-                q.red_part = ptr(ws[g].get(f"fold_red_{k}", (-(-Gs[g] // 256) + 1, n + n * n), torch.float32))
-                q.dz, q.lddz = _fptr(d_zcat[g], zoff), nt
-                if training:   # the latent-slicing backward rides in the same kernel (spv_fold_prob.out_priv)
-                    q.zcol, q.out_priv, q.out_poe, q.n_p, q.n_s = zoff, ptr(d_priv[g]), ptr(d_poe[g]), n_p, n_s
-                i += 1
-        if da_first:   # the rate heads' latent gradient (softmax fix on the side stream) joins d_zcat here
-            cur.wait_event(sm_done)
-            _run_red(red2)
-        if bc_done is not None:
-            cur.wait_event(bc_done)
-        if wm_late:
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            issue_wm(ev)
-        _abi.call("spv_bn_fold_bwd", C.byref(fb), stream_ptr())
-        # ---- latent slicing backward (training: already done by the z-statistics kernel of spv_bn_fold_bwd) ---------------------
-        if not training:
-            za = SpvZsplitArgs()
-            za.B, za.n_p, za.n_s, za.ngroups = B, n_p, n_s, NG
-            for g in range(NG):
-                za.d_zcat[g], za.d_priv[g], za.d_poe[g] = ptr(d_zcat[g]), ptr(d_priv[g]), ptr(d_poe[g])
-            _abi.call("spv_zsplit_bwd", C.byref(za), stream_ptr())
-        grads = []
-        for g in range(NG):
-            grads += [d_priv[g], d_poe[g]]
-        for g in range(NG):
-            grads += [pg[g][j][1] for j in range(N_DEC_PARAMS)]
-        if ctx.n_kl:
-            grads += [gk] * ctx.n_kl
-        return (None,) * 11 + tuple(grads)
+        held = _trunk_bwd(r, [ctx.decoders[g] for g in range(NG)], par, training, ws, pg, dAm, d_zcat)   # noqa: F841  (see _trunk_bwd)
 
+        def joins():   # what the main stream picks up between building the BatchNorm-fold backward's block and launching it
+            if da_first:   # the rate heads' latent gradient (softmax fix on the side stream) joins d_zcat here
+                cur.wait_event(sm_done)
+                _run_red(red2)
+            if bc_done is not None:
+                cur.wait_event(bc_done)
+            if wm_late:
+                ev = torch.cuda.Event()
+                ev.record(cur)
+                issue_wm(ev)
 
-class _DecOperands:
-    """one group's decoder operand set as ``spv_dec_lse`` leaves it (the inputs of spv_dec_materialize and spv_dec_expected)"""
-    __slots__ = ("p", "B", "G", "Bp", "Gp", "Am", "Wm", "par", "keep")
+        d_priv, d_poe = _fold_bwd(r, training, ws, pg, dWp, dWs, d_zcat, joins)
+        grads = [t for g in range(NG) for t in (d_priv[g], d_poe[g])] + [pg[g][j][1] for g in range(NG) for j in range(N_DEC_PARAMS)]
+        return (None,) * 11 + tuple(grads) + (gk,) * ctx.n_kl
 
 
 @torch.no_grad()
 def _prepare_decoder(decoder, px_r: torch.Tensor, private_log_z: torch.Tensor, poe_log_z: torch.Tensor, library: torch.Tensor,
                      training: bool, nsplit: int, ws: Workspace, par=None, *, logits: bool, split_rows: Optional[int] = None) -> _DecOperands:
-    """The operand preparation of ``DecoderFused.forward`` for ONE group, outside autograd -- latent slicing quirk, BatchNorm fold
-    (batch statistics in training mode, WITHOUT touching the running statistics: momentum 0), mixing trunk, the Wm / Am operand
-    images, the tiled logits GEMM (``logits``: only spv_dec_materialize reads that array) and the softmax statistics over all G
-    genes (spv_dec_lse).  Shared by ``materialize_decoder`` and ``expected_expression``.  ``split_rows``: the size of the minibatch
-    whose gene split spv_dec_lse takes (``_dec_params``: ``split_Bp``); None = this call's own row count."""
-    dev = private_log_z.device
+    """ONE group's decoder operands outside autograd: the front end of ``DecoderFused.forward`` (the ``_front_*`` stages) over a
+    workspace of its own names ("mat_"), with momentum 0 (batch statistics in training mode, WITHOUT touching the running statistics)
+    and always the unfolded mixing trunk (whose roundings define the read-outs' values); then the tiled logits GEMM (``logits``: only
+    spv_dec_materialize reads that array) and the softmax statistics over all G genes (spv_dec_lse).  Shared by every read-out.
+    ``split_rows``: the size of the minibatch whose gene split spv_dec_lse takes (``_dec_params``: ``split_Bp``); None = this call's
+    own row count."""
     par = list(par) if par is not None else decoder_params(decoder, px_r)   # (``par``: spVIPESmodule._decoder_operands' covariate-extended set)
     pz, qz = _cont(private_log_z), _cont(poe_log_z)
-    B, n_p, n_s = pz.shape[0], pz.shape[1], qz.shape[1]
-    nt = n_p + n_s
-    sl = dec_slots(decoder)
-    n_m = par[6].shape[0]
-    _check_latent_sizes(sl, n_p, n_s, n_m)
-    G = par[0].shape[0]
-    Bp, Gp = round_up(B, DEC_CELLS_PER_WG), round_up(G, 256)
-    mlo = nsplit == 3
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    zcat = new(B, nt)
-    Am = Am_hi, Am_lo = _bf16_image(ws, "mat_Am", Bp, KMP, mlo)
-    Aps = _bf16_image(ws, "mat_Aps", Bp, sl.KPS, True)
-    za = _zsplit_args(B, Bp, n_p, n_s, n_m, sl, [(pz, qz)], [zcat], [Am], [Aps])
-    _abi.call("spv_zsplit_fwd", C.byref(za), stream_ptr())
-    zsum, zz = [new(n_p), new(n_s)], [new(n_p, n_p), new(n_s, n_s)]
-    if training:
-        _wgrad(_zstats_batch(B, n_p, n_s, [zcat], [zsum], [zz]), ws)
-    Wps = _bf16_image(ws, "mat_Wps", Gp, sl.KPS, True)
-    fstat = [new(G, 2), new(G, 2)]
-    fb = _fold_batch(B, training, 0.0, sl)   # momentum 0: running statistics untouched
-    _add_fold(fb, decoder, par, n_p, n_s, zcat, zsum, zz, fstat, Wps, G, Gp, sl)
-    _abi.call("spv_bn_fold_fwd", C.byref(fb), stream_ptr())
-    Wm_hi, Wm_lo = _bf16_image(ws, "mat_Wm", Gp, KMP, mlo)
-    _pack(_cont(par[10]), Wm_hi, Wm_lo, extra_col=_cont(par[11]))
-    # mixing trunk
-    pre_a, m, tstat = new(B, n_m), new(B, n_m), new(n_m, 2)
-    b = _lin_batch(B)
-    _add_lin(b, N=n_m, K=nt, W=ptr(par[6]), bias=ptr(par[7]), X=ptr(zcat), ldx=nt, Y=ptr(pre_a), ldy=n_m)
-    _abi.call("spv_linear_fwd", C.byref(b), stream_ptr())
-    nblk = -(-B // _abi.BN_ROWS)
-    bn = _trunk_bn_batch(B, training, 0.0, [decoder], [par], [pre_a], [m], [tstat], [ws.get("mat_bn_part", (nblk, n_m, 2), torch.float32)], n_m, [Am], Bp)
-    _abi.call("spv_bn_fwd", C.byref(bn), stream_ptr())
+    B, G, n_m, mlo = pz.shape[0], par[0].shape[0], par[6].shape[0], nsplit == 3
+    r = _DecFront(private_log_z.device, B, [G], pz.shape[1], qz.shape[1], n_m, dec_slots(decoder), mlo)
+    _front_latents(r, [(pz, qz)], [ws], "mat_")
+    _front_zstats(r, training, False, [ws])
+    _front_fold(r, [decoder], [par], training, 0.0, [ws], "mat_")
+    _run_fold(r)
+    r.Wm = [_front_wm(r, 0, par, ws, "mat_", reuse=False)]
+    r.pre_a, r.m, r.tstat = [r.new(B, n_m)], [r.new(B, n_m)], [r.new(n_m, 2)]
+    _front_trunk(r, [decoder], [par], training, False, 0.0, [ws], "mat_bn_part")
+    Bp, Gp, (Am_hi, Am_lo), (Wm_hi, Wm_lo) = r.Bp, r.Gps[0], r.Am[0], r.Wm[0]
     tiled = None
     if logits:
         tiled = ws.get("mat_logits_" + ("f32" if mlo else "f16"), (Bp, Gp), torch.float32 if mlo else torch.float16)
         _abi.call("spv_dec_logits", ptr(Am_hi), ptr(Am_lo), ptr(Wm_hi), ptr(Wm_lo), KMP, Bp, Gp, nsplit, ptr(tiled), int(mlo), stream_ptr())
-    p = _dec_params(ws, "mat_", B, G, Bp, Gp, mlo, sl, tiled, Wps, Aps, split_Bp=None if split_rows is None else round_up(int(split_rows), DEC_CELLS_PER_WG))
+    p = _dec_params(ws, "mat_", B, G, Bp, Gp, mlo, r.sl, tiled, r.Wps[0], r.Aps[0], split_Bp=None if split_rows is None else round_up(int(split_rows), DEC_CELLS_PER_WG))
     lib = _cont(library.flatten())
     if lib.numel() != B:
         raise _abi.SpvError("decoder: the library vector must hold one value per cell")
     _abi.call("spv_dec_lse", C.byref(p), ptr(lib), stream_ptr())
     o = _DecOperands()
-    o.p, o.B, o.G, o.Bp, o.Gp, o.Am, o.Wm, o.par = p, B, G, Bp, Gp, (Am_hi, Am_lo), (Wm_hi, Wm_lo), par
-    o.keep = (pz, qz, lib)
+    o.p, o.B, o.G, o.Bp, o.Gp, o.Am, o.Wm, o.par, o.keep = p, B, G, Bp, Gp, r.Am[0], r.Wm[0], par, (pz, qz, lib)
     return o
 
 

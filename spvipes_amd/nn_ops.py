@@ -33,10 +33,13 @@ def _lin_batch(B: int, relu: bool = False, drop_p: float = 0.0, seed=0, accumula
 
 
 def _add_lin(b: SpvLinearBatch, *, N: int, K: int, W=None, X=None, ldx=0, bias=None, Y=None, ldy=0, dY=None, lddy=0, dX=None, lddx=0,
-             dW=None, db=None, keep=None, W2=None, n_w2=0) -> None:
+             dW=None, db=None, keep=None, W2=None, n_w2=0, img=None) -> None:
+    """``img`` = (hi, lo, leading dimension, rows): the bf16 operand image spv_linear_fwd also writes Y into (without it the fields stay zero)"""
     q = b.p[b.nprob]
     q.X, q.ldx, q.W, q.bias, q.Y, q.ldy, q.keep, q.W2, q.n_w2 = X, ldx, W, bias, Y, ldy, keep, W2, n_w2
     q.dY, q.lddy, q.dX, q.lddx, q.dW, q.db, q.N, q.K = dY, lddy, dX, lddx, dW, db, N, K
+    if img is not None:
+        q.img_hi, q.img_lo, q.ld_img, q.img_rows = img
     b.nprob += 1
 
 

@@ -24,7 +24,8 @@ import json
 import os
 import sys
 
-ROWS = ("label_bf16", "label_fp32", "paired", "cluster", "three_groups", "narrow_nb3", "wide_nb12", "readouts")
+ROWS = ("label_bf16", "label_fp32", "paired", "cluster", "three_groups", "narrow_nb3", "wide_nb12", "readouts",
+        "readouts_fp32", "readouts_wide", "readouts_stats")
 GS, H, N_S, N_P, CELLS = (300, 280), 32, 10, 5, 512
 
 
@@ -131,23 +132,35 @@ def training_row(row: str, B: int, dev, evaluate: bool):
     trainer._forward_backward(rows, torch.full((), 1.0, device=dev), noise={k: v.to(dev) for k, v in _noise(torch, B, NG, 1).items()})
 
 
-def readout_row(B: int, dev):
+def readout_row(row: str, B: int, dev):
     """the module's read-outs of one minibatch, in eval() and in train() mode: materialised ``generative`` outputs, expected_expression,
-    sample_counts, sample_count_stats"""
+    sample_counts, sample_count_stats.  "readouts": bf16, narrow layout; "readouts_fp32": precision="fp32"; "readouts_wide": n_batch = 12,
+    decoder_slots="auto", with batch codes; "readouts_stats": expression_stats over a two-segment tile plan (eval() only)"""
     import numpy as np
     import torch
-    from spvipes_amd.data import make_synthetic_group
+    from spvipes_amd.data import expression_tile_plan, make_synthetic_group
     from spvipes_amd.module import spVIPESmodule
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
     groups = [make_synthetic_group(g, CELLS, GS[g], dev) for g in range(2)]
+    wide = dict(n_batch=12, decoder_slots="auto") if row == "readouts_wide" else {}
     module = spVIPESmodule({0: GS[0], 1: GS[1]}, use_labels=True, n_hidden=H, n_dimensions_shared=N_S, n_dimensions_private=N_P, dropout_rate=0.0,
-                           precision="bf16").to(dev)
+                           precision="fp32" if row == "readouts_fp32" else "bf16", **wide).to(dev)
     rows = [torch.tensor(rng.permutation(CELLS)[:B], dtype=torch.int32, device=dev) for _ in range(2)]
-    tensors = tuple({"counts": groups[g].counts, "rows": rows[g], "indices": rows[g].float().unsqueeze(1), "groups": None, "batch": None,
+    batch = [torch.tensor(rng.integers(0, 12, size=B), dtype=torch.int32, device=dev) if wide else None for _ in range(2)]
+    tensors = tuple({"counts": groups[g].counts, "rows": rows[g], "indices": rows[g].float().unsqueeze(1), "groups": None, "batch": batch[g],
                      "labels": groups[g].labels[rows[g].long()].unsqueeze(1)} for g in range(2))
     noise = {k: v.to(dev) for k, v in _noise(torch, B, 2, 1).items()}
     genes = np.arange(3, 200)
+    if row == "readouts_stats":
+        module.eval()
+        with torch.no_grad():
+            inf, _ = module(tensors, inference_kwargs={"noise": noise}, compute_loss=False)
+            for g in range(2):
+                perm, tile_seg, tile_n = (torch.as_tensor(a, device=dev) for a in expression_tile_plan(rng.integers(0, 2, size=B), 2))
+                module.expression_stats(inf, g, genes=genes, perm=perm, tile_seg=tile_seg, tile_n=tile_n, n_seg=2,
+                                        stats=torch.zeros(2, 8, len(genes), dtype=torch.float64, device=dev))
+        return
     for training in (False, True):
         module.train(training)
         with torch.no_grad():
@@ -183,7 +196,7 @@ def main():
         tracer = Tracer(f, a.record_only)
         tracer.install()
         for B in a.batch:
-            readout_row(B, dev) if a.row == "readouts" else training_row(a.row, B, dev, a.eval)
+            readout_row(a.row, B, dev) if a.row.startswith("readouts") else training_row(a.row, B, dev, a.eval)
             torch.cuda.synchronize()
             f.write(json.dumps({"end_of": a.row, "B": B}) + "\n")
     print(f"{a.row}: trace of {a.root} written to {a.out}", flush=True)
