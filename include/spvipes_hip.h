@@ -541,6 +541,46 @@ int64_t spv_count_stats_ws_bytes(int32_t G, int32_t n_slabs);
 int spv_count_totals(const spv_counts* x, int32_t n_cells, int32_t G, double* total, void* stream);
 int spv_csr_totals(const int64_t* indptr, const int32_t* cols, const void* vals, int32_t dtype, int32_t n_cells, int32_t G, double* total, void* stream);
 
+/* Exact k-nearest neighbours (spVIPES.latent_neighbors of the user API): for query row i of Q the k rows of C nearest to it, nothing
+ * of size n_q x n_c stored.
+ * Distance: d(i, j) is the squared Euclidean distance as ONE fp32 chain -- acc = +0; for t = 0 .. D-1 ascending: u = Q[i][t] - C[j][t]
+ * (one rounding), acc = fmaf(u, u, acc) (one rounding).  Never the |q|^2 + |c|^2 - 2 q.c form.
+ * Order and fill: row i of idx / dist holds the k candidates with the smallest (d, j) in lexicographic order, ascending: equal
+ * distances go to the smaller candidate index.  A candidate whose d is not < +inf (overflow, NaN, non-finite input) is never
+ * returned, nor is candidate exclude[i] (exclude int32 [n_q] or NULL; a value outside [0, n_c) excludes nothing).  With fewer than k
+ * candidates left the remaining slots are idx = -1, dist = +inf.  Columns >= k and rows >= n_q are never written.
+ * Independence: the result is a function of (Q, C, D, k, exclude) alone -- the same bit for bit for every n_split (chunks without a
+ * candidate included) and for every tiling, two calls agree bit for bit, a query's row does not depend on the other queries of the
+ * call, and permuting the candidates permutes idx accordingly wherever distances are distinct.
+ * Launches: a partial pass, one workgroup per (tile of spv_knn_tile_q() queries, chunk of the candidates; spv_knn_tile_c() of them
+ * in LDS at a time), writes each chunk's sorted list into ws, and a merge pass folds the chunks' lists in the same (d, j) order;
+ * n_split == 1 is ONE launch that writes idx / dist itself and needs no workspace.  n_split = 0 stands for
+ * spv_knn_splits(n_q, n_c), a pure function of the shapes (no device query) that stays 1 while the query tiles fill the chip.
+ * ws: spv_knn_ws_bytes(n_q, k, n_split) bytes with the RESOLVED n_split (0 for n_split <= 1 or a non-positive shape), 8-byte
+ * aligned, overwritten by every call.  Nothing is allocated.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null Q / C / idx / dist; ws null when its size is not 0; D outside
+ * [1, SPV_KNN_DMAX]; k outside [1, SPV_KNN_KMAX]; n_split outside [0, SPV_KNN_SPLIT_MAX]; n_q < 1; n_c < 0; ld_q < D; ld_c < D;
+ * ld_out < k; n_q * ld_out or n_split * n_q * k beyond 2^31 - 1.  n_c == 0 is valid: every slot is -1 / +inf. */
+#define SPV_KNN_DMAX 64
+#define SPV_KNN_KMAX 64
+#define SPV_KNN_SPLIT_MAX 64
+typedef struct spv_knn_args {
+  const float* Q; int64_t ld_q; int32_t n_q;      /* queries    fp32 [n_q][ld_q], ld_q >= D */
+  const float* C; int64_t ld_c; int32_t n_c;      /* candidates fp32 [n_c][ld_c], ld_c >= D */
+  int32_t D;                                      /* 1 .. SPV_KNN_DMAX */
+  int32_t k;                                      /* 1 .. SPV_KNN_KMAX */
+  const int32_t* exclude;                         /* [n_q] or NULL */
+  int32_t n_split;                                /* 0 = spv_knn_splits(n_q, n_c); else 1 .. SPV_KNN_SPLIT_MAX chunks of the candidates */
+  int32_t* idx; float* dist; int64_t ld_out;      /* [n_q][ld_out], ld_out >= k */
+  void* ws;                                       /* spv_knn_ws_bytes(n_q, k, n_split) bytes */
+} spv_knn_args;
+int spv_knn(const spv_knn_args* a, void* stream);
+int32_t spv_knn_splits(int32_t n_q, int32_t n_c);
+int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split);
+/* queries per workgroup and candidates per LDS tile of the partial pass */
+int32_t spv_knn_tile_q(void);
+int32_t spv_knn_tile_c(void);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

@@ -273,6 +273,16 @@ class SpvCountStatsArgs(C.Structure):
                 ("ld_out", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+KNN_DMAX, KNN_KMAX, KNN_SPLIT_MAX = 64, 64, 64   # SPV_KNN_DMAX / SPV_KNN_KMAX / SPV_KNN_SPLIT_MAX
+
+
+class SpvKnnArgs(C.Structure):
+    """the arguments of spv_knn (include/spvipes_hip.h: spv_knn_args)"""
+    _fields_ = [("Q", C.c_void_p), ("ld_q", C.c_int64), ("n_q", C.c_int32), ("C", C.c_void_p), ("ld_c", C.c_int64), ("n_c", C.c_int32),
+                ("D", C.c_int32), ("k", C.c_int32), ("exclude", C.c_void_p), ("n_split", C.c_int32), ("idx", C.c_void_p), ("dist", C.c_void_p),
+                ("ld_out", C.c_int64), ("ws", C.c_void_p)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -350,6 +360,11 @@ _SIGNATURES = {
     "spv_count_stats_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "spv_count_totals": (C.c_int, [C.POINTER(SpvCounts), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "spv_csr_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spv_knn": (C.c_int, [C.POINTER(SpvKnnArgs), C.c_void_p]),
+    "spv_knn_splits": (C.c_int32, [C.c_int32, C.c_int32]),
+    "spv_knn_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_knn_tile_q": (C.c_int32, []),
+    "spv_knn_tile_c": (C.c_int32, []),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

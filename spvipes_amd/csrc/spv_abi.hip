@@ -12,6 +12,7 @@
 #include "spv_de.h"
 #include "spv_de_median.h"
 #include "spv_count_stats.h"
+#include "spv_knn.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -1043,6 +1044,58 @@ extern "C" int spv_count_stats(const spv_count_stats_args* x, void* stream) {
   rc = count_stats_partial_launch(x, a, (hipStream_t)stream);
   if (rc != SPV_OK) return rc;
   return count_stats_merge_launch(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// exact k-nearest neighbours (spv_knn.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_knn_tile_q(void) { return KNN_TQ; }
+extern "C" int32_t spv_knn_tile_c(void) { return KNN_TC; }
+extern "C" int32_t spv_knn_splits(int32_t n_q, int32_t n_c) { return knn_splits(n_q, n_c); }
+extern "C" int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
+  if (n_q < 1 || k < 1 || n_split <= 1) return 0;
+  return (int64_t)n_split * n_q * k * 8;
+}
+
+// the one-time opt-in to the largest dynamic LDS a call can ask for (k = SPV_KNN_KMAX: beyond the 64 KiB a kernel gets unasked)
+template <int DP>
+static void knn_partial_launch(const KnnArgs& a, dim3 grid, hipStream_t s) {
+  static bool raised = false;
+  if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_partial_kernel<DP>), hipFuncAttributeMaxDynamicSharedMemorySize, knn_lds_bytes(DP, KNN_KMAX)); raised = true; }
+  hipLaunchKernelGGL((knn_partial_kernel<DP>), grid, dim3(KNN_TQ), knn_lds_bytes(DP, a.k), s, a);
+}
+
+extern "C" int spv_knn(const spv_knn_args* x, void* stream) {
+  if (!x) return fail(SPV_ERR_ARG, "spv_knn: null arguments%s");
+  if (!x->Q) return fail(SPV_ERR_ARG, "spv_knn: null Q%s");
+  if (!x->C) return fail(SPV_ERR_ARG, "spv_knn: null C%s");
+  if (!x->idx) return fail(SPV_ERR_ARG, "spv_knn: null idx%s");
+  if (!x->dist) return fail(SPV_ERR_ARG, "spv_knn: null dist%s");
+  if (x->D < 1 || x->D > KNN_DMAX) return fail(SPV_ERR_ARG, "spv_knn: D must lie in [1, 64]%s");
+  if (x->k < 1 || x->k > KNN_KMAX) return fail(SPV_ERR_ARG, "spv_knn: k must lie in [1, 64]%s");
+  if (x->n_split < 0 || x->n_split > KNN_SPLIT_MAX) return fail(SPV_ERR_ARG, "spv_knn: n_split must be 0 or lie in [1, 64]%s");
+  if (x->n_q < 1) return fail(SPV_ERR_ARG, "spv_knn: n_q < 1%s");
+  if (x->n_c < 0) return fail(SPV_ERR_ARG, "spv_knn: n_c < 0%s");
+  if (x->ld_q < x->D) return fail(SPV_ERR_ARG, "spv_knn: ld_q < D%s");
+  if (x->ld_c < x->D) return fail(SPV_ERR_ARG, "spv_knn: ld_c < D%s");
+  if (x->ld_out < x->k) return fail(SPV_ERR_ARG, "spv_knn: ld_out < k%s");
+  if ((int64_t)x->n_q * x->ld_out > INT32_MAX || x->ld_out > INT32_MAX) return fail(SPV_ERR_ARG, "spv_knn: n_q * ld_out exceeds 2^31 - 1%s");
+  const int n_split = x->n_split ? x->n_split : knn_splits(x->n_q, x->n_c);
+  if ((int64_t)n_split * x->n_q * x->k > INT32_MAX) return fail(SPV_ERR_ARG, "spv_knn: the workspace (n_split * n_q * k entries) exceeds 2^31 - 1%s");
+  if (n_split > 1 && !x->ws) return fail(SPV_ERR_ARG, "spv_knn: null ws%s");
+  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "spv_knn: ws must be 8-byte aligned%s");
+  const KnnArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->k, x->exclude, n_split, knn_chunk(x->n_c, n_split),
+                  x->idx, x->dist, (int)x->ld_out, (knn_key_t*)x->ws};
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((x->n_q + KNN_TQ - 1) / KNN_TQ);
+  const dim3 grid(tiles, (unsigned)n_split);
+  if (x->D <= 16) knn_partial_launch<16>(a, grid, s);
+  else if (x->D <= 32) knn_partial_launch<32>(a, grid, s);
+  else knn_partial_launch<64>(a, grid, s);
+  int rc = launch_status(n_split == 1 ? "spv_knn" : "spv_knn (partial pass)");
+  if (rc != SPV_OK || n_split == 1) return rc;
+  hipLaunchKernelGGL(knn_merge_kernel, dim3(tiles), dim3(KNN_TQ), knn_lds_bytes(0, x->k), s, a);   // at most the 64 KiB a kernel gets unasked
+  return launch_status("spv_knn (merge pass)");
 }
 
 extern "C" int spv_count_totals(const spv_counts* x, int32_t n_cells, int32_t G, double* total, void* stream) {

@@ -901,3 +901,75 @@ def expression_stats_frame(names, sizes, index, table, n_samples: int, sums=None
     if sums is not None:
         frame.attrs["sums"] = np.asarray(sums)
     return frame
+
+
+# ---- neighbours in latent space (model.latent_neighbors / transfer_labels): host-side argument handling and the label vote ------
+NEIGHBOR_SETS = (0, 1, "both")
+
+
+def check_neighbor_args(k, query, target, latent: str):
+    """The refusals of ``latent_neighbors``, ahead of any device work -> (k, query groups, target groups, exclude self?): ``k`` an integer in
+    [1, KNN_KMAX]; ``query`` / ``target`` 0, 1 or "both" (group 0's cells, then group 1's); ``latent`` "shared" or "private", the latter
+    only within ONE group (the two groups' private spaces are not comparable).  Self-exclusion applies when every query cell is also a
+    target cell."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _abi.KNN_KMAX:
+        raise ValueError(f"k must be an integer in [1, {_abi.KNN_KMAX}], got {k!r}")
+    if latent not in ("shared", "private"):
+        raise ValueError(f"latent must be 'shared' or 'private', got {latent!r}")
+    sets = []
+    for name, v in (("query", query), ("target", target)):
+        if isinstance(v, bool) or not (v == "both" if isinstance(v, str) else isinstance(v, (int, np.integer)) and v in (0, 1)):
+            raise ValueError(f"{name} must be 0, 1 or 'both', got {v!r}")
+        sets.append((0, 1) if isinstance(v, str) else (int(v),))
+    if latent == "private" and (sets[0] != sets[1] or len(sets[0]) != 1):
+        raise ValueError("latent='private' needs query == target, one group: the private spaces of the two groups are not comparable")
+    return int(k), sets[0], sets[1], set(sets[0]) <= set(sets[1])
+
+
+def neighbor_self_positions(query_groups, target_groups, sizes) -> np.ndarray:
+    """Each query cell's own position in the target cells' order (query set contained in the target set), int32 [n_query]"""
+    start, off = {}, 0
+    for g in target_groups:
+        start[g], off = off, off + int(sizes[g])
+    return np.concatenate([start[g] + np.arange(int(sizes[g]), dtype=np.int32) for g in query_groups]).astype(np.int32)
+
+
+def vote_labels(indices, codes, n_labels: int):
+    """Majority vote of the neighbours' labels -> (predicted int64 [n], confidence fp64 [n], n_neighbors int64 [n]).  ``indices``
+    [n, k]: positions into ``codes`` (one integer label code in [0, n_labels) per source cell), -1 = no neighbour, ignored.  Uniform
+    weights; ties go to the smallest code; ``confidence`` is the share of the cell's valid neighbours that voted for the winner.  A
+    cell without a valid neighbour gets predicted = -1, confidence = nan."""
+    idx = np.asarray(indices)
+    codes = np.asarray(codes).ravel()
+    if idx.ndim != 2:
+        raise ValueError(f"indices must be a 2-d array [cells, k], got {idx.ndim} dimensions")
+    if n_labels < 1 or (codes.size and (codes.min() < 0 or codes.max() >= n_labels)):
+        raise ValueError(f"codes must lie in [0, n_labels = {n_labels})")
+    valid = idx >= 0
+    if (idx[valid] >= codes.shape[0]).any() or (idx < -1).any():
+        raise ValueError(f"indices must be -1 or lie in [0, {codes.shape[0]})")
+    n = idx.shape[0]
+    votes = np.zeros((n, int(n_labels)), dtype=np.int64)
+    rows = np.broadcast_to(np.arange(n)[:, None], idx.shape)
+    np.add.at(votes, (rows[valid], codes[idx[valid]].astype(np.int64)), 1)
+    n_valid = valid.sum(1).astype(np.int64)
+    predicted = votes.argmax(1).astype(np.int64)   # the first maximum: the smallest code on ties
+    with np.errstate(invalid="ignore", divide="ignore"):
+        confidence = votes[np.arange(n), predicted] / n_valid.astype(np.float64)
+    predicted[n_valid == 0] = -1
+    confidence[n_valid == 0] = np.nan
+    return predicted, confidence, n_valid
+
+
+def transfer_frame(names, categories, predicted, confidence, n_valid):
+    """The frame transfer_labels returns: indexed by the target cells' names; ``predicted`` (the label, None without a valid neighbour),
+    ``confidence``, ``n_neighbors``"""
+    import pandas as pd
+
+    cats = np.asarray(categories, dtype=object)
+    lab = np.empty(len(predicted), dtype=object)
+    ok = np.asarray(predicted) >= 0
+    lab[ok] = cats[np.asarray(predicted)[ok]]
+    lab[~ok] = None
+    return pd.DataFrame({"predicted": lab, "confidence": np.asarray(confidence, dtype=np.float64), "n_neighbors": np.asarray(n_valid, dtype=np.int64)},
+                        index=pd.Index(np.asarray(names)))

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, RowBlocks, check_de_args, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
+from .data import (MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
                    csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
                    latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions)
 from .module import spVIPESmodule
@@ -650,6 +650,68 @@ class spVIPES:
         sums = stats.cpu().numpy()
         table = expression_stats_table(sums, [sizes[k] * n_samples for k in range(n_seg)])
         return expression_stats_frame(names, sizes, index, table, n_samples, sums=sums)
+
+    # ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _latents_on_device(self, group_indices_list, latent: str = "shared", give_mean: bool = True, batch_size: Optional[int] = None, _noise=None) -> dict:
+        """{0: fp32 device tensor [n_cells_0, n_latent], 1: ...}: the ``latent`` ("shared" | "private") embedding of every cell of
+        ``group_indices_list[g]``, from the minibatch walk of ``get_latent_representation``, never copied to the host.  ``give_mean``: the
+        posterior means (``logtheta_loc``; deterministic), else the sampled ``log_z`` / ``logtheta_log_z`` -- what
+        ``get_latent_representation(normalized=False)`` returns under the same ``_noise``."""
+        stats, key = ("poe_stats", "logtheta_loc" if give_mean else "logtheta_log_z") if latent == "shared" else ("private_stats", "logtheta_loc" if give_mean else "log_z")
+        blocks = RowBlocks([len(g) for g in group_indices_list], False)
+        for step, tensors, (B0, B1) in self._eval_minibatches(group_indices_list, batch_size, None):
+            out = self._infer(tensors, _noise, step, B0, B1)
+            blocks.add([out[stats][g][key].float() for g in range(2)])
+        return {g: z.contiguous() for g, z in blocks.result().items()}
+
+    @torch.no_grad()
+    def latent_neighbors(self, group_indices_list: List[List[int]], k: int = 15, query=0, target=1, latent: str = "shared", give_mean: bool = True,
+                         include_self: bool = False, batch_size: Optional[int] = None, return_numpy: bool = True, _noise=None) -> dict:
+        """Each query cell's ``k`` nearest target cells in latent space, exact (the fused kernel spv_knn: no queries x targets matrix
+        exists at any time) -> {"indices" int32 [n_query, k]: positions into the target cells' order, ascending in
+        (distance, position), -1 where fewer than k exist; "distances" fp32 [n_query, k]: Euclidean (the square root of the kernel's
+        values; inf next to a -1); "query_obs" / "target_obs": the adata row numbers of the query and target cells, so
+        ``target_obs[indices]`` are adata rows}.
+        ``query`` / ``target``: 0, 1 or "both" (group 0's cells of ``group_indices_list``, then group 1's).  ``latent``: "shared" or
+        "private"; "private" only within one group (query == target, not "both": the groups' private spaces are not comparable).
+        ``give_mean``: neighbours among the posterior means (deterministic: two calls agree bit for bit), else among one sampled embedding,
+        the rows of ``get_latent_representation(normalized=False)``.  When every query cell is also a target cell its own row is left
+        out, unless ``include_self``.  ``return_numpy=False`` keeps the two arrays on the device.  ``_noise`` (tests only): as
+        ``get_latent_representation`` takes it."""
+        k, q_groups, t_groups, contained = check_neighbor_args(k, query, target, latent)
+        from .knn_ops import knn
+        z = self._latents_on_device(group_indices_list, latent, give_mean, batch_size, _noise)
+        Q, T = (z[gs[0]] if len(gs) == 1 else torch.cat([z[g] for g in gs]) for gs in (q_groups, t_groups))
+        sizes = [int(z[g].shape[0]) for g in range(2)]
+        exclude = None
+        if contained and not include_self:
+            exclude = torch.as_tensor(neighbor_self_positions(q_groups, t_groups, sizes), device=self.device)
+        if Q.shape[0] < 1:
+            raise ValueError("latent_neighbors: the query set is empty")
+        idx, d2 = knn(Q, T, k, exclude=exclude)
+        dist = torch.sqrt(d2)
+        obs = [np.concatenate([np.asarray(group_indices_list[g], dtype=np.int64) for g in gs]) for gs in (q_groups, t_groups)]
+        return {"indices": idx.cpu().numpy() if return_numpy else idx, "distances": dist.cpu().numpy() if return_numpy else dist,
+                "query_obs": obs[0], "target_obs": obs[1]}
+
+    def transfer_labels(self, group_indices_list: List[List[int]], source=1, target=0, labels="cell_type", k: int = 15, **neighbor_kwargs):
+        """Labels for the ``target`` group's cells by a vote of their ``k`` nearest ``source`` cells in latent space
+        (``latent_neighbors(query=target, target=source, k=k, **neighbor_kwargs)``; ``data.vote_labels``: uniform weights, ties to the
+        label that sorts first) -> DataFrame indexed by the target cells' ``obs_names`` (their adata row numbers without any) with
+        ``predicted`` (None for a cell without a valid neighbour), ``confidence`` (the share of the cell's valid neighbours that voted for
+        it) and ``n_neighbors`` (the valid ones).  ``source`` / ``target``: 0 or 1.  ``labels``: an ``obs`` column, or an array with one
+        entry per source cell."""
+        src, tgt = check_group(source), check_group(target)
+        check_neighbor_args(k, tgt, src, neighbor_kwargs.get("latent", "shared"))
+        if "query" in neighbor_kwargs or "target" in neighbor_kwargs or "return_numpy" in neighbor_kwargs:
+            raise ValueError("transfer_labels sets query, target and return_numpy itself")
+        cells = np.asarray(group_indices_list[src], dtype=np.int64)
+        cats, codes = np.unique(group_cell_labels(self.adata.obs, labels, cells, src), return_inverse=True)
+        nb = self.latent_neighbors(group_indices_list, k=k, query=tgt, target=src, **neighbor_kwargs)
+        predicted, confidence, n_valid = vote_labels(nb["indices"], codes, len(cats))
+        names = getattr(self.adata, "obs_names", None)
+        return transfer_frame(nb["query_obs"] if names is None else np.asarray(names)[nb["query_obs"]], cats, predicted, confidence, n_valid)
 
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}
