@@ -101,7 +101,7 @@ __global__ void nb_tables_pair_kernel(NbTabArgs a0, NbTabArgs a1) {
 enum { CNT_U16_ALIGNED = 0, CNT_U16_ANY = 1, CNT_F32 = 2 };
 template <int CM> struct RawCounts;
 template <> struct RawCounts<CNT_U16_ALIGNED> { u2v w; };          // one 8-byte load (matrix base, ld, col_off 4-aligned)
-template <> struct RawCounts<CNT_U16_ANY> { unsigned short w[4]; };
+template <> struct RawCounts<CNT_U16_ANY> { unsigned w[4]; };   // (zero-extended: one register each, nothing packs them while they are in flight)
 template <> struct RawCounts<CNT_F32> { float w[4]; };
 
 // branch-free: lanes (or genes) with nothing to read fetch element 0 of the matrix and decode() masks them
@@ -363,9 +363,16 @@ template <typename T>
 __device__ __forceinline__ void store4b(void* base, unsigned elem_off, const float (&v)[4]) {
   store4<T>(reinterpret_cast<char*>(base) + (size_t)(elem_off * (unsigned)sizeof(T)), 0, v);
 }
-template <typename T>
-__device__ __forceinline__ void load4b(const void* base, unsigned elem_off, float (&v)[4]) {
-  load4<T>(reinterpret_cast<const char*>(base) + (size_t)(elem_off * (unsigned)sizeof(T)), 0, v);
+// 4 consecutive mixing logits kept as they were stored: the f16 -> f32 conversion happens where a value is used, so nothing reads
+// the destination registers of the load while it is in flight
+template <typename LT> struct RawLogits;
+template <> struct RawLogits<_Float16> { typedef __attribute__((ext_vector_type(4))) _Float16 h4v; h4v w; };
+template <> struct RawLogits<float> { f4v w; };
+template <typename LT>
+__device__ __forceinline__ RawLogits<LT> load_logits4_raw(const void* base, unsigned elem_off) {
+  RawLogits<LT> r;
+  r.w = *reinterpret_cast<const decltype(r.w)*>(reinterpret_cast<const char*>(base) + (size_t)(elem_off * (unsigned)sizeof(LT)));
+  return r;
 }
 
 // fp32-mode gradient arrays: a bf16 hi plane followed by a bf16 lo plane (v = hi + lo to ~2^-17), each [Bp][Gp] in
@@ -529,22 +536,32 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
       }
     };
 
-    // software pipeline: counts two chunks ahead (undecoded), logits and (count, gene) table rows one chunk ahead;
-    // every load is issued before the stores of the chunk in flight, so its wait never drains those stores
-    RawCounts<CM> rawA = load_counts4_raw<CM>(p, row_of_cell, gbeg + 4 * gq, cell_ok), rawB = rawA, rawC = rawA;
-    float ellA[4];
-    float2 tabA[4];
-    load4b<LT>(p.logits, tile_off(gbeg), ellA);
-    if (nchunks > 1) rawB = load_counts4_raw<CM>(p, row_of_cell, gbeg + 16 + 4 * gq, cell_ok);
+    // Software pipeline over the chunks, in two named register sets (ping / pong by chunk parity).  While chunk c is evaluated its own
+    // set holds c's logits, c's (count, gene) table rows and, until they are decoded, c's count words; the other set holds the count
+    // words of c + 1.  Chunk c decodes its count words and fetches those of c + 2 into the same registers, fetches the logits and table
+    // rows of c + 1 into the other set, evaluates, and stores its gradients last.  Nothing is ever moved between the sets: a copy of a
+    // load's destination would have to wait for the load.  The vector-memory queue retires in order and counts stores, so at every
+    // wait the stores of the chunk before lie BEHIND what is waited for (its loads were issued ahead of its stores) and stay in
+    // flight.  The first chunk is peeled whole -- loads, evaluation, stores -- so that the loop is entered with the queue it has on
+    // its back edge (the compiler sizes the waits for the merged state); an odd chunk out is a single-chunk tail.  Loads are
+    // branch-free and past the end fetch the last chunk again (unused): the memory stream is the same on every path.
+    struct ChunkRegs { RawCounts<CM> raw; RawLogits<LT> ell; float2 tab[4]; };
+    ChunkRegs ping, pong;
+    // (the first chunk's index is made opaque per cell tile: the masks and addresses of the peeled chunk would otherwise be hoisted
+    // out of the cell-tile loop and held in registers across the whole chunk loop)
+    int cfirst = 0;
+    asm volatile("" : "+s"(cfirst));
+    const int gfirst = gbeg + 16 * cfirst;
+    ping.raw = load_counts4_raw<CM>(p, row_of_cell, gfirst + 4 * gq, cell_ok);
+    ping.ell = load_logits4_raw<LT>(p.logits, tile_off(gfirst));
+    pong.raw = load_counts4_raw<CM>(p, row_of_cell, gbeg + 16 * min(cfirst + 1, nchunks - 1) + 4 * gq, cell_ok);
     {
       float c0[4];
-      decode_counts4<CM>(p, rawA, row_of_cell, gbeg + 4 * gq, cell_ok, c0);
-      gather_tab(c0, gbeg, tabA);
+      decode_counts4<CM>(p, ping.raw, row_of_cell, gfirst + 4 * gq, cell_ok, c0);
+      gather_tab(c0, gfirst, ping.tab);
     }
 
-    NB_STAMP(2);
-    for (int c = 0; c < nchunks; ++c) {
-      if (c == 1) NB_STAMP(3);
+    auto chunk = [&](const int c, ChunkRegs& cur, ChunkRegs& nxt) __attribute__((always_inline)) {
       const int g0 = gbeg + 16 * c;
       const unsigned toff = tile_off(g0);
       // ---- y_p, y_s for this chunk: A[row = gene][k = 8 gq + i] from the LDS slice ------------------------------
@@ -561,20 +578,18 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
         ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_lo, bs_hi[s], ys, 0, 0, 0);
         ys = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws_hi, bs_hi[s], ys, 0, 0, 0);
       }
-      // ---- issue the loads of the following chunks (past the end: the last chunk again, unused) ------------------
+      // ---- this chunk's counts out of their words, then the loads of the following chunks ------------------------
       const int g1 = gbeg + 16 * min(c + 1, nchunks - 1), g2 = gbeg + 16 * min(c + 2, nchunks - 1);
-      float ellB[4];
-      float2 tabB[4];
-      rawC = load_counts4_raw<CM>(p, row_of_cell, g2 + 4 * gq, cell_ok);
-      if constexpr ((SPV_NB_ABLATE & 4) != 0) { ellB[0] = ellA[1]; ellB[1] = ellA[2]; ellB[2] = ellA[3]; ellB[3] = ellA[0]; }
-      else load4b<LT>(p.logits, tile_off(g1), ellB);
+      float cntA[4];
+      decode_counts4<CM>(p, cur.raw, row_of_cell, g0 + 4 * gq, cell_ok, cntA);
+      cur.raw = load_counts4_raw<CM>(p, row_of_cell, g2 + 4 * gq, cell_ok);
+      if constexpr ((SPV_NB_ABLATE & 4) != 0) { nxt.ell.w[0] = cur.ell.w[1]; nxt.ell.w[1] = cur.ell.w[2]; nxt.ell.w[2] = cur.ell.w[3]; nxt.ell.w[3] = cur.ell.w[0]; }
+      else nxt.ell = load_logits4_raw<LT>(p.logits, tile_off(g1));
       {
         float cB[4];
-        decode_counts4<CM>(p, rawB, row_of_cell, g1 + 4 * gq, cell_ok, cB);
-        gather_tab(cB, g1, tabB);
+        decode_counts4<CM>(p, nxt.raw, row_of_cell, g1 + 4 * gq, cell_ok, cB);
+        gather_tab(cB, g1, nxt.tab);
       }
-      float cntA[4];
-      decode_counts4<CM>(p, rawA, row_of_cell, g0 + 4 * gq, cell_ok, cntA);
       const int gq0 = g0 + 4 * gq;  // first of this lane's 4 consecutive genes
       float o_dl[4], o_tp[4], o_ts[4], dth4[4];
 #pragma unroll
@@ -588,8 +603,8 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
         const float theta = gt.x, dlt = gt.z, thlt2 = gt.w;
         const float cj = cntA[j];
         const float x = log1p_count(cj);
-        const float F = tabA[j].x, Psi = tabA[j].y;
-        const float el_ = ellA[j];
+        const float F = cur.tab[j].x, Psi = cur.tab[j].y;
+        const float el_ = (float)cur.ell.w[j];
         const float mu1 = __builtin_amdgcn_exp2f(fmaf(yp[j], NB_LOG2E, ap2)), mu2 = __builtin_amdgcn_exp2f(fmaf(ys[j], NB_LOG2E, as2));
         const float e1 = mu1 + SPV_EPS_NB, e2 = mu2 + SPV_EPS_NB;
         const float S1 = theta + e1, S2 = theta + e2;   // theta + mu + eps (one add fewer per component than the left-to-right sum)
@@ -620,8 +635,12 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
           o_dl[j] = fmaf(wk, sig, -wr2);
           o_tp[j] = wr1 * g1;
           o_ts[j] = wr2 * g2;
-          tp_sum += o_tp[j];
-          ts_sum += o_ts[j];
+          {   // plain adds of the rounded products, the values the arrays store: left to the compiler, some copies of the chunk code
+              // fuse the product into the sum and a cell's total would depend on which copy evaluated the chunk
+#pragma clang fp contract(off)
+            tp_sum += o_tp[j];
+            ts_sum += o_ts[j];
+          }
           dth4[j] = fmaf(wr1, dn1, fmaf(wr2, dn2, wk * Psi));
         }
       }
@@ -668,11 +687,17 @@ __device__ __forceinline__ void dec_nb_body(const DecParams& p) {
         }
         }
       }
+    };
 
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { ellA[j] = ellB[j]; tabA[j] = tabB[j]; }
-      rawA = rawB; rawB = rawC;
+    NB_STAMP(2);
+    chunk(cfirst, ping, pong);
+    NB_STAMP(3);
+    int c = cfirst + 1;
+    for (; c + 1 < nchunks; c += 2) {
+      chunk(c, pong, ping);
+      chunk(c + 1, ping, pong);
     }
+    if (c < nchunks) chunk(c, pong, ping);
     NB_STAMP(4);
     // the four gene groups of a cell sit in lanes c16, c16+16, c16+32, c16+48
     rec += __shfl_xor(rec, 16, 64); rec += __shfl_xor(rec, 32, 64);

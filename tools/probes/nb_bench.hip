@@ -4,7 +4,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -DSPV_NB_OCC=3 -o nb_bench nb_bench.hip && ./nb_bench [B G]
 // Prints the average launch time, the per-SIMD issue rate implied by the instruction count given on the command line
 // (optional 3rd arg, wave-instructions per launch from a --pmc SQ_INSTS_VALU pass) and a checksum of the outputs (so that
-// two variants can be compared for equal results).
+// two variants can be compared for equal results; NB_DUMP=<file> writes every output word).  -DNB_FP32_MODE times the fp32-mode instantiation instead (fp32 logits, gradients as bf16 hi / lo
+// planes); ./nb_bench 4096 30000 is then the C5 shape.
 #include "../../spvipes_amd/csrc/spv_decoder.h"
 #include <algorithm>
 #include <cstdio>
@@ -14,6 +15,12 @@
 #include <vector>
 
 using namespace spv;
+#ifdef NB_FP32_MODE
+typedef split_t grad_t; typedef float logit_t;
+#else
+typedef bf16_t grad_t; typedef _Float16 logit_t;
+#endif
+constexpr bool FP32_MODE = sizeof(logit_t) == 4;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
 static unsigned short f2bf_host(float f) {
@@ -53,8 +60,8 @@ int main(int argc, char** argv) {
     for (int k = 0; k < 25; ++k) put(Ahi, Alo, (size_t)b * DEC_KPS + DEC_KP + k, nrm(rng));
     put(Ahi, Alo, (size_t)b * DEC_KPS + DEC_KP + 25, 1.f);
   }
-  std::vector<_Float16> logits((size_t)Bp * Gp);
-  for (auto& l : logits) l = (_Float16)(1.5f * nrm(rng));
+  std::vector<logit_t> logits((size_t)Bp * Gp);
+  for (auto& l : logits) l = (logit_t)(1.5f * nrm(rng));
   std::vector<float> pxr(G);
   for (auto& v : pxr) v = nrm(rng);
   std::vector<float> ap(Bp), as(Bp), w(Bp, 0.f);
@@ -63,7 +70,7 @@ int main(int argc, char** argv) {
   DecParams p{};
   p.X = upload(X); p.ldx = G; p.rows = upload(rows); p.col_off = 0; p.count_is_u16 = 1;
   p.B = B; p.G = G; p.Bp = Bp; p.Gp = Gp;
-  p.logits = upload(logits); p.n_gene_tiles = Gp / 32; p.logits_f32 = 0;
+  p.logits = upload(logits); p.n_gene_tiles = Gp / 32; p.logits_f32 = FP32_MODE;
   p.Wps_hi = upload(Whi); p.Wps_lo = upload(Wlo); p.Aps_hi = upload(Ahi); p.Aps_lo = upload(Alo);
   float* d_pxr = upload(pxr);
   float4* gene_tab = dalloc<float4>(Gp); float2* cnt_tab = dalloc<float2>((size_t)NB_CMAX * Gp);
@@ -75,8 +82,9 @@ int main(int argc, char** argv) {
   p.nb_cell_tiles = getenv("NB_CELL_TILES") ? atoi(getenv("NB_CELL_TILES")) : 1;
   p.rec_part = dalloc<float>((size_t)nbs * Bp); p.tp_part = dalloc<float>((size_t)nbs * Bp); p.ts_part = dalloc<float>((size_t)nbs * Bp);
   p.dtheta_part = dalloc<float>((size_t)(Bp / 64) * Gp);
-  p.dL = dalloc<unsigned short>((size_t)Bp * Gp); p.tP = dalloc<unsigned short>((size_t)Bp * Gp); p.tS = dalloc<unsigned short>((size_t)Bp * Gp);
-  p.grads_f32 = 0;
+  const size_t planes = FP32_MODE ? 2 : 1;   // fp32 mode: a hi and a lo plane per gradient array
+  p.dL = dalloc<unsigned short>(planes * Bp * Gp); p.tP = dalloc<unsigned short>(planes * Bp * Gp); p.tS = dalloc<unsigned short>(planes * Bp * Gp);
+  p.grads_f32 = FP32_MODE;
   CK(hipDeviceSynchronize());
 
   dim3 grid(((Bp + NB_CELLS_PER_WG - 1) / NB_CELLS_PER_WG + p.nb_cell_tiles - 1) / p.nb_cell_tiles, nbs);
@@ -85,7 +93,7 @@ int main(int argc, char** argv) {
   CK(hipMemcpyToSymbol(HIP_SYMBOL(g_nb_stamps), &d_st, sizeof(d_st)));
   CK(hipDeviceSynchronize());
 #endif
-  auto launch = [&]() { hipLaunchKernelGGL((dec_nb_kernel<true, bf16_t, _Float16, CNT_U16_ALIGNED>), grid, dim3(256), 0, 0, p); };
+  auto launch = [&]() { hipLaunchKernelGGL((dec_nb_kernel<true, grad_t, logit_t, CNT_U16_ALIGNED>), grid, dim3(256), 0, 0, p); };
   for (int i = 0; i < 5; ++i) launch();
   CK(hipDeviceSynchronize());
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -120,14 +128,32 @@ int main(int argc, char** argv) {
   std::vector<float> rec((size_t)nbs * Bp), dth((size_t)(Bp / 64) * Gp);
   CK(hipMemcpy(rec.data(), p.rec_part, rec.size() * 4, hipMemcpyDeviceToHost));
   CK(hipMemcpy(dth.data(), p.dtheta_part, dth.size() * 4, hipMemcpyDeviceToHost));
-  std::vector<unsigned short> tS((size_t)Bp * Gp);
+  std::vector<unsigned short> tS(planes * Bp * Gp);
   CK(hipMemcpy(tS.data(), p.tS, tS.size() * 2, hipMemcpyDeviceToHost));
   double s1 = 0, s2 = 0, s3 = 0;
   for (float v : rec) s1 += v;
   for (float v : dth) s2 += v;
   for (size_t i = 0; i < tS.size(); i += 7) s3 += bf2f_host(tS[i]);
-  printf("dec_nb_kernel<train,bf16,f16,u16-aligned> OCC=%d  B=%d G=%d grid=%dx%d: %.1f us/launch   rec=%.6e dtheta=%.6e tS~=%.6e\n", SPV_NB_OCC, B, G, grid.x,
+  printf("dec_nb_kernel<train,%s,u16-aligned> OCC=%d  B=%d G=%d grid=%dx%d: %.1f us/launch   rec=%.6e dtheta=%.6e tS~=%.6e\n", FP32_MODE ? "split,f32" : "bf16,f16", SPV_NB_OCC, B, G, grid.x,
          grid.y, us, s1, s2, s3);
+  {  // order-sensitive 64-bit hash of every output word: equal between two builds only if the outputs are bit-identical
+    unsigned long long h = 1469598103934665603ull;
+    auto mix = [&](const void* ptr, size_t bytes) { const unsigned* w = (const unsigned*)ptr; for (size_t i = 0; i < bytes / 4; ++i) h = (h ^ w[i]) * 1099511628211ull; };
+    std::vector<unsigned short> g(planes * Bp * Gp);
+    for (void* src : {p.dL, p.tP, p.tS}) { CK(hipMemcpy(g.data(), src, g.size() * 2, hipMemcpyDeviceToHost)); mix(g.data(), g.size() * 2); }
+    std::vector<float> part((size_t)nbs * Bp);
+    for (float* src : {p.tp_part, p.ts_part}) { CK(hipMemcpy(part.data(), src, part.size() * 4, hipMemcpyDeviceToHost)); mix(part.data(), part.size() * 4); }
+    mix(rec.data(), rec.size() * 4); mix(dth.data(), dth.size() * 4);
+    printf("  output hash %016llx  (dL, tP, tS, tp_part, ts_part, rec_part, dtheta_part)\n", h);
+    if (const char* path = getenv("NB_DUMP")) {   // the same words, raw, in that order, for an element-wise comparison of two builds
+      FILE* f = fopen(path, "wb");
+      if (!f) { printf("cannot write %s\n", path); return 1; }
+      for (void* src : {p.dL, p.tP, p.tS}) { CK(hipMemcpy(g.data(), src, g.size() * 2, hipMemcpyDeviceToHost)); fwrite(g.data(), 2, g.size(), f); }
+      for (float* src : {p.tp_part, p.ts_part}) { CK(hipMemcpy(part.data(), src, part.size() * 4, hipMemcpyDeviceToHost)); fwrite(part.data(), 4, part.size(), f); }
+      fwrite(rec.data(), 4, rec.size(), f); fwrite(dth.data(), 4, dth.size(), f);
+      fclose(f);
+    }
+  }
   if (instrs > 0) printf("  %.1f M wave-instr / 1024 SIMDs / (%.1f us x 2.4 GHz) = %.3f instr/cycle/SIMD\n", instrs / 1e6, us, instrs / 1024.0 / (us * 2400.0));
   return 0;
 }
