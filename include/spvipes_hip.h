@@ -581,6 +581,55 @@ int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split);
 int32_t spv_knn_tile_q(void);
 int32_t spv_knn_tile_c(void);
 
+/* Entropic optimal transport between two point clouds (spVIPES.compute_transport_plan of the user API): the two reductions a
+ * log-domain Sinkhorn iteration and a sparse plan need, over all (query, candidate) pairs, nothing of size n_q x n_c stored.
+ * Per pair: c(i, j) = the distance of spv_knn above, the same bits (so c(x, y) and c(y, x) are the same bits: u and -u square
+ * alike), and t(i, j) = fmaf(-c(i, j), inv_eps, h[j]), ONE rounding.  h fp32 [n_c]: the caller's psi_j + log b_j.
+ * spv_ot_softmin: L[i] = log sum_j exp(t(i, j)), fp32 [n_q].  Per query a running (m, sum) pair over its chunk in ascending j, one exp
+ * per candidate -- e = exp(-|t - m|); t > m: sum = fmaf(sum, e, 1), m = t; else sum += e -- and L = m + log(sum).  A t that is not finite
+ * contributes nothing: h[j] = -inf marks a candidate of zero mass, an overflowing cost gives t = -inf, a NaN is skipped.  A query
+ * without a contributing candidate (n_c == 0 included) gets L = -inf.
+ * spv_ot_topk: row i of idx / val holds the k candidates with the largest t(i, j), in descending t, equal t to the smaller j; a t
+ * that is not finite is never selected.  val = exp(t(i, j) + r[i]) (r fp32 [n_q]: phi_i + log a_i), i.e. the plan entry P_ij;
+ * mass[i] = the fp32 sum of row i's val, added in list order from +0.  With fewer than k selectable candidates the remaining slots
+ * are idx = -1, val = 0.  Columns >= k and rows >= n_q are never written.  idx is exact: a function of the t bits alone, the same for
+ * every n_split and tiling, and a query's row does not depend on the other queries of the call.
+ * Launches: as spv_knn -- a partial pass of (tiles of spv_ot_tile_q() queries) x (n_split chunks of the candidates,
+ * spv_ot_tile_c() of them in LDS at a time) workgroups, and for n_split > 1 a merge pass, one lane per query, that folds the chunks'
+ * (m, sum) pairs / sorted lists from ws IN CHUNK ORDER.  No floating-point atomics: for fixed shapes and n_split two calls agree bit
+ * for bit.  L under DIFFERENT n_split agrees within its rounding bound only (a sum's grouping changes its rounding), not bit for bit.
+ * n_split = 0 stands for spv_ot_splits(n_q, n_c), a pure function of the shapes.
+ * ws: spv_ot_ws_bytes(n_q, k, n_split) bytes with the RESOLVED n_split; k = 0 asks for spv_ot_softmin's size.  8-byte aligned,
+ * overwritten by every call.  Nothing is allocated.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG, both entry points: null arguments / Q / C / h; ws null when its size is not 0 or
+ * not 8-byte aligned; D outside [1, SPV_OT_DMAX]; n_split outside [0, SPV_OT_SPLIT_MAX]; n_q < 1; n_c < 0; ld_q < D; ld_c < D;
+ * inv_eps not a positive finite number; n_split * n_q (softmin) or n_split * n_q * k (topk) beyond 2^31 - 1.  spv_ot_softmin: null L.
+ * spv_ot_topk: null r / idx / val / mass; k outside [1, SPV_OT_KMAX]; ld_out < k; n_q * ld_out beyond 2^31 - 1. */
+#define SPV_OT_DMAX 64
+#define SPV_OT_KMAX 64
+#define SPV_OT_SPLIT_MAX 64
+typedef struct spv_ot_args {
+  const float* Q; int64_t ld_q; int32_t n_q;      /* queries    fp32 [n_q][ld_q], ld_q >= D */
+  const float* C; int64_t ld_c; int32_t n_c;      /* candidates fp32 [n_c][ld_c], ld_c >= D */
+  int32_t D;                                      /* 1 .. SPV_OT_DMAX */
+  int32_t k;                                      /* spv_ot_topk: 1 .. SPV_OT_KMAX; spv_ot_softmin ignores it */
+  const float* h;                                 /* [n_c] */
+  const float* r;                                 /* [n_q], spv_ot_topk */
+  float inv_eps;                                  /* s = 1 / epsilon, > 0 */
+  int32_t n_split;                                /* 0 = spv_ot_splits(n_q, n_c); else 1 .. SPV_OT_SPLIT_MAX chunks of the candidates */
+  float* L;                                       /* [n_q], spv_ot_softmin */
+  int32_t* idx; float* val; int64_t ld_out;       /* [n_q][ld_out], ld_out >= k, spv_ot_topk */
+  float* mass;                                    /* [n_q], spv_ot_topk */
+  void* ws;                                       /* spv_ot_ws_bytes(n_q, k or 0, n_split) bytes */
+} spv_ot_args;
+int spv_ot_softmin(const spv_ot_args* a, void* stream);
+int spv_ot_topk(const spv_ot_args* a, void* stream);
+int32_t spv_ot_splits(int32_t n_q, int32_t n_c);
+int64_t spv_ot_ws_bytes(int32_t n_q, int32_t k, int32_t n_split);
+/* queries per workgroup and candidates per LDS tile of the partial passes */
+int32_t spv_ot_tile_q(void);
+int32_t spv_ot_tile_c(void);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

@@ -283,6 +283,16 @@ class SpvKnnArgs(C.Structure):
                 ("ld_out", C.c_int64), ("ws", C.c_void_p)]
 
 
+OT_DMAX, OT_KMAX, OT_SPLIT_MAX = 64, 64, 64   # SPV_OT_DMAX / SPV_OT_KMAX / SPV_OT_SPLIT_MAX
+
+
+class SpvOtArgs(C.Structure):
+    """the arguments of spv_ot_softmin / spv_ot_topk (include/spvipes_hip.h: spv_ot_args)"""
+    _fields_ = [("Q", C.c_void_p), ("ld_q", C.c_int64), ("n_q", C.c_int32), ("C", C.c_void_p), ("ld_c", C.c_int64), ("n_c", C.c_int32),
+                ("D", C.c_int32), ("k", C.c_int32), ("h", C.c_void_p), ("r", C.c_void_p), ("inv_eps", C.c_float), ("n_split", C.c_int32),
+                ("L", C.c_void_p), ("idx", C.c_void_p), ("val", C.c_void_p), ("ld_out", C.c_int64), ("mass", C.c_void_p), ("ws", C.c_void_p)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -365,6 +375,12 @@ _SIGNATURES = {
     "spv_knn_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "spv_knn_tile_q": (C.c_int32, []),
     "spv_knn_tile_c": (C.c_int32, []),
+    "spv_ot_softmin": (C.c_int, [C.POINTER(SpvOtArgs), C.c_void_p]),
+    "spv_ot_topk": (C.c_int, [C.POINTER(SpvOtArgs), C.c_void_p]),
+    "spv_ot_splits": (C.c_int32, [C.c_int32, C.c_int32]),
+    "spv_ot_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_ot_tile_q": (C.c_int32, []),
+    "spv_ot_tile_c": (C.c_int32, []),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

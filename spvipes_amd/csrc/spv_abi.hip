@@ -13,6 +13,7 @@
 #include "spv_de_median.h"
 #include "spv_count_stats.h"
 #include "spv_knn.h"
+#include "spv_ot.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -49,6 +50,13 @@ template <auto K, typename... Args>
 static void launch_lds(dim3 grid, dim3 block, int bytes, hipStream_t s, Args... args) {
   static bool raised = false;
   if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); raised = true; }
+  hipLaunchKernelGGL(K, grid, block, bytes, s, args...);
+}
+// the same with the opt-in made once to `most`, the largest size any call of K can ask for, and the launch taking `bytes` <= most
+template <auto K, typename... Args>
+static void launch_lds_upto(dim3 grid, dim3 block, int most, int bytes, hipStream_t s, Args... args) {
+  static bool raised = false;
+  if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, most); raised = true; }
   hipLaunchKernelGGL(K, grid, block, bytes, s, args...);
 }
 
@@ -1096,6 +1104,80 @@ extern "C" int spv_knn(const spv_knn_args* x, void* stream) {
   if (rc != SPV_OK || n_split == 1) return rc;
   hipLaunchKernelGGL(knn_merge_kernel, dim3(tiles), dim3(KNN_TQ), knn_lds_bytes(0, x->k), s, a);   // at most the 64 KiB a kernel gets unasked
   return launch_status("spv_knn (merge pass)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// entropic optimal transport: fused soft-min and top-k over all pairs (spv_ot.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_ot_tile_q(void) { return KNN_TQ; }
+extern "C" int32_t spv_ot_tile_c(void) { return KNN_TC; }
+extern "C" int32_t spv_ot_splits(int32_t n_q, int32_t n_c) { return knn_splits(n_q, n_c); }
+extern "C" int64_t spv_ot_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
+  if (n_q < 1 || k < 0 || n_split <= 1) return 0;
+  return (int64_t)n_split * n_q * (k ? k : 1) * 8;
+}
+
+// what both entry points refuse, then the kernels' arguments with the resolved chunks; `topk`: the checks of k and the lists
+static int ot_check(const spv_ot_args* x, const char* who, bool topk, OtArgs& a) {
+  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
+  if (!x->Q) return fail(SPV_ERR_ARG, "%s: null Q", who);
+  if (!x->C) return fail(SPV_ERR_ARG, "%s: null C", who);
+  if (!x->h) return fail(SPV_ERR_ARG, "%s: null h", who);
+  if (!topk && !x->L) return fail(SPV_ERR_ARG, "%s: null L", who);
+  if (topk && !x->r) return fail(SPV_ERR_ARG, "%s: null r", who);
+  if (topk && !x->idx) return fail(SPV_ERR_ARG, "%s: null idx", who);
+  if (topk && !x->val) return fail(SPV_ERR_ARG, "%s: null val", who);
+  if (topk && !x->mass) return fail(SPV_ERR_ARG, "%s: null mass", who);
+  if (x->D < 1 || x->D > KNN_DMAX) return fail(SPV_ERR_ARG, "%s: D must lie in [1, 64]", who);
+  if (topk && (x->k < 1 || x->k > KNN_KMAX)) return fail(SPV_ERR_ARG, "%s: k must lie in [1, 64]", who);
+  if (x->n_split < 0 || x->n_split > KNN_SPLIT_MAX) return fail(SPV_ERR_ARG, "%s: n_split must be 0 or lie in [1, 64]", who);
+  if (x->n_q < 1) return fail(SPV_ERR_ARG, "%s: n_q < 1", who);
+  if (x->n_c < 0) return fail(SPV_ERR_ARG, "%s: n_c < 0", who);
+  if (x->ld_q < x->D) return fail(SPV_ERR_ARG, "%s: ld_q < D", who);
+  if (x->ld_c < x->D) return fail(SPV_ERR_ARG, "%s: ld_c < D", who);
+  if (!(x->inv_eps > 0.f && x->inv_eps < INFINITY)) return fail(SPV_ERR_ARG, "%s: inv_eps must be a positive finite number", who);
+  if (topk && x->ld_out < x->k) return fail(SPV_ERR_ARG, "%s: ld_out < k", who);
+  if (topk && ((int64_t)x->n_q * x->ld_out > INT32_MAX || x->ld_out > INT32_MAX)) return fail(SPV_ERR_ARG, "%s: n_q * ld_out exceeds 2^31 - 1", who);
+  const int n_split = x->n_split ? x->n_split : knn_splits(x->n_q, x->n_c);
+  if ((int64_t)n_split * x->n_q * (topk ? x->k : 1) > INT32_MAX) return fail(SPV_ERR_ARG, "%s: the workspace (n_split * n_q [* k] entries) exceeds 2^31 - 1", who);
+  if (n_split > 1 && !x->ws) return fail(SPV_ERR_ARG, "%s: null ws", who);
+  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "%s: ws must be 8-byte aligned", who);
+  a = OtArgs{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, topk ? x->k : 0, x->h, x->r, x->inv_eps, n_split,
+             knn_chunk(x->n_c, n_split), x->L, x->idx, x->val, (long)x->ld_out, x->mass, x->ws};
+  return SPV_OK;
+}
+
+extern "C" int spv_ot_softmin(const spv_ot_args* x, void* stream) {
+  OtArgs a;
+  int rc = ot_check(x, "spv_ot_softmin", false, a);
+  if (rc != SPV_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((a.n_q + KNN_TQ - 1) / KNN_TQ);
+  const dim3 grid(tiles, (unsigned)a.n_split), block(KNN_TQ);
+  if (a.D <= 16) hipLaunchKernelGGL((ot_softmin_kernel<16>), grid, block, ot_softmin_lds_bytes(16), s, a);
+  else if (a.D <= 32) hipLaunchKernelGGL((ot_softmin_kernel<32>), grid, block, ot_softmin_lds_bytes(32), s, a);
+  else hipLaunchKernelGGL((ot_softmin_kernel<64>), grid, block, ot_softmin_lds_bytes(64), s, a);
+  rc = launch_status(a.n_split == 1 ? "spv_ot_softmin" : "spv_ot_softmin (partial pass)");
+  if (rc != SPV_OK || a.n_split == 1) return rc;
+  hipLaunchKernelGGL(ot_softmin_merge_kernel, dim3(tiles), block, 0, s, a);
+  return launch_status("spv_ot_softmin (merge pass)");
+}
+
+extern "C" int spv_ot_topk(const spv_ot_args* x, void* stream) {
+  OtArgs a;
+  int rc = ot_check(x, "spv_ot_topk", true, a);
+  if (rc != SPV_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((a.n_q + KNN_TQ - 1) / KNN_TQ);
+  const dim3 grid(tiles, (unsigned)a.n_split), block(KNN_TQ);
+  // the opt-in is to the largest LDS a call can ask for (k = SPV_OT_KMAX: beyond the 64 KiB a kernel gets unasked), the launch takes what k needs
+  if (a.D <= 16) launch_lds_upto<ot_topk_kernel<16>>(grid, block, ot_topk_lds_bytes(16, KNN_KMAX), ot_topk_lds_bytes(16, a.k), s, a);
+  else if (a.D <= 32) launch_lds_upto<ot_topk_kernel<32>>(grid, block, ot_topk_lds_bytes(32, KNN_KMAX), ot_topk_lds_bytes(32, a.k), s, a);
+  else launch_lds_upto<ot_topk_kernel<64>>(grid, block, ot_topk_lds_bytes(64, KNN_KMAX), ot_topk_lds_bytes(64, a.k), s, a);
+  rc = launch_status(a.n_split == 1 ? "spv_ot_topk" : "spv_ot_topk (partial pass)");
+  if (rc != SPV_OK || a.n_split == 1) return rc;
+  hipLaunchKernelGGL(ot_topk_merge_kernel, dim3(tiles), block, ot_topk_lds_bytes(0, a.k) - ot_tile_words(0) * 4, s, a);   // at most the 64 KiB a kernel gets unasked
+  return launch_status("spv_ot_topk (merge pass)");
 }
 
 extern "C" int spv_count_totals(const spv_counts* x, int32_t n_cells, int32_t G, double* total, void* stream) {

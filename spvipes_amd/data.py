@@ -973,3 +973,55 @@ def transfer_frame(names, categories, predicted, confidence, n_valid):
     lab[~ok] = None
     return pd.DataFrame({"predicted": lab, "confidence": np.asarray(confidence, dtype=np.float64), "n_neighbors": np.asarray(n_valid, dtype=np.int64)},
                         index=pd.Index(np.asarray(names)))
+
+
+# ---- transport plans from two top-k passes (ot_ops.transport_plan / model.compute_transport_plan): host-side assembly and refusals ------
+def plan_union_csr(idx_rows, val_rows, idx_cols, val_cols, n0: int, n1: int):
+    """The sparse plan [n0, n1] whose support is the union of two top-k passes -> CSR (indptr int64 [n0 + 1], indices int32, data fp32),
+    columns ascending within a row.  ``idx_rows`` / ``val_rows`` [n0, k]: per cell i of group 0 its kept cells j of group 1 (-1 = empty
+    slot) and the entries P_ij; ``idx_cols`` / ``val_cols`` [n1, k]: per cell j of group 1 its kept cells i of group 0 and P_ij.  A pair
+    both passes kept takes the ROW pass's value (the two differ by rounding order only)."""
+    idx_rows, idx_cols = np.asarray(idx_rows), np.asarray(idx_cols)
+    val_rows, val_cols = np.asarray(val_rows, dtype=np.float32), np.asarray(val_cols, dtype=np.float32)
+    n0, n1 = int(n0), int(n1)
+    if idx_rows.ndim != 2 or idx_rows.shape[0] != n0 or val_rows.shape != idx_rows.shape:
+        raise ValueError(f"plan_union_csr: the row pass must be two arrays [{n0}, k]")
+    if idx_cols.ndim != 2 or idx_cols.shape[0] != n1 or val_cols.shape != idx_cols.shape:
+        raise ValueError(f"plan_union_csr: the column pass must be two arrays [{n1}, k]")
+    if (idx_rows < -1).any() or (idx_rows >= n1).any() or (idx_cols < -1).any() or (idx_cols >= n0).any():
+        raise ValueError("plan_union_csr: indices must be -1 or lie inside the other group")
+    keep_r, keep_c = idx_rows >= 0, idx_cols >= 0
+    i_r = np.broadcast_to(np.arange(n0, dtype=np.int64)[:, None], idx_rows.shape)[keep_r]
+    j_c = np.broadcast_to(np.arange(n1, dtype=np.int64)[:, None], idx_cols.shape)[keep_c]
+    key_r = i_r * n1 + idx_rows[keep_r].astype(np.int64)
+    key_c = idx_cols[keep_c].astype(np.int64) * n1 + j_c
+    keys = np.concatenate([key_r, key_c])
+    vals = np.concatenate([val_rows[keep_r], val_cols[keep_c]])
+    uniq, first = np.unique(keys, return_index=True)   # `first`: the row pass's entry where both kept the pair
+    indptr = np.zeros(n0 + 1, dtype=np.int64)
+    np.add.at(indptr, uniq // max(n1, 1) + 1, 1)
+    return np.cumsum(indptr), (uniq % max(n1, 1)).astype(np.int32), vals[first].astype(np.float32)
+
+
+def check_transport_args(rep, obs_idx, k):
+    """The refusals of ``compute_transport_plan`` ahead of any device work -> (X0, X1 float32 C-contiguous [n_g, D], k): ``rep``
+    [n_obs, D] with 1 <= D <= OT_DMAX, finite; ``obs_idx`` the two groups' row positions; ``k`` an integer in [1, OT_KMAX]."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _abi.OT_KMAX:
+        raise ValueError(f"k must be an integer in [1, {_abi.OT_KMAX}], got {k!r}")
+    rep = np.asarray(rep)
+    if rep.ndim != 2 or not np.issubdtype(rep.dtype, np.number):
+        raise ValueError(f"use_rep must be a numeric array [n_obs, D], got shape {rep.shape}")
+    if not 1 <= rep.shape[1] <= _abi.OT_DMAX:
+        raise ValueError(f"use_rep must have between 1 and {_abi.OT_DMAX} columns, got {rep.shape[1]}")
+    if len(obs_idx) != 2:
+        raise ValueError("a transport plan couples exactly two groups")
+    parts = []
+    for g, rows in enumerate(obs_idx):
+        rows = np.asarray(rows)
+        if rows.size < 1 or rows.min() < 0 or rows.max() >= rep.shape[0]:
+            raise ValueError(f"group {g}: its rows must be non-empty and lie inside use_rep's {rep.shape[0]} rows")
+        part = np.ascontiguousarray(rep[rows], dtype=np.float32)
+        if not np.isfinite(part).all():
+            raise ValueError(f"group {g}: use_rep holds non-finite values")
+        parts.append(part)
+    return parts[0], parts[1], int(k)

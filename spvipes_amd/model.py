@@ -20,10 +20,11 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
+from .data import (MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, check_transport_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
                    csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
                    latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions)
 from .module import spVIPESmodule
+from .plan import SparsePlan
 from .train import Trainer, default_max_epochs
 
 _SETUP_KEY = "_spvipes_amd_setup"
@@ -65,7 +66,9 @@ class spVIPES:
         if plan_key:
             if adata.uns.get(plan_key) is None:
                 raise ValueError(f"Transport plan not found in adata.uns['{plan_key}']")
-            transport_plan = torch.tensor(np.asarray(adata.uns[plan_key]), dtype=torch.float32, device=self.device)
+            transport_plan = adata.uns[plan_key]
+            if not (is_sparse(transport_plan) or isinstance(transport_plan, SparsePlan)):   # a sparse plan goes to the module as it is, never densified
+                transport_plan = torch.tensor(np.asarray(transport_plan), dtype=torch.float32, device=self.device)
         pair_data = "processed_transport_labels" not in adata.obs  # :249
         use_labels = setup.get("label_key") is not None  # :251
         # batch covariates (setup_anndata(batch_key=...): CategoricalObsField(BATCH_KEY), :358; n_batch = its number of categories, :230):
@@ -135,6 +138,43 @@ class spVIPES:
                 raise ValueError(f"adata.uns['{k}'] missing: build the AnnData with prepare_adatas (or the same schema)")
         adata.uns[_SETUP_KEY] = {"groups_key": groups_key, "match_clusters": match_clusters, "transport_plan_key": transport_plan_key,
                                  "label_key": label_key, "batch_key": batch_key, "layer": layer}
+
+    @classmethod
+    def compute_transport_plan(cls, adata, use_rep, k: int = 32, key_added: str = "transport_plan", device: Optional[str] = None,
+                               **sinkhorn_kwargs):
+        """The optimal-transport plan between the two groups' cells that the paired and cluster-matched PoE modes read, from a
+        low-dimensional representation both groups share (PCA, or this model's own shared latents from a label-free run): entropic OT
+        with squared Euclidean cost by log-domain Sinkhorn iterations, truncated to each cell's ``k`` largest entries in either
+        direction (``ot_ops.transport_plan``).  No n0 x n1 matrix exists at any time; needs no model and no training.
+        ``use_rep``: a key of ``adata.obsm`` or an array [n_obs, D], 1 <= D <= 64; rows are split by ``adata.uns["groups_obs_indices"]``.
+        Writes the scipy CSR plan [n0, n1] (fp32) to ``adata.uns[key_added]`` and, where absent, ``obs["indices"]`` (each cell's position
+        within its group); then ``setup_anndata(..., transport_plan_key=key_added)`` takes it.  ``sinkhorn_kwargs``: ``epsilon``,
+        ``scale_cost``, ``a``, ``b``, ``max_iter``, ``tol``, ``check_every`` of ``ot_ops.sinkhorn``.  Returns the ``TransportPlan``: the
+        potentials, the iteration count and error, and ``row_kept`` / ``col_kept``, the share of each cell's mass the truncation kept."""
+        if "groups_obs_indices" not in adata.uns:
+            raise ValueError("adata.uns['groups_obs_indices'] missing: build the AnnData with prepare_adatas (or the same schema)")
+        if isinstance(use_rep, str):
+            obsm = getattr(adata, "obsm", None)
+            if obsm is None or use_rep not in obsm:
+                raise KeyError(f"use_rep '{use_rep}' not found in adata.obsm")
+            use_rep = obsm[use_rep]
+        obs_idx = [np.asarray(v) for v in adata.uns["groups_obs_indices"]]
+        rep = np.asarray(use_rep)
+        if rep.ndim == 2 and rep.shape[0] != adata.n_obs:
+            raise ValueError(f"use_rep must have one row per cell ({adata.n_obs}), got {rep.shape[0]}")
+        X0, X1, k = check_transport_args(rep, obs_idx, k)
+        if not torch.cuda.is_available():
+            raise _abi.SpvError("spvipes_amd needs an MI355X: there is no CPU fallback for the hot path")
+        from .ot_ops import transport_plan
+        dev = torch.device(device or "cuda:0")
+        result = transport_plan(torch.from_numpy(X0).to(dev), torch.from_numpy(X1).to(dev), k=k, **sinkhorn_kwargs)
+        adata.uns[key_added] = result.to_scipy()
+        if "indices" not in adata.obs:
+            pos = np.zeros(adata.n_obs, dtype=np.int32)
+            for rows in obs_idx:
+                pos[rows] = np.arange(len(rows), dtype=np.int32)
+            adata.obs["indices"] = pos
+        return result
 
     # ------------------------------------------------------------------------------------------
     def _local_rows(self, g: int, indices: Sequence[int]) -> np.ndarray:

@@ -1,0 +1,251 @@
+"""Entropic optimal transport on the device: the fused kernels spv_ot_softmin / spv_ot_topk (csrc/spv_ot.h; include/spvipes_hip.h
+states the contract), the log-domain Sinkhorn driver on top of them and the sparse plan it ends in.  ``spVIPES.compute_transport_plan``
+runs it on a common low-dimensional representation of the two groups; nothing of size n0 x n1 is ever stored."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _abi
+from ._abi import OT_DMAX, OT_KMAX, OT_SPLIT_MAX, SpvOtArgs, ptr, stream_ptr
+from .data import plan_union_csr
+from .knn_ops import _workspace
+
+
+def ot_tiles() -> Tuple[int, int]:
+    """(queries per workgroup, candidates per LDS tile) of the partial passes"""
+    lib = _abi.load()
+    return int(lib.spv_ot_tile_q()), int(lib.spv_ot_tile_c())
+
+
+def ot_splits(n_q: int, n_c: int) -> int:
+    """Chunks of the candidates both kernels use for this shape when ``n_split`` is 0: a pure function of the shapes"""
+    return int(_abi.load().spv_ot_splits(int(n_q), int(n_c)))
+
+
+def ot_ws_bytes(n_q: int, k: int, n_split: int) -> int:
+    """Bytes of workspace for ``n_split`` chunks (the resolved number, not 0); ``k`` = 0 asks for ot_softmin's: 0 for one chunk"""
+    return int(_abi.load().spv_ot_ws_bytes(int(n_q), int(k), int(n_split)))
+
+
+def _rows(t, name: str) -> None:
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 1
+            or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        raise _abi.SpvError(f"ot: {name} must be an fp32 device tensor [rows, D] with unit column stride")
+
+
+def _vector(t, n: int, dev, name: str) -> None:
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n
+            or not t.is_contiguous()):
+        raise _abi.SpvError(f"ot: {name} must be a contiguous fp32 device tensor with {n} entries")
+
+
+def _common(X, Y, h, inv_eps, n_split) -> SpvOtArgs:
+    """the checks and the argument fields ot_softmin and ot_topk share"""
+    _rows(X, "X"), _rows(Y, "Y")
+    dev, n_q, n_c, D = X.device, int(X.shape[0]), int(Y.shape[0]), int(X.shape[1])
+    if Y.device != dev or int(Y.shape[1]) != D:
+        raise _abi.SpvError("ot: X and Y must share a device and have the same number of columns")
+    if n_q < 1:
+        raise ValueError("ot: X has no rows")
+    if not 1 <= D <= OT_DMAX:
+        raise ValueError(f"ot: D must lie in [1, {OT_DMAX}], got {D}")
+    _vector(h, n_c, dev, "h")
+    inv_eps = float(inv_eps)
+    if not (0.0 < inv_eps < math.inf) or not (0.0 < float(np.float32(inv_eps)) < math.inf):
+        raise ValueError(f"ot: inv_eps must be a positive finite number in fp32, got {inv_eps!r}")
+    if isinstance(n_split, bool) or int(n_split) != n_split or not 0 <= int(n_split) <= OT_SPLIT_MAX:
+        raise ValueError(f"ot: n_split must be 0 or an integer in [1, {OT_SPLIT_MAX}], got {n_split!r}")
+    a = SpvOtArgs()
+    a.Q, a.ld_q, a.n_q = ptr(X), (X.stride(0) if n_q > 1 else D), n_q
+    a.C, a.ld_c, a.n_c = (ptr(Y) if n_c else ptr(X)), (Y.stride(0) if n_c > 1 else D), n_c   # an empty tensor has no address; nothing is read
+    a.D, a.h, a.inv_eps, a.n_split = D, (ptr(h) if n_c else ptr(X)), inv_eps, int(n_split)
+    return a
+
+
+def ot_softmin(X: torch.Tensor, Y: torch.Tensor, h: torch.Tensor, inv_eps: float, n_split: int = 0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """L[i] = log sum_j exp(t_ij), t_ij = fma(-c_ij, inv_eps, h[j]) with c_ij the squared Euclidean distance of ``knn_ops.knn`` (the
+    same bits) -> fp32 [n_q].  ``X`` [n_q >= 1, D], ``Y`` [n_c >= 0, D]: fp32 device tensors with unit column stride (row strides may
+    exceed D), 1 <= D <= OT_DMAX; ``h`` contiguous fp32 [n_c], -inf marks a candidate without mass.  A t that is not finite adds
+    nothing; a query without a contributing candidate gets -inf.  ``n_split``: chunks of the candidates, 0 = ``ot_splits(n_q, n_c)``;
+    different values agree within rounding, not bit for bit.  ``out``: a contiguous fp32 tensor [>= n_q]; a view of its first n_q
+    entries is returned and nothing else is written.  Deterministic: two calls agree bit for bit."""
+    a = _common(X, Y, h, inv_eps, n_split)
+    dev, n_q = X.device, int(X.shape[0])
+    if out is None:
+        out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev or out.dtype != torch.float32 or out.dim() != 1
+          or out.numel() < n_q or not out.is_contiguous()):
+        raise _abi.SpvError(f"ot_softmin: out must be a contiguous fp32 device tensor with at least {n_q} entries")
+    ws = _workspace(ot_ws_bytes(n_q, 0, int(n_split) or ot_splits(n_q, int(Y.shape[0]))), dev)
+    a.L, a.ws = ptr(out), ptr(ws)
+    _abi.call("spv_ot_softmin", C.byref(a), stream_ptr())
+    return out[:n_q]
+
+
+def ot_topk(X: torch.Tensor, Y: torch.Tensor, h: torch.Tensor, r: torch.Tensor, inv_eps: float, k: int, n_split: int = 0,
+            out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """For every row of ``X`` the ``k`` rows of ``Y`` with the largest t_ij (``ot_softmin``'s t, the same bits) -> (idx int32 [n_q, k],
+    val fp32 [n_q, k], mass fp32 [n_q]), descending in t, equal t to the smaller index, a non-finite t never: val = exp(t_ij + r[i])
+    is the plan entry for r = phi + log a, mass the sum of the row's val in list order; rows with fewer than k selectable candidates
+    end in idx = -1 / val = 0.  ``r`` contiguous fp32 [n_q]; 1 <= k <= OT_KMAX; the rest as ``ot_softmin``.  idx is the same for every
+    ``n_split``.  ``out``: (idx, val) tensors [n_q, >= k] with one common row stride and unit column stride and mass [>= n_q]; views
+    are returned and nothing else is written."""
+    a = _common(X, Y, h, inv_eps, n_split)
+    dev, n_q = X.device, int(X.shape[0])
+    _vector(r, n_q, dev, "r")
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= OT_KMAX:
+        raise ValueError(f"ot_topk: k must be an integer in [1, {OT_KMAX}], got {k!r}")
+    k = int(k)
+    if out is None:
+        idx = torch.empty((n_q, k), dtype=torch.int32, device=dev)
+        val = torch.empty((n_q, k), dtype=torch.float32, device=dev)
+        mass = torch.empty(n_q, dtype=torch.float32, device=dev)
+    else:
+        idx, val, mass = out
+        for t, dt, name in ((idx, torch.int32, "idx"), (val, torch.float32, "val")):
+            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != dt or t.dim() != 2 or t.shape[0] != n_q
+                    or t.shape[1] < k or (t.shape[1] > 1 and t.stride(1) != 1) or (n_q > 1 and t.stride(0) < k)):
+                raise _abi.SpvError(f"ot_topk: out {name} must be a device tensor [{n_q}, >= {k}] of {dt} with unit column stride")
+        if n_q > 1 and idx.stride(0) != val.stride(0):
+            raise _abi.SpvError("ot_topk: out idx and val must have the same row stride")
+        if (not isinstance(mass, torch.Tensor) or not mass.is_cuda or mass.device != dev or mass.dtype != torch.float32 or mass.dim() != 1
+                or mass.numel() < n_q or not mass.is_contiguous()):
+            raise _abi.SpvError(f"ot_topk: out mass must be a contiguous fp32 device tensor with at least {n_q} entries")
+    ws = _workspace(ot_ws_bytes(n_q, k, int(n_split) or ot_splits(n_q, int(Y.shape[0]))), dev)
+    a.k, a.r = k, ptr(r)
+    a.idx, a.val, a.ld_out = ptr(idx), ptr(val), (idx.stride(0) if n_q > 1 else max(k, int(idx.shape[1])))
+    a.mass, a.ws = ptr(mass), ptr(ws)
+    _abi.call("spv_ot_topk", C.byref(a), stream_ptr())
+    return idx[:, :k], val[:, :k], mass[:n_q]
+
+
+def mean_sq_cost(X0: torch.Tensor, X1: torch.Tensor) -> float:
+    """The mean of |x_i - y_j|^2 over ALL pairs in closed form from the moments, in fp64: mean|x|^2 + mean|y|^2 - 2 mean(x).mean(y).
+    No pairwise pass."""
+    x, y = X0.detach().double(), X1.detach().double()
+    return float((x * x).sum(1).mean() + (y * y).sum(1).mean() - 2.0 * torch.dot(x.mean(0), y.mean(0)))
+
+
+def _marginal(w, n: int, dev, name: str) -> torch.Tensor:
+    """log of a marginal as fp32 [n]: uniform by default; zeros are allowed and become -inf"""
+    if w is None:
+        return torch.full((n,), -math.log(n), dtype=torch.float32, device=dev)
+    w = torch.as_tensor(w).detach().to(dev, torch.float64).reshape(-1)
+    if w.numel() != n or not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or not float(w.sum()) > 0:
+        raise ValueError(f"sinkhorn: {name} must hold {n} finite non-negative weights with a positive sum")
+    return torch.log(w / w.sum()).to(torch.float32)
+
+
+@dataclass
+class SinkhornResult:
+    """``phi`` [n0], ``psi`` [n1]: the dimensionless potentials (fp32 device tensors); ``log_a`` / ``log_b`` the log marginals;
+    ``inv_eps`` the scalar s the kernels saw (1 / (epsilon x cost scale)); ``cost_scale`` what the cost was divided by;
+    ``n_iter`` iterations run; ``error`` the last max_i |phi_new - phi_old| read (nan if never read); ``converged``: error <= tol."""
+    phi: torch.Tensor
+    psi: torch.Tensor
+    log_a: torch.Tensor
+    log_b: torch.Tensor
+    inv_eps: float
+    cost_scale: float
+    n_iter: int
+    error: float
+    converged: bool
+
+
+def sinkhorn(X0: torch.Tensor, X1: torch.Tensor, epsilon: float = 0.05, scale_cost: Optional[str] = "mean", a=None, b=None,
+             max_iter: int = 2000, tol: float = 1e-3, check_every: int = 10) -> SinkhornResult:
+    """Log-domain Sinkhorn iterations between the rows of ``X0`` [n0, D] and ``X1`` [n1, D] (fp32 device tensors) with cost
+    c_ij = |x_i - y_j|^2 and plan P_ij = a_i b_j exp(phi_i + psi_j - s c_ij).  ``scale_cost="mean"`` divides the cost by the mean of all
+    c_ij (``mean_sq_cost``), ``None`` uses ``epsilon`` as given: s = 1 / (epsilon x scale).  ``a`` / ``b``: the marginals, uniform by default,
+    normalised to sum 1; zeros are allowed.  One iteration is phi = -softmin(X0, X1, psi + log b), then psi = -softmin(X1, X0, phi + log a).
+    Every ``check_every`` iterations the host reads max_i |phi_new - phi_old| over the cells with mass -- the largest log-deviation of
+    the row marginal -- ONCE and stops at <= ``tol``; ``tol=0`` runs all ``max_iter``."""
+    _rows(X0, "X0"), _rows(X1, "X1")
+    if X0.device != X1.device or X0.shape[1] != X1.shape[1]:
+        raise _abi.SpvError("sinkhorn: X0 and X1 must share a device and have the same number of columns")
+    n0, n1, dev = int(X0.shape[0]), int(X1.shape[0]), X0.device
+    if n0 < 1 or n1 < 1:
+        raise ValueError("sinkhorn: both groups need at least one row")
+    if scale_cost not in ("mean", None):
+        raise ValueError(f"sinkhorn: scale_cost must be 'mean' or None, got {scale_cost!r}")
+    if not (float(epsilon) > 0 and math.isfinite(float(epsilon))):
+        raise ValueError(f"sinkhorn: epsilon must be a positive finite number, got {epsilon!r}")
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 1 or int(check_every) != check_every or int(check_every) < 1:
+        raise ValueError("sinkhorn: max_iter and check_every must be positive integers")
+    if not float(tol) >= 0:
+        raise ValueError(f"sinkhorn: tol must be >= 0, got {tol!r}")
+    scale = mean_sq_cost(X0, X1) if scale_cost == "mean" else 1.0
+    if not (scale > 0 and math.isfinite(scale)):
+        raise ValueError("sinkhorn: the mean cost is not a positive finite number (all points equal, or non-finite input)")
+    s = float(np.float32(1.0 / (float(epsilon) * scale)))
+    log_a, log_b = _marginal(a, n0, dev, "a"), _marginal(b, n1, dev, "b")
+    live = torch.isfinite(log_a)
+    phi, psi = torch.zeros(n0, dtype=torch.float32, device=dev), torch.zeros(n1, dtype=torch.float32, device=dev)
+    L0, L1 = torch.empty_like(phi), torch.empty_like(psi)
+    n_iter, err, done = 0, float("nan"), False
+    for it in range(1, int(max_iter) + 1):
+        ot_softmin(X0, X1, psi + log_b, s, out=L0)
+        check = tol > 0 and (it % int(check_every) == 0 or it == int(max_iter))
+        if check:
+            delta = torch.where(live, (L0 + phi).abs(), torch.zeros_like(phi)).max()   # phi_new = -L0
+        torch.neg(L0, out=phi)
+        ot_softmin(X1, X0, phi + log_a, s, out=L1)
+        torch.neg(L1, out=psi)
+        n_iter = it
+        if check:
+            err = float(delta)   # the one host sync
+            if err <= tol:
+                done = True
+                break
+    return SinkhornResult(phi, psi, log_a, log_b, s, scale, n_iter, err, done)
+
+
+class TransportPlan:
+    """What ``transport_plan`` returns: the sparse plan as CSR arrays on the host (``indptr`` int64 [n0 + 1], ``indices`` int32,
+    ``data`` fp32; columns ascending within a row), the Sinkhorn result (``sinkhorn``: potentials and diagnostics) and the share of
+    every cell's mass the truncation to k entries per pass kept: ``row_kept`` = row_mass / a [n0], ``col_kept`` = col_mass / b [n1]
+    (numpy fp32; nan for a cell without mass).  ``row_mass`` / ``col_mass`` are the kernels' own sums of each pass's kept entries."""
+
+    def __init__(self, indptr, indices, data, shape, sinkhorn_result, row_mass, col_mass, row_kept, col_kept, k):
+        self.indptr, self.indices, self.data, self.shape = indptr, indices, data, (int(shape[0]), int(shape[1]))
+        self.sinkhorn, self.k = sinkhorn_result, int(k)
+        self.row_mass, self.col_mass, self.row_kept, self.col_kept = row_mass, col_mass, row_kept, col_kept
+
+    @property
+    def nnz(self) -> int:
+        return int(self.indices.shape[0])
+
+    def to_scipy(self):
+        """scipy CSR [n0, n1], fp32"""
+        import scipy.sparse as sp
+
+        return sp.csr_matrix((self.data, self.indices, self.indptr), shape=self.shape)
+
+    def sparse_plan(self, device):
+        """the device-resident form the PoE kernels walk (plan.SparsePlan)"""
+        from .plan import SparsePlan
+
+        return SparsePlan.from_scipy(self.to_scipy(), device)
+
+
+def transport_plan(X0: torch.Tensor, X1: torch.Tensor, k: int = 32, **sinkhorn_kwargs) -> TransportPlan:
+    """``sinkhorn``, then two ``ot_topk`` passes -- every cell of group 0 against group 1 and every cell of group 1 against group 0,
+    ``k`` entries each -- and their union as one sparse plan; a pair both passes kept takes the row pass's value."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= OT_KMAX:
+        raise ValueError(f"transport_plan: k must be an integer in [1, {OT_KMAX}], got {k!r}")
+    res = sinkhorn(X0, X1, **sinkhorn_kwargs)
+    rows = ot_topk(X0, X1, res.psi + res.log_b, res.phi + res.log_a, res.inv_eps, int(k))
+    cols = ot_topk(X1, X0, res.phi + res.log_a, res.psi + res.log_b, res.inv_eps, int(k))
+    host = [t.cpu().numpy() for t in (*rows, *cols)]
+    indptr, indices, data = plan_union_csr(host[0], host[1], host[3], host[4], X0.shape[0], X1.shape[0])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        row_kept = (host[2] / np.exp(res.log_a.cpu().numpy())).astype(np.float32)
+        col_kept = (host[5] / np.exp(res.log_b.cpu().numpy())).astype(np.float32)
+    return TransportPlan(indptr, indices, data, (X0.shape[0], X1.shape[0]), res, host[2], host[5], row_kept, col_kept, k)
