@@ -630,6 +630,42 @@ int64_t spv_ot_ws_bytes(int32_t n_q, int32_t k, int32_t n_split);
 int32_t spv_ot_tile_q(void);
 int32_t spv_ot_tile_c(void);
 
+/* Segmented distance sums (spVIPES.latent_silhouette / integration_scores of the user API): for query row i of Q and every segment s
+ * of the candidates C, which come ARRANGED BY SEGMENT, the fp64 sum of the Euclidean distances to the segment's rows; nothing of size
+ * n_q x n_c stored.
+ *   S[s][i] = sum over j in [seg_ptr[s], seg_ptr[s + 1]) of (double) d(i, j),   d(i, j) = fl32(sqrt(d2(i, j)))
+ * d2 is the distance of spv_knn above, the same bits; the root is the correctly rounded fp32 one.  A query that is also a candidate
+ * adds d = +0 for itself.  An empty segment gives +0.  A non-finite candidate row makes its segment's sums NaN / inf, a non-finite
+ * query row all of its own sums, nothing else.
+ * seg_ptr: int32 [n_seg + 1] ON THE DEVICE, ascending, seg_ptr[0] = 0, seg_ptr[n_seg] = n_c; empty segments are allowed.  It cannot
+ * be checked from the host: any other content gives unspecified sums, never an access outside seg_ptr, S or ws.
+ * Layout of S: SEGMENT-MAJOR, fp64 [n_seg][ld_s] with ld_s >= n_q -- S[s * ld_s + i] -- so that the lanes of a workgroup, one query
+ * each, write consecutive doubles when a segment ends.  Columns >= n_q are never written.
+ * Order of addition: ascending j within a chunk of the candidates, ascending chunk across chunks, from +0; no floating-point atomics.
+ * For fixed shapes and n_split two calls agree bit for bit, and a query's sums do not depend on the other queries of the call.  Under
+ * DIFFERENT n_split the sums may differ in the last bits of fp64, except where every partial sum is exact.
+ * Launches: as spv_knn -- a partial pass of (tiles of spv_knn_tile_q() queries) x (n_split chunks of the candidates) workgroups, and
+ * for n_split > 1 a merge pass over the workspace; n_split == 1 is ONE launch that writes S itself.  n_split = 0 stands for
+ * spv_silhouette_splits(n_q, n_c), a pure function of the shapes.
+ * ws: spv_silhouette_ws_bytes(n_q, n_seg, n_split) bytes with the RESOLVED n_split (0 for n_split <= 1 or a non-positive shape;
+ * 64-bit arithmetic), 8-byte aligned, overwritten by every call.  Nothing is allocated.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null arguments / Q / C / seg_ptr / S; ws null when its size is not 0, or not
+ * 8-byte aligned; D outside [1, SPV_KNN_DMAX]; n_seg outside [1, SPV_SILHOUETTE_SEG_MAX]; n_split outside [0, SPV_KNN_SPLIT_MAX];
+ * n_q < 1; n_c < 0; ld_q < D; ld_c < D; ld_s < n_q.  n_c == 0 is valid: every sum is +0. */
+#define SPV_SILHOUETTE_SEG_MAX 256
+typedef struct spv_silhouette_args {
+  const float* Q; int64_t ld_q; int32_t n_q;      /* queries    fp32 [n_q][ld_q], ld_q >= D */
+  const float* C; int64_t ld_c; int32_t n_c;      /* candidates fp32 [n_c][ld_c], ld_c >= D, arranged by segment */
+  int32_t D;                                      /* 1 .. SPV_KNN_DMAX */
+  const int32_t* seg_ptr; int32_t n_seg;          /* [n_seg + 1] on the device; 1 .. SPV_SILHOUETTE_SEG_MAX segments */
+  int32_t n_split;                                /* 0 = spv_silhouette_splits(n_q, n_c); else 1 .. SPV_KNN_SPLIT_MAX chunks of the candidates */
+  double* S; int64_t ld_s;                        /* [n_seg][ld_s], ld_s >= n_q */
+  void* ws;                                       /* spv_silhouette_ws_bytes(n_q, n_seg, n_split) bytes */
+} spv_silhouette_args;
+int spv_silhouette_sums(const spv_silhouette_args* a, void* stream);
+int32_t spv_silhouette_splits(int32_t n_q, int32_t n_c);
+int64_t spv_silhouette_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

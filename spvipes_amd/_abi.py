@@ -293,6 +293,16 @@ class SpvOtArgs(C.Structure):
                 ("L", C.c_void_p), ("idx", C.c_void_p), ("val", C.c_void_p), ("ld_out", C.c_int64), ("mass", C.c_void_p), ("ws", C.c_void_p)]
 
 
+SIL_SEG_MAX = 256   # SPV_SILHOUETTE_SEG_MAX
+
+
+class SpvSilhouetteArgs(C.Structure):
+    """the arguments of spv_silhouette_sums (include/spvipes_hip.h: spv_silhouette_args)"""
+    _fields_ = [("Q", C.c_void_p), ("ld_q", C.c_int64), ("n_q", C.c_int32), ("C", C.c_void_p), ("ld_c", C.c_int64), ("n_c", C.c_int32),
+                ("D", C.c_int32), ("seg_ptr", C.c_void_p), ("n_seg", C.c_int32), ("n_split", C.c_int32), ("S", C.c_void_p), ("ld_s", C.c_int64),
+                ("ws", C.c_void_p)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -381,6 +391,9 @@ _SIGNATURES = {
     "spv_ot_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "spv_ot_tile_q": (C.c_int32, []),
     "spv_ot_tile_c": (C.c_int32, []),
+    "spv_silhouette_sums": (C.c_int, [C.POINTER(SpvSilhouetteArgs), C.c_void_p]),
+    "spv_silhouette_splits": (C.c_int32, [C.c_int32, C.c_int32]),
+    "spv_silhouette_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

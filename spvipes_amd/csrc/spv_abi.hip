@@ -14,6 +14,7 @@
 #include "spv_count_stats.h"
 #include "spv_knn.h"
 #include "spv_ot.h"
+#include "spv_silhouette.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -1178,6 +1179,43 @@ extern "C" int spv_ot_topk(const spv_ot_args* x, void* stream) {
   if (rc != SPV_OK || a.n_split == 1) return rc;
   hipLaunchKernelGGL(ot_topk_merge_kernel, dim3(tiles), block, ot_topk_lds_bytes(0, a.k) - ot_tile_words(0) * 4, s, a);   // at most the 64 KiB a kernel gets unasked
   return launch_status("spv_ot_topk (merge pass)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// segmented distance sums for the silhouette widths (spv_silhouette.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_silhouette_splits(int32_t n_q, int32_t n_c) { return sil_splits(n_q, n_c); }
+extern "C" int64_t spv_silhouette_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split) { return sil_ws_bytes(n_q, n_seg, n_split); }
+
+extern "C" int spv_silhouette_sums(const spv_silhouette_args* x, void* stream) {
+  if (!x) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null arguments%s");
+  if (!x->Q) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null Q%s");
+  if (!x->C) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null C%s");
+  if (!x->seg_ptr) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null seg_ptr%s");
+  if (!x->S) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null S%s");
+  if (x->D < 1 || x->D > KNN_DMAX) return fail(SPV_ERR_ARG, "spv_silhouette_sums: D must lie in [1, 64]%s");
+  if (x->n_seg < 1 || x->n_seg > SIL_SEG_MAX) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_seg must lie in [1, 256]%s");
+  if (x->n_split < 0 || x->n_split > KNN_SPLIT_MAX) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_split must be 0 or lie in [1, 64]%s");
+  if (x->n_q < 1) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_q < 1%s");
+  if (x->n_c < 0) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_c < 0%s");
+  if (x->ld_q < x->D) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ld_q < D%s");
+  if (x->ld_c < x->D) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ld_c < D%s");
+  if (x->ld_s < x->n_q) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ld_s < n_q%s");
+  const int n_split = x->n_split ? x->n_split : sil_splits(x->n_q, x->n_c);
+  if (n_split > 1 && !x->ws) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null ws%s");
+  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ws must be 8-byte aligned%s");
+  const SilArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->seg_ptr, x->n_seg, n_split, knn_chunk(x->n_c, n_split),
+                  x->S, (long)x->ld_s, (double*)x->ws};
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((x->n_q + KNN_TQ - 1) / KNN_TQ);
+  const dim3 grid(tiles, (unsigned)n_split), block(KNN_TQ);
+  if (a.D <= 16) hipLaunchKernelGGL((sil_partial_kernel<16>), grid, block, sil_lds_bytes(16), s, a);
+  else if (a.D <= 32) hipLaunchKernelGGL((sil_partial_kernel<32>), grid, block, sil_lds_bytes(32), s, a);
+  else hipLaunchKernelGGL((sil_partial_kernel<64>), grid, block, sil_lds_bytes(64), s, a);
+  int rc = launch_status(n_split == 1 ? "spv_silhouette_sums" : "spv_silhouette_sums (partial pass)");
+  if (rc != SPV_OK || n_split == 1) return rc;
+  hipLaunchKernelGGL(sil_merge_kernel, dim3(tiles, (unsigned)a.n_seg), block, 0, s, a);
+  return launch_status("spv_silhouette_sums (merge pass)");
 }
 
 extern "C" int spv_count_totals(const spv_counts* x, int32_t n_cells, int32_t G, double* total, void* stream) {

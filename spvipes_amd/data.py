@@ -1025,3 +1025,146 @@ def check_transport_args(rep, obs_idx, k):
             raise ValueError(f"group {g}: use_rep holds non-finite values")
         parts.append(part)
     return parts[0], parts[1], int(k)
+
+
+# ---- silhouette widths in latent space (model.latent_silhouette / integration_scores): host-side arrangement, the per-cell values from
+# the kernel's exact sums, and the scores -- pure numpy ------
+SILHOUETTE_MAX_LABELS = _abi.SIL_SEG_MAX // 2   # two segments (group 0, group 1) per label
+
+
+def check_silhouette_args(cells, latent: str):
+    """The refusals of ``latent_silhouette``, ahead of any device work -> the groups of ``cells``: 0, 1 or "both" (group 0's cells, then
+    group 1's); ``latent`` "shared" or "private", the latter only with ONE group (the two groups' private spaces are not comparable)."""
+    if latent not in ("shared", "private"):
+        raise ValueError(f"latent must be 'shared' or 'private', got {latent!r}")
+    if isinstance(cells, bool) or not (cells == "both" if isinstance(cells, str) else isinstance(cells, (int, np.integer)) and cells in (0, 1)):
+        raise ValueError(f"cells must be 0, 1 or 'both', got {cells!r}")
+    groups = (0, 1) if isinstance(cells, str) else (int(cells),)
+    if latent == "private" and len(groups) != 1:
+        raise ValueError("latent='private' needs cells 0 or 1: the private spaces of the two groups are not comparable")
+    return groups
+
+
+def silhouette_segments(label_codes, group_of_cell, n_labels: int):
+    """The arrangement of the cells by (label, group) the kernel's candidates need -> (perm int64 [n]: the cells in segment order, each
+    segment's cells in their given order; seg_ptr int32 [2 * n_labels + 1]; sizes int64 [2 * n_labels]).  Segment 2 * t + g holds the
+    cells of label code t in group g: group 0 then group 1 within each label; a segment without a cell is empty, not left out."""
+    codes, grp = np.asarray(label_codes).ravel().astype(np.int64), np.asarray(group_of_cell).ravel().astype(np.int64)
+    n_labels = int(n_labels)
+    if codes.shape != grp.shape:
+        raise ValueError(f"one label code and one group per cell, got {codes.shape[0]} and {grp.shape[0]}")
+    if not 1 <= n_labels <= SILHOUETTE_MAX_LABELS:
+        raise ValueError(f"the number of labels must lie in [1, {SILHOUETTE_MAX_LABELS}], got {n_labels}")
+    if codes.size and (codes.min() < 0 or codes.max() >= n_labels):
+        raise ValueError(f"label codes must lie in [0, n_labels = {n_labels})")
+    if grp.size and (grp.min() < 0 or grp.max() > 1):
+        raise ValueError("group_of_cell must hold 0 or 1")
+    seg = 2 * codes + grp
+    perm = np.argsort(seg, kind="stable").astype(np.int64)
+    sizes = np.bincount(seg, minlength=2 * n_labels).astype(np.int64)
+    seg_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    return perm, seg_ptr, sizes
+
+
+def _silhouette_width(a, b, single):
+    """(b - a) / max(a, b), 0 where ``single`` (the cell is alone in its cluster) or max(a, b) = 0"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = np.maximum(a, b)
+        s = (b - a) / m
+    s = np.where(m == 0, 0.0, s)
+    return np.where(single, 0.0, s)
+
+
+def silhouette_table(S, sizes, label_codes, group_of_cell) -> dict:
+    """The per-cell silhouette values, in fp64, from the exact distance sums.  ``S`` [n, 2 * n_labels]: cell i's summed distance to
+    the cells of each (label, group) segment, ``sizes`` the segments' cell counts (``silhouette_segments``' order), ``label_codes`` /
+    ``group_of_cell`` [n] the cells' own.  Returns arrays [n]:
+      a, b, silhouette_label   the label silhouette (sklearn's ``silhouette_samples``): with n_t the cells of the cell's label t in both
+                               groups, a = S_t / (n_t - 1) (its own distance is +0), b = min over the labels u != t that have cells of
+                               S_u / n_u, s = (b - a) / max(a, b); s = 0 and a = NaN for the only cell of a label; s = 0 where
+                               max(a, b) = 0; b = s = NaN when no other label has a cell
+      nearest_label            the code u that gives b, the smallest on ties; -1 when there is none
+      silhouette_group         the same width inside the cell's label with its own group g as the cluster and the other group as the
+                               neighbour: a = S_{t,g} / (n_{t,g} - 1), b = S_{t,1-g} / n_{t,1-g}; 0 for the only cell of (t, g); NaN for a
+                               label that has cells in one group only"""
+    S = np.asarray(S, dtype=np.float64)
+    sizes = np.asarray(sizes, dtype=np.int64).ravel()
+    codes, grp = np.asarray(label_codes).ravel().astype(np.int64), np.asarray(group_of_cell).ravel().astype(np.int64)
+    n, L = codes.shape[0], sizes.shape[0] // 2
+    if S.shape != (n, 2 * L) or sizes.shape[0] != 2 * L or grp.shape[0] != n:
+        raise ValueError(f"S must be [cells, 2 * n_labels] = [{n}, {2 * L}], got {S.shape}")
+    rows = np.arange(n)
+    S_lab, n_lab = S[:, 0::2] + S[:, 1::2], sizes[0::2] + sizes[1::2]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a = S_lab[rows, codes] / (n_lab[codes] - 1).astype(np.float64)
+        mean_to = S_lab / n_lab.astype(np.float64)[None, :]
+    a = np.where(n_lab[codes] == 1, np.nan, a)
+    mean_to = np.where((n_lab > 0)[None, :], mean_to, np.inf)
+    mean_to[rows, codes] = np.inf
+    nearest = mean_to.argmin(axis=1) if L else np.zeros(n, dtype=np.int64)
+    b = mean_to[rows, nearest] if n else np.zeros(0)
+    none = ~(b < np.inf) & ~np.isnan(b)
+    b = np.where(none, np.nan, b)
+    nearest = np.where(none, -1, nearest).astype(np.int64)
+    s = _silhouette_width(a, b, n_lab[codes] == 1)
+    s = np.where(none, np.nan, s)
+
+    n_own, n_oth = sizes[2 * codes + grp], sizes[2 * codes + 1 - grp]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a_g = S[rows, 2 * codes + grp] / (n_own - 1).astype(np.float64)
+        b_g = S[rows, 2 * codes + 1 - grp] / n_oth.astype(np.float64)
+    s_g = _silhouette_width(a_g, b_g, n_own == 1)
+    s_g = np.where(n_oth > 0, s_g, np.nan)
+    return {"a": a, "b": b, "silhouette_label": s, "nearest_label": nearest, "silhouette_group": s_g}
+
+
+def silhouette_scores(table: dict, sizes, label_codes) -> dict:
+    """scIB's two scores and their per-label parts from ``silhouette_table``'s columns ->
+    {"label_asw": (mean_i s_i + 1) / 2 over all cells; "group_asw": the mean, over the labels with cells in both groups, of
+    mean_i (1 - |s_g,i|) over the label's cells (NaN without such a label); "label_mean" / "group_mean" [n_labels]: each label's mean
+    label silhouette and its 1 - |s_g| mean (NaN for a label without cells / not in both groups)}"""
+    sizes = np.asarray(sizes, dtype=np.int64).ravel()
+    codes = np.asarray(label_codes).ravel().astype(np.int64)
+    L = sizes.shape[0] // 2
+    s, s_g = np.asarray(table["silhouette_label"], dtype=np.float64), np.asarray(table["silhouette_group"], dtype=np.float64)
+    label_mean, group_mean = np.full(L, np.nan), np.full(L, np.nan)
+    for t in range(L):
+        own = codes == t
+        if own.any():
+            label_mean[t] = s[own].mean()
+            if sizes[2 * t] > 0 and sizes[2 * t + 1] > 0:
+                group_mean[t] = (1.0 - np.abs(s_g[own])).mean()
+    both = ~np.isnan(group_mean)
+    return {"label_asw": float((s.mean() + 1.0) / 2.0) if s.size else float("nan"),
+            "group_asw": float(group_mean[both].mean()) if both.any() else float("nan"), "label_mean": label_mean, "group_mean": group_mean}
+
+
+def silhouette_frame(names, group_of_cell, categories, label_codes, sizes, table: dict):
+    """The frame ``latent_silhouette`` returns: one row per cell, indexed by ``names``, with ``group``, ``label``, ``silhouette_label``,
+    ``a``, ``b``, ``nearest_label`` (None when there is no other label), ``silhouette_group``; ``attrs`` holds ``label_asw``,
+    ``group_asw`` and ``per_label``: indexed by the labels, ``n_group0`` / ``n_group1`` (cells), ``silhouette_label`` (its cells' mean) and
+    ``group_mixing`` (their 1 - |silhouette_group| mean)."""
+    import pandas as pd
+
+    cats = np.asarray(categories, dtype=object)
+    codes = np.asarray(label_codes).ravel().astype(np.int64)
+    sizes = np.asarray(sizes, dtype=np.int64).ravel()
+    near = np.empty(len(codes), dtype=object)
+    ok = np.asarray(table["nearest_label"]) >= 0
+    near[ok] = cats[np.asarray(table["nearest_label"])[ok]]
+    near[~ok] = None
+    frame = pd.DataFrame({"group": np.asarray(group_of_cell).astype(np.int64), "label": cats[codes], "silhouette_label": table["silhouette_label"],
+                          "a": table["a"], "b": table["b"], "nearest_label": near, "silhouette_group": table["silhouette_group"]},
+                         index=pd.Index(np.asarray(names)))
+    sc = silhouette_scores(table, sizes, codes)
+    frame.attrs["label_asw"], frame.attrs["group_asw"] = sc["label_asw"], sc["group_asw"]
+    frame.attrs["per_label"] = pd.DataFrame({"n_group0": sizes[0::2], "n_group1": sizes[1::2], "silhouette_label": sc["label_mean"],
+                                             "group_mixing": sc["group_mean"]}, index=pd.Index(cats))
+    return frame
+
+
+def silhouette_query_blocks(n: int, row_bytes: int, cap_bytes: int):
+    """[(first, end)] blocks of the n query cells such that a block x ``row_bytes`` (what one query costs in table and workspace) stays
+    within ``cap_bytes``; at least one cell per block"""
+    rows = max(1, int(cap_bytes) // max(1, int(row_bytes)))
+    return [(b, min(b + rows, int(n))) for b in range(0, int(n), rows)]

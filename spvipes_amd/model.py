@@ -22,7 +22,8 @@ import torch
 from . import _abi
 from .data import (MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, check_transport_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
                    csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
-                   latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions)
+                   latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions,
+                   SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table)
 from .module import spVIPESmodule
 from .plan import SparsePlan
 from .train import Trainer, default_max_epochs
@@ -752,6 +753,72 @@ class spVIPES:
         predicted, confidence, n_valid = vote_labels(nb["indices"], codes, len(cats))
         names = getattr(self.adata, "obs_names", None)
         return transfer_frame(nb["query_obs"] if names is None else np.asarray(names)[nb["query_obs"]], cats, predicted, confidence, n_valid)
+
+    _SILHOUETTE_TABLE_BYTES = 256 << 20   # cap on the fp64 [cells of a query block, segments] table of one kernel call plus its workspace: a memory condition, not a measurement
+
+    @torch.no_grad()
+    def latent_silhouette(self, group_indices_list: List[List[int]], labels="cell_type", cells="both", latent: str = "shared", give_mean: bool = True,
+                          batch_size: Optional[int] = None, _noise=None):
+        """The exact silhouette width of every cell of ``cells`` in latent space, by label and by group within its label (scIB's
+        ``silhouette`` and ``silhouette_batch``), from the fused kernel spv_silhouette_sums: no cells x cells matrix exists at any time and
+        nothing is subsampled.  Returns a DataFrame with one row per cell, in ``group_indices_list`` order (group
+        0's cells, then group 1's), indexed by ``obs_names`` (the adata row numbers without any):
+            group, label          the cell's group and label
+            a, b                  its mean Euclidean distance to the other cells of its label, and to the cells of the nearest other label
+            silhouette_label      (b - a) / max(a, b): ``sklearn.metrics.silhouette_samples``, 0 for the only cell of a label (a is NaN
+                                  there) and where max(a, b) = 0; NaN, like b, when the selection has one label only
+            nearest_label         the label that gives b, the one that sorts first on ties
+            silhouette_group      the same width inside the cell's label, its own group against the other group; 0 for the only cell of
+                                  its (label, group); NaN for a label with cells in one group only, so for every cell when ``cells``
+                                  is 0 or 1
+        ``attrs``: ``label_asw`` = (mean silhouette_label + 1) / 2; ``group_asw`` = the mean, over the labels present in both groups, of
+        the label's mean 1 - |silhouette_group| (NaN without such a label); ``per_label``: a frame per label with its cells in each group
+        (``n_group0`` / ``n_group1``), its mean ``silhouette_label`` and its ``group_mixing`` (the 1 - |silhouette_group| mean).
+        ``labels``: an ``obs`` column, or an array with one entry per cell of the selection; at most 128 distinct labels.
+        ``cells``: 0, 1 or "both".  ``latent``: "shared" or "private", "private" only with ``cells`` 0 or 1.  ``give_mean``: the
+        posterior means (deterministic: two calls agree bit for bit), else one sampled embedding, the rows of
+        ``get_latent_representation(normalized=False)``.  Non-finite latents are a ValueError.  ``_noise`` (tests only): as
+        ``get_latent_representation`` takes it.
+        The distances are the ones ``latent_neighbors`` reports, bit for bit; each is widened to fp64 and summed per (label, group) in a
+        fixed order, and every value of the frame is computed from those sums in fp64 on the host: only the [cells, 2 x labels] table of
+        sums leaves the device.  Very many cells go through the kernel in blocks of query cells whose table, with the kernel's workspace,
+        stays within 256 MiB; a cell's sums do not depend on the other cells of its block, so the blocking does not change a bit."""
+        groups = check_silhouette_args(cells, latent)
+        from .silhouette_ops import segment_distance_sums, silhouette_splits
+        obs_rows = np.concatenate([np.asarray(group_indices_list[g], dtype=np.int64).ravel() for g in groups])
+        group_of_cell = np.concatenate([np.full(len(group_indices_list[g]), g, dtype=np.int64) for g in groups])
+        n = len(obs_rows)
+        if n < 1:
+            raise ValueError("latent_silhouette: the selection has no cells")
+        if not isinstance(labels, str) and np.asarray(labels).ravel().shape[0] != n:
+            raise ValueError(f"labels: an array must hold one label per cell of the selection ({n}), got {np.asarray(labels).ravel().shape[0]}")
+        cats, codes = np.unique(group_cell_labels(self.adata.obs, labels, obs_rows, groups[0]), return_inverse=True)
+        if len(cats) > SILHOUETTE_MAX_LABELS:
+            raise ValueError(f"latent_silhouette takes at most {SILHOUETTE_MAX_LABELS} distinct labels, got {len(cats)}")
+        perm, seg_ptr, sizes = silhouette_segments(codes, group_of_cell, len(cats))
+        z = self._latents_on_device(group_indices_list, latent, give_mean, batch_size, _noise)
+        X = z[groups[0]] if len(groups) == 1 else torch.cat([z[g] for g in groups])
+        if not bool(torch.isfinite(X).all()):
+            raise ValueError("latent_silhouette: the latents hold non-finite values")
+        cand = X.index_select(0, torch.as_tensor(perm, device=self.device))
+        ptr_dev = torch.as_tensor(seg_ptr, device=self.device)
+        n_seg = len(sizes)
+        n_split = silhouette_splits(n, n)   # ONE chunk count, from the whole selection, for every query block: the sums must not depend on the blocking
+        row_bytes = 8 * n_seg * (1 + (n_split if n_split > 1 else 0))   # a query's row of the table and of every chunk's slab of the workspace
+        S = np.empty((n, n_seg), dtype=np.float64)
+        for b0, b1 in silhouette_query_blocks(n, row_bytes, self._SILHOUETTE_TABLE_BYTES):
+            S[b0:b1] = segment_distance_sums(X[b0:b1], cand, ptr_dev, n_split=n_split).cpu().numpy()
+        names = getattr(self.adata, "obs_names", None)
+        return silhouette_frame(obs_rows if names is None else np.asarray(names)[obs_rows], group_of_cell, cats, codes, sizes,
+                                silhouette_table(S, sizes, codes, group_of_cell))
+
+    def integration_scores(self, group_indices_list: List[List[int]], labels="cell_type", **kwargs) -> dict:
+        """How well the two groups are integrated in latent space, scIB's two silhouette scores from ONE ``latent_silhouette`` call
+        (``kwargs`` go to it) -> {"label_asw": do the labels stay apart, in [0, 1], larger is better; "group_asw": do the groups mix
+        within each label, in [0, 1], larger is better, NaN when no label has cells in both groups; "per_label": the frame of the parts}."""
+        check_silhouette_args(kwargs.get("cells", "both"), kwargs.get("latent", "shared"))
+        attrs = self.latent_silhouette(group_indices_list, labels=labels, **kwargs).attrs
+        return {"label_asw": attrs["label_asw"], "group_asw": attrs["group_asw"], "per_label": attrs["per_label"]}
 
     def get_loadings(self) -> dict:
         """:652-677: per-gene weights of the linear decoder, {(group, "private" | "shared"): DataFrame [genes, latent dims]}
