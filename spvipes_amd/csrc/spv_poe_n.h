@@ -2,7 +2,10 @@
 // _product_of_experts (module/spVIPESmodule.py:573-581) that SURVEY.md 8(d) prescribes for BASELINE config 4 (3 groups,
 // cluster-matched PoE).  THROUGHPUT ONLY: the reference cannot run more than two groups (data/prepare_adatas.py:94-95,
 // spVIPESmodule.py:283-286, 723-726), so there is nothing to be bit-compatible with; tests/test_gpu_three_groups.py checks the
-// kernels against a plain torch restatement of the definition below.
+// kernels against a plain torch restatement of the definition below, and tests/test_gpu_poe_n.py holds every output and both input
+// gradients to its float64 autograd form within bounds derived from these kernels' rounding chain (tests/_poe_n_reference.py, which
+// tests/test_poe_n_reference_cpu.py checks without a GPU).  Input domain of those tests: exp(-logvar) finite in fp32 (they go to
+// logvar ~ -30); beyond fp32 overflow of exp(-logvar) nothing is claimed, as for the two-group kernels.
 //
 // Definition.  Cell i of group g with component c = comp_g[i]; for every OTHER group h that has cells of component c in
 // its minibatch the expert is the component mean of h's shared-encoder statistics,
@@ -10,9 +13,12 @@
 // and with the always-on N(0, 1) prior expert (spVIPESmodule.py:346, 576)
 //     prec = 1 + exp(-logvar_g[i]) + sum_h exp(-mlogvar_h[c]),     num = loc_g[i] exp(-logvar_g[i]) + sum_h mloc_h[c] exp(-mlogvar_h[c])
 //     loc* = num / prec,  logvar* = -log prec,  scale* = exp(logvar* / 2);  the draw and the KL use scale*.clamp(min = 1e-6)
-// (for two groups and a uniform transport plan inside a component this is what _cluster_based_poe's plan-weighted experts
-// reduce to, :211-229).  All reductions run in a fixed order (per-segment partial sums in LDS, segments summed in index
-// order): no atomics, bit-reproducible.
+// Tie to upstream: with a transport plan that is uniform inside a component, _cluster_based_poe's plan-weighted experts (:211-229)
+// are component means too, but it fuses prior + mean_g[c] + mean_h[c] -- a cell's OWN posterior is not among its experts, and both means
+// are taken over the other minibatch's component mask.  The definition above equals it only when the two minibatches carry the same
+// codes at the same positions and each group's statistics are constant inside a component (then a cell's posterior is mean_g[c]);
+// tests/test_poe_n_reference_cpu.py holds exactly that.  All reductions run in a fixed order (per-segment partial sums in LDS,
+// segments summed in index order): no atomics, bit-reproducible.
 #pragma once
 #include "spv_common.h"
 #include "../../include/spvipes_hip.h"
