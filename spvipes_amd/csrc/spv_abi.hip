@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 using namespace spv;
 
@@ -1066,44 +1067,68 @@ extern "C" int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
   return (int64_t)n_split * n_q * k * 8;
 }
 
-// the one-time opt-in to the largest dynamic LDS a call can ask for (k = SPV_KNN_KMAX: beyond the 64 KiB a kernel gets unasked)
-template <int DP>
-static void knn_partial_launch(const KnnArgs& a, dim3 grid, hipStream_t s) {
-  static bool raised = false;
-  if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_partial_kernel<DP>), hipFuncAttributeMaxDynamicSharedMemorySize, knn_lds_bytes(DP, KNN_KMAX)); raised = true; }
-  hipLaunchKernelGGL((knn_partial_kernel<DP>), grid, dim3(KNN_TQ), knn_lds_bytes(DP, a.k), s, a);
+// ---- what the entry points of the pair scan share (spv_pair_scan.h): spv_knn here, spv_ot_softmin / spv_ot_topk and spv_silhouette_sums below
+struct ScanPlan { int n_split, per; dim3 grid; };   // chunks (resolved), candidates per chunk, (query tiles, chunks)
+
+// What every one of them refuses about the two sides, D, n_split and ws, in `who`'s name; the chunks -- n_split, or splits(n_q, n_c) for
+// 0 -- and the grid.  X: any of the argument structs (they share these fields).  own(n_split) checks the caller's other fields, ahead of ws.
+template <typename X, typename Own>
+static int scan_check(const X* x, const char* who, int (*splits)(int, int), ScanPlan& p, Own own) {
+  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
+  if (!x->Q) return fail(SPV_ERR_ARG, "%s: null Q", who);
+  if (!x->C) return fail(SPV_ERR_ARG, "%s: null C", who);
+  if (x->D < 1 || x->D > KNN_DMAX) return fail(SPV_ERR_ARG, "%s: D must lie in [1, 64]", who);
+  if (x->n_split < 0 || x->n_split > KNN_SPLIT_MAX) return fail(SPV_ERR_ARG, "%s: n_split must be 0 or lie in [1, 64]", who);
+  if (x->n_q < 1) return fail(SPV_ERR_ARG, "%s: n_q < 1", who);
+  if (x->n_c < 0) return fail(SPV_ERR_ARG, "%s: n_c < 0", who);
+  if (x->ld_q < x->D) return fail(SPV_ERR_ARG, "%s: ld_q < D", who);
+  if (x->ld_c < x->D) return fail(SPV_ERR_ARG, "%s: ld_c < D", who);
+  p.n_split = x->n_split ? x->n_split : splits(x->n_q, x->n_c);
+  const int rc = own(p.n_split);
+  if (rc != SPV_OK) return rc;
+  if (p.n_split > 1 && !x->ws) return fail(SPV_ERR_ARG, "%s: null ws", who);
+  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "%s: ws must be 8-byte aligned", who);
+  p.per = knn_chunk(x->n_c, p.n_split);
+  p.grid = dim3((unsigned)((x->n_q + KNN_TQ - 1) / KNN_TQ), (unsigned)p.n_split);
+  return SPV_OK;
+}
+
+// the scan kernels' form for D columns: launch(DP) with DP = 16 / 32 / 64 as a compile-time constant
+template <typename Launch>
+static void scan_dispatch(int D, Launch launch) {
+  if (D <= 16) launch(std::integral_constant<int, 16>());
+  else if (D <= 32) launch(std::integral_constant<int, 32>());
+  else launch(std::integral_constant<int, 64>());
+}
+
+// (idx, values) rows of k entries, ld_out apart and indexed in 32 bits (spv_knn, spv_ot_topk)
+template <typename X>
+static int scan_check_rows(const X* x, const char* who) {
+  if (x->k < 1 || x->k > KNN_KMAX) return fail(SPV_ERR_ARG, "%s: k must lie in [1, 64]", who);
+  if (x->ld_out < x->k) return fail(SPV_ERR_ARG, "%s: ld_out < k", who);
+  if ((int64_t)x->n_q * x->ld_out > INT32_MAX || x->ld_out > INT32_MAX) return fail(SPV_ERR_ARG, "%s: n_q * ld_out exceeds 2^31 - 1", who);
+  return SPV_OK;
 }
 
 extern "C" int spv_knn(const spv_knn_args* x, void* stream) {
-  if (!x) return fail(SPV_ERR_ARG, "spv_knn: null arguments%s");
-  if (!x->Q) return fail(SPV_ERR_ARG, "spv_knn: null Q%s");
-  if (!x->C) return fail(SPV_ERR_ARG, "spv_knn: null C%s");
-  if (!x->idx) return fail(SPV_ERR_ARG, "spv_knn: null idx%s");
-  if (!x->dist) return fail(SPV_ERR_ARG, "spv_knn: null dist%s");
-  if (x->D < 1 || x->D > KNN_DMAX) return fail(SPV_ERR_ARG, "spv_knn: D must lie in [1, 64]%s");
-  if (x->k < 1 || x->k > KNN_KMAX) return fail(SPV_ERR_ARG, "spv_knn: k must lie in [1, 64]%s");
-  if (x->n_split < 0 || x->n_split > KNN_SPLIT_MAX) return fail(SPV_ERR_ARG, "spv_knn: n_split must be 0 or lie in [1, 64]%s");
-  if (x->n_q < 1) return fail(SPV_ERR_ARG, "spv_knn: n_q < 1%s");
-  if (x->n_c < 0) return fail(SPV_ERR_ARG, "spv_knn: n_c < 0%s");
-  if (x->ld_q < x->D) return fail(SPV_ERR_ARG, "spv_knn: ld_q < D%s");
-  if (x->ld_c < x->D) return fail(SPV_ERR_ARG, "spv_knn: ld_c < D%s");
-  if (x->ld_out < x->k) return fail(SPV_ERR_ARG, "spv_knn: ld_out < k%s");
-  if ((int64_t)x->n_q * x->ld_out > INT32_MAX || x->ld_out > INT32_MAX) return fail(SPV_ERR_ARG, "spv_knn: n_q * ld_out exceeds 2^31 - 1%s");
-  const int n_split = x->n_split ? x->n_split : knn_splits(x->n_q, x->n_c);
-  if ((int64_t)n_split * x->n_q * x->k > INT32_MAX) return fail(SPV_ERR_ARG, "spv_knn: the workspace (n_split * n_q * k entries) exceeds 2^31 - 1%s");
-  if (n_split > 1 && !x->ws) return fail(SPV_ERR_ARG, "spv_knn: null ws%s");
-  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "spv_knn: ws must be 8-byte aligned%s");
-  const KnnArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->k, x->exclude, n_split, knn_chunk(x->n_c, n_split),
+  ScanPlan p;
+  int rc = scan_check(x, "spv_knn", knn_splits, p, [&](int n_split) {
+    if (!x->idx) return fail(SPV_ERR_ARG, "spv_knn: null idx%s");
+    if (!x->dist) return fail(SPV_ERR_ARG, "spv_knn: null dist%s");
+    const int rc = scan_check_rows(x, "spv_knn");
+    if (rc != SPV_OK) return rc;
+    if ((int64_t)n_split * x->n_q * x->k > INT32_MAX) return fail(SPV_ERR_ARG, "spv_knn: the workspace (n_split * n_q * k entries) exceeds 2^31 - 1%s");
+    return SPV_OK;
+  });
+  if (rc != SPV_OK) return rc;
+  const KnnArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->k, x->exclude, p.n_split, p.per,
                   x->idx, x->dist, (int)x->ld_out, (knn_key_t*)x->ws};
   hipStream_t s = (hipStream_t)stream;
-  const unsigned tiles = (unsigned)((x->n_q + KNN_TQ - 1) / KNN_TQ);
-  const dim3 grid(tiles, (unsigned)n_split);
-  if (x->D <= 16) knn_partial_launch<16>(a, grid, s);
-  else if (x->D <= 32) knn_partial_launch<32>(a, grid, s);
-  else knn_partial_launch<64>(a, grid, s);
-  int rc = launch_status(n_split == 1 ? "spv_knn" : "spv_knn (partial pass)");
-  if (rc != SPV_OK || n_split == 1) return rc;
-  hipLaunchKernelGGL(knn_merge_kernel, dim3(tiles), dim3(KNN_TQ), knn_lds_bytes(0, x->k), s, a);   // at most the 64 KiB a kernel gets unasked
+  // the opt-in is to the largest LDS a call can ask for (k = SPV_KNN_KMAX: beyond the 64 KiB a kernel gets unasked), the launch takes what k needs
+  scan_dispatch(a.D, [&](auto dp) { constexpr int DP = decltype(dp)::value; launch_lds_upto<knn_partial_kernel<DP>>(p.grid, dim3(KNN_TQ), knn_lds_bytes(DP, KNN_KMAX), knn_lds_bytes(DP, a.k), s, a); });
+  rc = launch_status(p.n_split == 1 ? "spv_knn" : "spv_knn (partial pass)");
+  if (rc != SPV_OK || p.n_split == 1) return rc;
+  hipLaunchKernelGGL(knn_merge_kernel, dim3(p.grid.x), dim3(KNN_TQ), knn_lds_bytes(0, x->k), s, a);   // at most the 64 KiB a kernel gets unasked
   return launch_status("spv_knn (merge pass)");
 }
 
@@ -1119,65 +1144,50 @@ extern "C" int64_t spv_ot_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
 }
 
 // what both entry points refuse, then the kernels' arguments with the resolved chunks; `topk`: the checks of k and the lists
-static int ot_check(const spv_ot_args* x, const char* who, bool topk, OtArgs& a) {
-  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
-  if (!x->Q) return fail(SPV_ERR_ARG, "%s: null Q", who);
-  if (!x->C) return fail(SPV_ERR_ARG, "%s: null C", who);
-  if (!x->h) return fail(SPV_ERR_ARG, "%s: null h", who);
-  if (!topk && !x->L) return fail(SPV_ERR_ARG, "%s: null L", who);
-  if (topk && !x->r) return fail(SPV_ERR_ARG, "%s: null r", who);
-  if (topk && !x->idx) return fail(SPV_ERR_ARG, "%s: null idx", who);
-  if (topk && !x->val) return fail(SPV_ERR_ARG, "%s: null val", who);
-  if (topk && !x->mass) return fail(SPV_ERR_ARG, "%s: null mass", who);
-  if (x->D < 1 || x->D > KNN_DMAX) return fail(SPV_ERR_ARG, "%s: D must lie in [1, 64]", who);
-  if (topk && (x->k < 1 || x->k > KNN_KMAX)) return fail(SPV_ERR_ARG, "%s: k must lie in [1, 64]", who);
-  if (x->n_split < 0 || x->n_split > KNN_SPLIT_MAX) return fail(SPV_ERR_ARG, "%s: n_split must be 0 or lie in [1, 64]", who);
-  if (x->n_q < 1) return fail(SPV_ERR_ARG, "%s: n_q < 1", who);
-  if (x->n_c < 0) return fail(SPV_ERR_ARG, "%s: n_c < 0", who);
-  if (x->ld_q < x->D) return fail(SPV_ERR_ARG, "%s: ld_q < D", who);
-  if (x->ld_c < x->D) return fail(SPV_ERR_ARG, "%s: ld_c < D", who);
-  if (!(x->inv_eps > 0.f && x->inv_eps < INFINITY)) return fail(SPV_ERR_ARG, "%s: inv_eps must be a positive finite number", who);
-  if (topk && x->ld_out < x->k) return fail(SPV_ERR_ARG, "%s: ld_out < k", who);
-  if (topk && ((int64_t)x->n_q * x->ld_out > INT32_MAX || x->ld_out > INT32_MAX)) return fail(SPV_ERR_ARG, "%s: n_q * ld_out exceeds 2^31 - 1", who);
-  const int n_split = x->n_split ? x->n_split : knn_splits(x->n_q, x->n_c);
-  if ((int64_t)n_split * x->n_q * (topk ? x->k : 1) > INT32_MAX) return fail(SPV_ERR_ARG, "%s: the workspace (n_split * n_q [* k] entries) exceeds 2^31 - 1", who);
-  if (n_split > 1 && !x->ws) return fail(SPV_ERR_ARG, "%s: null ws", who);
-  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "%s: ws must be 8-byte aligned", who);
-  a = OtArgs{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, topk ? x->k : 0, x->h, x->r, x->inv_eps, n_split,
-             knn_chunk(x->n_c, n_split), x->L, x->idx, x->val, (long)x->ld_out, x->mass, x->ws};
+static int ot_check(const spv_ot_args* x, const char* who, bool topk, OtArgs& a, ScanPlan& p) {
+  const int rc = scan_check(x, who, knn_splits, p, [&](int n_split) {
+    if (!x->h) return fail(SPV_ERR_ARG, "%s: null h", who);
+    if (!topk && !x->L) return fail(SPV_ERR_ARG, "%s: null L", who);
+    if (topk && !x->r) return fail(SPV_ERR_ARG, "%s: null r", who);
+    if (topk && !x->idx) return fail(SPV_ERR_ARG, "%s: null idx", who);
+    if (topk && !x->val) return fail(SPV_ERR_ARG, "%s: null val", who);
+    if (topk && !x->mass) return fail(SPV_ERR_ARG, "%s: null mass", who);
+    if (!(x->inv_eps > 0.f && x->inv_eps < INFINITY)) return fail(SPV_ERR_ARG, "%s: inv_eps must be a positive finite number", who);
+    const int rc = topk ? scan_check_rows(x, who) : SPV_OK;
+    if (rc != SPV_OK) return rc;
+    if ((int64_t)n_split * x->n_q * (topk ? x->k : 1) > INT32_MAX) return fail(SPV_ERR_ARG, "%s: the workspace (n_split * n_q [* k] entries) exceeds 2^31 - 1", who);
+    return SPV_OK;
+  });
+  if (rc != SPV_OK) return rc;
+  a = OtArgs{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, topk ? x->k : 0, x->h, x->r, x->inv_eps, p.n_split,
+             p.per, x->L, x->idx, x->val, (long)x->ld_out, x->mass, x->ws};
   return SPV_OK;
 }
 
 extern "C" int spv_ot_softmin(const spv_ot_args* x, void* stream) {
   OtArgs a;
-  int rc = ot_check(x, "spv_ot_softmin", false, a);
+  ScanPlan p;
+  int rc = ot_check(x, "spv_ot_softmin", false, a, p);
   if (rc != SPV_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned tiles = (unsigned)((a.n_q + KNN_TQ - 1) / KNN_TQ);
-  const dim3 grid(tiles, (unsigned)a.n_split), block(KNN_TQ);
-  if (a.D <= 16) hipLaunchKernelGGL((ot_softmin_kernel<16>), grid, block, ot_softmin_lds_bytes(16), s, a);
-  else if (a.D <= 32) hipLaunchKernelGGL((ot_softmin_kernel<32>), grid, block, ot_softmin_lds_bytes(32), s, a);
-  else hipLaunchKernelGGL((ot_softmin_kernel<64>), grid, block, ot_softmin_lds_bytes(64), s, a);
+  scan_dispatch(a.D, [&](auto dp) { constexpr int DP = decltype(dp)::value; hipLaunchKernelGGL((ot_softmin_kernel<DP>), p.grid, dim3(KNN_TQ), ot_softmin_lds_bytes(DP), s, a); });
   rc = launch_status(a.n_split == 1 ? "spv_ot_softmin" : "spv_ot_softmin (partial pass)");
   if (rc != SPV_OK || a.n_split == 1) return rc;
-  hipLaunchKernelGGL(ot_softmin_merge_kernel, dim3(tiles), block, 0, s, a);
+  hipLaunchKernelGGL(ot_softmin_merge_kernel, dim3(p.grid.x), dim3(KNN_TQ), 0, s, a);
   return launch_status("spv_ot_softmin (merge pass)");
 }
 
 extern "C" int spv_ot_topk(const spv_ot_args* x, void* stream) {
   OtArgs a;
-  int rc = ot_check(x, "spv_ot_topk", true, a);
+  ScanPlan p;
+  int rc = ot_check(x, "spv_ot_topk", true, a, p);
   if (rc != SPV_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned tiles = (unsigned)((a.n_q + KNN_TQ - 1) / KNN_TQ);
-  const dim3 grid(tiles, (unsigned)a.n_split), block(KNN_TQ);
   // the opt-in is to the largest LDS a call can ask for (k = SPV_OT_KMAX: beyond the 64 KiB a kernel gets unasked), the launch takes what k needs
-  if (a.D <= 16) launch_lds_upto<ot_topk_kernel<16>>(grid, block, ot_topk_lds_bytes(16, KNN_KMAX), ot_topk_lds_bytes(16, a.k), s, a);
-  else if (a.D <= 32) launch_lds_upto<ot_topk_kernel<32>>(grid, block, ot_topk_lds_bytes(32, KNN_KMAX), ot_topk_lds_bytes(32, a.k), s, a);
-  else launch_lds_upto<ot_topk_kernel<64>>(grid, block, ot_topk_lds_bytes(64, KNN_KMAX), ot_topk_lds_bytes(64, a.k), s, a);
+  scan_dispatch(a.D, [&](auto dp) { constexpr int DP = decltype(dp)::value; launch_lds_upto<ot_topk_kernel<DP>>(p.grid, dim3(KNN_TQ), ot_topk_lds_bytes(DP, KNN_KMAX), ot_topk_lds_bytes(DP, a.k), s, a); });
   rc = launch_status(a.n_split == 1 ? "spv_ot_topk" : "spv_ot_topk (partial pass)");
   if (rc != SPV_OK || a.n_split == 1) return rc;
-  hipLaunchKernelGGL(ot_topk_merge_kernel, dim3(tiles), block, ot_topk_lds_bytes(0, a.k) - ot_tile_words(0) * 4, s, a);   // at most the 64 KiB a kernel gets unasked
+  hipLaunchKernelGGL(ot_topk_merge_kernel, dim3(p.grid.x), dim3(KNN_TQ), ot_topk_lds_bytes(0, a.k) - ot_tile_words(0) * 4, s, a);   // at most the 64 KiB a kernel gets unasked
   return launch_status("spv_ot_topk (merge pass)");
 }
 
@@ -1188,33 +1198,22 @@ extern "C" int32_t spv_silhouette_splits(int32_t n_q, int32_t n_c) { return sil_
 extern "C" int64_t spv_silhouette_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split) { return sil_ws_bytes(n_q, n_seg, n_split); }
 
 extern "C" int spv_silhouette_sums(const spv_silhouette_args* x, void* stream) {
-  if (!x) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null arguments%s");
-  if (!x->Q) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null Q%s");
-  if (!x->C) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null C%s");
-  if (!x->seg_ptr) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null seg_ptr%s");
-  if (!x->S) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null S%s");
-  if (x->D < 1 || x->D > KNN_DMAX) return fail(SPV_ERR_ARG, "spv_silhouette_sums: D must lie in [1, 64]%s");
-  if (x->n_seg < 1 || x->n_seg > SIL_SEG_MAX) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_seg must lie in [1, 256]%s");
-  if (x->n_split < 0 || x->n_split > KNN_SPLIT_MAX) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_split must be 0 or lie in [1, 64]%s");
-  if (x->n_q < 1) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_q < 1%s");
-  if (x->n_c < 0) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_c < 0%s");
-  if (x->ld_q < x->D) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ld_q < D%s");
-  if (x->ld_c < x->D) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ld_c < D%s");
-  if (x->ld_s < x->n_q) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ld_s < n_q%s");
-  const int n_split = x->n_split ? x->n_split : sil_splits(x->n_q, x->n_c);
-  if (n_split > 1 && !x->ws) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null ws%s");
-  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ws must be 8-byte aligned%s");
-  const SilArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->seg_ptr, x->n_seg, n_split, knn_chunk(x->n_c, n_split),
+  ScanPlan p;
+  int rc = scan_check(x, "spv_silhouette_sums", sil_splits, p, [&](int) {
+    if (!x->seg_ptr) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null seg_ptr%s");
+    if (!x->S) return fail(SPV_ERR_ARG, "spv_silhouette_sums: null S%s");
+    if (x->n_seg < 1 || x->n_seg > SIL_SEG_MAX) return fail(SPV_ERR_ARG, "spv_silhouette_sums: n_seg must lie in [1, 256]%s");
+    if (x->ld_s < x->n_q) return fail(SPV_ERR_ARG, "spv_silhouette_sums: ld_s < n_q%s");
+    return SPV_OK;
+  });
+  if (rc != SPV_OK) return rc;
+  const SilArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->seg_ptr, x->n_seg, p.n_split, p.per,
                   x->S, (long)x->ld_s, (double*)x->ws};
   hipStream_t s = (hipStream_t)stream;
-  const unsigned tiles = (unsigned)((x->n_q + KNN_TQ - 1) / KNN_TQ);
-  const dim3 grid(tiles, (unsigned)n_split), block(KNN_TQ);
-  if (a.D <= 16) hipLaunchKernelGGL((sil_partial_kernel<16>), grid, block, sil_lds_bytes(16), s, a);
-  else if (a.D <= 32) hipLaunchKernelGGL((sil_partial_kernel<32>), grid, block, sil_lds_bytes(32), s, a);
-  else hipLaunchKernelGGL((sil_partial_kernel<64>), grid, block, sil_lds_bytes(64), s, a);
-  int rc = launch_status(n_split == 1 ? "spv_silhouette_sums" : "spv_silhouette_sums (partial pass)");
-  if (rc != SPV_OK || n_split == 1) return rc;
-  hipLaunchKernelGGL(sil_merge_kernel, dim3(tiles, (unsigned)a.n_seg), block, 0, s, a);
+  scan_dispatch(a.D, [&](auto dp) { constexpr int DP = decltype(dp)::value; hipLaunchKernelGGL((sil_partial_kernel<DP>), p.grid, dim3(KNN_TQ), sil_lds_bytes(DP), s, a); });
+  rc = launch_status(p.n_split == 1 ? "spv_silhouette_sums" : "spv_silhouette_sums (partial pass)");
+  if (rc != SPV_OK || p.n_split == 1) return rc;
+  hipLaunchKernelGGL(sil_merge_kernel, dim3(p.grid.x, (unsigned)a.n_seg), dim3(KNN_TQ), 0, s, a);
   return launch_status("spv_silhouette_sums (merge pass)");
 }
 

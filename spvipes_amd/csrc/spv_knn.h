@@ -2,12 +2,9 @@
 // k candidates with the smallest (squared Euclidean distance, candidate index), nothing of size queries x candidates ever stored.
 //
 // How the work is laid out on the chip
-//   * One query per lane, its vector in DP registers (D padded with zeros to DP = 16 / 32 / 64: fmaf(0, 0, acc) == acc).  A workgroup
-//     is KNN_TQ = 128 queries (2 waves) and one chunk of the candidates; the grid is (query tiles) x (chunks), the chunks chosen so
-//     that a few workgroups per CU exist when the query tiles alone do not fill the chip (knn_splits).
-//   * The chunk passes through LDS KNN_TC = 64 candidates at a time, [candidate][DP] fp32 with the padding written as zeros.  All
-//     lanes read the same address (a broadcast, no bank conflicts), 16 bytes per read.  Four candidates (two at DP = 64) are in flight per
-//     lane so that independent subtract-fma chains cover the VALU latency at 4 to 12 waves per CU.
+//   * The scan -- one query per lane, the grid (query tiles) x (chunks), the chunk passing through LDS a tile at a time, the chains in
+//     flight per lane -- is pair_scan of spv_pair_scan.h, which states the layout.  The chunks are chosen so that a few workgroups per
+//     CU exist when the query tiles alone do not fill the chip (knn_splits).
 //   * A pair (d, j) is ONE 64-bit key, the bits of d above j: d is never negative and never NaN where a key is made, so unsigned order
 //     of the keys is the order (d, j).  Per candidate the lane pays DP subtracts, DP fmas and the compare against the key of its
 //     current worst entry, kept in registers.
@@ -32,7 +29,7 @@ namespace spv {
 // ---- KNN-CORE-BEGIN ----
 constexpr int KNN_TQ = 128;        // queries per workgroup (one per lane)
 constexpr int KNN_TC = 64;         // candidates per LDS tile (a multiple of KNN_CAND)
-constexpr int KNN_CAND = 4;        // candidates in flight per lane (2 at DP = 64: see knn_partial_kernel)
+constexpr int KNN_CAND = 4;        // candidates in flight per lane (2 at DP = 64: see pair_scan)
 constexpr int KNN_DMAX = 64;       // SPV_KNN_DMAX
 constexpr int KNN_KMAX = 64;       // SPV_KNN_KMAX
 constexpr int KNN_SPLIT_MAX = 64;  // SPV_KNN_SPLIT_MAX
@@ -141,6 +138,10 @@ inline int knn_splits(int n_q, int n_c) {
 inline int knn_chunk(int n_c, int n_split) { return (int)(((long long)n_c + n_split - 1) / n_split); }
 // ---- KNN-CORE-END ----
 
+}  // namespace spv
+#include "spv_pair_scan.h"   // the scan, on the constants and knn_step above
+namespace spv {
+
 struct KnnArgs {
   const float* Q; long ld_q; int n_q;
   const float* C; long ld_c; int n_c;
@@ -153,6 +154,12 @@ struct KnnArgs {
 
 constexpr int knn_lds_bytes(int DP, int k) { return KNN_TC * DP * 4 + (k + KNN_SCAN - 1) / KNN_SCAN * KNN_SCAN * KNN_TQ * 8; }
 
+// query i's sorted keys as its row of idx / dist
+__device__ __forceinline__ void knn_write_row(const KnnArgs& a, int i, const knn_key_t* list) {
+  const int o = i * a.ld_out;
+  for (int s = 0; s < a.k; ++s) { const knn_key_t key = list[s * KNN_TQ]; a.dist[o + s] = knn_key_d(key); a.idx[o + s] = knn_key_j(key); }
+}
+
 // grid (query tiles, n_split), KNN_TQ threads, knn_lds_bytes(DP, k) of dynamic LDS.  The compiler issues a round's CAND x DP tile
 // reads ahead of its arithmetic and keeps the eight keys of a worst-entry round next to them: 96 registers at DP = 16, 176 at DP = 32
 // and, with two candidates in flight, 208 at DP = 64, no scratch -- 2 waves per SIMD for the two larger forms, i.e. 4 workgroups per
@@ -164,56 +171,22 @@ __global__ __launch_bounds__(KNN_TQ) __attribute__((amdgpu_waves_per_eu(2))) voi
   knn_key_t* const list = reinterpret_cast<knn_key_t*>(knn_lds + KNN_TC * DP) + threadIdx.x;   // [k][KNN_TQ], this lane's column
   const int lane = threadIdx.x, i = blockIdx.x * KNN_TQ + lane, k = a.k;
   const bool live = i < a.n_q;
-  constexpr int CAND = DP > 32 ? KNN_CAND / 2 : KNN_CAND;   // CAND x DP tile words are in flight next to the DP of the query
 
   float q[DP];
-#pragma unroll
-  for (int t = 0; t < DP; ++t) q[t] = (live && t < a.D) ? a.Q[(long)i * a.ld_q + t] : 0.f;
+  scan_load_query<DP>(a, i, live, q);
   const int ex = (live && a.exclude) ? a.exclude[i] : -1;
   knn_clear(list, KNN_TQ, k);
   knn_pad(list, KNN_TQ, k);
   KnnTop top;
   knn_top_init(top);
 
-  const long first = (long)blockIdx.y * a.per;
-  const int c0 = first < a.n_c ? (int)first : a.n_c;
-  const int c1 = first + a.per < a.n_c ? (int)(first + a.per) : a.n_c;
-  for (int j0 = c0; j0 < c1; j0 += KNN_TC) {
-    const int n = c1 - j0 < KNN_TC ? c1 - j0 : KNN_TC;
-    __syncthreads();   // the previous tile has been read by every lane
-    for (int e = lane; e < KNN_TC * DP; e += KNN_TQ) {
-      const int r = e / DP, t = e % DP;
-      tile[e] = (r < n && t < a.D) ? a.C[(long)(j0 + r) * a.ld_c + t] : 0.f;
-    }
-    __syncthreads();
-    for (int r = 0; r < n; r += CAND) {   // rows n .. KNN_TC - 1 of the tile are zeros: computed, never offered
-      float acc[CAND];
-#pragma unroll
-      for (int u = 0; u < CAND; ++u) acc[u] = 0.f;
-#pragma unroll
-      for (int t = 0; t < DP; t += 4) {
-#pragma unroll
-        for (int u = 0; u < CAND; ++u) {
-          const f4v c = *reinterpret_cast<const f4v*>(tile + (r + u) * DP + t);
-          acc[u] = knn_step(acc[u], q[t + 0], c[0]);
-          acc[u] = knn_step(acc[u], q[t + 1], c[1]);
-          acc[u] = knn_step(acc[u], q[t + 2], c[2]);
-          acc[u] = knn_step(acc[u], q[t + 3], c[3]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < CAND; ++u) {
-        const int j = j0 + r + u;
-        if (r + u < n && j != ex && knn_better(acc[u], j, top.worst)) knn_keep(top, list, KNN_TQ, k, knn_key(acc[u], j));
-      }
-    }
-  }
+  pair_scan<DP>(a, q, tile, [&](int j, int, bool in, float d2) {   // rows past the chunk's end: computed, never offered
+    if (in && j != ex && knn_better(d2, j, top.worst)) knn_keep(top, list, KNN_TQ, k, knn_key(d2, j));
+  });
   if (!live) return;
   knn_sort(list, KNN_TQ, top.fill);
-  if (a.n_split == 1) {
-    const int o = i * a.ld_out;
-    for (int s = 0; s < k; ++s) { const knn_key_t key = list[s * KNN_TQ]; a.dist[o + s] = knn_key_d(key); a.idx[o + s] = knn_key_j(key); }
-  } else {
+  if (a.n_split == 1) knn_write_row(a, i, list);
+  else {
     const int o = ((int)blockIdx.y * a.n_q + i) * k;
     for (int s = 0; s < k; ++s) a.ws[o + s] = list[s * KNN_TQ];
   }
@@ -227,8 +200,7 @@ __global__ __launch_bounds__(KNN_TQ) void knn_merge_kernel(const KnnArgs a) {
   knn_key_t* const list = reinterpret_cast<knn_key_t*>(knn_lds) + threadIdx.x;
   knn_clear(list, KNN_TQ, k);
   for (int c = 0; c < a.n_split; ++c) knn_merge(list, KNN_TQ, k, a.ws + (c * a.n_q + i) * k);
-  const int o = i * a.ld_out;
-  for (int s = 0; s < k; ++s) { const knn_key_t key = list[s * KNN_TQ]; a.dist[o + s] = knn_key_d(key); a.idx[o + s] = knn_key_j(key); }
+  knn_write_row(a, i, list);
 }
 
 }  // namespace spv

@@ -13,9 +13,8 @@
 //     knn_keep / knn_sort / knn_merge on a 64-bit key whose UNSIGNED order is (t descending, j ascending): the usual sign-flip map of
 //     the float's bits, complemented, above j (ot_key).  val = exp(t + r_i) with r_i = phi_i + log a_i is the plan entry itself;
 //     mass_i is the sum of the row's kept val in list order.
-//   * Layout as spv_knn: one query per lane with its vector in DP registers (D padded with zeros to 16 / 32 / 64), KNN_TQ queries and
-//     one chunk of the candidates per workgroup, KNN_TC candidates (and their h) in LDS at a time, four of them (two at DP = 64) in
-//     flight per lane, the grid (query tiles) x (chunks), the chunk count knn_splits' pure function of the shapes.
+//   * Layout: pair_scan of spv_pair_scan.h, which states it (one query per lane, the grid (query tiles) x (chunks), the chunk through
+//     LDS a tile at a time), with the tile's h staged behind the tile; the chunk count is knn_splits' pure function of the shapes.
 //   * n_split > 1: every (query tile, chunk) writes its (m, sum) pairs / its sorted keys to the workspace and a merge kernel, one lane
 //     per query again, folds them IN CHUNK ORDER.  No floating-point atomics anywhere.
 // What is reproducible: for fixed (shapes, n_split) two calls agree bit for bit, for both kernels.  idx of ot_topk is a function of the
@@ -104,34 +103,9 @@ constexpr int ot_tile_words(int DP) { return KNN_TC * DP + KNN_TC; }
 constexpr int ot_softmin_lds_bytes(int DP) { return ot_tile_words(DP) * 4; }
 constexpr int ot_topk_lds_bytes(int DP, int k) { return ot_tile_words(DP) * 4 + (k + KNN_SCAN - 1) / KNN_SCAN * KNN_SCAN * KNN_TQ * 8; }
 
-// candidates [j0, j0 + n) into the tile, [candidate][DP] with the padding and the rows from n on written as zeros; their h behind it,
-// -inf from n on (such a row's t is never finite)
-template <int DP>
-__device__ __forceinline__ void ot_load_tile(const OtArgs& a, float* tile, int j0, int n) {
-  float* const th = tile + KNN_TC * DP;
-  for (int e = threadIdx.x; e < KNN_TC * DP; e += KNN_TQ) {
-    const int r = e / DP, t = e % DP;
-    tile[e] = (r < n && t < a.D) ? a.C[(long)(j0 + r) * a.ld_c + t] : 0.f;
-  }
+// pair_scan's staging step: the h of candidates [j0, j0 + n) behind the tile, -inf from n on (such a row's t is never finite)
+__device__ __forceinline__ void ot_stage_h(const OtArgs& a, float* th, int j0, int n) {
   for (int r = threadIdx.x; r < KNN_TC; r += KNN_TQ) th[r] = r < n ? a.h[j0 + r] : -INFINITY;
-}
-
-// CAND candidates' costs from tile row r on
-template <int DP, int CAND>
-__device__ __forceinline__ void ot_costs(const float* tile, int r, const float (&q)[DP], float (&acc)[CAND]) {
-#pragma unroll
-  for (int u = 0; u < CAND; ++u) acc[u] = 0.f;
-#pragma unroll
-  for (int t = 0; t < DP; t += 4) {
-#pragma unroll
-    for (int u = 0; u < CAND; ++u) {
-      const f4v c = *reinterpret_cast<const f4v*>(tile + (r + u) * DP + t);
-      acc[u] = knn_step(acc[u], q[t + 0], c[0]);
-      acc[u] = knn_step(acc[u], q[t + 1], c[1]);
-      acc[u] = knn_step(acc[u], q[t + 2], c[2]);
-      acc[u] = knn_step(acc[u], q[t + 3], c[3]);
-    }
-  }
 }
 
 // grid (query tiles, n_split), KNN_TQ threads, ot_softmin_lds_bytes(DP) of dynamic LDS
@@ -139,32 +113,17 @@ template <int DP>
 __global__ __launch_bounds__(KNN_TQ) __attribute__((amdgpu_waves_per_eu(2))) void ot_softmin_kernel(const OtArgs a) {
   extern __shared__ __align__(16) float ot_lds[];
   float* const tile = ot_lds;                    // [KNN_TC][DP]
-  const float* const th = ot_lds + KNN_TC * DP;  // [KNN_TC]
+  float* const th = ot_lds + KNN_TC * DP;        // [KNN_TC]
   const int lane = threadIdx.x, i = blockIdx.x * KNN_TQ + lane;
   const bool live = i < a.n_q;
-  constexpr int CAND = DP > 32 ? KNN_CAND / 2 : KNN_CAND;
 
   float q[DP];
-#pragma unroll
-  for (int t = 0; t < DP; ++t) q[t] = (live && t < a.D) ? a.Q[(long)i * a.ld_q + t] : 0.f;
+  scan_load_query<DP>(a, i, live, q);
   OtLse st;
   ot_lse_init(st);
 
-  const long first = (long)blockIdx.y * a.per;
-  const int c0 = first < a.n_c ? (int)first : a.n_c;
-  const int c1 = first + a.per < a.n_c ? (int)(first + a.per) : a.n_c;
-  for (int j0 = c0; j0 < c1; j0 += KNN_TC) {
-    const int n = c1 - j0 < KNN_TC ? c1 - j0 : KNN_TC;
-    __syncthreads();   // the previous tile has been read by every lane
-    ot_load_tile<DP>(a, tile, j0, n);
-    __syncthreads();
-    for (int r = 0; r < n; r += CAND) {   // rows n .. KNN_TC - 1 carry h = -inf: computed, never added
-      float acc[CAND];
-      ot_costs<DP, CAND>(tile, r, q, acc);
-#pragma unroll
-      for (int u = 0; u < CAND; ++u) ot_update(st, ot_t(acc[u], a.s, th[r + u]));
-    }
-  }
+  pair_scan<DP>(a, q, tile, [&](int j0, int n) { ot_stage_h(a, th, j0, n); },
+                [&](int, int row, bool, float c) { ot_update(st, ot_t(c, a.s, th[row])); });   // rows past the chunk's end carry h = -inf: computed, never added
   if (!live) return;
   if (a.n_split == 1) a.L[i] = ot_lse_value(st);
   else reinterpret_cast<OtLse*>(a.ws)[(long)blockIdx.y * a.n_q + i] = st;
@@ -202,39 +161,23 @@ template <int DP>
 __global__ __launch_bounds__(KNN_TQ) __attribute__((amdgpu_waves_per_eu(2))) void ot_topk_kernel(const OtArgs a) {
   extern __shared__ __align__(16) float ot_lds[];
   float* const tile = ot_lds;
-  const float* const th = ot_lds + KNN_TC * DP;
+  float* const th = ot_lds + KNN_TC * DP;
   knn_key_t* const list = reinterpret_cast<knn_key_t*>(ot_lds + ot_tile_words(DP)) + threadIdx.x;   // [k][KNN_TQ], this lane's column
   const int lane = threadIdx.x, i = blockIdx.x * KNN_TQ + lane, k = a.k;
   const bool live = i < a.n_q;
-  constexpr int CAND = DP > 32 ? KNN_CAND / 2 : KNN_CAND;
 
   float q[DP];
-#pragma unroll
-  for (int t = 0; t < DP; ++t) q[t] = (live && t < a.D) ? a.Q[(long)i * a.ld_q + t] : 0.f;
+  scan_load_query<DP>(a, i, live, q);
   ot_clear(list, KNN_TQ, k);
   knn_pad(list, KNN_TQ, k);
   KnnTop top;
   ot_top_init(top);
 
-  const long first = (long)blockIdx.y * a.per;
-  const int c0 = first < a.n_c ? (int)first : a.n_c;
-  const int c1 = first + a.per < a.n_c ? (int)(first + a.per) : a.n_c;
-  for (int j0 = c0; j0 < c1; j0 += KNN_TC) {
-    const int n = c1 - j0 < KNN_TC ? c1 - j0 : KNN_TC;
-    __syncthreads();
-    ot_load_tile<DP>(a, tile, j0, n);
-    __syncthreads();
-    for (int r = 0; r < n; r += CAND) {
-      float acc[CAND];
-      ot_costs<DP, CAND>(tile, r, q, acc);
-#pragma unroll
-      for (int u = 0; u < CAND; ++u) {
-        const int j = j0 + r + u;
-        const float t = ot_t(acc[u], a.s, th[r + u]);
-        if (r + u < n && ot_better(t, j, top.worst)) knn_keep(top, list, KNN_TQ, k, ot_key(t, j));
-      }
-    }
-  }
+  pair_scan<DP>(a, q, tile, [&](int j0, int n) { ot_stage_h(a, th, j0, n); },
+                [&](int j, int row, bool in, float c) {
+                  const float t = ot_t(c, a.s, th[row]);
+                  if (in && ot_better(t, j, top.worst)) knn_keep(top, list, KNN_TQ, k, ot_key(t, j));
+                });
   if (!live) return;
   knn_sort(list, KNN_TQ, top.fill);
   if (a.n_split == 1) ot_write_row(a, i, list);

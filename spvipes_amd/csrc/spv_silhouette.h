@@ -9,11 +9,9 @@
 // flags compile to v_sqrt_f32 plus the two-neighbour fma correction: correctly rounded (the bare 1-ulp instruction is what __fsqrt_rn
 // gives here, not this).
 //
-// How the work is laid out on the chip: spv_knn's scan with another reduction.
-//   * One query per lane, its vector in DP registers (D padded with zeros to DP = 16 / 32 / 64).  A workgroup is KNN_TQ = 128 queries
-//     and one chunk of the candidates; the grid is (query tiles) x (chunks), the chunk count a knn_splits-style pure function of the shapes (sil_splits).
-//   * The chunk passes through LDS KNN_TC = 64 candidates at a time, [candidate][DP] fp32, read as 16-byte broadcasts; four candidates
-//     (two at DP = 64) are in flight per lane.
+// How the work is laid out on the chip: pair_scan of spv_pair_scan.h, which states the layout (one query per lane, the grid
+// (query tiles) x (chunks), the chunk through LDS a tile at a time), with this reduction.  The chunk count is a knn_splits-style pure
+// function of the shapes (sil_splits).
 //   * The candidates come ARRANGED BY SEGMENT, so each lane keeps ONE fp64 accumulator: a segment's end is the same candidate for
 //     every lane, a uniform (scalar) compare and branch per candidate.  At a boundary the lane writes its accumulator to its column of S
 //     and clears it (sil_advance); per candidate it pays the DP-term chain, one sqrtf, one convert and one fp64 add (sil_add).  Bins
@@ -128,11 +126,9 @@ __global__ __launch_bounds__(KNN_TQ) __attribute__((amdgpu_waves_per_eu(2))) voi
   const int lane = threadIdx.x;
   const long i = (long)blockIdx.x * KNN_TQ + lane;
   const bool live = i < a.n_q;
-  constexpr int CAND = DP > 32 ? KNN_CAND / 2 : KNN_CAND;
 
   float q[DP];
-#pragma unroll
-  for (int t = 0; t < DP; ++t) q[t] = (live && t < a.D) ? a.Q[i * a.ld_q + t] : 0.f;
+  scan_load_query<DP>(a, i, live, q);
 
   // this lane's column: of S itself, or of this chunk's slab of the workspace
   const long st = a.n_split == 1 ? a.ld_s : (long)a.n_q;
@@ -140,41 +136,12 @@ __global__ __launch_bounds__(KNN_TQ) __attribute__((amdgpu_waves_per_eu(2))) voi
   SilWalk w;
   sil_walk_init(w, a.seg_ptr);
 
-  const long first = (long)blockIdx.y * a.per;
-  const int c0 = first < a.n_c ? (int)first : a.n_c;
-  const int c1 = first + a.per < a.n_c ? (int)(first + a.per) : a.n_c;
-  for (int j0 = c0; j0 < c1; j0 += KNN_TC) {
-    const int n = c1 - j0 < KNN_TC ? c1 - j0 : KNN_TC;
-    __syncthreads();   // the previous tile has been read by every lane
-    for (int e = lane; e < KNN_TC * DP; e += KNN_TQ) {
-      const int r = e / DP, t = e % DP;
-      tile[e] = (r < n && t < a.D) ? a.C[(long)(j0 + r) * a.ld_c + t] : 0.f;
+  pair_scan<DP>(a, q, tile, [&](int j, int, bool in, float d2) {   // rows past the chunk's end: computed, never added
+    if (in) {   // the same for every lane, as are the boundaries
+      sil_advance(w, j, a.seg_ptr, a.n_seg, out, st, live);
+      sil_add(w, d2);
     }
-    __syncthreads();
-    for (int r = 0; r < n; r += CAND) {   // rows n .. KNN_TC - 1 of the tile are zeros: computed, never added
-      float acc[CAND];
-#pragma unroll
-      for (int u = 0; u < CAND; ++u) acc[u] = 0.f;
-#pragma unroll
-      for (int t = 0; t < DP; t += 4) {
-#pragma unroll
-        for (int u = 0; u < CAND; ++u) {
-          const f4v c = *reinterpret_cast<const f4v*>(tile + (r + u) * DP + t);
-          acc[u] = knn_step(acc[u], q[t + 0], c[0]);
-          acc[u] = knn_step(acc[u], q[t + 1], c[1]);
-          acc[u] = knn_step(acc[u], q[t + 2], c[2]);
-          acc[u] = knn_step(acc[u], q[t + 3], c[3]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < CAND; ++u) {
-        if (r + u < n) {   // the same for every lane, as are the boundaries
-          sil_advance(w, j0 + r + u, a.seg_ptr, a.n_seg, out, st, live);
-          sil_add(w, acc[u]);
-        }
-      }
-    }
-  }
+  });
   sil_finish(w, a.n_seg, out, st, live);
 }
 

@@ -12,9 +12,9 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import OT_DMAX, OT_KMAX, OT_SPLIT_MAX, SpvOtArgs, ptr, stream_ptr
+from ._abi import OT_DMAX, OT_KMAX, OT_SPLIT_MAX, SpvOtArgs, ptr, stream_ptr   # the limits: part of this module's interface
+from ._scan_ops import _fill_sides, _k, _n_split, _out_pair, _rows, _sides, _workspace
 from .data import plan_union_csr
-from .knn_ops import _workspace
 
 
 def ot_tiles() -> Tuple[int, int]:
@@ -33,12 +33,6 @@ def ot_ws_bytes(n_q: int, k: int, n_split: int) -> int:
     return int(_abi.load().spv_ot_ws_bytes(int(n_q), int(k), int(n_split)))
 
 
-def _rows(t, name: str) -> None:
-    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 1
-            or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
-        raise _abi.SpvError(f"ot: {name} must be an fp32 device tensor [rows, D] with unit column stride")
-
-
 def _vector(t, n: int, dev, name: str) -> None:
     if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n
             or not t.is_contiguous()):
@@ -47,24 +41,14 @@ def _vector(t, n: int, dev, name: str) -> None:
 
 def _common(X, Y, h, inv_eps, n_split) -> SpvOtArgs:
     """the checks and the argument fields ot_softmin and ot_topk share"""
-    _rows(X, "X"), _rows(Y, "Y")
-    dev, n_q, n_c, D = X.device, int(X.shape[0]), int(Y.shape[0]), int(X.shape[1])
-    if Y.device != dev or int(Y.shape[1]) != D:
-        raise _abi.SpvError("ot: X and Y must share a device and have the same number of columns")
-    if n_q < 1:
-        raise ValueError("ot: X has no rows")
-    if not 1 <= D <= OT_DMAX:
-        raise ValueError(f"ot: D must lie in [1, {OT_DMAX}], got {D}")
+    dev, n_q, n_c, D = _sides("ot", X, Y, ("X", "Y"))
     _vector(h, n_c, dev, "h")
     inv_eps = float(inv_eps)
     if not (0.0 < inv_eps < math.inf) or not (0.0 < float(np.float32(inv_eps)) < math.inf):
         raise ValueError(f"ot: inv_eps must be a positive finite number in fp32, got {inv_eps!r}")
-    if isinstance(n_split, bool) or int(n_split) != n_split or not 0 <= int(n_split) <= OT_SPLIT_MAX:
-        raise ValueError(f"ot: n_split must be 0 or an integer in [1, {OT_SPLIT_MAX}], got {n_split!r}")
     a = SpvOtArgs()
-    a.Q, a.ld_q, a.n_q = ptr(X), (X.stride(0) if n_q > 1 else D), n_q
-    a.C, a.ld_c, a.n_c = (ptr(Y) if n_c else ptr(X)), (Y.stride(0) if n_c > 1 else D), n_c   # an empty tensor has no address; nothing is read
-    a.D, a.h, a.inv_eps, a.n_split = D, (ptr(h) if n_c else ptr(X)), inv_eps, int(n_split)
+    _fill_sides(a, X, Y)
+    a.h, a.inv_eps, a.n_split = (ptr(h) if n_c else ptr(X)), inv_eps, _n_split("ot", n_split)
     return a
 
 
@@ -100,27 +84,19 @@ def ot_topk(X: torch.Tensor, Y: torch.Tensor, h: torch.Tensor, r: torch.Tensor, 
     a = _common(X, Y, h, inv_eps, n_split)
     dev, n_q = X.device, int(X.shape[0])
     _vector(r, n_q, dev, "r")
-    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= OT_KMAX:
-        raise ValueError(f"ot_topk: k must be an integer in [1, {OT_KMAX}], got {k!r}")
-    k = int(k)
+    k = _k("ot_topk", k)
     if out is None:
-        idx = torch.empty((n_q, k), dtype=torch.int32, device=dev)
-        val = torch.empty((n_q, k), dtype=torch.float32, device=dev)
+        idx, val, ld_out = _out_pair("ot_topk", None, "val", n_q, k, dev)
         mass = torch.empty(n_q, dtype=torch.float32, device=dev)
     else:
         idx, val, mass = out
-        for t, dt, name in ((idx, torch.int32, "idx"), (val, torch.float32, "val")):
-            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != dt or t.dim() != 2 or t.shape[0] != n_q
-                    or t.shape[1] < k or (t.shape[1] > 1 and t.stride(1) != 1) or (n_q > 1 and t.stride(0) < k)):
-                raise _abi.SpvError(f"ot_topk: out {name} must be a device tensor [{n_q}, >= {k}] of {dt} with unit column stride")
-        if n_q > 1 and idx.stride(0) != val.stride(0):
-            raise _abi.SpvError("ot_topk: out idx and val must have the same row stride")
+        idx, val, ld_out = _out_pair("ot_topk", (idx, val), "val", n_q, k, dev)
         if (not isinstance(mass, torch.Tensor) or not mass.is_cuda or mass.device != dev or mass.dtype != torch.float32 or mass.dim() != 1
                 or mass.numel() < n_q or not mass.is_contiguous()):
             raise _abi.SpvError(f"ot_topk: out mass must be a contiguous fp32 device tensor with at least {n_q} entries")
     ws = _workspace(ot_ws_bytes(n_q, k, int(n_split) or ot_splits(n_q, int(Y.shape[0]))), dev)
     a.k, a.r = k, ptr(r)
-    a.idx, a.val, a.ld_out = ptr(idx), ptr(val), (idx.stride(0) if n_q > 1 else max(k, int(idx.shape[1])))
+    a.idx, a.val, a.ld_out = ptr(idx), ptr(val), ld_out
     a.mass, a.ws = ptr(mass), ptr(ws)
     _abi.call("spv_ot_topk", C.byref(a), stream_ptr())
     return idx[:, :k], val[:, :k], mass[:n_q]
@@ -167,7 +143,7 @@ def sinkhorn(X0: torch.Tensor, X1: torch.Tensor, epsilon: float = 0.05, scale_co
     normalised to sum 1; zeros are allowed.  One iteration is phi = -softmin(X0, X1, psi + log b), then psi = -softmin(X1, X0, phi + log a).
     Every ``check_every`` iterations the host reads max_i |phi_new - phi_old| over the cells with mass -- the largest log-deviation of
     the row marginal -- ONCE and stops at <= ``tol``; ``tol=0`` runs all ``max_iter``."""
-    _rows(X0, "X0"), _rows(X1, "X1")
+    _rows("ot", X0, "X0"), _rows("ot", X1, "X1")
     if X0.device != X1.device or X0.shape[1] != X1.shape[1]:
         raise _abi.SpvError("sinkhorn: X0 and X1 must share a device and have the same number of columns")
     n0, n1, dev = int(X0.shape[0]), int(X1.shape[0]), X0.device
@@ -238,11 +214,10 @@ class TransportPlan:
 def transport_plan(X0: torch.Tensor, X1: torch.Tensor, k: int = 32, **sinkhorn_kwargs) -> TransportPlan:
     """``sinkhorn``, then two ``ot_topk`` passes -- every cell of group 0 against group 1 and every cell of group 1 against group 0,
     ``k`` entries each -- and their union as one sparse plan; a pair both passes kept takes the row pass's value."""
-    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= OT_KMAX:
-        raise ValueError(f"transport_plan: k must be an integer in [1, {OT_KMAX}], got {k!r}")
+    k = _k("transport_plan", k)
     res = sinkhorn(X0, X1, **sinkhorn_kwargs)
-    rows = ot_topk(X0, X1, res.psi + res.log_b, res.phi + res.log_a, res.inv_eps, int(k))
-    cols = ot_topk(X1, X0, res.phi + res.log_a, res.psi + res.log_b, res.inv_eps, int(k))
+    rows = ot_topk(X0, X1, res.psi + res.log_b, res.phi + res.log_a, res.inv_eps, k)
+    cols = ot_topk(X1, X0, res.phi + res.log_a, res.psi + res.log_b, res.inv_eps, k)
     host = [t.cpu().numpy() for t in (*rows, *cols)]
     indptr, indices, data = plan_union_csr(host[0], host[1], host[3], host[4], X0.shape[0], X1.shape[0])
     with np.errstate(divide="ignore", invalid="ignore"):

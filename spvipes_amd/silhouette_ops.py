@@ -3,15 +3,13 @@ contract).  ``spVIPES.latent_silhouette`` runs it on the latents; nothing of siz
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from . import _abi
-from ._abi import KNN_DMAX, KNN_SPLIT_MAX, SIL_SEG_MAX, SpvSilhouetteArgs, ptr, stream_ptr
-
-_WS: Dict[tuple, torch.Tensor] = {}   # (device, bytes) -> the workspace of that size; a few shapes per process
-_WS_KEEP = 4
+from ._abi import SIL_SEG_MAX, SpvSilhouetteArgs, ptr, stream_ptr
+from ._scan_ops import _WS, _fill_sides, _n_split, _sides, _workspace   # _WS: the benchmarks clear it
 
 
 def silhouette_splits(n_q: int, n_c: int) -> int:
@@ -22,24 +20,6 @@ def silhouette_splits(n_q: int, n_c: int) -> int:
 def silhouette_ws_bytes(n_q: int, n_seg: int, n_split: int) -> int:
     """Bytes of workspace for ``n_split`` chunks (the resolved number, not 0): 0 for one chunk"""
     return int(_abi.load().spv_silhouette_ws_bytes(int(n_q), int(n_seg), int(n_split)))
-
-
-def _workspace(nbytes: int, device) -> Optional[torch.Tensor]:
-    if nbytes == 0:
-        return None
-    key = (str(device), nbytes)
-    ws = _WS.get(key)
-    if ws is None:
-        while len(_WS) >= _WS_KEEP:
-            _WS.pop(next(iter(_WS)))
-        ws = _WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
-
-
-def _rows(t, name: str) -> None:
-    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 1
-            or (t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):   # no rows: no strides to speak of
-        raise _abi.SpvError(f"segment_distance_sums: {name} must be an fp32 device tensor [rows, D] with unit column stride")
 
 
 def segment_distance_sums(Q: torch.Tensor, C_: torch.Tensor, seg_ptr: torch.Tensor, n_split: int = 0,
@@ -57,16 +37,8 @@ def segment_distance_sums(Q: torch.Tensor, C_: torch.Tensor, seg_ptr: torch.Tens
     of the result does not depend on the other rows of ``Q``; different values may differ in the last bits of fp64.
     ``out``: an fp64 device tensor [n_seg, >= n_q] with unit column stride (segment-major, as stored); the transposed view of its first
     n_q columns is returned and nothing else is written."""
-    _rows(Q, "Q"), _rows(C_, "C")
-    dev, n_q, n_c, D = Q.device, int(Q.shape[0]), int(C_.shape[0]), int(Q.shape[1])
-    if C_.device != dev or int(C_.shape[1]) != D:
-        raise _abi.SpvError("segment_distance_sums: Q and C must share a device and have the same number of columns")
-    if n_q < 1:
-        raise ValueError("segment_distance_sums: Q has no rows")
-    if not 1 <= D <= KNN_DMAX:
-        raise ValueError(f"segment_distance_sums: D must lie in [1, {KNN_DMAX}], got {D}")
-    if isinstance(n_split, bool) or int(n_split) != n_split or not 0 <= int(n_split) <= KNN_SPLIT_MAX:
-        raise ValueError(f"segment_distance_sums: n_split must be 0 or an integer in [1, {KNN_SPLIT_MAX}], got {n_split!r}")
+    dev, n_q, n_c, D = _sides("segment_distance_sums", Q, C_)
+    n_split = _n_split("segment_distance_sums", n_split)
     if (not isinstance(seg_ptr, torch.Tensor) or not seg_ptr.is_cuda or seg_ptr.device != dev or seg_ptr.dtype != torch.int32 or seg_ptr.dim() != 1
             or not seg_ptr.is_contiguous()):
         raise _abi.SpvError("segment_distance_sums: seg_ptr must be a contiguous int32 device tensor [n_seg + 1]")
@@ -78,12 +50,10 @@ def segment_distance_sums(Q: torch.Tensor, C_: torch.Tensor, seg_ptr: torch.Tens
     elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev or out.dtype != torch.float64 or out.dim() != 2
           or out.shape[0] != n_seg or out.shape[1] < n_q or (out.shape[1] > 1 and out.stride(1) != 1) or (n_seg > 1 and out.stride(0) < n_q)):
         raise _abi.SpvError(f"segment_distance_sums: out must be an fp64 device tensor [{n_seg}, >= {n_q}] with unit column stride")
-    splits = int(n_split) or silhouette_splits(n_q, n_c)
-    ws = _workspace(silhouette_ws_bytes(n_q, n_seg, splits), dev)
+    ws = _workspace(silhouette_ws_bytes(n_q, n_seg, n_split or silhouette_splits(n_q, n_c)), dev)
     a = SpvSilhouetteArgs()
-    a.Q, a.ld_q, a.n_q = ptr(Q), (Q.stride(0) if n_q > 1 else D), n_q
-    a.C, a.ld_c, a.n_c = (ptr(C_) if n_c else ptr(Q)), (C_.stride(0) if n_c > 1 else D), n_c   # an empty tensor has no address; nothing is read
-    a.D, a.seg_ptr, a.n_seg, a.n_split = D, ptr(seg_ptr), n_seg, int(n_split)
+    _fill_sides(a, Q, C_)
+    a.seg_ptr, a.n_seg, a.n_split = ptr(seg_ptr), n_seg, n_split
     a.S, a.ld_s, a.ws = ptr(out), (out.stride(0) if n_seg > 1 else max(n_q, int(out.shape[1]))), ptr(ws)
     _abi.call("spv_silhouette_sums", C.byref(a), stream_ptr())
     return out[:, :n_q].t()

@@ -27,7 +27,9 @@ groups = [make_synthetic_group(g, cells, genes, dev) for g in range(2)]
 module = spVIPESmodule({0: genes, 1: genes}, use_labels=True, n_hidden=128, n_dimensions_shared=25, n_dimensions_private=10,
                        precision="bf16").to(dev)
 tr = Trainer(module, [g.counts for g in groups], labels=[g.labels for g in groups])
-tr.world, tr.overlap = 2, True          # what a rank of a 2-GPU job sees
+tr.world, tr._pg_world, tr.overlap = 2, 2, True   # what a rank of a 2-GPU job sees; _pg_world: capture() then drains the device and
+                                                    # captures in thread-local mode, as it does for every real group of more than one rank
+                                                    # (without it the watchdog's event query during the global-mode capture aborts the process)
 dist.broadcast(tr.fp.flat, src=0)
 sampler = MinibatchSampler([cells, cells], B, dev, seed=0)
 module.train()
