@@ -215,9 +215,13 @@ int spv_gemm_bf16_uses_dma(int32_t a_kmajor, int32_t M, int32_t N, int32_t K, in
  *   a_kmajor == 0: A is mem[m][k] (k contiguous); a_kmajor == 1: A is mem[k][m];
  *   a_tiles > 0: A is a tiled [cells][genes] array (above) with a_tiles gene tiles per cell tile;
  *                a_kmajor then says whether K runs over cells (1) or over genes (0); lda is unused.
- *   B is always k-major: mem[k][n].   Operands zero padded to tile multiples (64 x 320 / 128 x 32,
- *   K to a multiple of 64).
- *   splits > 1: C is a stack of `splits` fp32 slabs (slab_stride elements apart), one per K range. */
+ *   B is always k-major: mem[k][n].   Operands zero padded to tile multiples: K to a multiple of 64 in both; M to a multiple
+ *   of 128 where N <= 32 or spv_gemm_bf16_uses_dma() says 1, of 64 otherwise; the columns of B to 32 from the given pointer
+ *   where N <= 32 (they may hold other finite data: only columns < N are stored), to a multiple of 320 otherwise.  Nothing
+ *   beyond those extents is read (tests/test_gpu_gemm_family.py surrounds every operand with NaN words).
+ *   splits > 1: C is a stack of `splits` fp32 slabs (slab_stride elements apart), one per K range of
+ *   ceil(ceil(K / 64) / splits) * 64 indices; a trailing split whose range starts at or beyond K writes a slab of zeros and
+ *   reads nothing. */
 int spv_gemm_bf16(int32_t a_kmajor, const uint16_t* A_hi, const uint16_t* A_lo, int64_t lda,
                   const uint16_t* B_hi, const uint16_t* B_lo, int64_t ldb,
                   float* C, int64_t ldc, int32_t M, int32_t N, int32_t K,
@@ -253,8 +257,10 @@ int spv_gemm_bf16_grouped(const spv_gemm_args* groups, int32_t n_groups, void* s
 /* Weight gradients of both rate heads' regressors (BatchNorm folded) in one streaming pass, bf16 mode:
  *   slabP[split][g][0..15] = sum_{cells of the split} tP(cell, g) * Aps[cell][0..15]
  *   slabS[split][g][0..31] = sum_{cells of the split} tS(cell, g) * Aps[cell][16..47]        (backward of nn/networks.py:314-320)
- * tP / tS: bf16 [Bp][Gp] in accumulator-tile order (a_tiles = Gp / 32 >= round_up(G, 256) / 32), already softmax-corrected
- * (spv_dec_softmax_bwd); Aps: bf16 [Bp][48] latent operand image; Bp % 64 == 0.  Sum the slabs with spv_reduce_slabs. */
+ * tP / tS: bf16 [Bp][Gp] in accumulator-tile order (a_tiles = Gp / 32 >= round_up(G, 128) / 32: the kernel walks 128-gene tiles; the
+ * decoder's Gp = round_up(G, 256) covers that), already softmax-corrected (spv_dec_softmax_bwd); Aps: bf16 [Bp][48] latent operand
+ * image; Bp % 64 == 0.  `splits` may exceed Bp / 64: a split without cells writes a slab of zeros and reads nothing.  Sum the slabs
+ * with spv_reduce_slabs. */
 int spv_dec_heads_wgrad(const uint16_t* tP, const uint16_t* tS, int32_t a_tiles, const uint16_t* Aps, int32_t G, int32_t Bp,
                         int32_t splits, float* slabP, float* slabS, void* stream);
 

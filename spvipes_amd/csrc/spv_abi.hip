@@ -537,8 +537,9 @@ extern "C" int spv_gemm_bf16_grouped(const spv_gemm_args* g, int32_t n, void* st
 extern "C" int spv_dec_heads_wgrad(const uint16_t* tP, const uint16_t* tS, int32_t a_tiles, const uint16_t* Aps, int32_t G, int32_t Bp,
                                    int32_t splits, float* slabP, float* slabS, void* stream) {
   if (!tP || !tS || !Aps || !slabP || !slabS) return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: null pointer%s");
+  // (a workgroup walks DH_BM = 128 genes: gene tiles up to round_up(G, 128) / 32 of every cell tile are what the kernel reads)
   if (G <= 0 || Bp <= 0 || (Bp % DH_BK) != 0 || splits <= 0 || (long)a_tiles * 32 < ((long)G + DH_BM - 1) / DH_BM * DH_BM)
-    return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: Bp must be a multiple of 64 and the tile arrays must cover round_up(G, 256) genes%s");
+    return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: Bp must be a multiple of 64 and the tile arrays must cover round_up(G, 128) genes%s");
   if (!aligned16(tP, tS, Aps)) return fail(SPV_ERR_ARG, "spv_dec_heads_wgrad: operands must be 16-byte aligned%s");
   const int mtiles = (G + DH_BM - 1) / DH_BM, ktiles = Bp / DH_BK;
   const int k_per_split = (ktiles + splits - 1) / splits * DH_BK;

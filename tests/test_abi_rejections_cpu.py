@@ -168,7 +168,7 @@ DEC_OPERANDS = "decoder: missing packed regressor operands"
 DEC_KSLOTS = "decoder: kslots must be 0 (16 / 32 K slots) or 1 (32 / 64)"
 FWD_SPLIT_ONLY_DMA = "spv_enc_fc1_fwd: a split (nsplit 3) resident image is only taken by the LDS-DMA kernel (ask spv_enc_fc1_fwd_uses_dma)"
 WGRAD_SPLIT_ONLY_DMA = "spv_enc_fc1_wgrad: a split (nsplit 3) resident image is only taken by the LDS-DMA kernel (ask spv_enc_fc1_wgrad_split_uses_dma)"
-HEADS_WGRAD_SHAPE = "spv_dec_heads_wgrad: Bp must be a multiple of 64 and the tile arrays must cover round_up(G, 256) genes"
+HEADS_WGRAD_SHAPE = "spv_dec_heads_wgrad: Bp must be a multiple of 64 and the tile arrays must cover round_up(G, 128) genes"
 NB_SPLITS = "spv_dec_nb_fwd: nb_genes_per_split must be a multiple of 32, at most 160, and the splits must cover G"
 
 # (case, entry point, arguments, return code, spv_last_error()) -- recorded from the library before the wrappers were rewritten around shared
