@@ -636,6 +636,45 @@ int64_t spv_ot_ws_bytes(int32_t n_q, int32_t k, int32_t n_split);
 int32_t spv_ot_tile_q(void);
 int32_t spv_ot_tile_c(void);
 
+/* The plan's log mass between every query and every SEGMENT of the candidates (spVIPES.match_transport_clusters of the user API):
+ * the candidates come ARRANGED BY SEGMENT, and for query row i and segment s
+ *   L[s][i] = log sum over j in [seg_ptr[s], seg_ptr[s + 1]) of exp(t(i, j)),   t(i, j) = fmaf(-c(i, j), inv_eps, h[j])
+ * with spv_ot_softmin's c and t, the same bits; nothing of size n_q x n_c stored.  With h = psi + log b and r_i = phi_i + log a_i of a
+ * Sinkhorn result, exp(L[s][i] + r_i) is the mass the untruncated plan puts between cell i and the cells of segment s.
+ * Per lane ONE running (m, sum) pair, updated as spv_ot_softmin's; at a segment's end (the same candidate for every lane) it is
+ * written and re-initialised.  A t that is not finite contributes nothing; a segment without a contributing candidate -- an empty
+ * one, n_c == 0 -- gives -inf.
+ * seg_ptr: int32 [n_seg + 1] ON THE DEVICE, ascending, seg_ptr[0] = 0, seg_ptr[n_seg] = n_c; empty segments are allowed.  It cannot
+ * be checked from the host: any other content gives unspecified values, never an access outside seg_ptr, L or ws.
+ * Layout of L: SEGMENT-MAJOR, fp32 [n_seg][ld_l] with ld_l >= n_q -- L[s * ld_l + i].  Columns >= n_q are never written.
+ * Launches: a partial pass of (tiles of spv_ot_tile_q() queries) x (n_split chunks of the candidates) workgroups; n_split == 1 is ONE
+ * launch that writes L itself; for n_split > 1 every (tile, chunk) writes all n_seg states to ws and a merge pass, one lane per
+ * (query, segment), folds them IN CHUNK ORDER.  No floating-point atomics: for fixed shapes and n_split two calls agree bit for bit,
+ * and a query's values do not depend on the other queries of the call.  Different n_split agree within spv_ot_softmin's rounding
+ * bound, not bit for bit.  The chunks of a given n_split are spv_ot_softmin's: with n_seg == 1 and the same EXPLICIT n_split, L[0]
+ * equals spv_ot_softmin's L bit for bit.  n_split = 0 stands for spv_ot_segment_splits(n_q, n_c), a pure function of the shapes
+ * (more chunks than spv_ot_splits: a chunk's state is small).
+ * ws: spv_ot_segment_ws_bytes(n_q, n_seg, n_split) bytes with the RESOLVED n_split (0 for n_split <= 1 or a non-positive shape;
+ * 64-bit arithmetic), 8-byte aligned, overwritten by every call.  Nothing is allocated.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null arguments / Q / C / h / seg_ptr / L; ws null when its size is not 0, or not
+ * 8-byte aligned; D outside [1, SPV_OT_DMAX]; n_split outside [0, SPV_OT_SPLIT_MAX]; n_q < 1; n_c < 0; ld_q < D; ld_c < D; inv_eps
+ * not a positive finite number; n_seg outside [1, SPV_OT_SEG_MAX]; ld_l < n_q; n_seg * ld_l or n_split * n_seg * n_q beyond 2^31 - 1. */
+#define SPV_OT_SEG_MAX 256
+typedef struct spv_ot_seg_args {
+  const float* Q; int64_t ld_q; int32_t n_q;      /* queries    fp32 [n_q][ld_q], ld_q >= D */
+  const float* C; int64_t ld_c; int32_t n_c;      /* candidates fp32 [n_c][ld_c], ld_c >= D, arranged by segment */
+  int32_t D;                                      /* 1 .. SPV_OT_DMAX */
+  const float* h;                                 /* [n_c] */
+  float inv_eps;                                  /* s = 1 / epsilon, > 0 */
+  const int32_t* seg_ptr; int32_t n_seg;          /* [n_seg + 1] on the device; 1 .. SPV_OT_SEG_MAX segments */
+  int32_t n_split;                                /* 0 = spv_ot_segment_splits(n_q, n_c); else 1 .. SPV_OT_SPLIT_MAX chunks of the candidates */
+  float* L; int64_t ld_l;                         /* [n_seg][ld_l], ld_l >= n_q */
+  void* ws;                                       /* spv_ot_segment_ws_bytes(n_q, n_seg, n_split) bytes */
+} spv_ot_seg_args;
+int spv_ot_segment_lse(const spv_ot_seg_args* a, void* stream);
+int32_t spv_ot_segment_splits(int32_t n_q, int32_t n_c);
+int64_t spv_ot_segment_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split);
+
 /* Segmented distance sums (spVIPES.latent_silhouette / integration_scores of the user API): for query row i of Q and every segment s
  * of the candidates C, which come ARRANGED BY SEGMENT, the fp64 sum of the Euclidean distances to the segment's rows; nothing of size
  * n_q x n_c stored.

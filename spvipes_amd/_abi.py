@@ -293,6 +293,16 @@ class SpvOtArgs(C.Structure):
                 ("L", C.c_void_p), ("idx", C.c_void_p), ("val", C.c_void_p), ("ld_out", C.c_int64), ("mass", C.c_void_p), ("ws", C.c_void_p)]
 
 
+OT_SEG_MAX = 256   # SPV_OT_SEG_MAX
+
+
+class SpvOtSegArgs(C.Structure):
+    """the arguments of spv_ot_segment_lse (include/spvipes_hip.h: spv_ot_seg_args)"""
+    _fields_ = [("Q", C.c_void_p), ("ld_q", C.c_int64), ("n_q", C.c_int32), ("C", C.c_void_p), ("ld_c", C.c_int64), ("n_c", C.c_int32),
+                ("D", C.c_int32), ("h", C.c_void_p), ("inv_eps", C.c_float), ("seg_ptr", C.c_void_p), ("n_seg", C.c_int32), ("n_split", C.c_int32),
+                ("L", C.c_void_p), ("ld_l", C.c_int64), ("ws", C.c_void_p)]
+
+
 SIL_SEG_MAX = 256   # SPV_SILHOUETTE_SEG_MAX
 
 
@@ -391,6 +401,9 @@ _SIGNATURES = {
     "spv_ot_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "spv_ot_tile_q": (C.c_int32, []),
     "spv_ot_tile_c": (C.c_int32, []),
+    "spv_ot_segment_lse": (C.c_int, [C.POINTER(SpvOtSegArgs), C.c_void_p]),
+    "spv_ot_segment_splits": (C.c_int32, [C.c_int32, C.c_int32]),
+    "spv_ot_segment_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "spv_silhouette_sums": (C.c_int, [C.POINTER(SpvSilhouetteArgs), C.c_void_p]),
     "spv_silhouette_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_silhouette_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

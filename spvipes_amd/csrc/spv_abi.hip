@@ -14,6 +14,7 @@
 #include "spv_count_stats.h"
 #include "spv_knn.h"
 #include "spv_ot.h"
+#include "spv_ot_segments.h"
 #include "spv_silhouette.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
@@ -1068,7 +1069,7 @@ extern "C" int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
   return (int64_t)n_split * n_q * k * 8;
 }
 
-// ---- what the entry points of the pair scan share (spv_pair_scan.h): spv_knn here, spv_ot_softmin / spv_ot_topk and spv_silhouette_sums below
+// ---- what the entry points of the pair scan share (spv_pair_scan.h): spv_knn here, spv_ot_softmin / spv_ot_topk, spv_ot_segment_lse and spv_silhouette_sums below
 struct ScanPlan { int n_split, per; dim3 grid; };   // chunks (resolved), candidates per chunk, (query tiles, chunks)
 
 // What every one of them refuses about the two sides, D, n_split and ws, in `who`'s name; the chunks -- n_split, or splits(n_q, n_c) for
@@ -1190,6 +1191,36 @@ extern "C" int spv_ot_topk(const spv_ot_args* x, void* stream) {
   if (rc != SPV_OK || a.n_split == 1) return rc;
   hipLaunchKernelGGL(ot_topk_merge_kernel, dim3(p.grid.x), dim3(KNN_TQ), ot_topk_lds_bytes(0, a.k) - ot_tile_words(0) * 4, s, a);   // at most the 64 KiB a kernel gets unasked
   return launch_status("spv_ot_topk (merge pass)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// the plan's log mass between every query and every segment of the candidates (spv_ot_segments.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_ot_segment_splits(int32_t n_q, int32_t n_c) { return otseg_splits(n_q, n_c); }
+extern "C" int64_t spv_ot_segment_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split) { return otseg_ws_bytes(n_q, n_seg, n_split); }
+
+extern "C" int spv_ot_segment_lse(const spv_ot_seg_args* x, void* stream) {
+  ScanPlan p;
+  int rc = scan_check(x, "spv_ot_segment_lse", otseg_splits, p, [&](int n_split) {
+    if (!x->h) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: null h%s");
+    if (!x->seg_ptr) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: null seg_ptr%s");
+    if (!x->L) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: null L%s");
+    if (!(x->inv_eps > 0.f && x->inv_eps < INFINITY)) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: inv_eps must be a positive finite number%s");
+    if (x->n_seg < 1 || x->n_seg > OT_SEG_MAX) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: n_seg must lie in [1, 256]%s");
+    if (x->ld_l < x->n_q) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: ld_l < n_q%s");
+    if (x->ld_l > INT32_MAX || (int64_t)x->n_seg * x->ld_l > INT32_MAX) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: n_seg * ld_l exceeds 2^31 - 1%s");
+    if ((int64_t)n_split * x->n_seg * x->n_q > INT32_MAX) return fail(SPV_ERR_ARG, "spv_ot_segment_lse: the workspace (n_split * n_seg * n_q entries) exceeds 2^31 - 1%s");
+    return SPV_OK;
+  });
+  if (rc != SPV_OK) return rc;
+  const OtSegArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->h, x->inv_eps, x->seg_ptr, x->n_seg, p.n_split, p.per,
+                    x->L, (long)x->ld_l, (OtLse*)x->ws};
+  hipStream_t s = (hipStream_t)stream;
+  scan_dispatch(a.D, [&](auto dp) { constexpr int DP = decltype(dp)::value; hipLaunchKernelGGL((otseg_partial_kernel<DP>), p.grid, dim3(KNN_TQ), ot_softmin_lds_bytes(DP), s, a); });
+  rc = launch_status(p.n_split == 1 ? "spv_ot_segment_lse" : "spv_ot_segment_lse (partial pass)");
+  if (rc != SPV_OK || p.n_split == 1) return rc;
+  hipLaunchKernelGGL(otseg_merge_kernel, dim3(p.grid.x, (unsigned)a.n_seg), dim3(KNN_TQ), 0, s, a);
+  return launch_status("spv_ot_segment_lse (merge pass)");
 }
 
 // ---------------------------------------------------------------------------------------------

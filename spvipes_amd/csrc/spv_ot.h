@@ -103,8 +103,10 @@ constexpr int ot_tile_words(int DP) { return KNN_TC * DP + KNN_TC; }
 constexpr int ot_softmin_lds_bytes(int DP) { return ot_tile_words(DP) * 4; }
 constexpr int ot_topk_lds_bytes(int DP, int k) { return ot_tile_words(DP) * 4 + (k + KNN_SCAN - 1) / KNN_SCAN * KNN_SCAN * KNN_TQ * 8; }
 
-// pair_scan's staging step: the h of candidates [j0, j0 + n) behind the tile, -inf from n on (such a row's t is never finite)
-__device__ __forceinline__ void ot_stage_h(const OtArgs& a, float* th, int j0, int n) {
+// pair_scan's staging step: the h of candidates [j0, j0 + n) behind the tile, -inf from n on (such a row's t is never finite).
+// `a`: any argument struct with the field h (OtArgs here, OtSegArgs of spv_ot_segments.h)
+template <typename Args>
+__device__ __forceinline__ void ot_stage_h(const Args& a, float* th, int j0, int n) {
   for (int r = threadIdx.x; r < KNN_TC; r += KNN_TQ) th[r] = r < n ? a.h[j0 + r] : -INFINITY;
 }
 

@@ -1168,3 +1168,213 @@ def silhouette_query_blocks(n: int, row_bytes: int, cap_bytes: int):
     within ``cap_bytes``; at least one cell per block"""
     rows = max(1, int(cap_bytes) // max(1, int(row_bytes)))
     return [(b, min(b + rows, int(n))) for b in range(0, int(n), rows)]
+
+
+# ---- cluster matching across the two groups from a transport plan (model.match_transport_clusters): k-means seeding, the entropy
+# criterion that chooses a clustering, the block scores and the Hungarian matching that names the clusters -- pure numpy / scipy ------
+def kmeans_pp_init(X, K: int, seed: int) -> np.ndarray:
+    """k-means++ seeding on the host in fp64 -> ``K`` DISTINCT rows of ``X`` [n, D] (in X's dtype), a function of (X, K, seed) alone.
+    The first row is drawn uniformly, every further one with probability proportional to its squared distance to the nearest row
+    chosen so far: a row equal to a chosen one has probability 0.  Fewer than K distinct rows: ValueError."""
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[0] < 1:
+        raise ValueError(f"kmeans_pp_init: X must be an array [n >= 1, D], got shape {X.shape}")
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= X.shape[0]:
+        raise ValueError(f"kmeans_pp_init: K must be an integer in [1, n = {X.shape[0]}], got {K!r}")
+    rng = np.random.default_rng(int(seed))
+    X64 = X.astype(np.float64)
+    chosen = [int(rng.integers(X.shape[0]))]
+    d2 = ((X64 - X64[chosen[0]]) ** 2).sum(1)
+    for _ in range(int(K) - 1):
+        cum = np.cumsum(d2)
+        if not cum[-1] > 0:
+            raise ValueError(f"kmeans_pp_init: X holds fewer than K = {K} distinct rows")
+        pick = min(int(np.searchsorted(cum, rng.random() * cum[-1], side="right")), X.shape[0] - 1)
+        while d2[pick] == 0:   # the draw landed on the end of the cumulative sum's range: the last row with weight
+            pick -= 1
+        chosen.append(pick)
+        d2 = np.minimum(d2, ((X64 - X64[pick]) ** 2).sum(1))
+    return X[np.array(chosen)].copy()
+
+
+def kmeans_update(X64: np.ndarray, labels: np.ndarray, d2: np.ndarray, K: int) -> np.ndarray:
+    """The centroid step of ``cluster_ops.kmeans`` -> fp32 [K, D]: per cluster the fp64 sum of its cells' rows in ascending cell order
+    (``np.bincount`` with weights), divided by the count, rounded to fp32.  A cluster without a cell takes the ROW of the cell with the
+    largest current squared distance ``d2`` (the smaller index on ties); several such clusters, in ascending order, take the largest,
+    the next largest, ...: a cell serves once.  The cell stays in its old cluster's mean; the next assignment moves it."""
+    counts = np.bincount(labels, minlength=K)
+    sums = np.stack([np.bincount(labels, weights=X64[:, t], minlength=K) for t in range(X64.shape[1])], axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cent = (sums / counts[:, None]).astype(np.float32)
+    left = np.asarray(d2, dtype=np.float64).copy()
+    for c in np.flatnonzero(counts == 0):
+        cell = int(np.argmax(left))
+        cent[c] = X64[cell].astype(np.float32)
+        left[cell] = -np.inf
+    return cent
+
+
+def cluster_segments(labels, K: int):
+    """The arrangement of one group's cells by cluster the segment kernel's candidates need -> (perm int64 [n]: the cells in cluster
+    order, each cluster's cells in their given order (a stable sort); seg_ptr int32 [K + 1]; sizes int64 [K])"""
+    labels = np.asarray(labels).ravel().astype(np.int64)
+    K = int(K)
+    if not 1 <= K <= _abi.OT_SEG_MAX:
+        raise ValueError(f"the number of clusters must lie in [1, {_abi.OT_SEG_MAX}], got {K}")
+    if labels.size and (labels.min() < 0 or labels.max() >= K):
+        raise ValueError(f"cluster labels must lie in [0, K = {K})")
+    sizes = np.bincount(labels, minlength=K).astype(np.int64)
+    return np.argsort(labels, kind="stable").astype(np.int64), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), sizes
+
+
+def cluster_entropy_score(logT) -> float:
+    """The reference's criterion for a clustering of one group (process_transport_plan, model/spvipes.py:55-67) from the LOG masses
+    ``logT`` [K, n_other] (log of the plan's mass between cluster c and cell i of the other group): every cluster's row normalised over
+    the other group's cells, its natural-log entropy, and MINUS the mean over the clusters -- higher is better.  All in fp64 through
+    the row's maximum, so nothing underflows: H = log Z - sum_i p_i (l_i - m) / Z with p_i = exp(l_i - m), Z = sum_i p_i.  A cluster
+    without any mass (every entry -inf; the reference divides 0 by 0 there) counts as the uniform distribution, ln(n_other): the least
+    informative a cluster can be, so a clustering gains nothing from having one."""
+    logT = np.asarray(logT, dtype=np.float64)
+    if logT.ndim != 2 or logT.shape[0] < 1 or logT.shape[1] < 1 or np.isnan(logT).any() or np.isposinf(logT).any():
+        raise ValueError("cluster_entropy_score: logT must be an array [K >= 1, n >= 1] of finite values or -inf")
+    m = logT.max(1)
+    live = np.isfinite(m)
+    H = np.full(logT.shape[0], np.log(logT.shape[1]))
+    if live.any():
+        d = logT[live] - m[live, None]   # <= 0, -inf where there is no mass
+        p = np.exp(d)
+        Z = p.sum(1)
+        H[live] = np.log(Z) - np.where(p > 0, p * np.where(p > 0, d, 0.0), 0.0).sum(1) / Z
+    return float(-H.mean())
+
+
+def cluster_pair_scores(logT1, labels0, sizes1, K0: Optional[int] = None):
+    """The plan's mass between the clusters of the two groups -> (M fp64 [K0, K1], score fp64 [K0, K1]).  ``logT1`` [K1, n0]: the log
+    mass between cluster c1 of group 1 and cell i of group 0; ``labels0`` [n0]: the cells' clusters in group 0; ``sizes1`` [K1]: the
+    cells per cluster of group 1.  M[c0, c1] = the fp64 sum over the cells i of c0, in ascending order, of exp(logT1[c1, i]);
+    score = M / (n_c0 n_c1), the MEAN plan entry of the block (0 for a block with an empty side)."""
+    logT1 = np.asarray(logT1, dtype=np.float64)
+    labels0 = np.asarray(labels0).ravel().astype(np.int64)
+    sizes1 = np.asarray(sizes1).ravel().astype(np.int64)
+    if logT1.ndim != 2 or logT1.shape[1] != labels0.shape[0] or sizes1.shape[0] != logT1.shape[0]:
+        raise ValueError("cluster_pair_scores: logT1 must be [K1, n0] with one label per column and one size per row")
+    K0 = int(labels0.max()) + 1 if K0 is None else int(K0)
+    if labels0.size and (labels0.min() < 0 or labels0.max() >= K0):
+        raise ValueError(f"cluster_pair_scores: labels0 must lie in [0, K0 = {K0})")
+    T = np.exp(logT1)
+    M = np.stack([np.bincount(labels0, weights=T[c1], minlength=K0) for c1 in range(T.shape[0])], axis=1)
+    cells = np.bincount(labels0, minlength=K0)[:, None] * sizes1[None, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return M, np.where(cells > 0, M / cells, 0.0)
+
+
+def match_cluster_labels(score) -> dict:
+    """Names for the clusters of both groups from the block scores ``score`` [K0, K1] (higher = more plan mass per pair of cells):
+    ``scipy.optimize.linear_sum_assignment(-score)``, the matched pairs named ``Cluster_0 ..`` in ``row_ind`` order (model/spvipes.py
+    :126-135), then every unmatched cluster -- there are |K0 - K1| -- its OWN further ``Cluster_m``, ascending in (group, cluster)
+    order.  -> {"names": ([K0 names], [K1 names]), "row_ind", "col_ind"}.  Deterministic: a function of ``score`` alone."""
+    from scipy.optimize import linear_sum_assignment
+
+    score = np.asarray(score, dtype=np.float64)
+    if score.ndim != 2 or score.shape[0] < 1 or score.shape[1] < 1 or not np.isfinite(score).all():
+        raise ValueError("match_cluster_labels: score must be a finite array [K0 >= 1, K1 >= 1]")
+    row_ind, col_ind = linear_sum_assignment(-score)
+    names = ([None] * score.shape[0], [None] * score.shape[1])
+    for m, (r, c) in enumerate(zip(row_ind, col_ind)):
+        names[0][int(r)] = names[1][int(c)] = f"Cluster_{m}"
+    m = len(row_ind)
+    for g in range(2):
+        for c in range(len(names[g])):
+            if names[g][c] is None:
+                names[g][c] = f"Cluster_{m}"
+                m += 1
+    return {"names": names, "row_ind": np.asarray(row_ind, dtype=np.int64), "col_ind": np.asarray(col_ind, dtype=np.int64)}
+
+
+def cluster_tables_from_matrix(plan, labels0, K0: int, labels1, K1: int):
+    """The two tables of log masses from a plain matrix plan [n0, n1] (dense array or scipy sparse), on the host in fp64 by products
+    with one-hot cluster matrices -> (logT0 [K0, n1]: cluster of group 0 x cell of group 1; logT1 [K1, n0]: cluster of group 1 x cell
+    of group 0); a zero mass becomes -inf.  NaN entries count as 0, as the reference's ``nan_to_num`` (:44)."""
+    import scipy.sparse as sp
+
+    labels0, labels1 = np.asarray(labels0).ravel().astype(np.int64), np.asarray(labels1).ravel().astype(np.int64)
+    n0, n1 = labels0.shape[0], labels1.shape[0]
+    if tuple(plan.shape) != (n0, n1):
+        raise ValueError(f"the plan must be [n0, n1] = [{n0}, {n1}], got {tuple(plan.shape)}")
+    one0 = sp.csr_matrix((np.ones(n0), (labels0, np.arange(n0))), shape=(int(K0), n0))   # [K0, n0]
+    one1 = sp.csr_matrix((np.ones(n1), (np.arange(n1), labels1)), shape=(n1, int(K1)))   # [n1, K1]
+    if sp.issparse(plan):
+        P = plan.astype(np.float64).tocsr()
+        P.data = np.nan_to_num(P.data, nan=0.0)
+        T0, T1 = np.asarray((one0 @ P).todense()), np.asarray((P @ one1).todense()).T
+    else:
+        P = np.nan_to_num(np.asarray(plan, dtype=np.float64), nan=0.0)
+        T0, T1 = np.asarray(one0 @ P), np.asarray((one1.T @ P.T))
+    if (T0 < 0).any() or (T1 < 0).any() or not np.isfinite(T0).all():
+        raise ValueError("the plan must hold finite non-negative entries")
+    with np.errstate(divide="ignore"):
+        return np.log(T0), np.log(T1)
+
+
+@dataclass
+class ClusterMatching:
+    """What ``match_transport_clusters`` returns and, as a dict without ``labels``, writes to ``uns["cluster_matching"]``:
+    ``n_clusters`` (K0, K1) chosen; ``candidates``: the K swept, or None; ``criterion``: per group {K: cluster_entropy_score};
+    ``mass`` / ``score`` fp64 [K0, K1]: the plan's mass per block and the mean entry per block; ``row_ind`` / ``col_ind``: the
+    assignment (cluster row_ind[m] of group 0 with cluster col_ind[m] of group 1 is ``Cluster_m``); ``names``: per group the new name
+    of every cluster; ``cluster_values``: per group what a cluster is called in ``group_cluster_labels`` (k-means index or the
+    ``cluster_key`` value); ``labels``: per group the cells' cluster index int64 [n_g]."""
+    n_clusters: tuple
+    candidates: Optional[tuple]
+    criterion: list
+    mass: np.ndarray
+    score: np.ndarray
+    row_ind: np.ndarray
+    col_ind: np.ndarray
+    names: tuple
+    labels: list
+    cluster_values: list
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k in ("n_clusters", "candidates", "criterion", "mass", "score", "row_ind", "col_ind", "names", "cluster_values")}
+
+
+def check_match_clusters_args(adata, rep, plan, n_clusters, cluster_key, n_init, seed):
+    """The refusals of ``match_transport_clusters`` ahead of any device work and of anything written -> (obs_idx, candidates: a tuple
+    of K per group or None with ``cluster_key``, swept: whether the criterion chooses).  ``rep``: the representation [n_obs, D] or
+    None (not needed with a matrix plan and ``cluster_key``)."""
+    if "groups_obs_indices" not in adata.uns:
+        raise ValueError("adata.uns['groups_obs_indices'] missing: build the AnnData with prepare_adatas (or the same schema)")
+    obs_idx = [np.asarray(v) for v in adata.uns["groups_obs_indices"]]
+    if len(obs_idx) != 2:
+        raise ValueError("cluster matching couples exactly two groups")
+    if any(len(v) < 1 for v in obs_idx):
+        raise ValueError("both groups need at least one cell")
+    if plan is not None and tuple(getattr(plan, "shape", ())) != (len(obs_idx[0]), len(obs_idx[1])):
+        raise ValueError(f"plan must be a TransportPlan or a matrix [n0, n1] = [{len(obs_idx[0])}, {len(obs_idx[1])}], "
+                         f"got shape {tuple(getattr(plan, 'shape', ()))}")
+    for name, v in (("n_init", n_init), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or (name == "n_init" and int(v) < 1) or int(v) < 0:
+            raise ValueError(f"{name} must be a {'positive' if name == 'n_init' else 'non-negative'} integer, got {v!r}")
+    if cluster_key is not None:
+        if cluster_key not in adata.obs:
+            raise KeyError(f"cluster_key '{cluster_key}' not found in adata.obs")
+        col = np.asarray(adata.obs[cluster_key])
+        for g, rows in enumerate(obs_idx):
+            if len(np.unique(col[rows])) > _abi.OT_SEG_MAX:
+                raise ValueError(f"group {g}: cluster_key holds more than {_abi.OT_SEG_MAX} clusters")
+        return obs_idx, None, False
+    if rep is None:
+        raise ValueError("use_rep is needed unless cluster_key names the clusters")
+    swept = not isinstance(n_clusters, (int, np.integer))
+    try:
+        cand = tuple(n_clusters) if swept else (n_clusters,)
+    except TypeError:
+        cand = ()
+    if not cand or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= int(c) <= _abi.OT_SEG_MAX for c in cand):
+        raise ValueError(f"n_clusters must be an integer or a non-empty sequence of integers in [1, {_abi.OT_SEG_MAX}], got {n_clusters!r}")
+    cand = tuple(int(c) for c in cand)
+    for g, rows in enumerate(obs_idx):
+        if not any(c <= len(rows) for c in cand):
+            raise ValueError(f"group {g}: every candidate of n_clusters exceeds its {len(rows)} cells")
+    return obs_idx, cand, swept

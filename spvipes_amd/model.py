@@ -9,8 +9,9 @@ this build: the AnnData object is duck-typed (``.X`` dense array or scipy.sparse
 ``uns["groups_lengths" | "groups_var_indices" | "groups_obs_indices" | ...]``, ``obs["groups"]``,
 ``obs["indices"]`` (data/prepare_adatas.py:97-132).
 
-What stays out: ``process_transport_plan`` (Leiden + Hungarian preprocessing, needs
-scanpy) -- cluster matching expects ``obs["processed_transport_labels"]`` to be present already.
+``process_transport_plan`` (:26-162, scanpy Leiden + Hungarian matching) has its counterpart in ``match_transport_clusters``:
+k-means (or the user's own clusters) in place of Leiden, the plan's cluster masses from a fused kernel, the same matching; it writes
+the ``obs["processed_transport_labels"]`` that cluster matching reads.
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from . import _abi
 from .data import (MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, check_transport_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
                    csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
                    latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions,
+                   ClusterMatching, check_match_clusters_args, cluster_entropy_score, cluster_pair_scores, cluster_tables_from_matrix, match_cluster_labels,
                    SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table)
 from .module import spVIPESmodule
 from .plan import SparsePlan
@@ -128,8 +130,8 @@ class spVIPES:
             adata.uns["transport_plan"] = adata.uns[transport_plan_key]
             if match_clusters and "processed_transport_labels" not in adata.obs:
                 raise NotImplementedError(
-                    "match_clusters=True needs obs['processed_transport_labels'] (the reference derives it with "
-                    "scanpy Leiden + Hungarian matching in process_transport_plan, which is outside this build)")
+                    "match_clusters=True needs obs['processed_transport_labels']: run spVIPES.match_transport_clusters(adata, ...) "
+                    "first (the counterpart of the reference's process_transport_plan), or write the column yourself")
             if "indices" not in adata.obs:
                 raise ValueError("'indices' must be present in adata.obs when using a transport plan")
         if label_key is not None and label_key not in adata.obs:
@@ -175,6 +177,102 @@ class spVIPES:
             for rows in obs_idx:
                 pos[rows] = np.arange(len(rows), dtype=np.int32)
             adata.obs["indices"] = pos
+        return result
+
+    @classmethod
+    def match_transport_clusters(cls, adata, use_rep=None, plan=None, n_clusters=(4, 6, 8, 12, 16, 24, 32), cluster_key: Optional[str] = None,
+                                 n_init: int = 4, seed: int = 0, device: Optional[str] = None):
+        """The labels the cluster-matched PoE mode reads (``setup_anndata(..., match_clusters=True)``), derived as the reference's
+        ``process_transport_plan`` derives them: clusters per group, chosen by the plan's entropy criterion, matched across the groups
+        by the Hungarian algorithm on the plan's mass between them.  No scanpy and no n0 x n1 matrix.
+        ``use_rep``: a key of ``adata.obsm`` or an array [n_obs, D], 1 <= D <= 64, as ``compute_transport_plan``.
+        ``plan``: the ``TransportPlan`` of ``compute_transport_plan`` -- the masses then come from its Sinkhorn potentials, i.e. from the
+        UNTRUNCATED plan, by the fused kernel (``ot_ops.ot_segment_lse``); the potentials mean something only on the representation
+        they were computed on, so pass the same ``use_rep`` (only the two row counts can be checked) --, or a plain matrix [n0, n1]
+        (dense array or scipy sparse), whose cluster sums are taken on the host in fp64, or None: ``compute_transport_plan(adata,
+        use_rep)`` runs first and writes the plan as usual.
+        ``n_clusters``: an int fixes K for both groups; a sequence is swept per group (candidates above the group's size are dropped)
+        and each group takes the K with the highest ``data.cluster_entropy_score``, the first on ties.  Clusters are k-means on
+        ``use_rep`` (``cluster_ops.kmeans_best`` with ``n_init`` seedings from ``seed``).  ``cluster_key``: an ``obs`` column with the
+        user's own per-cell clusters (Leiden run elsewhere, say) instead: no k-means, no sweep; a cluster is (group, value).  With a
+        matrix plan as well no device is needed, nor ``use_rep``.
+        Clusters are matched on score = block mass / (cells x cells), the MEAN plan entry of a block (the reference takes the median).
+        Writes ``obs["group_cluster_labels"]`` ("<group index>_<cluster>"), ``obs["processed_transport_labels"]`` ("Cluster_m": matched
+        pairs share a name, in ``row_ind`` order; every unmatched cluster gets its own) and ``uns["cluster_matching"]``: a dict with
+        ``n_clusters`` (K0, K1), ``candidates``, ``criterion`` (per group {K: score}), ``mass`` and ``score`` [K0, K1], ``row_ind`` /
+        ``col_ind`` and ``names`` (per group the clusters' new names).  Returns a ``data.ClusterMatching`` with the same contents and
+        the per-group labels.  Argument faults are refused before any device work and before anything is written."""
+        rep = None
+        if use_rep is not None:
+            if isinstance(use_rep, str):
+                obsm = getattr(adata, "obsm", None)
+                if obsm is None or use_rep not in obsm:
+                    raise KeyError(f"use_rep '{use_rep}' not found in adata.obsm")
+                rep = np.asarray(obsm[use_rep])
+            else:
+                rep = np.asarray(use_rep)
+            if rep.ndim == 2 and rep.shape[0] != adata.n_obs:
+                raise ValueError(f"use_rep must have one row per cell ({adata.n_obs}), got {rep.shape[0]}")
+        obs_idx, cand, swept = check_match_clusters_args(adata, rep, plan, n_clusters, cluster_key, n_init, seed)
+        matrix_plan = plan is not None and not hasattr(plan, "sinkhorn")
+        Xd = None
+        if not (matrix_plan and cluster_key is not None):
+            if rep is None:
+                raise ValueError("use_rep is needed: the plan's potentials are read on the representation they were computed on")
+            X0, X1, _ = check_transport_args(rep, obs_idx, 1)
+            if not torch.cuda.is_available():
+                raise _abi.SpvError("spvipes_amd needs an MI355X: there is no CPU fallback for the hot path")
+            dev = torch.device(device or "cuda:0")
+            Xd = [torch.from_numpy(X0).to(dev), torch.from_numpy(X1).to(dev)]
+            if plan is None:
+                plan = cls.compute_transport_plan(adata, rep, device=device)
+
+        def table(g, labels, K):
+            """log mass [K, n_other] between the clusters of group g and the cells of the other group"""
+            from .cluster_ops import cluster_transport_log_mass
+            return cluster_transport_log_mass(plan.sinkhorn, Xd[1 - g], Xd[g], labels, 1 - g, K)
+
+        labels, values, tables, criterion = [None, None], [None, None], [None, None], [{}, {}]
+        if cluster_key is not None:
+            col = np.asarray(adata.obs[cluster_key])
+            for g in range(2):
+                values[g], labels[g] = np.unique(col[obs_idx[g]], return_inverse=True)
+                labels[g] = labels[g].astype(np.int64)
+            if matrix_plan:
+                tables = list(cluster_tables_from_matrix(plan, labels[0], len(values[0]), labels[1], len(values[1])))
+            else:
+                tables = [table(g, labels[g], len(values[g])) for g in range(2)]
+            for g in range(2):
+                criterion[g][len(values[g])] = cluster_entropy_score(tables[g])
+        else:
+            from .cluster_ops import kmeans_best
+            for g in range(2):
+                best = None
+                for K in (c for c in cand if c <= len(obs_idx[g])):
+                    lab = kmeans_best(Xd[g], K, n_init, seed).labels
+                    if matrix_plan:
+                        other = np.zeros(len(obs_idx[1 - g]), dtype=np.int64)
+                        tab = cluster_tables_from_matrix(plan, *((lab, K, other, 1) if g == 0 else (other, 1, lab, K)))[g]
+                    else:
+                        tab = table(g, lab, K)
+                    criterion[g][K] = cluster_entropy_score(tab)
+                    if best is None or criterion[g][K] > criterion[g][best]:
+                        best, labels[g], tables[g] = K, lab, tab
+                values[g] = np.arange(best)
+        K0, K1 = len(values[0]), len(values[1])
+        mass, score = cluster_pair_scores(tables[1], labels[0], np.bincount(labels[1], minlength=K1), K0)
+        match = match_cluster_labels(score)
+        group_cluster = np.full(adata.n_obs, "", dtype=object)
+        processed = np.full(adata.n_obs, "", dtype=object)
+        for g in range(2):
+            group_cluster[obs_idx[g]] = np.array([f"{g}_{v}" for v in values[g]], dtype=object)[labels[g]]
+            processed[obs_idx[g]] = np.array(match["names"][g], dtype=object)[labels[g]]
+        result = ClusterMatching(n_clusters=(K0, K1), candidates=cand if swept else None, criterion=criterion, mass=mass, score=score,
+                                 row_ind=match["row_ind"], col_ind=match["col_ind"], names=match["names"], labels=labels,
+                                 cluster_values=[list(values[0]), list(values[1])])
+        adata.obs["group_cluster_labels"] = group_cluster.astype(str)
+        adata.obs["processed_transport_labels"] = processed.astype(str)
+        adata.uns["cluster_matching"] = result.as_dict()
         return result
 
     # ------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """Entropic optimal transport on the device: the fused kernels spv_ot_softmin / spv_ot_topk (csrc/spv_ot.h; include/spvipes_hip.h
 states the contract), the log-domain Sinkhorn driver on top of them and the sparse plan it ends in.  ``spVIPES.compute_transport_plan``
-runs it on a common low-dimensional representation of the two groups; nothing of size n0 x n1 is ever stored."""
+runs it on a common low-dimensional representation of the two groups; nothing of size n0 x n1 is ever stored.  ``ot_segment_lse``
+(csrc/spv_ot_segments.h) gives the untruncated plan's log mass per (cell, segment of the other group's cells) from the potentials:
+what ``cluster_ops`` / ``spVIPES.match_transport_clusters`` read."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import OT_DMAX, OT_KMAX, OT_SPLIT_MAX, SpvOtArgs, ptr, stream_ptr   # the limits: part of this module's interface
+from ._abi import OT_DMAX, OT_KMAX, OT_SEG_MAX, OT_SPLIT_MAX, SpvOtArgs, SpvOtSegArgs, ptr, stream_ptr   # the limits: part of this module's interface
 from ._scan_ops import _fill_sides, _k, _n_split, _out_pair, _rows, _sides, _workspace
 from .data import plan_union_csr
 
@@ -100,6 +102,59 @@ def ot_topk(X: torch.Tensor, Y: torch.Tensor, h: torch.Tensor, r: torch.Tensor, 
     a.mass, a.ws = ptr(mass), ptr(ws)
     _abi.call("spv_ot_topk", C.byref(a), stream_ptr())
     return idx[:, :k], val[:, :k], mass[:n_q]
+
+
+def ot_segment_splits(n_q: int, n_c: int) -> int:
+    """Chunks of the candidates spv_ot_segment_lse uses for this shape when ``n_split`` is 0: a pure function of the shapes"""
+    return int(_abi.load().spv_ot_segment_splits(int(n_q), int(n_c)))
+
+
+def ot_segment_ws_bytes(n_q: int, n_seg: int, n_split: int) -> int:
+    """Bytes of workspace for ``n_split`` chunks (the resolved number, not 0): 0 for one chunk"""
+    return int(_abi.load().spv_ot_segment_ws_bytes(int(n_q), int(n_seg), int(n_split)))
+
+
+def ot_segment_lse(X: torch.Tensor, Y: torch.Tensor, h: torch.Tensor, seg_ptr: torch.Tensor, inv_eps: float, n_split: int = 0,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """For every row of ``X`` and every segment of the rows of ``Y``: L[i, s] = log sum_{j in segment s} exp(t_ij) with ``ot_softmin``'s
+    t (the same bits) -> fp32 device tensor [n_q, n_seg].  The result is the TRANSPOSED VIEW of a segment-major buffer [n_seg, n_q] (the
+    kernel's layout), so ``result[:, s]`` is contiguous and ``result[i]`` is strided.  With h = psi + log b of a Sinkhorn result,
+    ``exp(L[i, s] + phi_i + log a_i)`` is the mass the untruncated plan puts between cell i and segment s.
+    A t that is not finite adds nothing; a segment without a contributing candidate (an empty one included) gives -inf.
+    ``X`` [n_q >= 1, D], ``Y`` [n_c >= 0, D], ``h`` [n_c], ``inv_eps``: as ``ot_softmin``.  ``seg_ptr``: contiguous int32 DEVICE tensor
+    [n_seg + 1], 1 <= n_seg <= OT_SEG_MAX, ascending from 0 to n_c (segment s is rows seg_ptr[s] .. seg_ptr[s + 1] - 1 of ``Y``).  It is
+    not read back for checking: other contents give unspecified values.
+    ``n_split``: chunks of the candidates, 0 = ``ot_segment_splits(n_q, n_c)``.  For a fixed value two calls agree bit for bit and a row
+    of the result does not depend on the other rows of ``X``; different values agree within rounding.  With one segment and the same
+    explicit ``n_split`` the column equals ``ot_softmin``'s result bit for bit.
+    ``out``: an fp32 device tensor [n_seg, >= n_q] with unit column stride (segment-major, as stored); the transposed view of its first
+    n_q columns is returned and nothing else is written."""
+    op = "ot_segment_lse"
+    dev, n_q, n_c, D = _sides(op, X, Y, ("X", "Y"))
+    _vector(h, n_c, dev, "h")
+    inv_eps = float(inv_eps)
+    if not (0.0 < inv_eps < math.inf) or not (0.0 < float(np.float32(inv_eps)) < math.inf):
+        raise ValueError(f"{op}: inv_eps must be a positive finite number in fp32, got {inv_eps!r}")
+    n_split = _n_split(op, n_split)
+    if (not isinstance(seg_ptr, torch.Tensor) or not seg_ptr.is_cuda or seg_ptr.device != dev or seg_ptr.dtype != torch.int32 or seg_ptr.dim() != 1
+            or not seg_ptr.is_contiguous()):
+        raise _abi.SpvError(f"{op}: seg_ptr must be a contiguous int32 device tensor [n_seg + 1]")
+    n_seg = int(seg_ptr.numel()) - 1
+    if not 1 <= n_seg <= OT_SEG_MAX:
+        raise ValueError(f"{op}: the number of segments must lie in [1, {OT_SEG_MAX}], got {n_seg}")
+    if out is None:
+        out = torch.empty((n_seg, n_q), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev or out.dtype != torch.float32 or out.dim() != 2
+          or out.shape[0] != n_seg or out.shape[1] < n_q or (out.shape[1] > 1 and out.stride(1) != 1) or (n_seg > 1 and out.stride(0) < n_q)):
+        raise _abi.SpvError(f"{op}: out must be an fp32 device tensor [{n_seg}, >= {n_q}] with unit column stride")
+    ws = _workspace(ot_segment_ws_bytes(n_q, n_seg, n_split or ot_segment_splits(n_q, n_c)), dev)
+    a = SpvOtSegArgs()
+    _fill_sides(a, X, Y)
+    a.h, a.inv_eps = (ptr(h) if n_c else ptr(X)), inv_eps
+    a.seg_ptr, a.n_seg, a.n_split = ptr(seg_ptr), n_seg, n_split
+    a.L, a.ld_l, a.ws = ptr(out), (out.stride(0) if n_seg > 1 else max(n_q, int(out.shape[1]))), ptr(ws)
+    _abi.call("spv_ot_segment_lse", C.byref(a), stream_ptr())
+    return out[:, :n_q].t()
 
 
 def mean_sq_cost(X0: torch.Tensor, X1: torch.Tensor) -> float:
