@@ -744,12 +744,22 @@ typedef struct spv_adam_image {
   float scale; int32_t _pad;
 } spv_adam_image;
 
+/* A range [begin, begin + count) of the flat buffer that spv_adam_step_images leaves alone: p, m, v (and images) there are neither
+ * read nor written, because the parameters in it have already taken this step (spv_reduce_slabs_adam).  begin is a multiple of 4
+ * (parameters start on 4-element boundaries) and so is count, unless the range ends the buffer. */
+#define SPV_ADAM_MAX_SKIP 8
+typedef struct spv_adam_range { int64_t begin, count; } spv_adam_range;
+
 /* spv_adam_step that also rewrites the bf16 images of the matrices it updates (the packed operands spv_pack_bf16 would otherwise
  * rebuild at the start of the next step: fc1 weights, [W_m | b_m]).  Image padding (rows / columns outside the matrix) is not
- * touched: the image must have been produced by spv_pack_bf16 once.  n_images may be 0. */
+ * touched: the image must have been produced by spv_pack_bf16 once.  n_images may be 0.
+ * skip: n_skip <= SPV_ADAM_MAX_SKIP ranges in ascending order, disjoint (n_skip may be 0: every element is updated).  The grid is
+ * sized for, and walks, only the elements outside them: a skipped range costs no memory traffic.  An image descriptor that lies in a
+ * skipped range is simply never reached. */
 int spv_adam_step_images(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                          float weight_decay, float bc1, float bc2, float grad_scale, const spv_adam_image* images, int32_t n_images,
-                         int64_t* step_counter, const int64_t* t_dev, double beta1_d, double beta2_d, void* stream);
+                         const spv_adam_range* skip, int32_t n_skip, int64_t* step_counter, const int64_t* t_dev, double beta1_d,
+                         double beta2_d, void* stream);
 /* step_counter (nullable): device int64 incremented by one per call (the counter spv_randn / the dropout masks are keyed by).
  * t_dev (nullable): device int64 = optimiser steps ALREADY taken; when given, bc1 / bc2 are ignored and the bias corrections
  * 1 - beta^(t_dev + 1) are formed on the device from beta1_d / beta2_d (double, as torch.optim.Adam forms them on the host): no
@@ -1076,6 +1086,21 @@ typedef struct spv_reduce_prob {
 } spv_reduce_prob;
 typedef struct spv_reduce_batch { spv_reduce_prob p[SPV_MAXR]; int32_t nprob; } spv_reduce_batch;
 int spv_reduce_slabs(const spv_reduce_batch* b, void* stream);
+
+/* Slab sum + Adam in one launch, for a gradient that nothing but the optimiser reads (the mixing head's d W_m / d b_m): per element
+ * of problem r (nslabs <= 8, no exp_scale, no accumulate, ld_dst == cols: the gradient slice is the parameter's own contiguous
+ * slice of the flat gradient buffer) g = alpha * (slabs in slab order) is stored to r.dst exactly as spv_reduce_slabs stores it, and
+ * p, m, v -- the parameter's slices of the flat value / moment buffers, rows * cols elements each -- take the step
+ * spv_adam_step_images would take with that g; arguments lr .. beta2_d as there.  img.dst != NULL: the updated value of element
+ * (r, c) also goes to img.dst[(r + row_off) * ld + c + col_off] in img.fmt (img.cols == cols, img.count == rows * cols; img.begin
+ * is not used).  Word for word the results of spv_reduce_slabs followed by spv_adam_step_images over the same elements.  The launch
+ * reads *t_dev and writes neither it nor a step counter: exclude the parameters from the step's spv_adam_step_images call (skip)
+ * and advance t_dev once, after that call. */
+#define SPV_MAXRA 8
+typedef struct spv_reduce_adam_prob { spv_reduce_prob r; float* p; float* m; float* v; spv_adam_image img; } spv_reduce_adam_prob;
+typedef struct spv_reduce_adam_batch { spv_reduce_adam_prob p[SPV_MAXRA]; int32_t nprob; } spv_reduce_adam_batch;
+int spv_reduce_slabs_adam(const spv_reduce_adam_batch* b, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          float bc1, float bc2, float grad_scale, const int64_t* t_dev, double beta1_d, double beta2_d, void* stream);
 
 /* Loss assembly (module/spVIPESmodule.py:870-872): rec_sum = sum_g sum_b w[b] * rec[g][b] and
  *   loss = rec_sum + (kl_weight / B) * sum_b sum_i kl[i][b]   (i < nkl <= 4 KL vectors of length B);

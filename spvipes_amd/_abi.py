@@ -162,6 +162,22 @@ class SpvAdamImage(C.Structure):
                 ("ld", C.c_int64), ("dst", C.c_void_p), ("scale", C.c_float), ("_pad", C.c_int32)]
 
 
+ADAM_MAX_SKIP = 8   # ranges of the flat buffer one spv_adam_step_images call can leave alone
+SPV_MAXRA = 8       # problems of one spv_reduce_slabs_adam launch
+
+
+class SpvAdamRange(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("count", C.c_int64)]
+
+
+class SpvReduceAdamProb(C.Structure):
+    _fields_ = [("r", SpvReduceProb), ("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("img", SpvAdamImage)]
+
+
+class SpvReduceAdamBatch(C.Structure):
+    _fields_ = [("p", SpvReduceAdamProb * SPV_MAXRA), ("nprob", C.c_int32)]
+
+
 class SpvPoeCompArgs(C.Structure):
     _fields_ = ([("ngroups", C.c_int32), ("n", C.c_int32), ("ncomp", C.c_int32), ("pad_", C.c_int32), ("B", C.c_int32 * SPV_POE_MAXG),
                  ("stats", C.c_void_p * SPV_POE_MAXG), ("ld", C.c_int64 * SPV_POE_MAXG), ("comp", C.c_void_p * SPV_POE_MAXG),
@@ -449,8 +465,10 @@ _SIGNATURES = {
     "spv_loss_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_adam_step_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                       C.c_void_p]),
+                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_double, C.c_double, C.c_void_p]),
+    "spv_reduce_slabs_adam": (C.c_int, [C.POINTER(SpvReduceAdamBatch), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "spv_gather_u32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "spv_randn": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "spv_counter_bump": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1355,26 +1355,20 @@ extern "C" int spv_dec_heads_bwd_grouped(const spv_dec_group* g, int32_t n, void
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, float gscale) {
   const long stride = (long)gridDim.x * blockDim.x * 4;
-  const float step = lr / bc1, isq = rsqrtf(bc2);
+  const AdamStep a = adam_prologue(lr, b1, b2, eps, wd, bc1, bc2, gscale, nullptr, 0.0, 0.0);
   for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
     if (i + 4 <= n) {
       f4v pp = *reinterpret_cast<f4v*>(p + i), gg = *reinterpret_cast<const f4v*>(g + i);
       f4v mm = *reinterpret_cast<f4v*>(m + i), vv = *reinterpret_cast<f4v*>(v + i);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float gr = gg[j] * gscale + wd * pp[j];
-        mm[j] = b1 * mm[j] + (1.f - b1) * gr;
-        vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;
-        pp[j] -= step * mm[j] / (sqrtf(vv[j]) * isq + eps);
+        float pj = pp[j], mj = mm[j], vj = vv[j];
+        adam_update(pj, gg[j], mj, vj, a);
+        pp[j] = pj; mm[j] = mj; vv[j] = vj;
       }
       *reinterpret_cast<f4v*>(p + i) = pp; *reinterpret_cast<f4v*>(m + i) = mm; *reinterpret_cast<f4v*>(v + i) = vv;
     } else {
-      for (long k = i; k < n; ++k) {
-        const float gr = g[k] * gscale + wd * p[k];
-        m[k] = b1 * m[k] + (1.f - b1) * gr;
-        v[k] = b2 * v[k] + (1.f - b2) * gr * gr;
-        p[k] -= step * m[k] / (sqrtf(v[k]) * isq + eps);
-      }
+      for (long k = i; k < n; ++k) adam_update(p[k], g[k], m[k], v[k], a);
     }
   }
 }
@@ -1448,44 +1442,37 @@ extern "C" int spv_randn(float* out, int64_t n, const int64_t* counter, uint64_t
 // mixing head's [W_m | b_m]): the step that follows then starts without its spv_pack_bf16 launches.  Same arithmetic as
 // adam_kernel; per 4-element chunk one range test per image (<= SPV_ADAM_MAX_IMAGES, all warp-uniform but at range borders).
 struct AdamImages { int n; spv_adam_image img[SPV_ADAM_MAX_IMAGES]; };
+// [begin, begin + count) ranges of the flat buffer the launch leaves alone (their parameters were updated where their gradient was
+// produced: spv_reduce_slabs_adam), ascending and disjoint, on 4-element boundaries.  The grid walks the n_kept elements that remain
+// and maps each 4-chunk to its place in the buffer: a skipped chunk costs neither a loop trip nor memory traffic.
+struct AdamSkips { int n; long begin[SPV_ADAM_MAX_SKIP], count[SPV_ADAM_MAX_SKIP]; };
 
 __global__ void adam_images_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                   long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, float gscale, AdamImages im,
-                                   long long* step_counter, const long long* t_dev, double b1d, double b2d) {
+                                   long n_kept, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, float gscale, AdamImages im,
+                                   AdamSkips sk, long long* step_counter, const long long* t_dev, double b1d, double b2d) {
   if (step_counter && blockIdx.x == 0 && threadIdx.x == 0) *step_counter += 1;   // (read by the NEXT step's spv_randn / dropout: stream order)
-  if (t_dev) {
-    // bias corrections 1 - beta^t from the DEVICE-resident count of completed steps (t = *t_dev + 1), in double like torch.optim.Adam's
-    // host arithmetic: the launch then carries no per-step host value and can sit inside the captured graph of the step.  Nobody
-    // writes *t_dev while this kernel runs (the caller advances it with spv_counter_bump afterwards).  beta^t by repeated squaring.
-    long long e = *t_dev + 1;
-    double r1 = 1.0, r2 = 1.0, x1 = b1d, x2 = b2d;
-    while (e > 0) { if (e & 1) { r1 *= x1; r2 *= x2; } x1 *= x1; x2 *= x2; e >>= 1; }
-    bc1 = (float)(1.0 - r1); bc2 = (float)(1.0 - r2);
-  }
+  const AdamStep a = adam_prologue(lr, b1, b2, eps, wd, bc1, bc2, gscale, t_dev, b1d, b2d);
   const long stride = (long)gridDim.x * blockDim.x * 4;
-  const float step = lr / bc1, isq = rsqrtf(bc2);
-  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+  for (long ik = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; ik < n_kept; ik += stride) {
     float out[4];
-    const int cnt = (i + 4 <= n) ? 4 : (int)(n - i);
+    const int cnt = (ik + 4 <= n_kept) ? 4 : (int)(n_kept - ik);
+    long i = ik;   // the chunk's offset in the buffer: past every skipped range that begins at or before it
+    for (int d = 0; d < sk.n; ++d) i += i >= sk.begin[d] ? sk.count[d] : 0;
     if (cnt == 4) {
       f4v pp = *reinterpret_cast<f4v*>(p + i), gg = *reinterpret_cast<const f4v*>(g + i);
       f4v mm = *reinterpret_cast<f4v*>(m + i), vv = *reinterpret_cast<f4v*>(v + i);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float gr = gg[j] * gscale + wd * pp[j];
-        mm[j] = b1 * mm[j] + (1.f - b1) * gr;
-        vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;
-        pp[j] -= step * mm[j] / (sqrtf(vv[j]) * isq + eps);
-        out[j] = pp[j];
+        float pj = pp[j], mj = mm[j], vj = vv[j];
+        adam_update(pj, gg[j], mj, vj, a);
+        pp[j] = pj; mm[j] = mj; vv[j] = vj;
+        out[j] = pj;
       }
       *reinterpret_cast<f4v*>(p + i) = pp; *reinterpret_cast<f4v*>(m + i) = mm; *reinterpret_cast<f4v*>(v + i) = vv;
     } else {
       for (int j = 0; j < cnt; ++j) {
         const long k = i + j;
-        const float gr = g[k] * gscale + wd * p[k];
-        m[k] = b1 * m[k] + (1.f - b1) * gr;
-        v[k] = b2 * v[k] + (1.f - b2) * gr * gr;
-        p[k] -= step * m[k] / (sqrtf(v[k]) * isq + eps);
+        adam_update(p[k], g[k], m[k], v[k], a);
         out[j] = p[k];
       }
     }
@@ -1493,30 +1480,25 @@ __global__ void adam_images_kernel(float* __restrict__ p, const float* __restric
       const spv_adam_image& q = im.img[d];
       const long k0 = i - q.begin;
       if (k0 + cnt <= 0 || k0 >= q.count) continue;
-      // (parameters start on 4-element boundaries of the flat buffer, so k0 >= 0 here; count need not be a multiple of 4)
-      const unsigned cols = (unsigned)q.cols;
-      unsigned r = (unsigned)k0 / cols, c = (unsigned)k0 - r * cols;
-      uint16_t* dst = q.dst + ((long)r + q.row_off) * q.ld + q.col_off;
-      const bool half = q.fmt == SPV_IMAGE_F16;   // (uniform per image: the fc1 weight images are f16 words of W * scale, spv_common.h)
-      if (cnt == 4 && k0 + 4 <= q.count && c + 4 <= cols && (((reinterpret_cast<uintptr_t>(dst + c)) & 7) == 0)) {
-        typedef __attribute__((ext_vector_type(4))) unsigned short us4;
-        *reinterpret_cast<us4*>(dst + c) = half ? us4{f2h(out[0] * q.scale), f2h(out[1] * q.scale), f2h(out[2] * q.scale), f2h(out[3] * q.scale)}
-                                                : us4{f2bf(out[0]), f2bf(out[1]), f2bf(out[2]), f2bf(out[3])};
-      } else {
-        for (int j = 0; j < cnt && k0 + j < q.count; ++j) {
-          dst[c] = half ? f2h(out[j] * q.scale) : f2bf(out[j]);
-          if (++c == cols) { c = 0; dst += q.ld; }
-        }
-      }
+      // (parameters start on 4-element boundaries of the flat buffer, so k0 >= 0 here)
+      adam_image_store(q, k0, cnt, out);
       break;   // ranges are disjoint
     }
   }
 }
 
+static bool adam_image_ok(const spv_adam_image& q) {   // (everything but the image's place in a flat buffer)
+  return q.dst && q.count > 0 && q.cols > 0 && q.ld >= q.cols + q.col_off && q.row_off >= 0 && q.col_off >= 0 && q.count < (1L << 31) &&
+         (q.fmt == SPV_IMAGE_BF16 || (q.fmt == SPV_IMAGE_F16 && q.scale > 0.f));
+}
+
 extern "C" int spv_adam_step_images(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                                     float weight_decay, float bc1, float bc2, float grad_scale, const spv_adam_image* images, int32_t n_images,
-                                    int64_t* step_counter, const int64_t* t_dev, double beta1_d, double beta2_d, void* stream) {
-  if (!p || !g || !m || !v || n < 0 || n_images < 0 || n_images > SPV_ADAM_MAX_IMAGES || (n_images && !images)) return fail(SPV_ERR_ARG, "spv_adam_step_images: bad arguments%s");
+                                    const spv_adam_range* skip, int32_t n_skip, int64_t* step_counter, const int64_t* t_dev, double beta1_d,
+                                    double beta2_d, void* stream) {
+  if (!p || !g || !m || !v || n < 0 || n_images < 0 || n_images > SPV_ADAM_MAX_IMAGES || (n_images && !images) || n_skip < 0 ||
+      n_skip > SPV_ADAM_MAX_SKIP || (n_skip && !skip))
+    return fail(SPV_ERR_ARG, "spv_adam_step_images: bad arguments%s");
   if (n == 0) return SPV_OK;
   if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15)
     return fail(SPV_ERR_ARG, "spv_adam_step_images: buffers must be 16-byte aligned%s");
@@ -1524,17 +1506,57 @@ extern "C" int spv_adam_step_images(float* p, const float* g, float* m, float* v
   im.n = n_images;
   for (int d = 0; d < n_images; ++d) {
     const spv_adam_image& q = images[d];
-    if (!q.dst || q.begin < 0 || (q.begin & 3) || q.count <= 0 || q.begin + q.count > n || q.cols <= 0 || q.ld < q.cols + q.col_off || q.row_off < 0 || q.col_off < 0 ||
-        q.count >= (1L << 31) || (q.fmt != SPV_IMAGE_BF16 && q.fmt != SPV_IMAGE_F16) || (q.fmt == SPV_IMAGE_F16 && !(q.scale > 0.f)))
+    if (!adam_image_ok(q) || q.begin < 0 || (q.begin & 3) || q.begin + q.count > n)
       return fail(SPV_ERR_ARG, "spv_adam_step_images: bad image descriptor%s");
     im.img[d] = q;
   }
-  long blocks = (n / 4 + 255) / 256;
+  AdamSkips sk{};
+  sk.n = n_skip;
+  long n_kept = n, end = 0;
+  for (int d = 0; d < n_skip; ++d) {   // ascending, disjoint, whole 4-chunks (a range that ends the buffer may end anywhere)
+    const spv_adam_range& r = skip[d];
+    if (r.begin < end || (r.begin & 3) || r.count <= 0 || r.begin + r.count > n || ((r.count & 3) && r.begin + r.count != n))
+      return fail(SPV_ERR_ARG, "spv_adam_step_images: bad skip range%s");
+    sk.begin[d] = r.begin; sk.count[d] = r.count;
+    end = r.begin + r.count;
+    n_kept -= r.count;
+  }
+  if (n_kept == 0) {   // nothing left to update: the step counter still advances
+    return step_counter ? spv_counter_bump(step_counter, stream) : SPV_OK;
+  }
+  long blocks = (n_kept / 4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_images_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1, beta2, eps,
-                     weight_decay, bc1, bc2, grad_scale, im, (long long*)step_counter, (const long long*)t_dev, beta1_d, beta2_d);
+  hipLaunchKernelGGL(adam_images_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n_kept, lr, beta1, beta2, eps,
+                     weight_decay, bc1, bc2, grad_scale, im, sk, (long long*)step_counter, (const long long*)t_dev, beta1_d, beta2_d);
   return launch_status("spv_adam_step_images");
+}
+
+// slab sums whose parameters take their Adam step in the same launch (reduce_adam_fused_kernel, spv_small.h)
+extern "C" int spv_reduce_slabs_adam(const spv_reduce_adam_batch* b, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                     float bc1, float bc2, float grad_scale, const int64_t* t_dev, double beta1_d, double beta2_d, void* stream) {
+  if (!b || b->nprob <= 0 || b->nprob > SPV_MAXRA) return fail(SPV_ERR_ARG, "spv_reduce_slabs_adam: bad batch%s");
+  ReduceAdamArgs a{};
+  a.nprob = b->nprob;
+  long blocks = 1;
+  for (int i = 0; i < b->nprob; ++i) {
+    const spv_reduce_adam_prob& q = b->p[i];
+    const spv_reduce_prob& r = q.r;
+    if (!r.src || !r.dst || r.nslabs <= 0 || r.nslabs > RED_FEW_MAX || r.rows <= 0 || r.cols <= 0 || r.ld_src < r.col_off + r.cols || r.col_off < 0 ||
+        (long)r.rows * r.cols >= (1l << 31) || r.ld_dst != r.cols || r.accumulate || r.exp_scale || !q.p || !q.m || !q.v)
+      return fail(SPV_ERR_ARG, "spv_reduce_slabs_adam: bad problem%s");
+    if (q.img.dst && (!adam_image_ok(q.img) || q.img.cols != r.cols || q.img.count != (long)r.rows * r.cols))
+      return fail(SPV_ERR_ARG, "spv_reduce_slabs_adam: bad image descriptor%s");
+    a.p[i] = q;
+    long t = ((long)r.rows * r.cols + 255) / 256;   // one pass; beyond 8192 workgroups a grid-stride loop
+    if (t > 8192) t = 8192;
+    a.nblk[i] = (unsigned)t;
+    if (t > blocks) blocks = t;
+  }
+  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.bc1 = bc1; a.bc2 = bc2; a.gscale = grad_scale;
+  a.t_dev = (const long long*)t_dev; a.b1d = beta1_d; a.b2d = beta2_d;
+  hipLaunchKernelGGL(reduce_adam_fused_kernel, dim3((unsigned)blocks, b->nprob), dim3(256), 0, (hipStream_t)stream, a);
+  return launch_status("spv_reduce_slabs_adam");
 }
 
 extern "C" int spv_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

@@ -9,6 +9,7 @@
 #pragma once
 #include "../../include/spvipes_hip.h"
 #include "spv_common.h"
+#include "spv_adam.h"
 
 namespace spv {
 
@@ -1811,6 +1812,53 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(spv_reduce_batch b) {
     __syncthreads();
     if (ty == 0 && ok) reduce_finish(q, r, c, ((s_part[0][tx] + s_part[1][tx]) + s_part[2][tx]) + s_part[3][tx], alpha);
     __syncthreads();
+  }
+}
+
+// ---- slab sum + Adam: a gradient that nothing but the optimiser reads takes its parameter's step where it is produced ----------
+// Per element of a parameter [rows][cols] (contiguous in the flat buffers: p, m, v and the gradient are indexed flat, (r, c) serves
+// only the slab and the image address): g = (slabs in slab order) * alpha with reduce_few_slabs' arithmetic, stored to the gradient
+// buffer as spv_reduce_slabs would, then adam_update and the image word -- what adam_images_kernel would do with that g at the end
+// of the step, minus its read of g and its place on the critical path.  Reads *t_dev, never writes it and bumps no counter.
+struct ReduceAdamArgs {
+  spv_reduce_adam_prob p[SPV_MAXRA]; int nprob;
+  unsigned nblk[SPV_MAXRA];   // workgroups that work on problem i (<= gridDim.x, the neediest problem's count): the others leave at once
+  float lr, b1, b2, eps, wd, bc1, bc2, gscale; const long long* t_dev; double b1d, b2d;
+};
+// NS known at compile time: the NS slab loads and the p / m / v loads of an element are all in flight together
+template <int NS>
+__device__ __forceinline__ void reduce_adam_few(const spv_reduce_adam_prob& q, unsigned nblk, float alpha, const AdamStep& a) {
+  const spv_reduce_prob& rq = q.r;
+  const unsigned cols = (unsigned)rq.cols, total = (unsigned)rq.rows * cols;   // (rows * cols < 2^31: spv_reduce_slabs_adam)
+  for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += nblk * 256u) {
+    const unsigned r = e / cols, c = e - r * cols;
+    const float* s = rq.src + (long)r * rq.ld_src + rq.col_off + c;
+    float t[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) t[k] = s[(long)k * rq.slab_stride];
+    float p = q.p[e], m = q.m[e], v = q.v[e];
+    const float g = __fmul_rn(reduce_ordered_sum<NS>(t), alpha);   // (a product of its own, as spv_reduce_slabs stores it: never fused into the update)
+    rq.dst[e] = g;
+    adam_update(p, g, m, v, a);
+    q.p[e] = p; q.m[e] = m; q.v[e] = v;
+    if (q.img.dst) q.img.dst[((long)r + q.img.row_off) * q.img.ld + q.img.col_off + c] = adam_image_word(q.img, p);
+  }
+}
+__global__ __launch_bounds__(256) void reduce_adam_fused_kernel(ReduceAdamArgs b) {
+  const spv_reduce_adam_prob& q = b.p[blockIdx.y];
+  const unsigned nblk = b.nblk[blockIdx.y];
+  if (blockIdx.x >= nblk) return;   // (the b_m problems need ~40 of the grid's workgroups: the rest skip the prologue too)
+  const float alpha = *(q.r.alpha ? q.r.alpha : &g_spv_one);
+  const AdamStep a = adam_prologue(b.lr, b.b1, b.b2, b.eps, b.wd, b.bc1, b.bc2, b.gscale, b.t_dev, b.b1d, b.b2d);
+  switch (q.r.nslabs) {   // (block-uniform; 1 .. RED_FEW_MAX: spv_reduce_slabs_adam)
+    case 1: reduce_adam_few<1>(q, nblk, alpha, a); break;
+    case 2: reduce_adam_few<2>(q, nblk, alpha, a); break;
+    case 3: reduce_adam_few<3>(q, nblk, alpha, a); break;
+    case 4: reduce_adam_few<4>(q, nblk, alpha, a); break;
+    case 5: reduce_adam_few<5>(q, nblk, alpha, a); break;
+    case 6: reduce_adam_few<6>(q, nblk, alpha, a); break;
+    case 7: reduce_adam_few<7>(q, nblk, alpha, a); break;
+    default: reduce_adam_few<8>(q, nblk, alpha, a); break;
   }
 }
 

@@ -85,6 +85,23 @@ def _run_red(b: SpvReduceBatch) -> None:
         _abi.call("spv_reduce_slabs", C.byref(b), stream_ptr())
 
 
+def _reduce_adam(b: SpvReduceBatch, params, targets) -> bool:
+    """``b``'s problems (problem i sums the gradient of params[i] into targets[i]) as one spv_reduce_slabs_adam launch, where a step
+    has armed it (ops.WM_ADAM) and every problem qualifies; False: nothing was launched and the caller runs the plain sum"""
+    fa = _ops.WM_ADAM
+    if fa is None or not b.nprob or b.nprob != len(params) or b.nprob > _abi.SPV_MAXRA or len(fa.taken) + b.nprob > _abi.ADAM_MAX_SKIP:
+        return False   # (the optimiser launch skips at most ADAM_MAX_SKIP ranges: counted before neighbours are merged)
+    ba = _abi.SpvReduceAdamBatch()
+    ba.nprob = b.nprob
+    for i in range(b.nprob):
+        q, r = ba.p[i], b.p[i]
+        if r.nslabs > 8 or r.accumulate or r.exp_scale or r.ld_dst != r.cols or not fa.fill(q, params[i], targets[i]):
+            return False
+        q.r = r
+    fa.launch(ba, params)
+    return True
+
+
 # ---- one function per argument block: every site that launches with a block gets it from here and sets no field of it itself ----
 def _zsplit_args(B: int, Bp: int, n_p: int, n_s: int, n_m: int, sl, lat, zcat, Am_img, Aps_img) -> SpvZsplitArgs:
     """spv_zsplit_fwd's block: per group ``lat`` = (private, poe) latents (contiguous fp32: the caller holds them) into ``zcat`` and, packed
@@ -752,7 +769,16 @@ class DecoderFused(torch.autograd.Function):
                     a = wm_slabs[g] if pair else st.gemm_a()
                     _add_red(red3, a, st.csp_m, G * KMP, KMP, G, KM - 1, pg[g][10][0], KM - 1, alpha=g_loss)                 # d W_m
                     _add_red(red3, a, st.csp_m, G * KMP, KMP, G, 1, pg[g][11][0], 1, col_off=KM - 1, alpha=g_loss)           # d b_m
-                _run_red(red3)
+                # Nothing but the optimiser reads these gradients, and nothing launched after this point in the step reads W_m, b_m or
+                # their image (the logits GEMM and the d A_m GEMMs, their only readers, are behind side.wait_stream(cur) above): in a step
+                # that ends with the optimiser the same launch takes their Adam step (train.FusedWmAdam) -- in large
+                # steps.  A small step (sched.pair: pair grids, everything on the caller's stream) would overlap the launch with nothing and
+                # only save the optimiser's 4-byte re-read of the gradient, for a one-element-per-thread kernel in place of the optimiser's
+                # 16-byte one: measured slower at C1 (lab notes Y), so the plain sum stays there.  (SPV_SERIAL_STREAMS=1, the per-kernel
+                # profiling mode of a large step, keeps the fused launch: the profile then shows the kernels the step runs.)
+                if sched.pair or not _reduce_adam(red3, [par[g][j] for g in range(NG) for j in (10, 11)],
+                                                   [pg[g][j][0] for g in range(NG) for j in (10, 11)]):
+                    _run_red(red3)
             if _ops.DEFER_JOIN:
                 _ops.defer(side, [g_loss])
             else:

@@ -295,6 +295,10 @@ def join(streams) -> None:
 # possible.  With DEFER_JOIN False the join happens before DecoderFused.backward returns (any caller may then read .grad);
 # train.Trainer sets it True around its backward pass and joins with ``join_pending`` right after it.
 DEFER_JOIN = False
+# train.FusedWmAdam of a step whose optimiser launch follows its backward pass unconditionally (set by train.Trainer around that pass,
+# else None): DecoderFused.backward then sums the d W_m / d b_m slabs with spv_reduce_slabs_adam, which also takes those parameters'
+# Adam step, and records them for the optimiser launch to skip.
+WM_ADAM = None
 # Settled by same-box A/B and no longer switches (the variants and their numbers: docs/lab_notes.md, "Schedule variants tried and
 # retired").  Forward: the fold / weight images / tables run beside the trunk on the side stream; the two groups' chains run on the group
 # streams, group 1 with its softmax statistics ahead of its logits GEMM; the latent and trunk kernels write the decoder's operand images.

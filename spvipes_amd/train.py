@@ -18,6 +18,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
 
+import ctypes as C
 import gc
 import os
 
@@ -141,20 +142,71 @@ class HipAdam:
         self.t = 0   # host copy of the step count (bookkeeping only: the kernel reads t_dev)
         self.t_dev = torch.zeros((), dtype=torch.int64, device=fp.flat.device)
 
-    def step(self, grad_scale: float = 1.0, images=None, counter=None):
+    def step(self, grad_scale: float = 1.0, images=None, counter=None, skip=()):
         """``images``: optional ctypes array of SpvAdamImage -- 16-bit operand images the kernel rewrites from the updated values;
-        ``counter``: optional 0-dim int64 device tensor the kernel increments (the step counter the module's noise is keyed by)"""
+        ``counter``: optional 0-dim int64 device tensor the kernel increments (the step counter the module's noise is keyed by);
+        ``skip``: [(begin, count)] ranges of the flat buffer that have already taken this step (``FusedWmAdam``)"""
         self.t += 1
-        self.launch(grad_scale, images, counter)
+        self.launch(grad_scale, images, counter, skip)
 
-    def launch(self, grad_scale: float = 1.0, images=None, counter=None):
+    def launch(self, grad_scale: float = 1.0, images=None, counter=None, skip=()):
         """the two launches of one step (Adam, then the device step count + 1); captured as they are by ``Trainer.capture``"""
         b1, b2 = self.betas
         n_img = len(images) if images is not None else 0
+        ranges = (_abi.SpvAdamRange * len(skip))(*[_abi.SpvAdamRange(b, c) for b, c in skip]) if skip else None
         _abi.call("spv_adam_step_images", _abi.ptr(self.fp.flat), _abi.ptr(self.fp.grad), _abi.ptr(self.m), _abi.ptr(self.v),
                   self.fp.numel, self.lr, b1, b2, self.eps, self.wd, 1.0, 1.0,
-                  grad_scale, images if n_img else None, n_img, _abi.ptr(counter), _abi.ptr(self.t_dev), float(b1), float(b2), _abi.stream_ptr())
+                  grad_scale, images if n_img else None, n_img, ranges, len(skip), _abi.ptr(counter), _abi.ptr(self.t_dev), float(b1), float(b2),
+                  _abi.stream_ptr())
         _abi.call("spv_counter_bump", _abi.ptr(self.t_dev), _abi.stream_ptr())
+
+
+class FusedWmAdam:
+    """One step's hand-over of parameters from the optimiser launch to the backward pass: ``DecoderFused.backward`` sums the mixing
+    head's weight-gradient slabs and applies Adam to ``W_m`` / ``b_m`` in the same launch (spv_reduce_slabs_adam, on the side stream,
+    while the main stream runs the small kernels of the fold / PoE / encoder-tail backward), and the step's spv_adam_step_images call
+    then skips what is recorded here.  Armed by ``Trainer`` only for a step that applies the optimiser on a single rank with gradient
+    scale 1, and used by the backward pass only in large steps (a small step runs on one stream: nothing
+    overlaps and the launch is slower than what it replaces); the launch reads ``HipAdam.t_dev``, which only the counter bump behind the
+    tail launch advances.  A step that raises between the fused launch and the tail launch leaves ``W_m`` / ``b_m`` one step ahead of the
+    other parameters and of ``t_dev``: such a trainer's state is not a state of the optimisation any more."""
+
+    def __init__(self, opt: HipAdam, images: Optional[dict] = None):
+        self.opt, self.images, self.taken = opt, images or {}, []
+
+    def fill(self, q, param: torch.Tensor, target: torch.Tensor) -> bool:
+        """the p / m / v / image fields of problem ``q`` (_abi.SpvReduceAdamProb) for ``param``, whose gradient kernel writes ``target``;
+        False where the pair is not a parameter's slice of the flat buffers and its gradient slice (the caller then keeps the plain sum)"""
+        fp = self.opt.fp
+        delta, n = param.data_ptr() - fp.flat.data_ptr(), param.numel()   # bytes from the start of the flat buffer
+        if param.dtype != torch.float32 or not param.is_contiguous() or delta < 0 or delta % 16 or delta // 4 + n > fp.numel:
+            return False   # (not a parameter's own 4-element-aligned slice of the flat buffer)
+        off = delta // 4
+        if target.data_ptr() != fp.grad.data_ptr() + delta:
+            return False   # (the gradient kernel does not write the parameter's slice of the flat gradient buffer)
+        q.p, q.m, q.v = fp.flat.data_ptr() + 4 * off, self.opt.m.data_ptr() + 4 * off, self.opt.v.data_ptr() + 4 * off
+        img = self.images.get(off)
+        if img is not None:
+            q.img = img
+        return True
+
+    def launch(self, batch, params) -> None:
+        b1, b2 = self.opt.betas
+        _abi.call("spv_reduce_slabs_adam", C.byref(batch), self.opt.lr, b1, b2, self.opt.eps, self.opt.wd, 1.0, 1.0, 1.0,
+                  _abi.ptr(self.opt.t_dev), float(b1), float(b2), _abi.stream_ptr())
+        fp = self.opt.fp
+        for p_ in params:   # (with its alignment padding: zero values, gradients and moments, which an Adam step leaves zero)
+            self.taken.append(((p_.data_ptr() - fp.flat.data_ptr()) // 4, (p_.numel() + 3) // 4 * 4))
+
+    def ranges(self):
+        """what the tail launch skips: ascending, neighbours merged ([W_m | b_m] of a group are one range)"""
+        out = []
+        for b, c in sorted(self.taken):
+            if out and out[-1][0] + out[-1][1] == b:
+                out[-1] = (out[-1][0], out[-1][1] + c)
+            else:
+                out.append((b, c))
+        return out
 
 
 class Trainer:
@@ -220,6 +272,9 @@ class Trainer:
     DEVICE_RNG = os.environ.get("SPV_DEVICE_RNG", "1") != "0"
     MULTI_GATHER = os.environ.get("SPV_MULTI_GATHER", "1") != "0"   # the groups' label gathers / row-index copies as one launch each (spv_gather_u32)
     ADAM_IN_GRAPH = os.environ.get("SPV_ADAM_IN_GRAPH", "1") != "0"  # single rank: the Adam launch is the captured graph's last node
+    # W_m / b_m take their Adam step inside their slab-sum launch (FusedWmAdam) instead of in the launch that ends the step; 0: the
+    # plain sum and the full tail launch (the A/B of docs/lab_notes.md)
+    FUSED_WM_ADAM = os.environ.get("SPV_FUSED_WM_ADAM", "1") != "0"
 
     def _image_specs(self):
         """[(workspace, key, image tensor, [(parameter, rows_off, col_off)], token parameters)] for every packed weight image"""
@@ -328,10 +383,19 @@ class Trainer:
             out.append(d)
         return tuple(out)
 
-    def _forward_backward(self, rows, kl_weight, noise=None):
+    def _fused_wm_adam(self, images) -> Optional[FusedWmAdam]:
+        """the hand-over object of a step that WILL apply the optimiser, or None: only on a single rank (no all-reduce comes between a
+        gradient and Adam) with gradient scale 1 = 1 / world.  ``images``: the step's image plan (None: no image is kept by Adam)"""
+        if not self.FUSED_WM_ADAM or self.world != 1:
+            return None
+        by_begin = {d.begin: d for d in images} if images is not None else {}
+        return FusedWmAdam(self.opt, by_begin)
+
+    def _forward_backward(self, rows, kl_weight, noise=None, fused: Optional[FusedWmAdam] = None):
         """forward + loss + backward.  With ``self.overlap`` only the decoder half of the backward pass runs here (down
         to the tensors that cross from the encoders into the decoder); ``_backward_encoders`` finishes it.
-        ``noise``: injected standard-normal draws (parity tests; see spVIPESmodule.inference)."""
+        ``noise``: injected standard-normal draws (parity tests; see spVIPESmodule.inference).  ``fused``: the optimiser launch follows
+        this call unconditionally and skips ``fused.ranges()`` (see FusedWmAdam)."""
         from . import nn_ops, ops
 
         if self.ZERO_GRADS_EACH_STEP:
@@ -345,6 +409,7 @@ class Trainer:
             self.module.split_backward = False
         nn_ops.GRAD_SINK = True  # small-layer gradients land directly in the flat buffer (see nn_ops.grad_out)
         ops.DEFER_JOIN = True    # side-stream gradient GEMMs are joined here, after the whole backward pass
+        ops.WM_ADAM = fused
         try:
             one = getattr(self, "_one", None)   # the backward seed d loss / d loss = 1, kept: autograd would otherwise launch a fill kernel per step
             if one is None or one.device != lo.loss.device:
@@ -372,6 +437,7 @@ class Trainer:
         finally:
             nn_ops.GRAD_SINK = False
             ops.DEFER_JOIN = False
+            ops.WM_ADAM = None
             ops.join_pending()
             ops.join_all_side_streams(self.device)
         return lo
@@ -442,9 +508,12 @@ class Trainer:
         gc.disable()
         try:
             with torch.cuda.graph(g, **mode):
-                self._static_lo = self._forward_backward(self._static_rows, self._klw)
+                # (only a graph that ends with the optimiser launch may hand parameters over to the backward pass: every replay applies it)
+                fused = self._fused_wm_adam(self._img_plan) if self._adam_in_graph else None
+                self._static_lo = self._forward_backward(self._static_rows, self._klw, fused=fused)
                 if self._adam_in_graph:
-                    self.opt.launch(grad_scale=1.0, images=self._img_plan, counter=getattr(self.module, "_rng_counter", None))
+                    self.opt.launch(grad_scale=1.0, images=self._img_plan, counter=getattr(self.module, "_rng_counter", None),
+                                    skip=fused.ranges() if fused is not None else ())
             if keep:
                 g.instantiate()
             self.graph = g
@@ -468,6 +537,7 @@ class Trainer:
         if kl_weight is None:
             kl_weight = kl_weight_at(self.epoch, self.global_step, self.n_epochs_kl_warmup, self.n_steps_kl_warmup)
         self._ensure_images()
+        fused = None
         if self.graph is not None:
             if self.MULTI_GATHER and all(r.dtype == torch.int32 and r.is_cuda and r.is_contiguous() and r.numel() == s.numel() for s, r in zip(self._static_rows, rows)):
                 _abi.gather_u32([(r, None, s) for s, r in zip(self._static_rows, rows)])   # one launch for all groups' row indices
@@ -480,7 +550,12 @@ class Trainer:
             self.graph.replay()
             lo = self._static_lo  # tensors are overwritten by the next replay
         else:
-            lo = self._forward_backward(rows, kl_weight, noise)
+            if optimizer_step:   # (the image plan this step's optimiser launches use: decided here, before the backward pass needs it)
+                plan = getattr(self, "_img_plan", None)
+                if plan is not None and not self._images_are_fresh():
+                    plan = None
+                fused = self._fused_wm_adam(plan)
+            lo = self._forward_backward(rows, kl_weight, noise, fused=fused)
         timed = self.world > 1
         if timed:   # GPU-time bracket of what the collectives leave exposed after the backward pass (bench.py reports it)
             if getattr(self, "_ev_ar", None) is None:
@@ -513,7 +588,8 @@ class Trainer:
             if plan is not None and not self._images_are_fresh():
                 plan = None   # (somebody wrote to a parameter since the images were made: plain Adam, and the images are rebuilt next step)
                 self.parameters_changed()
-            self.opt.step(grad_scale=1.0 / self.world, images=plan, counter=getattr(self.module, "_rng_counter", None))
+            self.opt.step(grad_scale=1.0 / self.world, images=plan, counter=getattr(self.module, "_rng_counter", None),
+                          skip=fused.ranges() if fused is not None else ())
             self.global_step += 1
         return lo
 
