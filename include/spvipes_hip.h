@@ -675,6 +675,52 @@ int spv_ot_segment_lse(const spv_ot_seg_args* a, void* stream);
 int32_t spv_ot_segment_splits(int32_t n_q, int32_t n_c);
 int64_t spv_ot_segment_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split);
 
+/* Barycentric projection through the untruncated plan (spVIPES.transport_project of the user API): for query row i the
+ * plan-weighted mean of the candidates' value rows,
+ *   out[v][i] = sum_j exp(t(i, j)) V[j][v] / sum_j exp(t(i, j)),   t(i, j) = fmaf(-c(i, j), inv_eps, h[j]),   L[i] = log sum_j exp(t(i, j))
+ * with spv_ot_softmin's c and t, the same bits; nothing of size n_q x n_c stored.  With h = psi + log b of a Sinkhorn result the
+ * weights are row i of the plan up to the row's own factor, which the quotient drops; exp(L[i] + phi_i + log a_i) is the row's mass.
+ * Per lane a running (m, sum) pair, updated as spv_ot_softmin's, and one accumulator per value column.  Per candidate with a finite
+ * t: d = t - m, e = exp(-|d|), and ONE fma per column: acc = fmaf(acc, e, V[j][v]) for d > 0, acc = fmaf(e, V[j][v], acc) otherwise.
+ * A t that is not finite contributes nothing and its value row enters no sum, whatever it holds.  out = acc / sum, the correctly
+ * rounded quotient.  A query without a contributing candidate (n_c == 0 included) gets L = -inf and NaN in every column.
+ * A column of ones repeats the sum's operations and comes back as exactly 1.0f.
+ * V: fp32 [n_c][ld_v], ld_v >= n_v.  Layout of out: VALUE-MAJOR, fp32 [n_v][ld_out] with ld_out >= n_q -- out[v * ld_out + i].  L: fp32
+ * [n_q], may be NULL.  Rows >= n_q, columns >= n_v and everything beyond the workspace's bytes are never written.
+ * Launches: a partial pass of (tiles of spv_ot_tile_q() queries) x (n_split chunks of the candidates) x (blocks of
+ * spv_ot_project_block(D) value columns) workgroups, every column block rescanning the distances; n_split == 1 is ONE launch that
+ * writes out and L; for n_split > 1 every workgroup writes (m, sum, its accumulators) to ws and a merge pass, one lane per (query,
+ * column), folds the chunks IN CHUNK ORDER: a later chunk with the larger m gives acc = fmaf(acc, e, its acc), otherwise (if its sum is
+ * positive) acc = fmaf(its acc, e, acc), next to spv_ot_softmin's merge of (m, sum).  No floating-point atomics: for fixed shapes and
+ * n_split two calls agree bit for bit; a query's row does not depend on the other queries of the call, and a column's values not on
+ * which other columns the call holds.  Different n_split agree within rounding.  The chunks of a given n_split are spv_ot_softmin's:
+ * at the same EXPLICIT n_split L equals spv_ot_softmin's L bit for bit.  n_split = 0 stands for spv_ot_project_splits(n_q, n_c, n_v), a
+ * pure function of the shapes.
+ * ws: spv_ot_project_ws_bytes(n_q, n_v, n_split) bytes with the RESOLVED n_split (0 for n_split <= 1 or a non-positive shape; 64-bit
+ * arithmetic; enough for every D), 8-byte aligned, overwritten by every call.  Nothing is allocated.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null arguments / Q / C / h / out; V null while n_c > 0; ws null when its size is not
+ * 0, or not 8-byte aligned; D outside [1, SPV_OT_DMAX]; n_v outside [1, SPV_OT_VAL_MAX]; n_split outside [0, SPV_OT_SPLIT_MAX]; n_q < 1;
+ * n_c < 0; ld_q < D; ld_c < D; ld_v < n_v; ld_out < n_q; inv_eps not a positive finite number; n_v * ld_out or the workspace's word
+ * count beyond 2^31 - 1. */
+#define SPV_OT_VAL_MAX 256
+typedef struct spv_ot_proj_args {
+  const float* Q; int64_t ld_q; int32_t n_q;      /* queries    fp32 [n_q][ld_q], ld_q >= D */
+  const float* C; int64_t ld_c; int32_t n_c;      /* candidates fp32 [n_c][ld_c], ld_c >= D */
+  int32_t D;                                      /* 1 .. SPV_OT_DMAX */
+  const float* h;                                 /* [n_c] */
+  float inv_eps;                                  /* s = 1 / epsilon, > 0 */
+  const float* V; int64_t ld_v; int32_t n_v;      /* values     fp32 [n_c][ld_v], ld_v >= n_v; 1 .. SPV_OT_VAL_MAX columns */
+  int32_t n_split;                                /* 0 = spv_ot_project_splits(n_q, n_c, n_v); else 1 .. SPV_OT_SPLIT_MAX chunks of the candidates */
+  float* out; int64_t ld_out;                     /* [n_v][ld_out], ld_out >= n_q */
+  float* L;                                       /* [n_q] or NULL */
+  void* ws;                                       /* spv_ot_project_ws_bytes(n_q, n_v, n_split) bytes */
+} spv_ot_proj_args;
+int spv_ot_project(const spv_ot_proj_args* a, void* stream);
+int32_t spv_ot_project_splits(int32_t n_q, int32_t n_c, int32_t n_v);
+int64_t spv_ot_project_ws_bytes(int32_t n_q, int32_t n_v, int32_t n_split);
+/* value columns per column block of the kernel form that serves D columns of Q / C; 0 for a D outside [1, SPV_OT_DMAX] */
+int32_t spv_ot_project_block(int32_t D);
+
 /* Segmented distance sums (spVIPES.latent_silhouette / integration_scores of the user API): for query row i of Q and every segment s
  * of the candidates C, which come ARRANGED BY SEGMENT, the fp64 sum of the Euclidean distances to the segment's rows; nothing of size
  * n_q x n_c stored.

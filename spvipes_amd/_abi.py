@@ -319,6 +319,16 @@ class SpvOtSegArgs(C.Structure):
                 ("L", C.c_void_p), ("ld_l", C.c_int64), ("ws", C.c_void_p)]
 
 
+OT_VAL_MAX = 256   # SPV_OT_VAL_MAX
+
+
+class SpvOtProjArgs(C.Structure):
+    """the arguments of spv_ot_project (include/spvipes_hip.h: spv_ot_proj_args)"""
+    _fields_ = [("Q", C.c_void_p), ("ld_q", C.c_int64), ("n_q", C.c_int32), ("C", C.c_void_p), ("ld_c", C.c_int64), ("n_c", C.c_int32),
+                ("D", C.c_int32), ("h", C.c_void_p), ("inv_eps", C.c_float), ("V", C.c_void_p), ("ld_v", C.c_int64), ("n_v", C.c_int32),
+                ("n_split", C.c_int32), ("out", C.c_void_p), ("ld_out", C.c_int64), ("L", C.c_void_p), ("ws", C.c_void_p)]
+
+
 SIL_SEG_MAX = 256   # SPV_SILHOUETTE_SEG_MAX
 
 
@@ -420,6 +430,10 @@ _SIGNATURES = {
     "spv_ot_segment_lse": (C.c_int, [C.POINTER(SpvOtSegArgs), C.c_void_p]),
     "spv_ot_segment_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_ot_segment_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_ot_project": (C.c_int, [C.POINTER(SpvOtProjArgs), C.c_void_p]),
+    "spv_ot_project_splits": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_ot_project_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_ot_project_block": (C.c_int32, [C.c_int32]),
     "spv_silhouette_sums": (C.c_int, [C.POINTER(SpvSilhouetteArgs), C.c_void_p]),
     "spv_silhouette_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_silhouette_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -15,6 +15,7 @@
 #include "spv_knn.h"
 #include "spv_ot.h"
 #include "spv_ot_segments.h"
+#include "spv_ot_project.h"
 #include "spv_silhouette.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
@@ -1069,13 +1070,13 @@ extern "C" int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
   return (int64_t)n_split * n_q * k * 8;
 }
 
-// ---- what the entry points of the pair scan share (spv_pair_scan.h): spv_knn here, spv_ot_softmin / spv_ot_topk, spv_ot_segment_lse and spv_silhouette_sums below
+// ---- what the entry points of the pair scan share (spv_pair_scan.h): spv_knn here, spv_ot_softmin / spv_ot_topk, spv_ot_segment_lse, spv_ot_project and spv_silhouette_sums below
 struct ScanPlan { int n_split, per; dim3 grid; };   // chunks (resolved), candidates per chunk, (query tiles, chunks)
 
 // What every one of them refuses about the two sides, D, n_split and ws, in `who`'s name; the chunks -- n_split, or splits(n_q, n_c) for
 // 0 -- and the grid.  X: any of the argument structs (they share these fields).  own(n_split) checks the caller's other fields, ahead of ws.
-template <typename X, typename Own>
-static int scan_check(const X* x, const char* who, int (*splits)(int, int), ScanPlan& p, Own own) {
+template <typename X, typename Splits, typename Own>
+static int scan_check(const X* x, const char* who, Splits splits, ScanPlan& p, Own own) {
   if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
   if (!x->Q) return fail(SPV_ERR_ARG, "%s: null Q", who);
   if (!x->C) return fail(SPV_ERR_ARG, "%s: null C", who);
@@ -1221,6 +1222,40 @@ extern "C" int spv_ot_segment_lse(const spv_ot_seg_args* x, void* stream) {
   if (rc != SPV_OK || p.n_split == 1) return rc;
   hipLaunchKernelGGL(otseg_merge_kernel, dim3(p.grid.x, (unsigned)a.n_seg), dim3(KNN_TQ), 0, s, a);
   return launch_status("spv_ot_segment_lse (merge pass)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// barycentric projection through the untruncated plan (spv_ot_project.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_ot_project_splits(int32_t n_q, int32_t n_c, int32_t n_v) { return otproj_splits(n_q, n_c, n_v); }
+extern "C" int64_t spv_ot_project_ws_bytes(int32_t n_q, int32_t n_v, int32_t n_split) { return otproj_ws_bytes(n_q, n_v, n_split); }
+extern "C" int32_t spv_ot_project_block(int32_t D) { return D < 1 || D > KNN_DMAX ? 0 : otproj_block(D <= 16 ? 16 : D <= 32 ? 32 : 64); }
+
+extern "C" int spv_ot_project(const spv_ot_proj_args* x, void* stream) {
+  ScanPlan p;
+  int rc = scan_check(x, "spv_ot_project", [&](int n_q, int n_c) { return otproj_splits(n_q, n_c, x->n_v); }, p, [&](int n_split) {
+    if (!x->h) return fail(SPV_ERR_ARG, "spv_ot_project: null h%s");
+    if (!x->out) return fail(SPV_ERR_ARG, "spv_ot_project: null out%s");
+    if (!x->V && x->n_c > 0) return fail(SPV_ERR_ARG, "spv_ot_project: null V%s");
+    if (!(x->inv_eps > 0.f && x->inv_eps < INFINITY)) return fail(SPV_ERR_ARG, "spv_ot_project: inv_eps must be a positive finite number%s");
+    if (x->n_v < 1 || x->n_v > OT_VAL_MAX) return fail(SPV_ERR_ARG, "spv_ot_project: n_v must lie in [1, 256]%s");
+    if (x->ld_v < x->n_v) return fail(SPV_ERR_ARG, "spv_ot_project: ld_v < n_v%s");
+    if (x->ld_out < x->n_q) return fail(SPV_ERR_ARG, "spv_ot_project: ld_out < n_q%s");
+    if (x->ld_out > INT32_MAX || (int64_t)x->n_v * x->ld_out > INT32_MAX) return fail(SPV_ERR_ARG, "spv_ot_project: n_v * ld_out exceeds 2^31 - 1%s");
+    if (otproj_ws_words(x->n_q, x->n_v, n_split) > INT32_MAX) return fail(SPV_ERR_ARG, "spv_ot_project: the workspace (n_split * (n_v + 2 * blocks) * n_q words) exceeds 2^31 - 1%s");
+    return SPV_OK;
+  });
+  if (rc != SPV_OK) return rc;
+  const int VB = spv_ot_project_block(x->D);
+  const OtProjArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->h, x->inv_eps, x->V, (long)x->ld_v, x->n_v, p.n_split, p.per,
+                     x->out, (long)x->ld_out, x->L, (float*)x->ws, otproj_ws_rows(x->n_v, VB)};
+  p.grid.z = (unsigned)((a.n_v + VB - 1) / VB);
+  hipStream_t s = (hipStream_t)stream;
+  scan_dispatch(a.D, [&](auto dp) { constexpr int DP = decltype(dp)::value; hipLaunchKernelGGL((otproj_partial_kernel<DP>), p.grid, dim3(KNN_TQ), otproj_lds_bytes(DP), s, a); });
+  rc = launch_status(p.n_split == 1 ? "spv_ot_project" : "spv_ot_project (partial pass)");
+  if (rc != SPV_OK || p.n_split == 1) return rc;
+  hipLaunchKernelGGL(otproj_merge_kernel, dim3(p.grid.x, (unsigned)a.n_v), dim3(KNN_TQ), 0, s, a, VB);
+  return launch_status("spv_ot_project (merge pass)");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1378,3 +1378,80 @@ def check_match_clusters_args(adata, rep, plan, n_clusters, cluster_key, n_init,
         if not any(c <= len(rows) for c in cand):
             raise ValueError(f"group {g}: every candidate of n_clusters exceeds its {len(rows)} cells")
     return obs_idx, cand, swept
+
+
+# ---- barycentric projection through the transport plan (model.transport_project): the refusals, the one-hot encoding of a label
+# column and the frame a label projection comes back as -- pure numpy / pandas ------
+def one_hot_labels(col):
+    """An ``obs`` column's values for some cells -> (categories: the sorted distinct values, one-hot float32 [n, n_categories])"""
+    cats, inv = np.unique(np.asarray(col), return_inverse=True)
+    hot = np.zeros((len(inv), len(cats)), dtype=np.float32)
+    hot[np.arange(len(inv)), inv] = 1.0
+    return cats, hot
+
+
+def label_projection_frame(probs, categories, index):
+    """The projection of one-hot labels [n, n_categories] -> pandas DataFrame indexed by ``index``: one probability column per category
+    (named str(category)), ``predicted`` (the category with the largest probability, the FIRST one on ties; None for a row of NaN: a
+    cell the plan gives no mass) and ``confidence`` (that probability)."""
+    import pandas as pd
+
+    probs = np.asarray(probs)
+    categories = np.asarray(categories)
+    if probs.ndim != 2 or probs.shape[1] != len(categories) or len(index) != probs.shape[0]:
+        raise ValueError("label_projection_frame: probs must be [len(index), len(categories)]")
+    frame = pd.DataFrame(probs, index=index, columns=[str(c) for c in categories])
+    none = np.isnan(probs).any(1)
+    best = np.argmax(np.where(none[:, None], 0.0, probs), axis=1)   # argmax: the first of equal entries
+    predicted = categories[best].astype(object)
+    predicted[none] = None
+    frame["predicted"] = predicted
+    frame["confidence"] = np.where(none, np.nan, probs[np.arange(len(best)), best])
+    return frame
+
+
+def check_transport_project_args(adata, rep, plan, values, onto, key_added):
+    """The refusals of ``transport_project`` ahead of any device work and of anything written -> (obs_idx, X0, X1 float32 [n_g, D],
+    V float32 C-contiguous [n_other, n_v], categories or None).  ``rep``: the representation [n_obs, D]; ``values``: an array
+    [n_other, n_v] or [n_obs, n_v], a key of ``obsm`` or the name of an ``obs`` column (then ``categories`` are its distinct values
+    among the other group's cells and V their one-hot encoding)."""
+    if "groups_obs_indices" not in adata.uns:
+        raise ValueError("adata.uns['groups_obs_indices'] missing: build the AnnData with prepare_adatas (or the same schema)")
+    obs_idx = [np.asarray(v) for v in adata.uns["groups_obs_indices"]]
+    if len(obs_idx) != 2:
+        raise ValueError("a transport plan couples exactly two groups")
+    if isinstance(onto, bool) or not isinstance(onto, (int, np.integer)) or int(onto) not in (0, 1):
+        raise ValueError(f"onto must be 0 or 1, the group whose cells receive the projection, got {onto!r}")
+    if key_added is not None and not isinstance(key_added, str):
+        raise ValueError(f"key_added must be a string or None, got {key_added!r}")
+    if not hasattr(plan, "sinkhorn"):
+        raise TypeError("plan must be the TransportPlan of compute_transport_plan: a plain matrix has no potentials, and the projection "
+                        "reads the untruncated plan from them.  The host route for a matrix is plan.to_scipy() @ values (or plan @ values), "
+                        "divided by the row sums")
+    n = (len(obs_idx[0]), len(obs_idx[1]))
+    if tuple(plan.shape) != n:
+        raise ValueError(f"plan couples {tuple(plan.shape)} cells, the groups hold {n}")
+    X0, X1, _ = check_transport_args(rep, obs_idx, 1)
+    other = obs_idx[1 - int(onto)]
+    categories = None
+    if isinstance(values, str):
+        obsm = getattr(adata, "obsm", None)
+        if obsm is not None and values in obsm:
+            values = obsm[values]
+        elif values in adata.obs:
+            categories, values = one_hot_labels(np.asarray(adata.obs[values])[other])
+        else:
+            raise KeyError(f"values '{values}' is neither a key of adata.obsm nor a column of adata.obs")
+    V = np.asarray(values)
+    if V.ndim != 2 or V.shape[1] < 1 or not (np.issubdtype(V.dtype, np.number) or V.dtype == bool):
+        raise ValueError(f"values must be a numeric array [n_other, n_v] or [n_obs, n_v] with n_v >= 1, got shape {V.shape}")
+    if V.shape[0] == adata.n_obs:
+        V = V[other]
+    elif V.shape[0] != len(other):
+        raise ValueError(f"values must have one row per cell of group {1 - int(onto)} ({len(other)}) or per cell of adata ({adata.n_obs}), "
+                         f"got {V.shape[0]}")
+    with np.errstate(over="ignore"):
+        V = np.ascontiguousarray(V, dtype=np.float32)
+    if not np.isfinite(V).all():
+        raise ValueError("values holds non-finite entries (after the conversion to float32)")
+    return obs_idx, X0, X1, V, categories

@@ -25,6 +25,7 @@ from .data import (MinibatchSampler, RowBlocks, check_de_args, check_neighbor_ar
                    csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
                    latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions,
                    ClusterMatching, check_match_clusters_args, cluster_entropy_score, cluster_pair_scores, cluster_tables_from_matrix, match_cluster_labels,
+                   check_transport_project_args, label_projection_frame,
                    SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table)
 from .module import spVIPESmodule
 from .plan import SparsePlan
@@ -274,6 +275,57 @@ class spVIPES:
         adata.obs["processed_transport_labels"] = processed.astype(str)
         adata.uns["cluster_matching"] = result.as_dict()
         return result
+
+    @classmethod
+    def transport_project(cls, adata, use_rep, plan, values, onto: int = 0, key_added: Optional[str] = None, device: Optional[str] = None):
+        """Push per-cell values of one group through the transport plan onto the other group's cells (the barycentric projection, the
+        ``push`` / ``pull`` of OT tool kits): for every cell i of group ``onto`` the plan-weighted mean sum_j P_ij V[j] / sum_j P_ij of
+        the OTHER group's values.  The weights are the UNTRUNCATED plan, read from the Sinkhorn potentials by one fused kernel
+        (``ot_ops.ot_project``): no n0 x n1 matrix, none of the stored plan's truncation to k entries per cell.
+        Needs no model and no training.
+        ``use_rep``: a key of ``adata.obsm`` or an array [n_obs, D], 1 <= D <= 64 -- the representation ``plan`` was computed on (the
+        potentials mean something only there; only the two row counts can be checked).  ``plan``: the ``TransportPlan`` of
+        ``compute_transport_plan``; a plain matrix is refused (it has no potentials: ``plan.to_scipy() @ values`` is the host route).
+        ``values`` describes the other group's cells: an array [n_other, n_v] or [n_obs, n_v] (the other group's rows are then taken
+        by ``uns["groups_obs_indices"]``), or a key of ``obsm`` -- coordinates give each cell's image in the other group's space,
+        log-expression of marker genes gives cross-group imputation --, or the name of an ``obs`` column: OT label transfer.  All
+        values must be finite; more than ``ot_ops.OT_VAL_MAX`` columns are walked in slices (a column's result does not depend on
+        the slicing).
+        Returns an ndarray fp32 [n_onto, n_v]; for an ``obs`` column a DataFrame indexed by the receiving cells' ``obs_names`` (their
+        row numbers where ``adata`` has none): one probability column per category among the other group's cells, ``predicted`` (the
+        most probable category, the first on ties) and ``confidence`` (its probability).  With ``key_added`` the array (the
+        probabilities) is also written to ``obsm[key_added]`` [n_obs, n_v], NaN in the other group's rows.  Argument faults are refused
+        before any device work and before anything is written."""
+        rep = use_rep
+        if isinstance(use_rep, str):
+            obsm = getattr(adata, "obsm", None)
+            if obsm is None or use_rep not in obsm:
+                raise KeyError(f"use_rep '{use_rep}' not found in adata.obsm")
+            rep = obsm[use_rep]
+        rep = np.asarray(rep)
+        if rep.ndim == 2 and rep.shape[0] != adata.n_obs:
+            raise ValueError(f"use_rep must have one row per cell ({adata.n_obs}), got {rep.shape[0]}")
+        obs_idx, X0, X1, V, categories = check_transport_project_args(adata, rep, plan, values, onto, key_added)
+        if key_added is not None and getattr(adata, "obsm", None) is None:
+            raise ValueError("key_added needs adata.obsm")
+        if not torch.cuda.is_available():
+            raise _abi.SpvError("spvipes_amd needs an MI355X: there is no CPU fallback for the hot path")
+        from .ot_ops import OT_VAL_MAX
+        from .ot_ops import transport_project as project
+        dev, onto = torch.device(device or "cuda:0"), int(onto)
+        Xd = [torch.from_numpy(X0).to(dev), torch.from_numpy(X1).to(dev)]
+        Vd = torch.from_numpy(V).to(dev)
+        out = np.empty((len(obs_idx[onto]), V.shape[1]), dtype=np.float32)
+        for v0 in range(0, V.shape[1], OT_VAL_MAX):
+            out[:, v0:v0 + OT_VAL_MAX] = project(plan.sinkhorn, Xd[onto], Xd[1 - onto], Vd[:, v0:v0 + OT_VAL_MAX], onto)[0].cpu().numpy()
+        if key_added is not None:
+            full = np.full((adata.n_obs, V.shape[1]), np.nan, dtype=np.float32)
+            full[obs_idx[onto]] = out
+            adata.obsm[key_added] = full
+        if categories is None:
+            return out
+        names = getattr(adata, "obs_names", None)
+        return label_projection_frame(out, categories, np.asarray(names)[obs_idx[onto]] if names is not None else obs_idx[onto])
 
     # ------------------------------------------------------------------------------------------
     def _local_rows(self, g: int, indices: Sequence[int]) -> np.ndarray:

@@ -2,7 +2,8 @@
 states the contract), the log-domain Sinkhorn driver on top of them and the sparse plan it ends in.  ``spVIPES.compute_transport_plan``
 runs it on a common low-dimensional representation of the two groups; nothing of size n0 x n1 is ever stored.  ``ot_segment_lse``
 (csrc/spv_ot_segments.h) gives the untruncated plan's log mass per (cell, segment of the other group's cells) from the potentials:
-what ``cluster_ops`` / ``spVIPES.match_transport_clusters`` read."""
+what ``cluster_ops`` / ``spVIPES.match_transport_clusters`` read.  ``ot_project`` (csrc/spv_ot_project.h) pushes per-cell values of one group
+through the untruncated plan onto the other group's cells: ``transport_project`` / ``spVIPES.transport_project``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,7 +15,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import OT_DMAX, OT_KMAX, OT_SEG_MAX, OT_SPLIT_MAX, SpvOtArgs, SpvOtSegArgs, ptr, stream_ptr   # the limits: part of this module's interface
+from ._abi import (OT_DMAX, OT_KMAX, OT_SEG_MAX, OT_SPLIT_MAX, OT_VAL_MAX, SpvOtArgs, SpvOtProjArgs, SpvOtSegArgs, ptr,   # the limits: part of this module's interface
+                   stream_ptr)
 from ._scan_ops import _fill_sides, _k, _n_split, _out_pair, _rows, _sides, _workspace
 from .data import plan_union_csr
 
@@ -157,6 +159,78 @@ def ot_segment_lse(X: torch.Tensor, Y: torch.Tensor, h: torch.Tensor, seg_ptr: t
     return out[:, :n_q].t()
 
 
+def ot_project_splits(n_q: int, n_c: int, n_v: int) -> int:
+    """Chunks of the candidates spv_ot_project uses for this shape when ``n_split`` is 0: a pure function of the shapes"""
+    return int(_abi.load().spv_ot_project_splits(int(n_q), int(n_c), int(n_v)))
+
+
+def ot_project_ws_bytes(n_q: int, n_v: int, n_split: int) -> int:
+    """Bytes of workspace for ``n_split`` chunks (the resolved number, not 0): 0 for one chunk"""
+    return int(_abi.load().spv_ot_project_ws_bytes(int(n_q), int(n_v), int(n_split)))
+
+
+def ot_project_block(D: int) -> int:
+    """Value columns per column block of the kernel form that serves ``D`` columns of X / Y"""
+    return int(_abi.load().spv_ot_project_block(int(D)))
+
+
+def ot_project(X: torch.Tensor, Y: torch.Tensor, h: torch.Tensor, V: torch.Tensor, inv_eps: float, n_split: int = 0,
+               out: Optional[torch.Tensor] = None, return_lse: bool = False):
+    """For every row of ``X`` the mean of the rows of ``V`` under the weights softmax_j(t_ij), ``ot_softmin``'s t (the same bits):
+    out[i, v] = sum_j exp(t_ij) V[j, v] / sum_j exp(t_ij) -> fp32 device tensor [n_q, n_v]; with ``return_lse`` (out, L) with
+    L[i] = log sum_j exp(t_ij), fp32 [n_q].  The result is the TRANSPOSED VIEW of a value-major buffer [n_v, n_q] (the kernel's
+    layout), so ``result[:, v]`` is contiguous and ``result[i]`` is strided.  With h = psi + log b of a Sinkhorn result this is the
+    barycentric projection through the untruncated plan.
+    A t that is not finite adds nothing, whatever its row of ``V`` holds; a query without a contributing candidate gets NaN in every
+    column and L = -inf.  A column of ones comes back as exactly 1.
+    ``X`` [n_q >= 1, D], ``Y`` [n_c >= 0, D], ``h`` [n_c], ``inv_eps``: as ``ot_softmin``.  ``V``: fp32 device tensor [n_c, n_v],
+    1 <= n_v <= OT_VAL_MAX, unit column stride (the row stride may exceed n_v).
+    ``n_split``: chunks of the candidates, 0 = ``ot_project_splits(n_q, n_c, n_v)``.  For a fixed value two calls agree bit for bit, a
+    row of the result does not depend on the other rows of ``X`` and a column not on the other columns of ``V``; different values
+    agree within rounding.  L equals ``ot_softmin``'s at the same explicit ``n_split`` bit for bit.
+    ``out``: an fp32 device tensor [n_v, >= n_q] with unit column stride (value-major, as stored); the transposed view of its first
+    n_q columns is returned and nothing else is written.  With ``return_lse`` a pair (out, L) is taken too, L a contiguous fp32 device
+    tensor [>= n_q] of which the first n_q entries are written and returned."""
+    op = "ot_project"
+    dev, n_q, n_c, D = _sides(op, X, Y, ("X", "Y"))
+    _vector(h, n_c, dev, "h")
+    inv_eps = float(inv_eps)
+    if not (0.0 < inv_eps < math.inf) or not (0.0 < float(np.float32(inv_eps)) < math.inf):
+        raise ValueError(f"{op}: inv_eps must be a positive finite number in fp32, got {inv_eps!r}")
+    n_split = _n_split(op, n_split)
+    if (not isinstance(V, torch.Tensor) or not V.is_cuda or V.device != dev or V.dtype != torch.float32 or V.dim() != 2 or V.shape[0] != n_c
+            or V.shape[1] < 1 or (n_c > 0 and V.shape[1] > 1 and V.stride(1) != 1) or (n_c > 1 and V.stride(0) < V.shape[1])):
+        raise _abi.SpvError(f"{op}: V must be an fp32 device tensor [{n_c}, n_v] with unit column stride")
+    n_v = int(V.shape[1])
+    if n_v > OT_VAL_MAX:
+        raise ValueError(f"{op}: V must have between 1 and {OT_VAL_MAX} columns, got {n_v}")
+    L = None
+    if isinstance(out, (tuple, list)):
+        if len(out) != 2 or not return_lse:
+            raise _abi.SpvError(f"{op}: out must be one tensor, or with return_lse a pair (out, L)")
+        out, L = out
+        if (not isinstance(L, torch.Tensor) or not L.is_cuda or L.device != dev or L.dtype != torch.float32 or L.dim() != 1 or L.numel() < n_q
+                or not L.is_contiguous()):
+            raise _abi.SpvError(f"{op}: out L must be a contiguous fp32 device tensor with at least {n_q} entries")
+    if out is None:
+        out = torch.empty((n_v, n_q), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev or out.dtype != torch.float32 or out.dim() != 2
+          or out.shape[0] != n_v or out.shape[1] < n_q or (out.shape[1] > 1 and out.stride(1) != 1) or (n_v > 1 and out.stride(0) < n_q)):
+        raise _abi.SpvError(f"{op}: out must be an fp32 device tensor [{n_v}, >= {n_q}] with unit column stride")
+    if return_lse and L is None:
+        L = torch.empty(n_q, dtype=torch.float32, device=dev)
+    ws = _workspace(ot_project_ws_bytes(n_q, n_v, n_split or ot_project_splits(n_q, n_c, n_v)), dev)
+    a = SpvOtProjArgs()
+    _fill_sides(a, X, Y)
+    a.h, a.inv_eps, a.n_split = (ptr(h) if n_c else ptr(X)), inv_eps, n_split
+    a.V, a.ld_v, a.n_v = (ptr(V) if n_c else None), (V.stride(0) if n_c > 1 else n_v), n_v
+    a.out, a.ld_out = ptr(out), (out.stride(0) if n_v > 1 else max(n_q, int(out.shape[1])))
+    a.L, a.ws = ptr(L), ptr(ws)
+    _abi.call("spv_ot_project", C.byref(a), stream_ptr())
+    res = out[:, :n_q].t()
+    return (res, L[:n_q]) if return_lse else res
+
+
 def mean_sq_cost(X0: torch.Tensor, X1: torch.Tensor) -> float:
     """The mean of |x_i - y_j|^2 over ALL pairs in closed form from the moments, in fp64: mean|x|^2 + mean|y|^2 - 2 mean(x).mean(y).
     No pairwise pass."""
@@ -236,6 +310,24 @@ def sinkhorn(X0: torch.Tensor, X1: torch.Tensor, epsilon: float = 0.05, scale_co
                 done = True
                 break
     return SinkhornResult(phi, psi, log_a, log_b, s, scale, n_iter, err, done)
+
+
+def transport_project(res: SinkhornResult, X_q: torch.Tensor, X_c: torch.Tensor, V: torch.Tensor, side: int):
+    """The barycentric projection of the value rows ``V`` [n_c, n_v] of the candidate cells ``X_c`` onto the query cells ``X_q`` through
+    the UNTRUNCATED plan P = a b exp(phi + psi - s c) of the Sinkhorn result ``res``: out[i] = sum_j P_ij V[j] / sum_j P_ij
+    -> (out fp32 device tensor [n_q, n_v], mass host fp64 [n_q]).  ``side``: the group of the QUERIES, 0 (``X_q`` is the X0 the
+    potentials were computed on, ``X_c`` the X1) or 1 (the other way round), as ``cluster_ops.cluster_transport_log_mass``.
+    mass_i = exp(L_i + r_i), r the queries' potential plus log marginal, formed in fp64 on the host: the row mass of the untruncated
+    plan, equal to the cell's marginal at convergence -- a diagnostic.  ``V`` with at most OT_VAL_MAX columns: one ``ot_project`` call."""
+    if side not in (0, 1):
+        raise ValueError(f"side must be 0 or 1, got {side!r}")
+    pot_q, pot_c = (res.phi + res.log_a, res.psi + res.log_b)[::1 if side == 0 else -1]
+    if pot_c.shape[0] != X_c.shape[0] or pot_q.shape[0] != X_q.shape[0]:
+        raise ValueError("transport_project: the potentials' sizes must match the two sides")
+    out, L = ot_project(X_q, X_c, pot_c, V, res.inv_eps, return_lse=True)
+    with np.errstate(over="ignore"):
+        mass = np.exp(L.cpu().numpy().astype(np.float64) + pot_q.cpu().numpy().astype(np.float64))
+    return out, mass
 
 
 class TransportPlan:
