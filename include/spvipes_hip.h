@@ -757,6 +757,74 @@ int spv_silhouette_sums(const spv_silhouette_args* a, void* stream);
 int32_t spv_silhouette_splits(int32_t n_q, int32_t n_c);
 int64_t spv_silhouette_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split);
 
+/* Exact t-SNE of a layout of at most SPV_TSNE_DMAX dimensions (spVIPES.latent_tsne / spVIPES.tsne of the user API): three entry points.
+ *
+ * spv_tsne_repulsion: the all-pairs half of the gradient, nothing of size n_q x n_c stored.  For query row i of Q over the candidates C
+ *   Zrow[i] = sum_j (double) w(i, j),   F[t][i] = sum_j (double) fl32(w2(i, j) * fl32(Q[i][t] - C[j][t])),   t < D
+ * with d2 the distance of spv_knn above, the same bits, w = fl32(1 / fl32(1 + d2)) (the correctly rounded quotient) and
+ * w2 = fl32(w * w).  exclude: int32 [n_q] or NULL, with spv_knn's meaning (candidate exclude[i] is skipped for query i; a value outside
+ * [0, n_c) skips nothing).  Layout of F: DIMENSION-MAJOR, fp64 [D][ld_f] with ld_f >= n_q -- F[t * ld_f + i].  Columns >= n_q of F,
+ * rows >= n_q and columns >= D of Q / C are never touched.
+ * Order of addition: one fp64 running sum per lane and output, ascending j within a chunk of the candidates, ascending chunk across
+ * chunks, from +0; no floating-point atomics.  For fixed shapes and n_split two calls agree bit for bit, and a query's sums do not
+ * depend on the other queries of the call.  Under DIFFERENT n_split the sums may differ in the last bits of fp64, except where every
+ * partial sum is exact.  n_c == 0 gives +0 everywhere.
+ * Launches: as spv_knn -- a partial pass of (tiles of spv_knn_tile_q() queries) x (n_split chunks of the candidates) workgroups, and for
+ * n_split > 1 a merge pass over the workspace [chunk][1 + D][n_q]; n_split == 1 is ONE launch that writes Zrow / F itself.  n_split = 0
+ * stands for spv_tsne_splits(n_q, n_c), a pure function of the shapes.
+ * ws: spv_tsne_ws_bytes(n_q, D, n_split) bytes with the RESOLVED n_split (0 for n_split <= 1 or a non-positive shape; 64-bit
+ * arithmetic), 8-byte aligned, overwritten by every call.  Nothing is allocated.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null arguments / Q / C / Zrow / F; ws null when its size is not 0, or not 8-byte
+ * aligned; D outside [1, SPV_TSNE_DMAX]; n_split outside [0, SPV_KNN_SPLIT_MAX]; n_q < 1; n_c < 0; ld_q < D; ld_c < D; ld_f < n_q. */
+#define SPV_TSNE_DMAX 4
+typedef struct spv_tsne_rep_args {
+  const float* Q; int64_t ld_q; int32_t n_q;      /* queries    fp32 [n_q][ld_q], ld_q >= D */
+  const float* C; int64_t ld_c; int32_t n_c;      /* candidates fp32 [n_c][ld_c], ld_c >= D */
+  int32_t D;                                      /* 1 .. SPV_TSNE_DMAX */
+  const int32_t* exclude;                         /* [n_q] or NULL */
+  int32_t n_split;                                /* 0 = spv_tsne_splits(n_q, n_c); else 1 .. SPV_KNN_SPLIT_MAX chunks of the candidates */
+  double* Zrow;                                   /* [n_q] */
+  double* F; int64_t ld_f;                        /* [D][ld_f], ld_f >= n_q */
+  void* ws;                                       /* spv_tsne_ws_bytes(n_q, D, n_split) bytes */
+} spv_tsne_rep_args;
+int spv_tsne_repulsion(const spv_tsne_rep_args* a, void* stream);
+int32_t spv_tsne_splits(int32_t n_q, int32_t n_c);
+int64_t spv_tsne_ws_bytes(int32_t n_q, int32_t D, int32_t n_split);
+
+/* spv_tsne_affinities: the perplexity calibration.  d2 fp32 [n][ld]: per row k squared distances in ascending order as spv_knn returns
+ * them, +inf marking an empty slot (idx = -1).  Per row, one lane, fp64: d_j = d2[j] - d2[0]; a binary search for beta from 1, at most 100
+ * steps, stopping at |H - log(perplexity)| <= 1e-5, H = log S + beta T / S with S = sum_j e_j, T = sum_j d_j e_j, e_j = exp(-beta d_j) in
+ * ascending j; beta doubles (halves) while its upper (lower) bound is infinite, else goes to the midpoint (the search of scikit-learn's
+ * _binary_search_perplexity).  P[i][j] = fl32(e_j / S), fp32 [n][ld]; an empty slot gets 0 and does not count; beta fp64 [n].  A row
+ * without a finite slot gets zeros and beta = 1.  Columns >= k are never touched.  P may be d2 (in place).
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null d2 / P / beta; n < 1; k outside [1, SPV_KNN_KMAX]; ld < k; perplexity not a
+ * finite number >= 1. */
+int spv_tsne_affinities(const float* d2, float* P, int64_t ld, int32_t n, int32_t k, double perplexity, double* beta, void* stream);
+
+/* spv_tsne_update: the sparse half of the gradient and the step, two launches.  First ONE workgroup adds Zrow [n] into Z[0] in a fixed
+ * order (256 strided lane sums in ascending order, then a pairwise tree).  Then one lane per row i of the symmetric CSR matrix P
+ * (indptr int64 [n + 1], cols int32 ascending per row, vals fp32; all on the device; a column outside [0, n) is skipped):
+ *   A[t]  = sum_j (double) fl32(fl32(p_ij w_ij) fl32(y_i,t - y_j,t))     in CSR order from +0, w_ij as in spv_tsne_repulsion on y_in
+ *   g[t]  = 4 (alpha A[t] - F[t][i] / Z)                                    fp64
+ *   gain  = fl32(max(u g < 0 ? gain + 0.2 : gain * 0.8, min_gain)),  u = fl32(momentum u - lr gain g),  y_out = fl32(y_in + u)
+ * (scikit-learn's gradient descent step).  y_in / y_out fp32 [n][ld_y], two different arrays: y_in is only read; u and gain fp32
+ * [n][ld_y], updated in place.  Optional outputs: kl_row fp64 [n] = sum_j p_ij (log p_ij - log w_ij), so that KL = sum(kl_row) + log Z[0]
+ * where the entries of P sum to 1; grad fp64 [D][n] = g.  The order of addition is fixed: two calls on the same inputs agree bit for bit.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null arguments / y_in / y_out / indptr / cols / vals / Zrow / F / Z / u / gain;
+ * y_out == y_in; n < 1; D outside [1, SPV_TSNE_DMAX]; ld_y < D; ld_f < n; alpha, momentum, lr or min_gain negative or not finite. */
+typedef struct spv_tsne_upd_args {
+  const float* y_in; float* y_out; int64_t ld_y;  /* fp32 [n][ld_y], ld_y >= D */
+  int32_t n; int32_t D;                           /* rows; 1 .. SPV_TSNE_DMAX */
+  const int64_t* indptr; const int32_t* cols; const float* vals;   /* CSR P */
+  const double* Zrow; const double* F; int64_t ld_f;               /* of spv_tsne_repulsion; ld_f >= n */
+  double* Z;                                      /* [1], written */
+  float* u; float* gain;                          /* [n][ld_y], in place */
+  double alpha, momentum, lr, min_gain;           /* exaggeration, momentum, learning rate, floor of the gain */
+  double* kl_row;                                 /* [n] or NULL */
+  double* grad;                                   /* [D][n] or NULL */
+} spv_tsne_upd_args;
+int spv_tsne_update(const spv_tsne_upd_args* a, void* stream);
+
 /* The latent gradient of the two rate heads alone: what spv_dec_softmax_bwd computes into dz_part, WITHOUT the in-place correction of
  * tP / tS (a read-only pass: bf16 gradient arrays only).  Lets the caller put the write-back pass, which only the regressor
  * weight-gradient GEMMs wait for, beside the backward pass's critical chain instead of on it. */

@@ -339,6 +339,24 @@ class SpvSilhouetteArgs(C.Structure):
                 ("ws", C.c_void_p)]
 
 
+TSNE_DMAX = 4   # SPV_TSNE_DMAX
+
+
+class SpvTsneRepArgs(C.Structure):
+    """the arguments of spv_tsne_repulsion (include/spvipes_hip.h: spv_tsne_rep_args)"""
+    _fields_ = [("Q", C.c_void_p), ("ld_q", C.c_int64), ("n_q", C.c_int32), ("C", C.c_void_p), ("ld_c", C.c_int64), ("n_c", C.c_int32),
+                ("D", C.c_int32), ("exclude", C.c_void_p), ("n_split", C.c_int32), ("Zrow", C.c_void_p), ("F", C.c_void_p), ("ld_f", C.c_int64),
+                ("ws", C.c_void_p)]
+
+
+class SpvTsneUpdArgs(C.Structure):
+    """the arguments of spv_tsne_update (include/spvipes_hip.h: spv_tsne_upd_args)"""
+    _fields_ = [("y_in", C.c_void_p), ("y_out", C.c_void_p), ("ld_y", C.c_int64), ("n", C.c_int32), ("D", C.c_int32), ("indptr", C.c_void_p),
+                ("cols", C.c_void_p), ("vals", C.c_void_p), ("Zrow", C.c_void_p), ("F", C.c_void_p), ("ld_f", C.c_int64), ("Z", C.c_void_p),
+                ("u", C.c_void_p), ("gain", C.c_void_p), ("alpha", C.c_double), ("momentum", C.c_double), ("lr", C.c_double),
+                ("min_gain", C.c_double), ("kl_row", C.c_void_p), ("grad", C.c_void_p)]
+
+
 TRUNK_KMAX = 48
 
 
@@ -437,6 +455,11 @@ _SIGNATURES = {
     "spv_silhouette_sums": (C.c_int, [C.POINTER(SpvSilhouetteArgs), C.c_void_p]),
     "spv_silhouette_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_silhouette_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_tsne_repulsion": (C.c_int, [C.POINTER(SpvTsneRepArgs), C.c_void_p]),
+    "spv_tsne_splits": (C.c_int32, [C.c_int32, C.c_int32]),
+    "spv_tsne_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_tsne_affinities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "spv_tsne_update": (C.c_int, [C.POINTER(SpvTsneUpdArgs), C.c_void_p]),
     "spv_dec_dz": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_softmax_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spv_dec_heads_bwd": (C.c_int, [C.POINTER(SpvDecParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,6 +17,7 @@
 #include "spv_ot_segments.h"
 #include "spv_ot_project.h"
 #include "spv_silhouette.h"
+#include "spv_tsne.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -1070,7 +1071,7 @@ extern "C" int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
   return (int64_t)n_split * n_q * k * 8;
 }
 
-// ---- what the entry points of the pair scan share (spv_pair_scan.h): spv_knn here, spv_ot_softmin / spv_ot_topk, spv_ot_segment_lse, spv_ot_project and spv_silhouette_sums below
+// ---- what the entry points of the pair scan share (spv_pair_scan.h): spv_knn here, spv_ot_softmin / spv_ot_topk, spv_ot_segment_lse, spv_ot_project, spv_silhouette_sums and spv_tsne_repulsion below
 struct ScanPlan { int n_split, per; dim3 grid; };   // chunks (resolved), candidates per chunk, (query tiles, chunks)
 
 // What every one of them refuses about the two sides, D, n_split and ws, in `who`'s name; the chunks -- n_split, or splits(n_q, n_c) for
@@ -1282,6 +1283,74 @@ extern "C" int spv_silhouette_sums(const spv_silhouette_args* x, void* stream) {
   if (rc != SPV_OK || p.n_split == 1) return rc;
   hipLaunchKernelGGL(sil_merge_kernel, dim3(p.grid.x, (unsigned)a.n_seg), dim3(KNN_TQ), 0, s, a);
   return launch_status("spv_silhouette_sums (merge pass)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// exact t-SNE: the all-pairs half, the perplexity calibration, the sparse half with the step (spv_tsne.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_tsne_splits(int32_t n_q, int32_t n_c) { return tsne_splits(n_q, n_c); }
+extern "C" int64_t spv_tsne_ws_bytes(int32_t n_q, int32_t D, int32_t n_split) { return tsne_ws_bytes(n_q, D, n_split); }
+
+extern "C" int spv_tsne_repulsion(const spv_tsne_rep_args* x, void* stream) {
+  ScanPlan p;
+  int rc = scan_check(x, "spv_tsne_repulsion", tsne_splits, p, [&](int) {
+    if (x->D > TSNE_DMAX) return fail(SPV_ERR_ARG, "spv_tsne_repulsion: D must lie in [1, 4]%s");
+    if (!x->Zrow) return fail(SPV_ERR_ARG, "spv_tsne_repulsion: null Zrow%s");
+    if (!x->F) return fail(SPV_ERR_ARG, "spv_tsne_repulsion: null F%s");
+    if (x->ld_f < x->n_q) return fail(SPV_ERR_ARG, "spv_tsne_repulsion: ld_f < n_q%s");
+    return SPV_OK;
+  });
+  if (rc != SPV_OK) return rc;
+  const TsneArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, x->exclude, p.n_split, p.per, x->Zrow, x->F, (long)x->ld_f,
+                   (double*)x->ws};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(tsne_partial_kernel, p.grid, dim3(KNN_TQ), 0, s, a);
+  rc = launch_status(p.n_split == 1 ? "spv_tsne_repulsion" : "spv_tsne_repulsion (partial pass)");
+  if (rc != SPV_OK || p.n_split == 1) return rc;
+  hipLaunchKernelGGL(tsne_merge_kernel, dim3(p.grid.x, (unsigned)(1 + a.D)), dim3(KNN_TQ), 0, s, a);
+  return launch_status("spv_tsne_repulsion (merge pass)");
+}
+
+extern "C" int spv_tsne_affinities(const float* d2, float* P, int64_t ld, int32_t n, int32_t k, double perplexity, double* beta, void* stream) {
+  if (!d2) return fail(SPV_ERR_ARG, "spv_tsne_affinities: null d2%s");
+  if (!P) return fail(SPV_ERR_ARG, "spv_tsne_affinities: null P%s");
+  if (!beta) return fail(SPV_ERR_ARG, "spv_tsne_affinities: null beta%s");
+  if (n < 1) return fail(SPV_ERR_ARG, "spv_tsne_affinities: n < 1%s");
+  if (k < 1 || k > KNN_KMAX) return fail(SPV_ERR_ARG, "spv_tsne_affinities: k must lie in [1, 64]%s");
+  if (ld < k) return fail(SPV_ERR_ARG, "spv_tsne_affinities: ld < k%s");
+  if (!(perplexity >= 1.0 && perplexity < INFINITY)) return fail(SPV_ERR_ARG, "spv_tsne_affinities: perplexity must be a finite number >= 1%s");
+  const TsneAffArgs a{d2, P, (long)ld, n, k, log(perplexity), beta};
+  hipLaunchKernelGGL(tsne_affinities_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (hipStream_t)stream, a);
+  return launch_status("spv_tsne_affinities");
+}
+
+extern "C" int spv_tsne_update(const spv_tsne_upd_args* x, void* stream) {
+  if (!x) return fail(SPV_ERR_ARG, "spv_tsne_update: null arguments%s");
+  if (!x->y_in) return fail(SPV_ERR_ARG, "spv_tsne_update: null y_in%s");
+  if (!x->y_out) return fail(SPV_ERR_ARG, "spv_tsne_update: null y_out%s");
+  if (!x->indptr) return fail(SPV_ERR_ARG, "spv_tsne_update: null indptr%s");
+  if (!x->cols) return fail(SPV_ERR_ARG, "spv_tsne_update: null cols%s");
+  if (!x->vals) return fail(SPV_ERR_ARG, "spv_tsne_update: null vals%s");
+  if (!x->Zrow) return fail(SPV_ERR_ARG, "spv_tsne_update: null Zrow%s");
+  if (!x->F) return fail(SPV_ERR_ARG, "spv_tsne_update: null F%s");
+  if (!x->Z) return fail(SPV_ERR_ARG, "spv_tsne_update: null Z%s");
+  if (!x->u) return fail(SPV_ERR_ARG, "spv_tsne_update: null u%s");
+  if (!x->gain) return fail(SPV_ERR_ARG, "spv_tsne_update: null gain%s");
+  if (x->y_out == x->y_in) return fail(SPV_ERR_ARG, "spv_tsne_update: y_out must not be y_in%s");
+  if (x->n < 1) return fail(SPV_ERR_ARG, "spv_tsne_update: n < 1%s");
+  if (x->D < 1 || x->D > TSNE_DMAX) return fail(SPV_ERR_ARG, "spv_tsne_update: D must lie in [1, 4]%s");
+  if (x->ld_y < x->D) return fail(SPV_ERR_ARG, "spv_tsne_update: ld_y < D%s");
+  if (x->ld_f < x->n) return fail(SPV_ERR_ARG, "spv_tsne_update: ld_f < n%s");
+  for (const double v : {x->alpha, x->momentum, x->lr, x->min_gain})
+    if (!(v >= 0.0 && v < INFINITY)) return fail(SPV_ERR_ARG, "spv_tsne_update: alpha, momentum, lr and min_gain must be finite and not negative%s");
+  const TsneUpdArgs a{x->y_in, x->y_out, (long)x->ld_y, x->n, x->D, (const long*)x->indptr, x->cols, x->vals, x->Zrow, x->F, (long)x->ld_f, x->Z,
+                      x->u, x->gain, x->alpha, x->momentum, x->lr, x->min_gain, x->kl_row, x->grad};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(tsne_zsum_kernel, dim3(1), dim3(TSNE_ZSUM_T), 0, s, a);
+  const int rc = launch_status("spv_tsne_update (sum of Zrow)");
+  if (rc != SPV_OK) return rc;
+  hipLaunchKernelGGL(tsne_update_kernel, dim3((unsigned)((a.n + 127) / 128)), dim3(128), 0, s, a);
+  return launch_status("spv_tsne_update");
 }
 
 extern "C" int spv_count_totals(const spv_counts* x, int32_t n_cells, int32_t G, double* total, void* stream) {

@@ -1027,6 +1027,139 @@ def check_transport_args(rep, obs_idx, k):
     return parts[0], parts[1], int(k)
 
 
+# ---- exact t-SNE (tsne_ops.tsne / model.latent_tsne / model.tsne): refusals, the symmetric affinities as CSR, the initial layout ------
+TSNE_SCHEDULE = ("early_exaggeration", "exaggeration_iter", "learning_rate", "momentum", "min_gain", "kl_every")
+
+
+def tsne_neighbors(perplexity: float, n: int) -> int:
+    """k = min(3 perplexity, KNN_KMAX, n - 1): the neighbours per cell the affinities rest on"""
+    return max(0, min(int(3 * perplexity), _abi.KNN_KMAX, int(n) - 1))
+
+
+def _number(v) -> bool:
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def check_tsne_args(n: int, perplexity=30.0, n_components=2, n_iter=1000, init="pca", seed=0, early_exaggeration=12.0, exaggeration_iter=250,
+                    learning_rate="auto", momentum=(0.5, 0.8), min_gain=0.01, kl_every=50) -> dict:
+    """The refusals of ``tsne`` / ``latent_tsne``, ahead of any device work -> the resolved settings, with ``n_neighbors`` =
+    ``tsne_neighbors(perplexity, n)`` and ``learning_rate`` = max(n / early_exaggeration / 4, 50) for "auto".  ``perplexity`` must lie in
+    [2, n_neighbors / 2]: the k-NN kernel returns at most 64 neighbours, so at most 32."""
+    n = int(n)
+    if not _number(perplexity) or perplexity < 2:
+        raise ValueError(f"perplexity must be a number >= 2, got {perplexity!r}")
+    k = tsne_neighbors(perplexity, n)
+    if perplexity > k / 2:
+        raise ValueError(f"perplexity must lie in [2, {k / 2:g}] for {n} cells: the affinities rest on k = min(3 perplexity, {_abi.KNN_KMAX}, n - 1) = {k} "
+                         f"neighbours and need k >= 2 perplexity, got {perplexity!r}")
+    if isinstance(n_components, bool) or not isinstance(n_components, (int, np.integer)) or not 1 <= int(n_components) <= _abi.TSNE_DMAX:
+        raise ValueError(f"n_components must be an integer in [1, {_abi.TSNE_DMAX}], got {n_components!r}")
+    for name, v, low in (("n_iter", n_iter, 1), ("exaggeration_iter", exaggeration_iter, 0), ("kl_every", kl_every, 1), ("seed", seed, 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < low:
+            raise ValueError(f"{name} must be an integer >= {low}, got {v!r}")
+    if isinstance(init, str):
+        if init not in ("pca", "random"):
+            raise ValueError(f"init must be 'pca', 'random' or an array [n, n_components], got {init!r}")
+    else:
+        a = np.asarray(init)
+        if a.shape != (n, int(n_components)) or not np.issubdtype(a.dtype, np.number) or not np.isfinite(a).all():
+            raise ValueError(f"init: an array must be finite and of shape ({n}, {int(n_components)}), got shape {a.shape}")
+    if not _number(early_exaggeration) or early_exaggeration < 1:
+        raise ValueError(f"early_exaggeration must be a number >= 1, got {early_exaggeration!r}")
+    if not (isinstance(learning_rate, str) and learning_rate == "auto") and (not _number(learning_rate) or learning_rate <= 0):
+        raise ValueError(f"learning_rate must be 'auto' or a positive number, got {learning_rate!r}")
+    if (not isinstance(momentum, (tuple, list)) or len(momentum) != 2 or not all(_number(m) and 0 <= m < 1 for m in momentum)):
+        raise ValueError(f"momentum must be two numbers in [0, 1): before and after the early exaggeration, got {momentum!r}")
+    if not _number(min_gain) or min_gain <= 0:
+        raise ValueError(f"min_gain must be a positive number, got {min_gain!r}")
+    lr = max(n / float(early_exaggeration) / 4.0, 50.0) if isinstance(learning_rate, str) else float(learning_rate)
+    return {"perplexity": float(perplexity), "n_neighbors": k, "n_components": int(n_components), "n_iter": int(n_iter), "seed": int(seed),
+            "early_exaggeration": float(early_exaggeration), "exaggeration_iter": int(exaggeration_iter), "learning_rate": lr,
+            "momentum": (float(momentum[0]), float(momentum[1])), "min_gain": float(min_gain), "kl_every": int(kl_every)}
+
+
+def check_tsne_schedule(schedule: dict) -> dict:
+    """``**schedule`` of ``latent_tsne`` / ``spVIPES.tsne``: only the names of ``TSNE_SCHEDULE``"""
+    unknown = sorted(set(schedule) - set(TSNE_SCHEDULE))
+    if unknown:
+        raise ValueError(f"unknown schedule argument(s) {unknown}: the schedule takes {list(TSNE_SCHEDULE)}")
+    return dict(schedule)
+
+
+def check_tsne_rep(rep, n_obs: Optional[int] = None) -> np.ndarray:
+    """``use_rep`` of ``spVIPES.tsne`` -> float32 C-contiguous [n_obs, D], 1 <= D <= KNN_DMAX, finite"""
+    rep = np.asarray(rep)
+    if rep.ndim != 2 or not np.issubdtype(rep.dtype, np.number):
+        raise ValueError(f"use_rep must be a numeric array [n_obs, D], got shape {rep.shape}")
+    if n_obs is not None and rep.shape[0] != n_obs:
+        raise ValueError(f"use_rep must have one row per cell ({n_obs}), got {rep.shape[0]}")
+    if not 1 <= rep.shape[1] <= _abi.KNN_DMAX:
+        raise ValueError(f"use_rep must have between 1 and {_abi.KNN_DMAX} columns, got {rep.shape[1]}")
+    rep = np.ascontiguousarray(rep, dtype=np.float32)
+    if not np.isfinite(rep).all():
+        raise ValueError("use_rep holds non-finite values")
+    return rep
+
+
+def tsne_symmetrize(idx, P, n: int):
+    """The joint affinities P = (P_cond + P_cond^T) / 2n as CSR (indptr int64 [n + 1], cols int32 ascending within a row, vals fp32) from
+    the conditional ones: ``idx`` int [n, k] each cell's neighbours (-1 = empty slot), ``P`` [n, k] their conditional affinities.  A pair
+    either cell lists is an entry; the sums are formed in fp64 and rounded once.  With rows of ``P`` summing to 1 the entries sum to 1."""
+    idx, P, n = np.asarray(idx), np.asarray(P, dtype=np.float64), int(n)
+    if idx.ndim != 2 or idx.shape[0] != n or P.shape != idx.shape:
+        raise ValueError(f"tsne_symmetrize: idx and P must be two arrays [{n}, k]")
+    if (idx < -1).any() or (idx >= n).any():
+        raise ValueError("tsne_symmetrize: indices must be -1 or lie in [0, n)")
+    keep = idx >= 0
+    i = np.broadcast_to(np.arange(n, dtype=np.int64)[:, None], idx.shape)[keep]
+    j = idx[keep].astype(np.int64)
+    keys = np.concatenate([i * n + j, j * n + i])
+    uniq, inverse = np.unique(keys, return_inverse=True)
+    vals = np.bincount(inverse.ravel(), weights=np.concatenate([P[keep], P[keep]]), minlength=len(uniq)) / (2.0 * n)
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(indptr, uniq // max(n, 1) + 1, 1)
+    return np.cumsum(indptr), (uniq % max(n, 1)).astype(np.int32), vals.astype(np.float32)
+
+
+def tsne_pca_layout(X, n_components: int) -> np.ndarray:
+    """The "pca" initial layout, float32 [n, n_components]: the rows of ``X`` centred and projected, in fp64, on the eigenvectors of their
+    covariance with the largest eigenvalues, each eigenvector's sign fixed so that its entry of largest magnitude (the first on ties) is
+    positive, the whole scaled so that the first column's standard deviation is 1e-4 (scikit-learn's scaling).  When X has fewer columns
+    than ``n_components`` the missing ones are zero."""
+    X = np.asarray(X, dtype=np.float64)
+    Xc = X - X.mean(axis=0, keepdims=True)
+    vals, vecs = np.linalg.eigh(Xc.T @ Xc / max(X.shape[0] - 1, 1))
+    V = vecs[:, np.argsort(-vals, kind="stable")[:n_components]]
+    lead = np.abs(V).argmax(axis=0)
+    V = V * np.where(V[lead, np.arange(V.shape[1])] < 0, -1.0, 1.0)[None, :]
+    Y = np.zeros((X.shape[0], n_components), dtype=np.float64)
+    Y[:, :V.shape[1]] = Xc @ V
+    sd = Y[:, 0].std()
+    return (Y / sd * 1e-4 if sd > 0 else Y).astype(np.float32)
+
+
+def tsne_initial_layout(init, X, n: int, n_components: int, seed: int) -> np.ndarray:
+    """float32 C-contiguous [n, n_components]: ``tsne_pca_layout(X)``, seeded normal draws scaled by 1e-4, or the given array"""
+    if isinstance(init, str) and init == "pca":
+        return np.ascontiguousarray(tsne_pca_layout(X, n_components))
+    if isinstance(init, str):
+        return np.ascontiguousarray((np.random.default_rng(seed).standard_normal((n, n_components)) * 1e-4).astype(np.float32))
+    return np.ascontiguousarray(np.asarray(init), dtype=np.float32)
+
+
+def tsne_frame(names, group_of_cell, result, perplexity: float):
+    """The frame ``latent_tsne`` returns: one row per cell, indexed by ``names``, with ``group`` and ``tsne_1`` .. ``tsne_n``; ``attrs``
+    holds ``kl_divergence``, ``kl_history``, ``perplexity`` and ``n_neighbors``."""
+    import pandas as pd
+
+    cols = {"group": np.asarray(group_of_cell).astype(np.int64)}
+    for t in range(result.embedding.shape[1]):
+        cols[f"tsne_{t + 1}"] = result.embedding[:, t]
+    frame = pd.DataFrame(cols, index=pd.Index(np.asarray(names)))
+    frame.attrs.update(kl_divergence=result.kl_divergence, kl_history=result.kl_history, perplexity=float(perplexity), n_neighbors=result.n_neighbors)
+    return frame
+
+
 # ---- silhouette widths in latent space (model.latent_silhouette / integration_scores): host-side arrangement, the per-cell values from
 # the kernel's exact sums, and the scores -- pure numpy ------
 SILHOUETTE_MAX_LABELS = _abi.SIL_SEG_MAX // 2   # two segments (group 0, group 1) per label

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, check_transport_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
+from .data import (check_tsne_args, check_tsne_rep, check_tsne_schedule, tsne_frame, MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, check_transport_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
                    csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
                    latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions,
                    ClusterMatching, check_match_clusters_args, cluster_entropy_score, cluster_pair_scores, cluster_tables_from_matrix, match_cluster_labels,
@@ -178,6 +178,32 @@ class spVIPES:
             for rows in obs_idx:
                 pos[rows] = np.arange(len(rows), dtype=np.int32)
             adata.obs["indices"] = pos
+        return result
+
+    @classmethod
+    def tsne(cls, adata, use_rep, key_added: str = "X_tsne", device: Optional[str] = None, perplexity: float = 30.0, n_components: int = 2,
+             n_iter: int = 1000, init="pca", seed: int = 0, **schedule):
+        """An exact t-SNE layout of a low-dimensional representation (PCA, or this model's latents written to ``obsm``), for looking at
+        it: ``tsne_ops.tsne`` on all cells of ``adata``; needs no model and no training.  ``use_rep``: a key of
+        ``adata.obsm`` or an array [n_obs, D], 1 <= D <= 64, finite.  Writes the fp32 layout [n_obs, n_components] to
+        ``adata.obsm[key_added]`` and returns the ``TsneResult`` (``embedding``, ``kl_divergence``, ``kl_history``, ``beta``,
+        ``n_neighbors``, ``affinities``).  ``perplexity`` in [2, 32]: the affinities rest on min(3 perplexity, 64, n - 1) exact neighbours.
+        ``n_iter`` steps are always all taken (no early stop).  ``schedule``: ``early_exaggeration``, ``exaggeration_iter``,
+        ``learning_rate``, ``momentum``, ``min_gain``, ``kl_every`` of ``tsne_ops.tsne``.  Deterministic: two calls agree bit for bit."""
+        if isinstance(use_rep, str):
+            obsm = getattr(adata, "obsm", None)
+            if obsm is None or use_rep not in obsm:
+                raise KeyError(f"use_rep '{use_rep}' not found in adata.obsm")
+            use_rep = obsm[use_rep]
+        rep = check_tsne_rep(use_rep, getattr(adata, "n_obs", None))
+        schedule = check_tsne_schedule(schedule)
+        check_tsne_args(rep.shape[0], perplexity, n_components, n_iter, init, seed, **schedule)
+        if not torch.cuda.is_available():
+            raise _abi.SpvError("spvipes_amd needs an MI355X: there is no CPU fallback for the hot path")
+        from .tsne_ops import tsne
+        dev = torch.device(device or "cuda:0")
+        result = tsne(torch.from_numpy(rep).to(dev), perplexity=perplexity, n_components=n_components, n_iter=n_iter, init=init, seed=seed, **schedule)
+        adata.obsm[key_added] = result.embedding
         return result
 
     @classmethod
@@ -961,6 +987,37 @@ class spVIPES:
         names = getattr(self.adata, "obs_names", None)
         return silhouette_frame(obs_rows if names is None else np.asarray(names)[obs_rows], group_of_cell, cats, codes, sizes,
                                 silhouette_table(S, sizes, codes, group_of_cell))
+
+    @torch.no_grad()
+    def latent_tsne(self, group_indices_list: List[List[int]], cells="both", latent: str = "shared", give_mean: bool = True, perplexity: float = 30.0,
+                    n_components: int = 2, n_iter: int = 1000, init="pca", seed: int = 0, batch_size: Optional[int] = None, _noise=None, **schedule):
+        """An exact t-SNE layout of the cells of ``cells`` in latent space, for looking at the embedding: ``tsne_ops.tsne`` on the very rows
+        ``latent_neighbors`` sees, which never leave the device.  The repulsive half of every gradient runs over
+        all pairs on the fused pair scan: no tree or grid approximation, no cells x cells matrix, and two calls agree bit for bit.
+        Returns a DataFrame with one row per cell, in ``group_indices_list`` order (group 0's cells, then group 1's), indexed by
+        ``obs_names`` (the adata row numbers without any): ``group`` and ``tsne_1`` .. ``tsne_n`` (fp32, centred).  ``attrs``:
+        ``kl_divergence`` (of the returned layout), ``kl_history`` ([steps taken, KL] every ``kl_every`` steps), ``perplexity``,
+        ``n_neighbors``.
+        ``cells``: 0, 1 or "both".  ``latent``: "shared" or "private", "private" only with ``cells`` 0 or 1.  ``give_mean``: the posterior
+        means, else one sampled embedding.  ``perplexity`` in [2, 32]: the affinities rest on each cell's min(3 perplexity, 64, n - 1)
+        exact nearest neighbours, the most the k-NN kernel returns, where scikit-learn's exact method uses all others.  ``n_components``
+        in [1, 4].  ``n_iter`` steps are always all taken: there is no early stop.  ``init``: "pca", "random" (``seed``) or an array.
+        ``schedule``: ``early_exaggeration`` (12), ``exaggeration_iter`` (250), ``learning_rate`` ("auto"), ``momentum`` ((0.5, 0.8)),
+        ``min_gain`` (0.01), ``kl_every`` (50): scikit-learn's exact-method defaults.  Non-finite latents are a ValueError.  ``_noise``
+        (tests only): as ``get_latent_representation`` takes it."""
+        groups = check_silhouette_args(cells, latent)
+        schedule = check_tsne_schedule(schedule)
+        obs_rows = np.concatenate([np.asarray(group_indices_list[g], dtype=np.int64).ravel() for g in groups])
+        group_of_cell = np.concatenate([np.full(len(group_indices_list[g]), g, dtype=np.int64) for g in groups])
+        check_tsne_args(len(obs_rows), perplexity, n_components, n_iter, init, seed, **schedule)
+        from .tsne_ops import tsne
+        z = self._latents_on_device(group_indices_list, latent, give_mean, batch_size, _noise)
+        X = z[groups[0]] if len(groups) == 1 else torch.cat([z[g] for g in groups])
+        if not bool(torch.isfinite(X).all()):
+            raise ValueError("latent_tsne: the latents hold non-finite values")
+        result = tsne(X, perplexity=perplexity, n_components=n_components, n_iter=n_iter, init=init, seed=seed, **schedule)
+        names = getattr(self.adata, "obs_names", None)
+        return tsne_frame(obs_rows if names is None else np.asarray(names)[obs_rows], group_of_cell, result, perplexity)
 
     def integration_scores(self, group_indices_list: List[List[int]], labels="cell_type", **kwargs) -> dict:
         """How well the two groups are integrated in latent space, scIB's two silhouette scores from ONE ``latent_silhouette`` call
