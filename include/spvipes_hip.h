@@ -587,6 +587,62 @@ int64_t spv_knn_ws_bytes(int32_t n_q, int32_t k, int32_t n_split);
 int32_t spv_knn_tile_q(void);
 int32_t spv_knn_tile_c(void);
 
+/* spv_knn_paged: the same search for k in [1, SPV_KNN_PAGED_KMAX], on spv_knn's arguments (the one difference is the range of k).
+ * Contract: row i of idx / dist holds the k candidates with the smallest (d, j) in lexicographic order, ascending; d is spv_knn's fp32
+ * chain, bit for bit; the exclusion, the fill (-1 / +inf) and the non-finite rules are spv_knn's.  The result is a function of
+ * (Q, C, D, k, exclude) alone: the same bit for bit for every n_split, independent of the other queries of the call, repeatable bit
+ * for bit, and its first min(k, 64) columns are what spv_knn returns for that k, bit for bit.  Columns >= k and rows >= n_q are never
+ * written.
+ * Mechanism: page p covers the columns [64 p, min(64 p + 64, k)) and is one more run of spv_knn's partial and merge passes (page 0 IS
+ * spv_knn's kernels, unchanged).  In page p >= 1 a candidate is offered only if its 64-bit key (the bits of d above j) is GREATER than
+ * the key of the query's column 64 p - 1 -- the whole key, not d alone, so a group of equal distances that straddles a page boundary
+ * splits by index.  A query whose previous page ended in an empty slot (-1 / +inf: the key after every key that can be made) gets
+ * nothing more: its remaining slots are -1 / +inf.  The `after` keys are READ FROM THE OUTPUT ARRAYS: page p reads column 64 p - 1 of
+ * idx / dist, which page p - 1 wrote earlier on the same stream, and writes columns >= 64 p only (or the workspace), so nothing a
+ * launch reads is written by it.  k <= 64 is one page: 1 or 2 launches; k = 256 is four: 4 or 8.
+ * ws: spv_knn_paged_ws_bytes(n_q, k, n_split) = n_split * n_q * min(k, 64) * 8 bytes with the RESOLVED n_split (0 for n_split <= 1 or
+ * a non-positive shape), 8-byte aligned, shared by the pages, overwritten by every call: a pure size function, nothing is allocated
+ * and no device property is queried.  n_split = 0 stands for spv_knn_splits(n_q, n_c).
+ * Rejected ahead of any HIP call with SPV_ERR_ARG, in spv_knn's words: null arguments / Q / C / idx / dist; ws null when its size is
+ * not 0, or not 8-byte aligned; D outside [1, SPV_KNN_DMAX]; k outside [1, SPV_KNN_PAGED_KMAX]; n_split outside
+ * [0, SPV_KNN_SPLIT_MAX]; n_q < 1; n_c < 0; ld_q < D; ld_c < D; ld_out < k; n_q * ld_out or n_split * n_q * min(k, 64) beyond 2^31 - 1. */
+#define SPV_KNN_PAGED_KMAX 256
+int spv_knn_paged(const spv_knn_args* a, void* stream);
+int64_t spv_knn_paged_ws_bytes(int32_t n_q, int32_t k, int32_t n_split);
+
+/* spv_lisi: the local inverse Simpson index (LISI, Korsunsky et al. 2019) of every row of a neighbour list, for up to
+ * SPV_LISI_SETS_MAX label sets on ONE perplexity calibration (spVIPES.latent_lisi / spVIPES.lisi of the user API).
+ * Inputs: idx int32 / dist fp32 [n][ld] as spv_knn_paged writes them -- dist the SQUARED distance, ascending, -1 / +inf for an empty
+ * slot --, 1 <= k <= SPV_LISI_KMAX; codes int32 [n_sets][n_c], one code per candidate row and label set.  A slot whose dist is not
+ * < +inf does not count at all.  A slot whose idx lies outside [0, n_c), or whose code is negative, counts in the calibration (its
+ * distance is real) and for NO label.
+ * Per row, in fp64: r_j = (double) fl32(sqrt(dist_j)), the correctly rounded fp32 root (the distance latent_neighbors reports);
+ * d_j = r_j - r_0 (a shift that leaves the affinities and the entropy unchanged and keeps S >= 1: the published code's underflow case
+ * does not arise; a d_j < 0 of a list that does not ascend counts as 0).  Calibration, as compute_simpson of the published code: beta
+ * = 1; H = log S + beta T / S with S = sum_j e_j, T = sum_j d_j e_j, e_j = exp(-beta d_j); stop when |H - log(perplexity)| < 1e-5 or
+ * after 50 updates; an update doubles (halves) beta while its upper (lower) bound is infinite, else takes the midpoint.  Then
+ * p_j = e_j / S, simpson = sum over the labels l of (sum_{j in l} p_j)^2, computed as sum_j p_j s_j with s_j = sum_j' p_j' [code_j' ==
+ * code_j] over the slots with a code >= 0, and lisi = 1 / simpson (+inf when no slot has a label).
+ * Outputs: lisi fp64 [n_sets][n]; beta fp64 [n]; n_valid int32 [n], the slots that count; converged int32 [n], 0 where the 50 updates
+ * ran out.  A row whose slot 0 is not finite (an empty row) gets lisi = NaN, beta = 1, n_valid = 0, converged = 0.
+ * Order of addition: one wave per row; lane l holds the slots l, l + 64, l + 128, l + 192.  S, T, simpson and n_valid: the lane adds its
+ * slots in ascending slot from +0, then the 64 lane values fold by x += shfl_xor(x, m), m = 32, 16, 8, 4, 2, 1.  s_j: j' = 0 .. k-1 in
+ * ascending j' from +0 (a slot that does not match adds +0).  No atomics; two calls agree bit for bit; a row does not depend on the
+ * other rows of the call; only equality of codes is asked, so renaming the codes leaves every bit unchanged.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null arguments / idx / dist / codes / lisi / beta / n_valid / converged; n < 1; k
+ * outside [1, SPV_LISI_KMAX]; ld < k; n_c < 0; n_sets outside [1, SPV_LISI_SETS_MAX]; perplexity not a finite number >= 1. */
+#define SPV_LISI_KMAX 256
+#define SPV_LISI_SETS_MAX 8
+typedef struct spv_lisi_args {
+  const int32_t* idx; const float* dist; int64_t ld;   /* [n][ld], ld >= k */
+  int32_t n; int32_t k;                           /* rows; 1 .. SPV_LISI_KMAX slots per row */
+  const int32_t* codes; int32_t n_c; int32_t n_sets;   /* [n_sets][n_c]; 1 .. SPV_LISI_SETS_MAX */
+  double perplexity;                              /* finite, >= 1 */
+  double* lisi;                                   /* [n_sets][n] */
+  double* beta; int32_t* n_valid; int32_t* converged;   /* [n] */
+} spv_lisi_args;
+int spv_lisi(const spv_lisi_args* a, void* stream);
+
 /* Entropic optimal transport between two point clouds (spVIPES.compute_transport_plan of the user API): the two reductions a
  * log-domain Sinkhorn iteration and a sparse plan need, over all (query, candidate) pairs, nothing of size n_q x n_c stored.
  * Per pair: c(i, j) = the distance of spv_knn above, the same bits (so c(x, y) and c(y, x) are the same bits: u and -u square

@@ -299,7 +299,18 @@ class SpvKnnArgs(C.Structure):
                 ("ld_out", C.c_int64), ("ws", C.c_void_p)]
 
 
-OT_DMAX, OT_KMAX, OT_SPLIT_MAX = 64, 64, 64   # SPV_OT_DMAX / SPV_OT_KMAX / SPV_OT_SPLIT_MAX
+KNN_PAGED_KMAX = 256   # SPV_KNN_PAGED_KMAX: spv_knn_paged takes SpvKnnArgs with k up to this
+LISI_KMAX, LISI_SETS_MAX = 256, 8   # SPV_LISI_KMAX / SPV_LISI_SETS_MAX
+
+
+class SpvLisiArgs(C.Structure):
+    """the arguments of spv_lisi (include/spvipes_hip.h: spv_lisi_args)"""
+    _fields_ = [("idx", C.c_void_p), ("dist", C.c_void_p), ("ld", C.c_int64), ("n", C.c_int32), ("k", C.c_int32), ("codes", C.c_void_p),
+                ("n_c", C.c_int32), ("n_sets", C.c_int32), ("perplexity", C.c_double), ("lisi", C.c_void_p), ("beta", C.c_void_p),
+                ("n_valid", C.c_void_p), ("converged", C.c_void_p)]
+
+
+OT_DMAX, OT_KMAX, OT_SPLIT_MAX = 64, 64, 64  # SPV_OT_DMAX / SPV_OT_KMAX / SPV_OT_SPLIT_MAX
 
 
 class SpvOtArgs(C.Structure):
@@ -439,6 +450,9 @@ _SIGNATURES = {
     "spv_knn_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "spv_knn_tile_q": (C.c_int32, []),
     "spv_knn_tile_c": (C.c_int32, []),
+    "spv_knn_paged": (C.c_int, [C.POINTER(SpvKnnArgs), C.c_void_p]),
+    "spv_knn_paged_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_lisi": (C.c_int, [C.POINTER(SpvLisiArgs), C.c_void_p]),
     "spv_ot_softmin": (C.c_int, [C.POINTER(SpvOtArgs), C.c_void_p]),
     "spv_ot_topk": (C.c_int, [C.POINTER(SpvOtArgs), C.c_void_p]),
     "spv_ot_splits": (C.c_int32, [C.c_int32, C.c_int32]),

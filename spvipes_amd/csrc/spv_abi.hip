@@ -18,6 +18,7 @@
 #include "spv_ot_project.h"
 #include "spv_silhouette.h"
 #include "spv_tsne.h"
+#include "spv_lisi.h"
 #include "spv_small.h"
 #include "spv_poe_n.h"
 
@@ -1134,6 +1135,69 @@ extern "C" int spv_knn(const spv_knn_args* x, void* stream) {
   if (rc != SPV_OK || p.n_split == 1) return rc;
   hipLaunchKernelGGL(knn_merge_kernel, dim3(p.grid.x), dim3(KNN_TQ), knn_lds_bytes(0, x->k), s, a);   // at most the 64 KiB a kernel gets unasked
   return launch_status("spv_knn (merge pass)");
+}
+
+// the same search for up to SPV_KNN_PAGED_KMAX neighbours: page 0 is spv_knn's two kernels as they are, every later page one more run
+// of them on the candidates after the previous page's last key, which the partial pass reads from the column the previous page wrote
+extern "C" int64_t spv_knn_paged_ws_bytes(int32_t n_q, int32_t k, int32_t n_split) {
+  if (n_q < 1 || k < 1 || n_split <= 1) return 0;
+  return (int64_t)n_split * n_q * (k < KNN_KMAX ? k : KNN_KMAX) * 8;
+}
+
+extern "C" int spv_knn_paged(const spv_knn_args* x, void* stream) {
+  ScanPlan p;
+  int rc = scan_check(x, "spv_knn_paged", knn_splits, p, [&](int n_split) {
+    if (!x->idx) return fail(SPV_ERR_ARG, "spv_knn_paged: null idx%s");
+    if (!x->dist) return fail(SPV_ERR_ARG, "spv_knn_paged: null dist%s");
+    if (x->k < 1 || x->k > KNN_PAGED_KMAX) return fail(SPV_ERR_ARG, "spv_knn_paged: k must lie in [1, 256]%s");
+    if (x->ld_out < x->k) return fail(SPV_ERR_ARG, "spv_knn_paged: ld_out < k%s");
+    if ((int64_t)x->n_q * x->ld_out > INT32_MAX || x->ld_out > INT32_MAX) return fail(SPV_ERR_ARG, "spv_knn_paged: n_q * ld_out exceeds 2^31 - 1%s");
+    if ((int64_t)n_split * x->n_q * (x->k < KNN_KMAX ? x->k : KNN_KMAX) > INT32_MAX)
+      return fail(SPV_ERR_ARG, "spv_knn_paged: the workspace (n_split * n_q * min(k, 64) entries) exceeds 2^31 - 1%s");
+    return SPV_OK;
+  });
+  if (rc != SPV_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  for (int page = 0; page * KNN_KMAX < x->k; ++page) {
+    const int c0 = page * KNN_KMAX, kp = knn_page_cols(x->k, page);
+    const KnnArgs a{x->Q, (long)x->ld_q, x->n_q, x->C, (long)x->ld_c, x->n_c, x->D, kp, x->exclude, p.n_split, p.per,
+                    x->idx + c0, x->dist + c0, (int)x->ld_out, (knn_key_t*)x->ws};
+    scan_dispatch(a.D, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      if (page == 0) launch_lds_upto<knn_partial_kernel<DP>>(p.grid, dim3(KNN_TQ), knn_lds_bytes(DP, KNN_KMAX), knn_lds_bytes(DP, kp), s, a);
+      else launch_lds_upto<knn_partial_kernel<DP, true>>(p.grid, dim3(KNN_TQ), knn_lds_bytes(DP, KNN_KMAX), knn_lds_bytes(DP, kp), s, a);
+    });
+    rc = launch_status(p.n_split == 1 ? "spv_knn_paged" : "spv_knn_paged (partial pass)");
+    if (rc != SPV_OK) return rc;
+    if (p.n_split == 1) continue;
+    hipLaunchKernelGGL(knn_merge_kernel, dim3(p.grid.x), dim3(KNN_TQ), knn_lds_bytes(0, kp), s, a);
+    rc = launch_status("spv_knn_paged (merge pass)");
+    if (rc != SPV_OK) return rc;
+  }
+  return SPV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// LISI on the paged neighbour lists (spv_lisi.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int spv_lisi(const spv_lisi_args* x, void* stream) {
+  if (!x) return fail(SPV_ERR_ARG, "spv_lisi: null arguments%s");
+  if (!x->idx) return fail(SPV_ERR_ARG, "spv_lisi: null idx%s");
+  if (!x->dist) return fail(SPV_ERR_ARG, "spv_lisi: null dist%s");
+  if (!x->codes) return fail(SPV_ERR_ARG, "spv_lisi: null codes%s");
+  if (!x->lisi) return fail(SPV_ERR_ARG, "spv_lisi: null lisi%s");
+  if (!x->beta) return fail(SPV_ERR_ARG, "spv_lisi: null beta%s");
+  if (!x->n_valid) return fail(SPV_ERR_ARG, "spv_lisi: null n_valid%s");
+  if (!x->converged) return fail(SPV_ERR_ARG, "spv_lisi: null converged%s");
+  if (x->n < 1) return fail(SPV_ERR_ARG, "spv_lisi: n < 1%s");
+  if (x->k < 1 || x->k > LISI_KMAX) return fail(SPV_ERR_ARG, "spv_lisi: k must lie in [1, 256]%s");
+  if (x->ld < x->k) return fail(SPV_ERR_ARG, "spv_lisi: ld < k%s");
+  if (x->n_c < 0) return fail(SPV_ERR_ARG, "spv_lisi: n_c < 0%s");
+  if (x->n_sets < 1 || x->n_sets > LISI_SETS_MAX) return fail(SPV_ERR_ARG, "spv_lisi: n_sets must lie in [1, 8]%s");
+  if (!(x->perplexity >= 1.0 && x->perplexity < INFINITY)) return fail(SPV_ERR_ARG, "spv_lisi: perplexity must be a finite number >= 1%s");
+  const LisiArgs a{x->idx, x->dist, (long)x->ld, x->n, x->k, x->codes, x->n_c, x->n_sets, log(x->perplexity), x->lisi, x->beta, x->n_valid, x->converged};
+  hipLaunchKernelGGL(lisi_kernel, dim3((unsigned)((x->n + LISI_WAVES - 1) / LISI_WAVES)), dim3(LISI_WAVES * LISI_LANES), 0, (hipStream_t)stream, a);
+  return launch_status("spv_lisi");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -62,6 +62,16 @@ __host__ __device__ __forceinline__ int knn_key_j(knn_key_t key) { return (int)(
 // (d, j) goes ahead of the entry `worst`: a distance that is not < +inf (overflow, NaN) never does
 __host__ __device__ __forceinline__ bool knn_better(float d, int j, knn_key_t worst) { return d < INFINITY && knn_key(d, j) < worst; }
 
+// ---- paging (spv_knn_paged): page p of a query's list is its columns [64 p, 64 p + 64), the best KNN_KMAX keys AFTER the last key of
+// page p - 1.  The whole key is compared, not d alone: a group of equal distances that straddles a page boundary splits by index.
+// A page that ended in an empty slot has `after` = KNN_EMPTY, which no key that can be made exceeds: such a query gets nothing more.
+constexpr int KNN_PAGED_KMAX = 256;   // SPV_KNN_PAGED_KMAX
+__host__ __device__ __forceinline__ bool knn_after(float d, int j, knn_key_t after) { return knn_key(d, j) > after; }
+// the key a page's last column holds, from the row of idx / dist as it was written (-1 / +inf gives KNN_EMPTY)
+__host__ __device__ __forceinline__ knn_key_t knn_after_key(float d, int j) { return knn_key(d, j); }
+// columns of page p for k columns in all
+__host__ __device__ __forceinline__ int knn_page_cols(int k, int p) { return k - p * KNN_KMAX < KNN_KMAX ? k - p * KNN_KMAX : KNN_KMAX; }
+
 // k empty slots at stride `st`
 __host__ __device__ __forceinline__ void knn_clear(knn_key_t* list, int st, int k) {
   for (int s = 0; s < k; ++s) list[s * st] = KNN_EMPTY;
@@ -164,7 +174,12 @@ __device__ __forceinline__ void knn_write_row(const KnnArgs& a, int i, const knn
 // reads ahead of its arithmetic and keeps the eight keys of a worst-entry round next to them: 96 registers at DP = 16, 176 at DP = 32
 // and, with two candidates in flight, 208 at DP = 64, no scratch -- 2 waves per SIMD for the two larger forms, i.e. 4 workgroups per
 // CU (the LDS allows that up to k = 32 at DP = 32).  The bound keeps any later form from going past 256.
-template <int DP>
+// PAGED (spv_knn_paged, pages >= 1): a.idx / a.dist point at the page's first column and a.k is the page's width; the query's `after`
+// key is read from the column just before it, which the previous page wrote (this launch writes only columns >= 0 of the page, or the
+// workspace: no overlap), and a candidate is offered only if knn_after.  The flag is a compile-time one: the forms without it are the
+// code they were.  The paged forms carry the 64-bit key: 105 / 178 / 210 registers, no scratch
+// (4 / 2 / 2 waves per SIMD).
+template <int DP, bool PAGED = false>
 __global__ __launch_bounds__(KNN_TQ) __attribute__((amdgpu_waves_per_eu(2))) void knn_partial_kernel(const KnnArgs a) {
   extern __shared__ __align__(16) float knn_lds[];
   float* const tile = knn_lds;                                                             // [KNN_TC][DP]
@@ -175,13 +190,19 @@ __global__ __launch_bounds__(KNN_TQ) __attribute__((amdgpu_waves_per_eu(2))) voi
   float q[DP];
   scan_load_query<DP>(a, i, live, q);
   const int ex = (live && a.exclude) ? a.exclude[i] : -1;
+  knn_key_t after = KNN_EMPTY;   // a lane without a query is offered nothing
+  if (PAGED && live) after = knn_after_key(a.dist[i * a.ld_out - 1], a.idx[i * a.ld_out - 1]);
   knn_clear(list, KNN_TQ, k);
   knn_pad(list, KNN_TQ, k);
   KnnTop top;
   knn_top_init(top);
 
   pair_scan<DP>(a, q, tile, [&](int j, int, bool in, float d2) {   // rows past the chunk's end: computed, never offered
-    if (in && j != ex && knn_better(d2, j, top.worst)) knn_keep(top, list, KNN_TQ, k, knn_key(d2, j));
+    if (PAGED) {
+      if (in && j != ex && knn_better(d2, j, top.worst) && knn_after(d2, j, after)) knn_keep(top, list, KNN_TQ, k, knn_key(d2, j));
+    } else {
+      if (in && j != ex && knn_better(d2, j, top.worst)) knn_keep(top, list, KNN_TQ, k, knn_key(d2, j));
+    }
   });
   if (!live) return;
   knn_sort(list, KNN_TQ, top.fill);

@@ -1303,6 +1303,121 @@ def silhouette_query_blocks(n: int, row_bytes: int, cap_bytes: int):
     return [(b, min(b + rows, int(n))) for b in range(0, int(n), rows)]
 
 
+# ---- LISI in latent space (model.latent_lisi / spVIPES.lisi): the refusals, the frames and scIB's scaling -- pure numpy ------
+def lisi_neighbors(perplexity: float, n: int) -> int:
+    """k = min(int(3 perplexity) - 1, n - 1): the neighbours per cell LISI rests on, the cell itself left out (89 at perplexity 30)"""
+    return min(int(3 * perplexity) - 1, int(n) - 1)
+
+
+def check_lisi_args(n: int, perplexity=30.0) -> int:
+    """The refusals of ``latent_lisi`` / ``spVIPES.lisi`` about the perplexity, ahead of any device work -> k = ``lisi_neighbors``:
+    ``perplexity`` a finite number >= 1 that gives 1 <= k <= 256 (the most the paged k-NN returns) for ``n`` cells"""
+    if not _number(perplexity) or not np.isfinite(perplexity) or perplexity < 1:
+        raise ValueError(f"perplexity must be a finite number >= 1, got {perplexity!r}")
+    k = lisi_neighbors(perplexity, n)
+    if not 1 <= k <= _abi.KNN_PAGED_KMAX:
+        raise ValueError(f"perplexity {perplexity!r} and {int(n)} cells give k = min(int(3 perplexity) - 1, n - 1) = {k} neighbours per cell: "
+                         f"k must lie in [1, {_abi.KNN_PAGED_KMAX}]")
+    return k
+
+
+def _nanmedian(v) -> float:
+    v = np.asarray(v, dtype=np.float64)
+    v = v[~np.isnan(v)]
+    return float(np.median(v)) if v.size else float("nan")
+
+
+def lisi_scaled(median: float, n: int, kind: str) -> float:
+    """scIB's scaling of a median LISI to [0, 1], larger is better: ``kind`` "ilisi": (median - 1) / (n - 1) over n groups; "clisi":
+    (n - median) / (n - 1) over n labels; NaN for n < 2"""
+    if kind not in ("ilisi", "clisi"):
+        raise ValueError(f"kind must be 'ilisi' or 'clisi', got {kind!r}")
+    if int(n) < 2:
+        return float("nan")
+    return float((median - 1.0) / (n - 1.0) if kind == "ilisi" else (n - median) / (n - 1.0))
+
+
+def lisi_frame(names, group_of_cell, categories, label_codes, ilisi, clisi, n_valid, converged, perplexity: float, k: int):
+    """The frame ``latent_lisi`` returns: one row per cell, indexed by ``names``, with ``group``, ``label`` (None without labels),
+    ``ilisi`` (``None``: the selection holds one group, a NaN column), ``clisi`` (left out when ``clisi`` is None), ``n_neighbors`` and
+    ``converged``.  ``attrs``: ``ilisi_median`` / ``clisi_median`` (nan-medians), ``ilisi_scaled`` = (median - 1) / (n_groups - 1) and
+    ``clisi_scaled`` = (n_labels - median) / (n_labels - 1) (scIB's scaling; NaN with one group / one label; the clisi entries are left
+    out without labels), ``per_label`` (indexed by the labels: ``n_group0`` / ``n_group1`` cells, median ``ilisi``, median ``clisi``;
+    None without labels), ``perplexity``, ``n_neighbors`` (= k) and ``n_unconverged``."""
+    import pandas as pd
+
+    grp = np.asarray(group_of_cell).ravel().astype(np.int64)
+    n = grp.shape[0]
+    n_groups = len(np.unique(grp))
+    il = np.full(n, np.nan) if ilisi is None or n_groups < 2 else np.asarray(ilisi, dtype=np.float64).ravel()
+    n_valid, converged = np.asarray(n_valid).ravel().astype(np.int64), np.asarray(converged).ravel().astype(bool)
+    if il.shape[0] != n or n_valid.shape[0] != n or converged.shape[0] != n:
+        raise ValueError(f"one value per cell ({n}) of ilisi, n_valid and converged")
+    cols = {"group": grp}
+    if clisi is None:
+        cols["label"] = np.full(n, None, dtype=object)
+    else:
+        cats, codes = np.asarray(categories, dtype=object), np.asarray(label_codes).ravel().astype(np.int64)
+        cl = np.asarray(clisi, dtype=np.float64).ravel()
+        if codes.shape[0] != n or cl.shape[0] != n:
+            raise ValueError(f"one value per cell ({n}) of the label codes and clisi")
+        cols["label"] = cats[codes]
+    cols["ilisi"] = il
+    if clisi is not None:
+        cols["clisi"] = cl
+    cols["n_neighbors"], cols["converged"] = n_valid, converged
+    frame = pd.DataFrame(cols, index=pd.Index(np.asarray(names)))
+    frame.attrs["ilisi_median"] = _nanmedian(il)
+    frame.attrs["ilisi_scaled"] = lisi_scaled(frame.attrs["ilisi_median"], n_groups, "ilisi")
+    frame.attrs["per_label"] = None
+    if clisi is not None:
+        frame.attrs["clisi_median"] = _nanmedian(cl)
+        frame.attrs["clisi_scaled"] = lisi_scaled(frame.attrs["clisi_median"], len(cats), "clisi")
+        frame.attrs["per_label"] = pd.DataFrame({"n_group0": [int(((codes == t) & (grp == 0)).sum()) for t in range(len(cats))],
+                                                 "n_group1": [int(((codes == t) & (grp == 1)).sum()) for t in range(len(cats))],
+                                                 "ilisi": [_nanmedian(il[codes == t]) for t in range(len(cats))],
+                                                 "clisi": [_nanmedian(cl[codes == t]) for t in range(len(cats))]}, index=pd.Index(cats))
+    frame.attrs.update(perplexity=float(perplexity), n_neighbors=int(k), n_unconverged=int((~converged).sum()))
+    return frame
+
+
+def check_lisi_keys(obs, keys, n_obs: int):
+    """``keys`` of ``spVIPES.lisi`` -> [(key, categories, codes int32 [n_obs])]: one or more column names of ``obs`` (KeyError for an
+    unknown one, ValueError for none, a repeated one or a column of another length)"""
+    keys = [keys] if isinstance(keys, str) else list(keys)
+    if not keys or not all(isinstance(key, str) for key in keys) or len(set(keys)) != len(keys):
+        raise ValueError(f"keys must be one or more distinct obs column names, got {keys!r}")
+    out = []
+    for key in keys:
+        if key not in obs:
+            raise KeyError(f"keys: adata.obs has no column {key!r}")
+        col = np.asarray(obs[key]).ravel()
+        if col.shape[0] != int(n_obs):
+            raise ValueError(f"obs[{key!r}] must hold one entry per cell ({int(n_obs)}), got {col.shape[0]}")
+        cats, codes = np.unique(col, return_inverse=True)
+        out.append((key, cats, codes.astype(np.int32)))
+    return out
+
+
+def lisi_rep_frame(names, keyed, lisi, n_valid, converged, perplexity: float, k: int):
+    """The frame ``spVIPES.lisi`` returns: one row per cell, indexed by ``names``, a ``lisi_<key>`` column per entry of ``keyed``
+    (``check_lisi_keys``; ``lisi`` [len(keyed), n_obs]), ``n_neighbors`` and ``converged``.  ``attrs``: ``lisi_<key>_median`` (nan-median)
+    and ``n_<key>`` (its distinct values) per key, ``perplexity``, ``n_neighbors`` (= k) and ``n_unconverged``."""
+    import pandas as pd
+
+    lisi = np.asarray(lisi, dtype=np.float64)
+    converged = np.asarray(converged).ravel().astype(bool)
+    if lisi.ndim != 2 or lisi.shape[0] != len(keyed):
+        raise ValueError(f"lisi must be [keys, cells] = [{len(keyed)}, n], got {lisi.shape}")
+    cols = {f"lisi_{key}": lisi[t] for t, (key, _cats, _codes) in enumerate(keyed)}
+    cols["n_neighbors"], cols["converged"] = np.asarray(n_valid).ravel().astype(np.int64), converged
+    frame = pd.DataFrame(cols, index=pd.Index(np.asarray(names)))
+    for t, (key, cats, _codes) in enumerate(keyed):
+        frame.attrs[f"lisi_{key}_median"], frame.attrs[f"n_{key}"] = _nanmedian(lisi[t]), len(cats)
+    frame.attrs.update(perplexity=float(perplexity), n_neighbors=int(k), n_unconverged=int((~converged).sum()))
+    return frame
+
+
 # ---- cluster matching across the two groups from a transport plan (model.match_transport_clusters): k-means seeding, the entropy
 # criterion that chooses a clustering, the block scores and the Hungarian matching that names the clusters -- pure numpy / scipy ------
 def kmeans_pp_init(X, K: int, seed: int) -> np.ndarray:

@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _abi
-from ._abi import KNN_DMAX, KNN_KMAX, KNN_SPLIT_MAX, SpvKnnArgs, ptr, stream_ptr   # the limits: part of this module's interface
+from ._abi import KNN_DMAX, KNN_KMAX, KNN_PAGED_KMAX, KNN_SPLIT_MAX, SpvKnnArgs, ptr, stream_ptr  # the limits: part of this module's interface
 from ._scan_ops import _WS, _fill_sides, _k, _n_split, _out_pair, _sides, _workspace   # _WS: the benchmarks clear it
 
 
@@ -50,4 +50,32 @@ def knn(Q: torch.Tensor, C_: torch.Tensor, k: int, exclude: Optional[torch.Tenso
     a.k, a.exclude, a.n_split = k, ptr(exclude), n_split
     a.idx, a.dist, a.ld_out, a.ws = ptr(idx), ptr(dist), ld_out, ptr(ws)
     _abi.call("spv_knn", C.byref(a), stream_ptr())
+    return idx[:, :k], dist[:, :k]
+
+
+def knn_paged_ws_bytes(n_q: int, k: int, n_split: int) -> int:
+    """Bytes of workspace of ``knn_paged`` for ``n_split`` chunks (the resolved number, not 0): one page's worth, 0 for one chunk"""
+    return int(_abi.load().spv_knn_paged_ws_bytes(int(n_q), int(k), int(n_split)))
+
+
+def knn_paged(Q: torch.Tensor, C_: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None, n_split: int = 0,
+              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``knn`` for 1 <= k <= KNN_PAGED_KMAX (256), spv_knn_paged: columns [64 p, 64 p + 64) are one more run of ``knn``'s kernels over the
+    candidates that come after the previous page's last (dist, idx) key.  Every convention is ``knn``'s -- the arguments, ``out``, the
+    squared fp32 distance chain, the order (dist, idx), the fill -1 / +inf, the same bits for every ``n_split`` -- and the first
+    min(k, 64) columns are what ``knn`` returns for that k, bit for bit."""
+    dev, n_q, n_c, D = _sides("knn_paged", Q, C_)
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= KNN_PAGED_KMAX:
+        raise ValueError(f"knn_paged: k must be an integer in [1, {KNN_PAGED_KMAX}], got {k!r}")
+    k, n_split = int(k), _n_split("knn_paged", n_split)
+    if exclude is not None and (not isinstance(exclude, torch.Tensor) or not exclude.is_cuda or exclude.device != dev or exclude.dtype != torch.int32
+                                or exclude.dim() != 1 or exclude.numel() != n_q or not exclude.is_contiguous()):
+        raise _abi.SpvError(f"knn_paged: exclude must be a contiguous int32 device tensor with one entry per query ({n_q})")
+    idx, dist, ld_out = _out_pair("knn_paged", out, "dist", n_q, k, dev)
+    ws = _workspace(knn_paged_ws_bytes(n_q, k, n_split or knn_splits(n_q, n_c)), dev)
+    a = SpvKnnArgs()
+    _fill_sides(a, Q, C_)
+    a.k, a.exclude, a.n_split = k, ptr(exclude), n_split
+    a.idx, a.dist, a.ld_out, a.ws = ptr(idx), ptr(dist), ld_out, ptr(ws)
+    _abi.call("spv_knn_paged", C.byref(a), stream_ptr())
     return idx[:, :k], dist[:, :k]

@@ -26,7 +26,8 @@ from .data import (check_tsne_args, check_tsne_rep, check_tsne_schedule, tsne_fr
                    latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions,
                    ClusterMatching, check_match_clusters_args, cluster_entropy_score, cluster_pair_scores, cluster_tables_from_matrix, match_cluster_labels,
                    check_transport_project_args, label_projection_frame,
-                   SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table)
+                   SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table,
+                   check_lisi_args, check_lisi_keys, lisi_frame, lisi_rep_frame)
 from .module import spVIPESmodule
 from .plan import SparsePlan
 from .train import Trainer, default_max_epochs
@@ -205,6 +206,40 @@ class spVIPES:
         result = tsne(torch.from_numpy(rep).to(dev), perplexity=perplexity, n_components=n_components, n_iter=n_iter, init=init, seed=seed, **schedule)
         adata.obsm[key_added] = result.embedding
         return result
+
+    @classmethod
+    def lisi(cls, adata, use_rep, keys, perplexity: float = 30, device: Optional[str] = None):
+        """The LISI score of every cell of ``adata`` on any low-dimensional representation, for one or more ``obs`` columns: how a user sets
+        the shared latent (written to ``obsm``) against the ``X_pca`` they started from.  Needs no model and no training; the paged exact
+        k-NN and the fused kernel of ``latent_lisi``.  ``use_rep``: a key of ``adata.obsm`` or an array
+        [n_obs, D], 1 <= D <= 64, finite.  ``keys``: an ``obs`` column name or several.  Returns a DataFrame indexed by ``obs_names`` (row
+        numbers without any) with a ``lisi_<key>`` column per key, ``n_neighbors`` and ``converged``; ``attrs``: ``lisi_<key>_median``
+        and ``n_<key>`` per key, ``perplexity``, ``n_neighbors`` (k = min(int(3 perplexity) - 1, n_obs - 1), which must lie in [1, 256])
+        and ``n_unconverged``.  Deterministic: two calls agree bit for bit."""
+        if isinstance(use_rep, str):
+            obsm = getattr(adata, "obsm", None)
+            if obsm is None or use_rep not in obsm:
+                raise KeyError(f"use_rep '{use_rep}' not found in adata.obsm")
+            use_rep = obsm[use_rep]
+        rep = check_tsne_rep(use_rep, getattr(adata, "n_obs", None))
+        n = rep.shape[0]
+        k = check_lisi_args(n, perplexity)
+        keyed = check_lisi_keys(adata.obs, keys, n)
+        if not torch.cuda.is_available():
+            raise _abi.SpvError("spvipes_amd needs an MI355X: there is no CPU fallback for the hot path")
+        from .knn_ops import knn_paged
+        from .lisi_ops import LISI_SETS_MAX, lisi
+        dev = torch.device(device or "cuda:0")
+        X = torch.from_numpy(rep).to(dev)
+        idx, d2 = knn_paged(X, X, k, exclude=torch.arange(n, dtype=torch.int32, device=dev))
+        parts = []
+        for t0 in range(0, len(keyed), LISI_SETS_MAX):   # the calibration is a function of the row alone: every call repeats its bits
+            codes = torch.as_tensor(np.stack([c for _key, _cats, c in keyed[t0:t0 + LISI_SETS_MAX]]), device=dev)
+            out, _beta, n_valid, converged = lisi(idx, d2, codes, perplexity)
+            parts.append(out.cpu().numpy())
+        names = getattr(adata, "obs_names", None)
+        return lisi_rep_frame(np.arange(n) if names is None else np.asarray(names), keyed, np.concatenate(parts), n_valid.cpu().numpy(),
+                              converged.cpu().numpy(), perplexity, k)
 
     @classmethod
     def match_transport_clusters(cls, adata, use_rep=None, plan=None, n_clusters=(4, 6, 8, 12, 16, 24, 32), cluster_key: Optional[str] = None,
@@ -1018,6 +1053,53 @@ class spVIPES:
         result = tsne(X, perplexity=perplexity, n_components=n_components, n_iter=n_iter, init=init, seed=seed, **schedule)
         names = getattr(self.adata, "obs_names", None)
         return tsne_frame(obs_rows if names is None else np.asarray(names)[obs_rows], group_of_cell, result, perplexity)
+
+    @torch.no_grad()
+    def latent_lisi(self, group_indices_list: List[List[int]], labels="cell_type", cells="both", latent: str = "shared", give_mean: bool = True,
+                    perplexity: float = 30, batch_size: Optional[int] = None, _noise=None):
+        """The LISI scores (Korsunsky et al., the Harmony paper) of every cell of ``cells`` in latent space: the effective number of groups
+        (iLISI) and of labels (cLISI) in the cell's perplexity-weighted neighbourhood, from the paged exact k-NN spv_knn_paged and the
+        fused kernel spv_lisi, which calibrates each cell once for both.  No cells x cells matrix exists at any
+        time and nothing is subsampled.  Returns a DataFrame with one row per cell, in ``group_indices_list`` order (group 0's cells, then
+        group 1's), indexed by ``obs_names`` (the adata row numbers without any):
+            group, label          the cell's group and label (label None with ``labels=None``)
+            ilisi                 LISI over group membership, in [1, 2]; NaN when ``cells`` is 0 or 1
+            clisi                 LISI over the labels, in [1, number of labels]; left out with ``labels=None``
+            n_neighbors           the neighbours that counted; converged: False where the 50 updates of the search ran out
+        Neighbours: k = min(int(3 perplexity) - 1, n - 1) per cell, itself left out: 89 at the standard perplexity 30.  ``perplexity`` must
+        give 1 <= k <= 256, else ValueError before any device work.
+        ``attrs``: ``ilisi_median`` / ``clisi_median`` (nan-medians); ``ilisi_scaled`` = (median - 1) / (n_groups - 1) and ``clisi_scaled``
+        = (n_labels - median) / (n_labels - 1), scIB's scaling to [0, 1], larger is better, NaN with one group / one label; ``per_label``:
+        a frame per label with its cells in each group and its median ``ilisi`` and ``clisi``; ``perplexity``, ``n_neighbors`` (k),
+        ``n_unconverged``.
+        ``labels`` / ``cells`` / ``latent`` / ``give_mean`` / ``batch_size`` / ``_noise``: as ``latent_silhouette`` takes them (any number
+        of distinct labels).  Non-finite latents are a ValueError.  The distances are the ones ``latent_neighbors`` reports, bit for bit;
+        every order of addition is fixed, so with ``give_mean`` two calls agree bit for bit."""
+        groups = check_silhouette_args(cells, latent)
+        obs_rows = np.concatenate([np.asarray(group_indices_list[g], dtype=np.int64).ravel() for g in groups])
+        group_of_cell = np.concatenate([np.full(len(group_indices_list[g]), g, dtype=np.int64) for g in groups])
+        n = len(obs_rows)
+        if n < 1:
+            raise ValueError("latent_lisi: the selection has no cells")
+        k = check_lisi_args(n, perplexity)
+        cats = codes = None
+        if labels is not None:
+            if not isinstance(labels, str) and np.asarray(labels).ravel().shape[0] != n:
+                raise ValueError(f"labels: an array must hold one label per cell of the selection ({n}), got {np.asarray(labels).ravel().shape[0]}")
+            cats, codes = np.unique(group_cell_labels(self.adata.obs, labels, obs_rows, groups[0]), return_inverse=True)
+        from .knn_ops import knn_paged
+        from .lisi_ops import lisi
+        z = self._latents_on_device(group_indices_list, latent, give_mean, batch_size, _noise)
+        X = z[groups[0]] if len(groups) == 1 else torch.cat([z[g] for g in groups])
+        if not bool(torch.isfinite(X).all()):
+            raise ValueError("latent_lisi: the latents hold non-finite values")
+        idx, d2 = knn_paged(X, X, k, exclude=torch.arange(n, dtype=torch.int32, device=self.device))
+        sets = [group_of_cell] + ([] if codes is None else [codes])
+        out, _beta, n_valid, converged = lisi(idx, d2, torch.as_tensor(np.stack(sets).astype(np.int32), device=self.device), perplexity)
+        out = out.cpu().numpy()
+        names = getattr(self.adata, "obs_names", None)
+        return lisi_frame(obs_rows if names is None else np.asarray(names)[obs_rows], group_of_cell, cats, codes, out[0] if len(groups) > 1 else None,
+                          None if codes is None else out[1], n_valid.cpu().numpy(), converged.cpu().numpy(), perplexity, k)
 
     def integration_scores(self, group_indices_list: List[List[int]], labels="cell_type", **kwargs) -> dict:
         """How well the two groups are integrated in latent space, scIB's two silhouette scores from ONE ``latent_silhouette`` call
