@@ -813,6 +813,41 @@ int spv_silhouette_sums(const spv_silhouette_args* a, void* stream);
 int32_t spv_silhouette_splits(int32_t n_q, int32_t n_c);
 int64_t spv_silhouette_ws_bytes(int32_t n_q, int32_t n_seg, int32_t n_split);
 
+/* The fp64 Gram of an fp32 block (spVIPES.get_feature_correlation_matrix of the user API): over the counted rows r of x
+ *   sums[j] += sum_r (double) x[r][j]          gram[i][j] += sum_r (double) x[r][i] * (double) x[r][j],   i, j < n, BOTH triangles
+ * Every x is widened to fp64 first, so every product is exact; the sums run in v_mfma_f64_16x16x4_f64 accumulators with the rows fed
+ * in ascending order, and the tables carry summation error only: every element lies within gamma_m (|start| + sum |x_i x_j|) of the
+ * exact value, gamma_m = m u / (1 - m u), u = 2^-53, m = n_use + slabs + 1.
+ * rows: NULL -- rows 0 .. n_rows - 1 count and n_use is ignored -- or n_use strictly ascending row numbers in [0, n_rows) ON THE
+ * DEVICE.  They cannot be checked from the host: a number outside the block is clamped into it (a wrong row is added, nothing outside
+ * x is read), a repeated one is counted as often as it is listed.  Rows that are not listed and columns >= n of x are never read and
+ * may hold NaN.
+ * Both tables ACCUMULATE: zero them once, then one pair collects a whole walk.  gram[i][j] and its mirror gram[j][i] take the same
+ * addend -- the upper triangle is computed, diagonal tiles included, and stored twice -- so a table that is symmetric in bits stays so.
+ * Columns >= n of gram's rows are never touched.
+ * No floating-point atomics and every order fixed: one workgroup owns one 64 x 64 tile of the upper triangle and one slab of the counted
+ * rows; with spv_gram_slabs(n, n_use) > 1 the partial tiles go to ws and a merge launch of the same call adds them in ascending slab
+ * order from +0, then onto the tables.  Each table element has one writer.  The slab count is a pure function of (n, n_use): two calls
+ * agree bit for bit.  One slab (always at n >= 2048) is ONE launch and needs no workspace.
+ * ws: spv_gram_ws_bytes(n, n_use) bytes (at most 32 537 600, at n = 1984; 0 for one slab), 8-byte aligned, overwritten by every call;
+ * nothing beyond those bytes is touched.  Nothing is allocated.
+ * n_use == 0, or rows == NULL with n_rows == 0: success, nothing changes.
+ * Rejected ahead of any HIP call with SPV_ERR_ARG: null arguments / x / sums / gram; n outside [1, SPV_GRAM_MAX_N]; n_rows < 0;
+ * n_use < 0 (with rows); ld_x < n; ld_gram < n; x not 4-byte aligned; sums, gram or ws not 8-byte aligned; ws null or ws_bytes short
+ * when the shape needs a workspace. */
+#define SPV_GRAM_MAX_N 4096
+typedef struct spv_gram_args {
+  const float* x; int64_t ld_x; int32_t n_rows;   /* fp32 block [n_rows][ld_x >= n], unit column stride */
+  const int32_t* rows; int32_t n_use;             /* NULL, or n_use strictly ascending row numbers in [0, n_rows) on the device */
+  int32_t n;                                      /* columns, 1 .. SPV_GRAM_MAX_N */
+  double* sums;                                   /* [n] */
+  double* gram; int64_t ld_gram;                  /* [n][ld_gram >= n] */
+  void* ws; uint64_t ws_bytes;                    /* spv_gram_ws_bytes(n, n_use) bytes or more */
+} spv_gram_args;
+int spv_gram_f64(const spv_gram_args* a, void* stream);
+int32_t spv_gram_slabs(int32_t n, int32_t n_use);   /* row slabs used for this shape; a function of (n, n_use) only */
+uint64_t spv_gram_ws_bytes(int32_t n, int32_t n_use);
+
 /* Exact t-SNE of a layout of at most SPV_TSNE_DMAX dimensions (spVIPES.latent_tsne / spVIPES.tsne of the user API): three entry points.
  *
  * spv_tsne_repulsion: the all-pairs half of the gradient, nothing of size n_q x n_c stored.  For query row i of Q over the candidates C

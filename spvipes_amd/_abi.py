@@ -350,6 +350,15 @@ class SpvSilhouetteArgs(C.Structure):
                 ("ws", C.c_void_p)]
 
 
+GRAM_MAX_N = 4096   # SPV_GRAM_MAX_N
+
+
+class SpvGramArgs(C.Structure):
+    """the arguments of spv_gram_f64 (include/spvipes_hip.h: spv_gram_args)"""
+    _fields_ = [("x", C.c_void_p), ("ld_x", C.c_int64), ("n_rows", C.c_int32), ("rows", C.c_void_p), ("n_use", C.c_int32), ("n", C.c_int32),
+                ("sums", C.c_void_p), ("gram", C.c_void_p), ("ld_gram", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_uint64)]
+
+
 TSNE_DMAX = 4   # SPV_TSNE_DMAX
 
 
@@ -469,6 +478,9 @@ _SIGNATURES = {
     "spv_silhouette_sums": (C.c_int, [C.POINTER(SpvSilhouetteArgs), C.c_void_p]),
     "spv_silhouette_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_silhouette_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spv_gram_f64": (C.c_int, [C.POINTER(SpvGramArgs), C.c_void_p]),
+    "spv_gram_slabs": (C.c_int32, [C.c_int32, C.c_int32]),
+    "spv_gram_ws_bytes": (C.c_uint64, [C.c_int32, C.c_int32]),
     "spv_tsne_repulsion": (C.c_int, [C.POINTER(SpvTsneRepArgs), C.c_void_p]),
     "spv_tsne_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_tsne_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -17,6 +17,7 @@
 #include "spv_ot_segments.h"
 #include "spv_ot_project.h"
 #include "spv_silhouette.h"
+#include "spv_gram.h"
 #include "spv_tsne.h"
 #include "spv_lisi.h"
 #include "spv_small.h"
@@ -1347,6 +1348,43 @@ extern "C" int spv_silhouette_sums(const spv_silhouette_args* x, void* stream) {
   if (rc != SPV_OK || p.n_split == 1) return rc;
   hipLaunchKernelGGL(sil_merge_kernel, dim3(p.grid.x, (unsigned)a.n_seg), dim3(KNN_TQ), 0, s, a);
   return launch_status("spv_silhouette_sums (merge pass)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// the fp64 Gram of an fp32 block (spv_gram.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_gram_slabs(int32_t n, int32_t n_use) { return gram_slabs(n, n_use); }
+extern "C" uint64_t spv_gram_ws_bytes(int32_t n, int32_t n_use) { return (uint64_t)gram_ws_bytes(n, n_use); }
+
+extern "C" int spv_gram_f64(const spv_gram_args* x, void* stream) {
+  if (!x) return fail(SPV_ERR_ARG, "spv_gram_f64: null arguments%s");
+  if (!x->x) return fail(SPV_ERR_ARG, "spv_gram_f64: null x%s");
+  if (!x->sums) return fail(SPV_ERR_ARG, "spv_gram_f64: null sums%s");
+  if (!x->gram) return fail(SPV_ERR_ARG, "spv_gram_f64: null gram%s");
+  if (x->n < 1 || x->n > GRAM_MAX_N) return fail(SPV_ERR_ARG, "spv_gram_f64: n must lie in [1, 4096]%s");
+  if (x->n_rows < 0) return fail(SPV_ERR_ARG, "spv_gram_f64: n_rows < 0%s");
+  if (x->rows && x->n_use < 0) return fail(SPV_ERR_ARG, "spv_gram_f64: n_use < 0%s");
+  if (x->ld_x < x->n) return fail(SPV_ERR_ARG, "spv_gram_f64: ld_x < n%s");
+  if (x->ld_gram < x->n) return fail(SPV_ERR_ARG, "spv_gram_f64: ld_gram < n%s");
+  if (reinterpret_cast<uintptr_t>(x->x) & 3) return fail(SPV_ERR_ARG, "spv_gram_f64: x must be 4-byte aligned%s");
+  if (reinterpret_cast<uintptr_t>(x->sums) & 7) return fail(SPV_ERR_ARG, "spv_gram_f64: sums must be 8-byte aligned%s");
+  if (reinterpret_cast<uintptr_t>(x->gram) & 7) return fail(SPV_ERR_ARG, "spv_gram_f64: gram must be 8-byte aligned%s");
+  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "spv_gram_f64: ws must be 8-byte aligned%s");
+  const int n_use = x->rows ? x->n_use : x->n_rows;
+  const int slabs = gram_slabs(x->n, n_use);
+  const uint64_t need = (uint64_t)gram_ws_doubles(x->n, slabs) * 8;
+  if (need && !x->ws) return fail(SPV_ERR_ARG, "spv_gram_f64: null ws%s");
+  if (x->ws_bytes < need) return fail(SPV_ERR_ARG, "spv_gram_f64: ws_bytes is less than spv_gram_ws_bytes(n, n_use)%s");
+  if (n_use == 0 || x->n_rows == 0) return SPV_OK;   // nothing is counted: nothing changes
+  const int nt = gram_tiles(x->n), tiles = gram_tri_tiles(nt);
+  const GramArgs a{x->x, (long)x->ld_x, x->n_rows, x->rows, n_use, x->n, x->sums, x->gram, (long)x->ld_gram, (double*)x->ws,
+                   slabs, gram_slab_rows(n_use, slabs), nt, tiles};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(gram_partial_kernel, dim3((unsigned)tiles, (unsigned)slabs), dim3(GRAM_THREADS), 0, s, a);
+  int rc = launch_status(slabs == 1 ? "spv_gram_f64" : "spv_gram_f64 (partial pass)");
+  if (rc != SPV_OK || slabs == 1) return rc;
+  hipLaunchKernelGGL(gram_merge_kernel, dim3((unsigned)tiles, GRAM_T * GRAM_T / GRAM_THREADS), dim3(GRAM_THREADS), 0, s, a);
+  return launch_status("spv_gram_f64 (merge pass)");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -463,30 +463,42 @@ def vs_rest_frames(tables, index):
     return pd.concat([pd.DataFrame(table, index=index).assign(comparison=f"{name} vs Rest", group1=name, group2="Rest") for name, table in tables])
 
 
+def _first_positions(gi: np.ndarray) -> dict:
+    """adata row number -> its first position within ``gi``"""
+    where = {}
+    for i, c in enumerate(gi.tolist()):
+        where.setdefault(c, i)
+    return where
+
+
+def _population_positions(where: dict, idx, name: str, group: int) -> np.ndarray:
+    """One population given as adata row numbers -> positions (``where``: ``_first_positions``).  ValueError for anything but integers, an
+    empty population, a cell that is not in the group (naming it) and a cell listed twice."""
+    arr = np.asarray(idx)
+    if arr.dtype == bool or (arr.size and not np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError(f"{name} must hold adata row numbers (integers), got dtype {arr.dtype}")
+    arr = arr.astype(np.int64).ravel()
+    if arr.size == 0:
+        raise ValueError(f"{name} is empty: a population needs at least one cell")
+    for c in arr.tolist():
+        if c not in where:
+            raise ValueError(f"{name}: cell {c} is not in group_indices_list[{group}]")
+    if len(set(arr.tolist())) != arr.size:
+        u, k = np.unique(arr, return_counts=True)
+        raise ValueError(f"{name}: cell {int(u[k > 1][0])} is listed more than once")
+    return np.array([where[c] for c in arr.tolist()], dtype=np.int64)
+
+
 def de_populations(group_indices, idx1, idx2=None, group: int = 0):
     """The two populations of differential_expression as POSITIONS within ``group_indices`` (= ``group_indices_list[group]``, adata row
     numbers; position i is row i of what the read-out methods return for the group).  ``idx1`` / ``idx2``: adata row numbers;
     ``idx2=None`` takes every cell of ``group_indices`` that is not in ``idx1``.  ValueError for a cell that is not in
     ``group_indices`` (naming it), a cell listed twice, overlapping populations and an empty population."""
     gi = np.asarray(group_indices).astype(np.int64).ravel()
-    where = {}
-    for i, c in enumerate(gi.tolist()):
-        where.setdefault(c, i)
+    where = _first_positions(gi)
 
     def resolve(idx, name):
-        arr = np.asarray(idx)
-        if arr.dtype == bool or (arr.size and not np.issubdtype(arr.dtype, np.integer)):
-            raise ValueError(f"{name} must hold adata row numbers (integers), got dtype {arr.dtype}")
-        arr = arr.astype(np.int64).ravel()
-        if arr.size == 0:
-            raise ValueError(f"{name} is empty: a population needs at least one cell")
-        for c in arr.tolist():
-            if c not in where:
-                raise ValueError(f"{name}: cell {c} is not in group_indices_list[{group}]")
-        if len(set(arr.tolist())) != arr.size:
-            u, k = np.unique(arr, return_counts=True)
-            raise ValueError(f"{name}: cell {int(u[k > 1][0])} is listed more than once")
-        return np.array([where[c] for c in arr.tolist()], dtype=np.int64)
+        return _population_positions(where, idx, name, group)
 
     p1 = resolve(idx1, "idx1")
     if idx2 is None:
@@ -901,6 +913,72 @@ def expression_stats_frame(names, sizes, index, table, n_samples: int, sums=None
     if sums is not None:
         frame.attrs["sums"] = np.asarray(sums)
     return frame
+
+
+# ---- gene-gene correlation (model.get_feature_correlation_matrix): refusals, the counted cells and the host arithmetic -----------
+CORRELATION_MAX_GENES = 4096   # SPV_GRAM_MAX_N
+
+
+def check_correlation_args(correlation_type, n_sel: Optional[int] = None) -> None:
+    """The refusals of ``get_feature_correlation_matrix`` that are its own, ahead of any device work: ``correlation_type`` "pearson";
+    "spearman" is a NotImplementedError (ranks need a gene's whole column, which the streaming reduction never holds), anything else a
+    ValueError; more than 4096 selected genes a ValueError naming the table they would need."""
+    if isinstance(correlation_type, str) and correlation_type == "spearman":
+        raise NotImplementedError("correlation_type='spearman' is not implemented: ranks need every value of a gene at once, and the read-out "
+                                  "streams the cells through one Gram table; use 'pearson'")
+    if not isinstance(correlation_type, str) or correlation_type != "pearson":
+        raise ValueError(f"correlation_type must be 'pearson' (or 'spearman', which is not implemented), got {correlation_type!r}")
+    if n_sel is not None and n_sel > CORRELATION_MAX_GENES:
+        raise ValueError(f"{n_sel} genes selected: the fp64 table of their pairs would take n_sel^2 x 8 = {n_sel * n_sel * 8} bytes on the device; "
+                         f"select at most {CORRELATION_MAX_GENES} genes (gene_list)")
+
+
+def correlation_cells(group_indices, cells=None, group: int = 0) -> np.ndarray:
+    """Which positions of ``group_indices`` (= ``group_indices_list[group]``) ``get_feature_correlation_matrix`` counts -> a bool mask over
+    them.  ``cells``: None (every position) or adata row numbers, resolved like ``idx1`` of ``de_populations`` with its errors (named
+    ``cells``): not integers, empty, a cell outside the group, a cell listed twice."""
+    gi = np.asarray(group_indices).astype(np.int64).ravel()
+    if cells is None:
+        return np.ones(len(gi), dtype=bool)
+    mask = np.zeros(len(gi), dtype=bool)
+    mask[_population_positions(_first_positions(gi), cells, "cells", group)] = True
+    return mask
+
+
+def correlation_table(sums, gram, n) -> dict:
+    """Pearson correlation from the one-pass sums of ``n`` observations, pure float64 numpy: ``sums`` S [p] = sum x_i, ``gram`` C [p, p] =
+    sum x_i x_j ->
+        "mean" S / n                                  "cov"  (C - S S^T / n) / (n - 1)
+        "var"  the diagonal of cov, clamped at 0      "corr" cov_ij / sqrt(var_i var_j), clipped to [-1, 1]
+    The diagonal of corr is exactly 1 where var > 0; corr is NaN wherever var_i or var_j is 0; mean is NaN for n < 1 and cov, var
+    and corr for n < 2.  A symmetric C gives symmetric tables in bits (a * b is b * a).
+    Limit of the one-pass formula ("Limits"): C - S S^T / n is the difference of two numbers of size n mean^2, each
+    known to about n 2^-53 of itself, so a gene's variance -- and every correlation with it -- is lost once its relative spread
+    std / |mean| falls below about 2 sqrt(n 2^-53) (4e-6 for a million cells).  Such a gene comes out with var 0 and NaN correlations
+    or with noise; it is not diagnosed."""
+    S, Cm = np.asarray(sums), np.asarray(gram)
+    if S.dtype != np.float64 or S.ndim != 1 or Cm.dtype != np.float64 or Cm.shape != (S.shape[0], S.shape[0]):
+        raise ValueError(f"sums must be a float64 vector [p] and gram a float64 matrix [p, p], got {S.dtype} {S.shape} and {Cm.dtype} {Cm.shape}")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 0:
+        raise ValueError(f"n must be a non-negative integer, got {n!r}")
+    n, p = int(n), S.shape[0]
+    nan_v, nan_m = np.full(p, np.nan), np.full((p, p), np.nan)
+    if n < 1:
+        return {"mean": nan_v, "cov": nan_m, "var": nan_v.copy(), "corr": nan_m.copy()}
+    mean = S / n
+    if n < 2:
+        return {"mean": mean, "cov": nan_m, "var": nan_v, "corr": nan_m.copy()}
+    cov = (Cm - np.outer(S, S) / n) / (n - 1)
+    var = np.maximum(np.diagonal(cov), 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sd = np.sqrt(var)
+        corr = np.clip(cov / np.outer(sd, sd), -1.0, 1.0)   # (the product of the roots: var_i var_j may leave fp64's range)
+    dead = var <= 0.0
+    corr[dead, :] = np.nan
+    corr[:, dead] = np.nan
+    live = np.nonzero(~dead)[0]
+    corr[live, live] = 1.0
+    return {"mean": mean, "cov": cov, "var": var, "corr": corr}
 
 
 # ---- neighbours in latent space (model.latent_neighbors / transfer_labels): host-side argument handling and the label vote ------

@@ -27,7 +27,8 @@ from .data import (check_tsne_args, check_tsne_rep, check_tsne_schedule, tsne_fr
                    ClusterMatching, check_match_clusters_args, cluster_entropy_score, cluster_pair_scores, cluster_tables_from_matrix, match_cluster_labels,
                    check_transport_project_args, label_projection_frame,
                    SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table,
-                   check_lisi_args, check_lisi_keys, lisi_frame, lisi_rep_frame)
+                   check_lisi_args, check_lisi_keys, lisi_frame, lisi_rep_frame,
+                   check_correlation_args, correlation_cells, correlation_table)
 from .module import spVIPESmodule
 from .plan import SparsePlan
 from .train import Trainer, default_max_epochs
@@ -902,6 +903,68 @@ class spVIPES:
         sums = stats.cpu().numpy()
         table = expression_stats_table(sums, [sizes[k] * n_samples for k in range(n_seg)])
         return expression_stats_frame(names, sizes, index, table, n_samples, sums=sums)
+
+    @torch.no_grad()
+    def get_feature_correlation_matrix(self, group_indices_list: List[List[int]], group: int, gene_list=None, cells=None, component: str = "mixture",
+                                       library_size="latent", n_samples: int = 1, use_mean: bool = True, correlation_type: str = "pearson",
+                                       batch_size: Optional[int] = None, _noise=None):
+        """Which genes of ONE group the model moves together (scvi-tools' ``get_feature_correlation_matrix``): the Pearson correlation
+        of the decoded expression over the cells, a pandas DataFrame [n_sel, n_sel] labelled on both axes by the selected genes' names
+        as ``get_loadings`` labels them (their positions when the AnnData has none).  ``component`` separates the question the way
+        ``get_normalized_expression`` separates the values: "mixture" correlates the mixture's mean, "private" / "shared" the part of
+        it the private / the shared factors drive, "mixing" the mixing weight.
+
+        ``attrs``: ``mean`` and ``var`` (unbiased) of every selected gene, ``n_cells``, ``n_samples`` and ``sums`` = {"S": [n_sel],
+        "C": [n_sel, n_sel]}, the fp64 tables sum x_i and sum x_i x_j everything is derived from (``data.correlation_table``: cov =
+        (C - S S^T / n) / (n - 1) with n = n_cells * n_samples; a gene without variance has NaN in its row and column, the diagonal is
+        exactly 1 elsewhere; the one-pass formula loses a gene whose relative spread is below about 2 sqrt(n 2^-53)).
+
+        The correlated values are the very fp32 numbers ``get_normalized_expression(group_indices_list, gene_list, library_size,
+        component, n_samples=1, use_mean, batch_size)`` returns for those cells (same minibatch walk, same kernel), but no [n_cells,
+        n_sel] matrix is stored or copied: per step ONE [batch, n_sel] fp32 block is decoded on the device (``module.
+        expected_expression``, reused from step to step) and ONE HIP entry point (spv_gram_f64, an fp64 MFMA kernel) adds its counted
+        rows into the two tables.  Every product of two fp32 values is exact in fp64, so the tables carry summation error only.  Only
+        S and C leave the device.
+        ``gene_list``: None or this group's selection, as ``differential_expression`` takes it; at most 4096 genes (the table is
+        n_sel^2 x 8 bytes).  ``cells``: None (all of ``group_indices_list[group]``) or adata row numbers of cells of it, resolved like
+        ``idx1`` of ``differential_expression`` with its errors; ALL cells are still walked -- a cell's latents depend on its minibatch
+        mates -- and only steps without a counted cell are skipped.  ``library_size`` / ``use_mean`` / ``n_samples``:
+        ``get_normalized_expression``'s rules; with sampled latents every draw adds its block (``draw = step * n_samples + sample``),
+        so the correlation runs over n_cells * n_samples rows, scvi-tools' flattening.  ``correlation_type``: "pearson"; "spearman"
+        is a NotImplementedError (ranks need a gene's whole column).
+        Reproducibility: no floating-point atomics, every order of addition fixed: two calls with the same arguments agree bit for
+        bit, and the frame is symmetric in bits.  ``_noise`` (tests only): as ``get_normalized_expression`` takes it."""
+        import pandas as pd
+
+        from .gram_ops import gram_accumulate, gram_workspace
+
+        check_correlation_args(correlation_type)
+        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
+        g = check_group(group)
+        counted = correlation_cells(group_indices_list[g], cells, group=g)
+        n_g = len(counted)
+        _sel, dev_sel, n_sel, index = self._genes(g, gene_list, own=True)
+        check_correlation_args(correlation_type, n_sel)
+        S = torch.zeros(n_sel, dtype=torch.float64, device=self.device)
+        Cm = torch.zeros((n_sel, n_sel), dtype=torch.float64, device=self.device)
+        blk = ws = None
+        for step, tensors, B, _off, pos in walk_positions(self._eval_minibatches(group_indices_list, batch_size, None), g, n_g):
+            use = np.nonzero((pos >= 0) & counted[np.maximum(pos, 0)])[0]   # a cut row (pos -1) is never counted
+            if not use.size:
+                continue   # eval mode: steps are independent of each other
+            rows = None if use.size == B[g] else torch.as_tensor(use.astype(np.int32), device=self.device)
+            if blk is None or blk.shape[0] < B[g]:
+                blk = torch.empty((B[g], n_sel), dtype=torch.float32, device=self.device)
+                ws = gram_workspace(n_sel, B[g], self.device)   # the largest a step of this walk can need: it grows with the counted rows
+            for _smp, out in self._draws(step, tensors, B, n_samples, _noise):
+                x = self.module.expected_expression(out, g, genes=dev_sel, what=component, library_size=library_size, use_mean=use_mean, out=blk)
+                gram_accumulate(x, rows=rows, sums=S, gram=Cm, ws=ws)
+        n_cells = int(counted.sum())
+        sums = {"S": S.cpu().numpy(), "C": Cm.cpu().numpy()}
+        table = correlation_table(sums["S"], sums["C"], n_cells * n_samples)
+        frame = pd.DataFrame(table["corr"], index=index, columns=index)
+        frame.attrs.update(mean=table["mean"], var=table["var"], n_cells=n_cells, n_samples=n_samples, sums=sums)
+        return frame
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
