@@ -848,6 +848,64 @@ int spv_gram_f64(const spv_gram_args* a, void* stream);
 int32_t spv_gram_slabs(int32_t n, int32_t n_use);   /* row slabs used for this shape; a function of (n, n_use) only */
 uint64_t spv_gram_ws_bytes(int32_t n, int32_t n_use);
 
+/* Rank sums of the OBSERVED counts (spVIPES.rank_genes_groups of the user API: the Wilcoxon / Mann-Whitney rank-sum test of every
+ * label against the rest): a segmented column sort with tie runs.  The kernels work on a LIST of n positions, 1 <= n <= SPV_RANK_MAX_N.
+ * Position p names the cell x.rows[p - pos_off] (x.rows == NULL: cell p - pos_off) of a dense matrix that holds the positions
+ * [pos_off, pos_off + n_piece) -- spv_count_stats' addressing -- and carries a segment code seg[p] (int32 [n]; n_seg <=
+ * SPV_RANK_MAX_SEG) and an optional weight w[p] (fp32 [n], indexed by LIST POSITION, NULL = none).  A call covers a slab of n_sel <=
+ * spv_rank_gene_slab() selected genes (genes int32 [n_sel] with ids in [0, G), repeats allowed; NULL: genes 0 .. n_sel - 1, n_sel <= G).
+ * Key: for selected gene j the key of position p is the fp32 value key = (float) c * w[p], ONE fp32 multiply that is never contracted
+ * with anything ((float) c without w), c = the count of gene genes[j] in the cell: uint16, or a non-negative finite fp32.  Negative or
+ * NaN counts and negative weights are outside the contract.  Keys are non-negative: their bit pattern orders them; every zero key
+ * (also 0 * w and c * 0) is the one pattern 0.
+ * Outputs, per selected gene j, WRITTEN (not accumulated); columns >= n_sel of rank2 are never touched:
+ *     rank2[k][j] = the sum over the positions p of segment k of L + U + 1      int64 [n_seg][ld_rank2 >= n_sel]
+ *     ties[j]     = the sum over the runs of equal keys of t^3 - t              int64 [n_sel], at most 2^60 at n = 2^20
+ * with L = the number of list positions whose key in gene j is smaller than p's and U = the number whose key is smaller or equal, so
+ * that L + U + 1 is twice p's average rank.  Every sum is an integer sum collected with 64-bit integer atomics in LDS; there is no
+ * floating-point atomic; two calls agree bit for bit and the order inside a run of equal keys is free.
+ * A segment code outside [0, n_seg) is ranked with the others (it counts in their L and U) but adds to no sum and never indexes a
+ * table.  A row number outside [0, n_rows) and a gene id outside [0, G) read as a zero count and are never dereferenced.
+ * Two entry points over one workspace of spv_rank_ws_bytes(n, n_sel) = 8192 + 16 n n_sel bytes, 8-byte aligned:
+ *   spv_rank_stage  reads the piece [pos_off, pos_off + n_piece) of the list from x (a dense resident matrix, or a CSR chunk densified
+ *     by spv_csr_gather) and appends the piece's NON-ZERO keys, with their segment codes, to the genes' columns in the workspace (gene-major,
+ *     through an LDS transpose and one integer atomic cursor per gene; all zero keys form one run at the bottom and are accounted for from
+ *     counts: the positions of each segment are tallied here as well).  reset != 0 empties the columns first: set it for the first piece
+ *     of a list and only there.  A caller with the rows in pieces runs it once per piece (as spv_count_stats_partial); every position must
+ *     be staged exactly once (a piece staged twice is counted twice; nothing is written outside the workspace).  It reads x, G, n_rows,
+ *     n_piece, pos_off, n, n_seg, n_sel, reset, seg, w, genes, ws.
+ *   spv_rank_sums   sorts every staged column (one workgroup per gene: in LDS up to spv_rank_lds_capacity() non-zero keys, else by
+ *     radix passes of spv_rank_sort_tile() entries through the workspace's second half), walks the tie runs and writes rank2 and ties.
+ *     It reads n, n_seg, n_sel, rank2, ld_rank2, ties, ws; the staged columns are consumed (their order changes).
+ * Nothing is allocated.  Rejected ahead of any HIP call with SPV_ERR_ARG, both entry points: null arguments; n outside [1, SPV_RANK_MAX_N];
+ * n_seg outside [1, SPV_RANK_MAX_SEG]; n_sel outside [1, spv_rank_gene_slab()]; ws null, not 8-byte aligned, or ws_bytes short.
+ * spv_rank_stage: null x.X / seg; unknown dtype; G or n_rows < 1; n_piece < 1, pos_off < 0 or pos_off + n_piece > n; n_piece > n_rows
+ * without a row list; ld < col_off + G; n_sel > G without a gene list.  spv_rank_sums: null rank2 / ties; ld_rank2 < n_sel; rank2 or
+ * ties not 8-byte aligned. */
+#define SPV_RANK_MAX_N (1 << 20)
+#define SPV_RANK_MAX_SEG 1024
+typedef struct spv_rank_args {
+  spv_counts x;                            /* stage: the matrix that holds the piece */
+  int32_t G, n_rows, n_piece, pos_off;     /* stage */
+  int32_t n, n_seg, n_sel, reset;          /* the list, the segments, the gene slab; reset: stage only */
+  const int32_t* seg;                      /* [n] */
+  const float* w;                          /* [n] or NULL */
+  const int32_t* genes;                    /* [n_sel] or NULL */
+  int64_t* rank2; int64_t ld_rank2;        /* sums: [n_seg][ld_rank2 >= n_sel] */
+  int64_t* ties;                           /* sums: [n_sel] */
+  void* ws; int64_t ws_bytes;              /* spv_rank_ws_bytes(n, n_sel) bytes or more */
+} spv_rank_args;
+int spv_rank_stage(const spv_rank_args* a, void* stream);
+int spv_rank_sums(const spv_rank_args* a, void* stream);
+/* pure shape functions: the most genes per call; the workspace in bytes (8-byte multiple; 0 for a non-positive or out-of-range argument);
+ * the switch point between the LDS-resident sort and the radix passes (non-zero keys of one gene); the stage's tile of list positions;
+ * the entries one radix tile moves */
+int32_t spv_rank_gene_slab(void);
+int64_t spv_rank_ws_bytes(int32_t n, int32_t n_sel);
+int32_t spv_rank_lds_capacity(void);
+int32_t spv_rank_stage_tile(void);
+int32_t spv_rank_sort_tile(void);
+
 /* Exact t-SNE of a layout of at most SPV_TSNE_DMAX dimensions (spVIPES.latent_tsne / spVIPES.tsne of the user API): three entry points.
  *
  * spv_tsne_repulsion: the all-pairs half of the gradient, nothing of size n_q x n_c stored.  For query row i of Q over the candidates C

@@ -359,6 +359,16 @@ class SpvGramArgs(C.Structure):
                 ("sums", C.c_void_p), ("gram", C.c_void_p), ("ld_gram", C.c_int64), ("ws", C.c_void_p), ("ws_bytes", C.c_uint64)]
 
 
+RANK_MAX_N, RANK_MAX_SEG = 1 << 20, 1024   # SPV_RANK_MAX_N / SPV_RANK_MAX_SEG
+
+
+class SpvRankArgs(C.Structure):
+    """the arguments of spv_rank_stage / spv_rank_sums (include/spvipes_hip.h: spv_rank_args)"""
+    _fields_ = [("x", SpvCounts), ("G", C.c_int32), ("n_rows", C.c_int32), ("n_piece", C.c_int32), ("pos_off", C.c_int32), ("n", C.c_int32),
+                ("n_seg", C.c_int32), ("n_sel", C.c_int32), ("reset", C.c_int32), ("seg", C.c_void_p), ("w", C.c_void_p), ("genes", C.c_void_p),
+                ("rank2", C.c_void_p), ("ld_rank2", C.c_int64), ("ties", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 TSNE_DMAX = 4   # SPV_TSNE_DMAX
 
 
@@ -481,6 +491,13 @@ _SIGNATURES = {
     "spv_gram_f64": (C.c_int, [C.POINTER(SpvGramArgs), C.c_void_p]),
     "spv_gram_slabs": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_gram_ws_bytes": (C.c_uint64, [C.c_int32, C.c_int32]),
+    "spv_rank_stage": (C.c_int, [C.POINTER(SpvRankArgs), C.c_void_p]),
+    "spv_rank_sums": (C.c_int, [C.POINTER(SpvRankArgs), C.c_void_p]),
+    "spv_rank_gene_slab": (C.c_int32, []),
+    "spv_rank_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "spv_rank_lds_capacity": (C.c_int32, []),
+    "spv_rank_stage_tile": (C.c_int32, []),
+    "spv_rank_sort_tile": (C.c_int32, []),
     "spv_tsne_repulsion": (C.c_int, [C.POINTER(SpvTsneRepArgs), C.c_void_p]),
     "spv_tsne_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_tsne_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -18,6 +18,7 @@
 #include "spv_ot_project.h"
 #include "spv_silhouette.h"
 #include "spv_gram.h"
+#include "spv_rank.h"
 #include "spv_tsne.h"
 #include "spv_lisi.h"
 #include "spv_small.h"
@@ -1385,6 +1386,71 @@ extern "C" int spv_gram_f64(const spv_gram_args* x, void* stream) {
   if (rc != SPV_OK || slabs == 1) return rc;
   hipLaunchKernelGGL(gram_merge_kernel, dim3((unsigned)tiles, GRAM_T * GRAM_T / GRAM_THREADS), dim3(GRAM_THREADS), 0, s, a);
   return launch_status("spv_gram_f64 (merge pass)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// rank sums of the observed counts: segmented column sort with tie runs (spv_rank.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_rank_gene_slab(void) { return RANK_SLAB; }
+extern "C" int32_t spv_rank_lds_capacity(void) { return RANK_LDS_CAP; }
+extern "C" int32_t spv_rank_stage_tile(void) { return RANK_TP; }
+extern "C" int32_t spv_rank_sort_tile(void) { return RANK_THREADS; }
+extern "C" int64_t spv_rank_ws_bytes(int32_t n, int32_t n_sel) { return rank_ws_bytes(n, n_sel); }
+
+// what both entry points check: the list, the slab and the workspace
+static int rank_check(const spv_rank_args* x, const char* who) {
+  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
+  if (x->n < 1 || x->n > RANK_MAX_N) return fail(SPV_ERR_ARG, "%s: n must lie in [1, 2^20]", who);
+  if (x->n_seg < 1 || x->n_seg > RANK_MAX_SEG) return fail(SPV_ERR_ARG, "%s: n_seg must lie in [1, 1024]", who);
+  if (x->n_sel < 1 || x->n_sel > RANK_SLAB) return fail(SPV_ERR_ARG, "%s: n_sel must lie in [1, spv_rank_gene_slab()]", who);
+  if (!x->ws) return fail(SPV_ERR_ARG, "%s: null ws", who);
+  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "%s: ws must be 8-byte aligned", who);
+  if (x->ws_bytes < rank_ws_bytes(x->n, x->n_sel)) return fail(SPV_ERR_ARG, "%s: ws_bytes is less than spv_rank_ws_bytes(n, n_sel)", who);
+  return SPV_OK;
+}
+
+static RankArgs rank_args(const spv_rank_args* x) {
+  return RankArgs{x->x.X, (long)x->x.ld, x->x.rows, x->x.col_off, x->G, x->n_rows, x->n_piece, x->pos_off, x->n, x->n_seg, x->n_sel,
+                  x->seg, x->w, x->genes, (long long*)x->rank2, (long)x->ld_rank2, (long long*)x->ties, (char*)x->ws};
+}
+
+extern "C" int spv_rank_stage(const spv_rank_args* x, void* stream) {
+  const char* const who = "spv_rank_stage";
+  int rc = rank_check(x, who);
+  if (rc != SPV_OK) return rc;
+  if (!x->x.X) return fail(SPV_ERR_ARG, "%s: null count matrix", who);
+  if (!x->seg) return fail(SPV_ERR_ARG, "%s: null seg", who);
+  if (x->x.dtype != SPV_COUNT_U16 && x->x.dtype != SPV_COUNT_F32) return fail(SPV_ERR_ARG, "%s: unknown count dtype", who);
+  if (x->G <= 0 || x->n_rows <= 0) return fail(SPV_ERR_ARG, "%s: G and n_rows must be positive", who);
+  if (x->n_piece <= 0 || x->pos_off < 0 || (int64_t)x->pos_off + x->n_piece > x->n) return fail(SPV_ERR_ARG, "%s: the piece [pos_off, pos_off + n_piece) must be non-empty and lie in [0, n)", who);
+  if (!x->x.rows && x->n_piece > x->n_rows) return fail(SPV_ERR_ARG, "%s: without a row list n_piece must not exceed n_rows", who);
+  if (x->x.col_off < 0 || x->x.ld < (int64_t)x->x.col_off + x->G) return fail(SPV_ERR_ARG, "%s: ld < col_off + G", who);
+  if (!x->genes && x->n_sel > x->G) return fail(SPV_ERR_ARG, "%s: without a gene list n_sel must not exceed G", who);
+  const RankArgs a = rank_args(x);
+  hipStream_t s = (hipStream_t)stream;
+  if (x->reset) {
+    hipLaunchKernelGGL(rank_reset_kernel, dim3((RANK_SLAB + RANK_MAX_SEG) / 256), dim3(256), 0, s, (int*)x->ws);
+    rc = launch_status("spv_rank_stage (reset)");
+    if (rc != SPV_OK) return rc;
+  }
+  const dim3 grid((unsigned)((x->n_piece + RANK_TP - 1) / RANK_TP), (unsigned)((x->n_sel + RANK_TG - 1) / RANK_TG));
+  if (x->x.dtype == SPV_COUNT_U16) hipLaunchKernelGGL(rank_stage_kernel<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(rank_stage_kernel<false>, grid, dim3(256), 0, s, a);
+  return launch_status(who);
+}
+
+extern "C" int spv_rank_sums(const spv_rank_args* x, void* stream) {
+  const char* const who = "spv_rank_sums";
+  int rc = rank_check(x, who);
+  if (rc != SPV_OK) return rc;
+  if (!x->rank2) return fail(SPV_ERR_ARG, "%s: null rank2", who);
+  if (!x->ties) return fail(SPV_ERR_ARG, "%s: null ties", who);
+  if (x->ld_rank2 < x->n_sel) return fail(SPV_ERR_ARG, "%s: ld_rank2 < n_sel", who);
+  if (reinterpret_cast<uintptr_t>(x->rank2) & 7) return fail(SPV_ERR_ARG, "%s: rank2 must be 8-byte aligned", who);
+  if (reinterpret_cast<uintptr_t>(x->ties) & 7) return fail(SPV_ERR_ARG, "%s: ties must be 8-byte aligned", who);
+  const RankArgs a = rank_args(x);
+  hipLaunchKernelGGL(rank_sums_kernel, dim3((unsigned)x->n_sel), dim3(RANK_THREADS), 0, (hipStream_t)stream, a);
+  return launch_status(who);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -678,6 +678,54 @@ def count_table(own, n_own: int, other, n_other: int) -> dict:
             "raw_normalized_mean1": a[2] / n1, "raw_normalized_mean2": b[2] / n2}
 
 
+# ---- rank-sum test of the observed counts (model.rank_genes_groups): the result table from the kernel's integer tables -------------
+RANK_COLUMNS = ("scores", "u_statistic", "auc", "pvals", "pvals_adj")
+
+
+def benjamini_hochberg(pvals) -> np.ndarray:
+    """Benjamini-Hochberg adjusted p-values over the finite entries of ``pvals`` (m of them): the i-th smallest becomes
+    min(1, min over the i-th and every larger one of p * m / its place); a NaN stays NaN and is not counted in m"""
+    p = np.asarray(pvals, dtype=np.float64)
+    out = np.full(p.shape, np.nan)
+    ok = np.nonzero(np.isfinite(p))[0]
+    if ok.size:
+        order = ok[np.argsort(p[ok], kind="stable")]
+        adj = p[order] * ok.size / (1.0 + np.arange(ok.size))
+        out[order] = np.minimum(np.minimum.accumulate(adj[::-1])[::-1], 1.0)
+    return out
+
+
+def rank_test_table(rank2_k, ties, n1: int, n: int, tie_correct: bool = True) -> dict:
+    """The Wilcoxon / Mann-Whitney rank-sum test of one population of ``n1`` cells against the other ``n2 = n - n1`` of a ranked list,
+    per gene, from the integer tables of ``rank_ops.rank_sums``: ``rank2_k`` int64 [n_sel] = TWICE the rank sum R2 of the population
+    (ties at their mean rank) and ``ties`` int64 [n_sel] = T, the sum of t^3 - t over the runs of equal keys.  In fp64, column name ->
+    array, in RANK_COLUMNS order:
+        u_statistic = (R2 - n1 (n1 + 1)) / 2                      the population's Mann-Whitney U
+        auc         = U / (n1 n2)
+        var         = n1 n2 / 12 * ((n + 1) - T / (n (n - 1)))    T = 0 with ``tie_correct=False`` (scanpy's default)
+        scores      = (R2 - n1 (n + 1)) / (2 sqrt(var))           the z-score, without continuity correction
+        pvals       = 2 ndtr(-|scores|) = erfc(|scores| / sqrt 2)
+        pvals_adj   = ``benjamini_hochberg(pvals)`` over the selected genes
+    which is ``scipy.stats.mannwhitneyu(a, b, use_continuity=False, method="asymptotic")`` in statistic and p-value.  A gene whose keys
+    are all tied (var == 0) gets score 0 and p-value 1; an empty side (n1 == 0 or n1 == n) gives NaN in every column."""
+    r2, T = np.asarray(rank2_k).astype(np.float64).ravel(), np.asarray(ties).astype(np.float64).ravel()
+    if isinstance(n1, bool) or isinstance(n, bool) or not isinstance(n1, (int, np.integer)) or not isinstance(n, (int, np.integer)) or not 0 <= int(n1) <= int(n) or int(n) < 1:
+        raise ValueError(f"n1 and n must be integers with 0 <= n1 <= n and n >= 1, got {n1!r} and {n!r}")
+    if r2.shape != T.shape:
+        raise ValueError(f"rank2_k and ties must have one entry per gene each, got {r2.shape} and {T.shape}")
+    n1, n = int(n1), int(n)
+    n2 = n - n1
+    if n1 == 0 or n2 == 0:
+        return {k: np.full(r2.shape, np.nan) for k in RANK_COLUMNS}
+    f1, f2, fn = float(n1), float(n2), float(n)
+    u = (r2 - f1 * (f1 + 1.0)) / 2.0
+    var = f1 * f2 / 12.0 * ((fn + 1.0) - (T / (fn * (fn - 1.0)) if tie_correct else np.zeros_like(T)))
+    flat = np.logical_not(var > 0.0)
+    scores = np.where(flat, 0.0, (r2 - f1 * (fn + 1.0)) / (2.0 * np.sqrt(np.where(flat, 1.0, var))))
+    pvals = torch.special.erfc(torch.from_numpy(np.abs(scores) / math.sqrt(2.0))).numpy()
+    return {"scores": scores, "u_statistic": u, "auc": u / (f1 * f2), "pvals": pvals, "pvals_adj": benjamini_hochberg(pvals)}
+
+
 # ---- posterior-predictive check (model.posterior_predictive_check): segment codes of a walk and the result table -----------------
 PPC_STATS = ("mean", "var", "cv", "zero_fraction", "max")   # the columns ppc_table derives from a table of spv_dec_sample_stats
 

@@ -771,6 +771,71 @@ class spVIPES:
         return vs_rest_frames(((names[k], count_table(sums[k], sizes[k], rest[k], n_all - sizes[k])) for k in compared), index)
 
     @torch.no_grad()
+    def rank_genes_groups(self, group_indices_list: List[List[int]], group: int, idx1=None, idx2=None, groupby=None, labels=None, gene_list=None,
+                          target_sum: float = 1e4, normalize: bool = True, tie_correct: bool = True):
+        """The Wilcoxon / Mann-Whitney rank-sum test on the OBSERVED counts of ONE group (scanpy's
+        ``rank_genes_groups(method="wilcoxon")``): a pandas DataFrame of float64 columns per gene (``data.rank_test_table``)
+
+            scores        the z-score of the population's rank sum (ties at their mean rank, no continuity correction)
+            u_statistic   the population's Mann-Whitney U          auc   U / (n1 n2)
+            pvals         two-sided, from the normal approximation   pvals_adj   Benjamini-Hochberg over the selected genes
+
+        It needs no trained model and decodes nothing.  Exactly one of ``idx1`` / ``groupby`` selects the mode, and the populations,
+        labels, ``gene_list`` and ``target_sum`` are resolved exactly as ``count_statistics`` resolves them, with the same errors; the
+        frame's index, row order and ``comparison`` / ``group1`` / ``group2`` columns are that method's for the same arguments, so
+        ``pd.concat`` with its frame and with the DE frame lines up.  ``groupby``: ONE sort of all the group's cells per gene serves every
+        label; "rest" is every other cell of the group.  ``idx1`` (with ``idx2``): only the two populations are listed and ranked.
+        ``normalize=True`` ranks count * fp32(target_sum / the cell's total over ALL of the group's genes) (a cell without counts gets
+        the weight 0); log1p is monotone, so these are the ranks of scanpy's log-normalised data.  ``normalize=False`` ranks the raw
+        counts (``target_sum`` is still checked).  ``tie_correct``: the variance's tie term (scanpy's default is False).  At most 2^20
+        ranked cells and 1024 labels.
+        ``attrs``: ``n_cells`` (population -> its cells), ``rank2`` (int64 [n_populations, n_sel]: twice each population's rank sum),
+        ``ties`` (int64 [n_sel]: the sum of t^3 - t over the runs of equal keys) and ``populations`` (the rows of ``rank2``).
+        How it is computed: spv_rank_stage appends every gene's non-zero keys to its column, spv_rank_sums sorts the columns (a
+        segmented column sort) and walks the tie runs; every device output is an integer, so dense and sparse ``counts_storage`` give
+        the same frame bit for bit and two calls agree bit for bit."""
+        import pandas as pd
+
+        from .count_ops import count_totals
+        from .data import rank_test_table
+        from .rank_ops import rank_sums
+
+        target_sum = check_target_sum(target_sum)
+        if (idx1 is None) == (groupby is None):
+            raise ValueError("rank_genes_groups: give exactly one of idx1 (two populations) and groupby (every label against the rest)")
+        g = check_group(group)
+        cells = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
+        if groupby is None:
+            if labels is not None:
+                raise ValueError("rank_genes_groups: labels goes with groupby")
+            p1, p2 = de_populations(cells, idx1, idx2, group=g)
+            listed, code = np.concatenate([p1, p2]), np.concatenate([np.zeros(len(p1), np.int32), np.ones(len(p2), np.int32)])
+            names, compared = np.array(["idx1", "idx2"]), [0]
+        else:
+            if idx2 is not None:
+                raise ValueError("rank_genes_groups: idx2 goes with idx1")
+            cell_labels = group_cell_labels(self.adata.obs, groupby, cells, g, unique=True)
+            names, compared, _kept, _places = de_label_populations(cell_labels, labels, None, 0)
+            listed, code = np.arange(len(cells)), np.unique(cell_labels, return_inverse=True)[1].ravel().astype(np.int32)
+        n, n_seg = len(listed), len(names)
+        if n > _abi.RANK_MAX_N or n_seg > _abi.RANK_MAX_SEG:
+            raise ValueError(f"rank_genes_groups: at most 2^20 ranked cells and {_abi.RANK_MAX_SEG} labels, got {n} and {n_seg}")
+        sizes = np.bincount(code, minlength=n_seg).tolist()
+        _sel, dev_sel, _n_sel, index = self._genes(g, gene_list, own=True)
+        rows = torch.as_tensor(self._local_rows(g, cells[listed]).astype(np.int32), device=self.device)
+        w = None
+        if normalize:
+            total = count_totals(self.counts[g]).index_select(0, rows.long())
+            w = torch.where(total > 0, target_sum / total, torch.zeros_like(total)).to(torch.float32)
+        rank2, ties = (t.cpu().numpy() for t in rank_sums(self.counts[g], rows, torch.as_tensor(code, device=self.device), n_seg, w=w, genes=dev_sel))
+        if groupby is None:
+            frame = pd.DataFrame(rank_test_table(rank2[0], ties, sizes[0], n, bool(tie_correct)), index=index)
+        else:
+            frame = vs_rest_frames(((names[k], rank_test_table(rank2[k], ties, sizes[k], n, bool(tie_correct))) for k in compared), index)
+        frame.attrs.update(n_cells={names[k]: sizes[k] for k in range(n_seg)}, rank2=rank2, ties=ties, populations=list(names.tolist()))
+        return frame
+
+    @torch.no_grad()
     def posterior_predictive_check(self, group_indices_list: List[List[int]], group: int, n_samples: int = 25, groupby=None, labels=None,
                                    gene_list=None, library_size="latent", seed: int = 0, batch_size: Optional[int] = None, _noise=None):
         """A posterior-predictive check of ONE group's count model that never leaves the device (scvi-tools'
