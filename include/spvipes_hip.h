@@ -906,6 +906,50 @@ int32_t spv_rank_lds_capacity(void);
 int32_t spv_rank_stage_tile(void);
 int32_t spv_rank_sort_tile(void);
 
+/* The rank transform on the same column sort (rank_ops.rank_transform; spVIPES.get_feature_spearman_matrix / count_spearman_matrix of
+ * the user API): every list position gets its rank back, as the fp32 block spv_gram_f64 reads.  The list, the addressing of x, the
+ * weights, the gene slab and the key (ONE fp32 multiply, zero keys all the pattern 0) are spv_rank_stage's; there are no segments.
+ * Output, WRITTEN for every list position p < n and slab gene j < n_sel; columns >= n_sel of out are never touched:
+ *     out[p * ld_out + j] = (float)(L + U - n) = (float)(2 * average rank of p among the n keys of gene j - (n + 1))
+ * with L = the list positions whose key is smaller than p's and U = those whose key is smaller or equal.  An integer in
+ * [-(n - 1), n - 1], exact in fp32; every column sums to exactly 0 and its squares to exactly (n^3 - n - ties[j]) / 3.  All zero keys
+ * form one run at the bottom and are never stored or sorted: a zero key gets n_zero - n, a stored key of the run [s, e) of its sorted
+ * column 2 n_zero + s + e - n.
+ *     ties[j]    = the sum over the runs of equal keys, the zero run included, of t^3 - t (spv_rank_sums' ties)   int64 [n_sel] or NULL
+ *     nonzero[j] = the stored (non-zero) keys of gene j                                                            int32 [n_sel] or NULL
+ * Every output element has one writer; the walk and the store use no atomic of any kind (the shared sort keeps its integer LDS
+ * histogram, the stage its integer cursor; no floating-point atomic anywhere): two calls agree bit for bit.
+ * Two entry points over one workspace of spv_rank_values_ws_bytes(n, n_sel) = spv_rank_ws_bytes(n, n_sel) + 4 n n_sel bytes, rounded up
+ * to a multiple of 8, 8-byte aligned:
+ *   spv_rank_values_stage  spv_rank_stage with the list position in the place of the segment code: appends the NON-ZERO keys of the
+ *     piece [pos_off, pos_off + n_piece) to the genes' columns.  reset != 0 empties the columns first (the first piece of a list, and
+ *     only there); every position must be staged exactly once.  It reads x, G, n_rows, n_piece, pos_off, n, n_sel, reset, w, genes, ws.
+ *   spv_rank_values        sorts every staged column (spv_rank_sums' two routes), fills the gene's fp32 column in the workspace with the
+ *     zero run's value, scatters the stored entries' values by position, and a second launch moves 64 x 64 tiles into the row-major out.
+ *     It reads n, n_sel, out, ld_out, ties, nonzero, ws; the staged columns are consumed.  out may be the staged matrix itself: the
+ *     call reads the workspace only.
+ * A position word at or above n is never used as an address; a gene's stored keys are cut to n; a row number outside [0, n_rows) and a
+ * gene id outside [0, G) read as a zero key and are never dereferenced.
+ * Nothing is allocated.  Rejected ahead of any HIP call with SPV_ERR_ARG, both entry points: null arguments; n outside [1, SPV_RANK_MAX_N];
+ * n_sel outside [1, spv_rank_gene_slab()]; ws null, not 8-byte aligned, or ws_bytes short.  spv_rank_values_stage: null x.X; unknown
+ * dtype; G or n_rows < 1; n_piece < 1, pos_off < 0 or pos_off + n_piece > n; n_piece > n_rows without a row list; ld < col_off + G;
+ * n_sel > G without a gene list.  spv_rank_values: null out; out or nonzero not 4-byte aligned; ties not 8-byte aligned; ld_out < n_sel. */
+typedef struct spv_rank_values_args {
+  spv_counts x;                            /* stage: the matrix that holds the piece */
+  int32_t G, n_rows, n_piece, pos_off;     /* stage */
+  int32_t n, n_sel, reset;                 /* the list, the gene slab; reset: stage only */
+  const float* w;                          /* [n] or NULL */
+  const int32_t* genes;                    /* [n_sel] or NULL */
+  float* out; int64_t ld_out;              /* values: [n][ld_out >= n_sel], row-major */
+  int64_t* ties;                           /* values: [n_sel] or NULL */
+  int32_t* nonzero;                        /* values: [n_sel] or NULL */
+  void* ws; int64_t ws_bytes;              /* spv_rank_values_ws_bytes(n, n_sel) bytes or more */
+} spv_rank_values_args;
+int spv_rank_values_stage(const spv_rank_values_args* a, void* stream);
+int spv_rank_values(const spv_rank_values_args* a, void* stream);
+/* the workspace in bytes (8-byte multiple; 0 for a non-positive or out-of-range argument, like spv_rank_ws_bytes) */
+int64_t spv_rank_values_ws_bytes(int32_t n, int32_t n_sel);
+
 /* Exact t-SNE of a layout of at most SPV_TSNE_DMAX dimensions (spVIPES.latent_tsne / spVIPES.tsne of the user API): three entry points.
  *
  * spv_tsne_repulsion: the all-pairs half of the gradient, nothing of size n_q x n_c stored.  For query row i of Q over the candidates C

@@ -369,6 +369,13 @@ class SpvRankArgs(C.Structure):
                 ("rank2", C.c_void_p), ("ld_rank2", C.c_int64), ("ties", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+class SpvRankValuesArgs(C.Structure):
+    """the arguments of spv_rank_values_stage / spv_rank_values (include/spvipes_hip.h: spv_rank_values_args)"""
+    _fields_ = [("x", SpvCounts), ("G", C.c_int32), ("n_rows", C.c_int32), ("n_piece", C.c_int32), ("pos_off", C.c_int32), ("n", C.c_int32),
+                ("n_sel", C.c_int32), ("reset", C.c_int32), ("w", C.c_void_p), ("genes", C.c_void_p), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("ties", C.c_void_p), ("nonzero", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 TSNE_DMAX = 4   # SPV_TSNE_DMAX
 
 
@@ -498,6 +505,9 @@ _SIGNATURES = {
     "spv_rank_lds_capacity": (C.c_int32, []),
     "spv_rank_stage_tile": (C.c_int32, []),
     "spv_rank_sort_tile": (C.c_int32, []),
+    "spv_rank_values_stage": (C.c_int, [C.POINTER(SpvRankValuesArgs), C.c_void_p]),
+    "spv_rank_values": (C.c_int, [C.POINTER(SpvRankValuesArgs), C.c_void_p]),
+    "spv_rank_values_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "spv_tsne_repulsion": (C.c_int, [C.POINTER(SpvTsneRepArgs), C.c_void_p]),
     "spv_tsne_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_tsne_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

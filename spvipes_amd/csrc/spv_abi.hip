@@ -19,6 +19,7 @@
 #include "spv_silhouette.h"
 #include "spv_gram.h"
 #include "spv_rank.h"
+#include "spv_rank_values.h"
 #include "spv_tsne.h"
 #include "spv_lisi.h"
 #include "spv_small.h"
@@ -1397,16 +1398,46 @@ extern "C" int32_t spv_rank_stage_tile(void) { return RANK_TP; }
 extern "C" int32_t spv_rank_sort_tile(void) { return RANK_THREADS; }
 extern "C" int64_t spv_rank_ws_bytes(int32_t n, int32_t n_sel) { return rank_ws_bytes(n, n_sel); }
 
-// what both entry points check: the list, the slab and the workspace
+// what every entry point of the column sort checks: the list, the slab and the workspace (need: the bytes it takes; values: of the rank transform)
+static int rank_list_check(const char* who, int n, int n_sel, const void* ws, int64_t ws_bytes, int64_t need, bool values) {
+  if (n_sel < 1 || n_sel > RANK_SLAB) return fail(SPV_ERR_ARG, "%s: n_sel must lie in [1, spv_rank_gene_slab()]", who);
+  if (!ws) return fail(SPV_ERR_ARG, "%s: null ws", who);
+  if (reinterpret_cast<uintptr_t>(ws) & 7) return fail(SPV_ERR_ARG, "%s: ws must be 8-byte aligned", who);
+  if (ws_bytes < need) return fail(SPV_ERR_ARG, values ? "%s: ws_bytes is less than spv_rank_values_ws_bytes(n, n_sel)" : "%s: ws_bytes is less than spv_rank_ws_bytes(n, n_sel)", who);
+  return SPV_OK;
+}
+
 static int rank_check(const spv_rank_args* x, const char* who) {
   if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
   if (x->n < 1 || x->n > RANK_MAX_N) return fail(SPV_ERR_ARG, "%s: n must lie in [1, 2^20]", who);
   if (x->n_seg < 1 || x->n_seg > RANK_MAX_SEG) return fail(SPV_ERR_ARG, "%s: n_seg must lie in [1, 1024]", who);
-  if (x->n_sel < 1 || x->n_sel > RANK_SLAB) return fail(SPV_ERR_ARG, "%s: n_sel must lie in [1, spv_rank_gene_slab()]", who);
-  if (!x->ws) return fail(SPV_ERR_ARG, "%s: null ws", who);
-  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "%s: ws must be 8-byte aligned", who);
-  if (x->ws_bytes < rank_ws_bytes(x->n, x->n_sel)) return fail(SPV_ERR_ARG, "%s: ws_bytes is less than spv_rank_ws_bytes(n, n_sel)", who);
+  return rank_list_check(who, x->n, x->n_sel, x->ws, x->ws_bytes, rank_ws_bytes(x->n, x->n_sel), false);
+}
+
+// what both stage entry points check of the matrix, the piece and the gene slab
+static int rank_stage_check(const char* who, const spv_counts& c, int G, int n_rows, int n_piece, int pos_off, int n, int n_sel, const int32_t* genes) {
+  if (!c.X) return fail(SPV_ERR_ARG, "%s: null count matrix", who);
+  if (c.dtype != SPV_COUNT_U16 && c.dtype != SPV_COUNT_F32) return fail(SPV_ERR_ARG, "%s: unknown count dtype", who);
+  if (G <= 0 || n_rows <= 0) return fail(SPV_ERR_ARG, "%s: G and n_rows must be positive", who);
+  if (n_piece <= 0 || pos_off < 0 || (int64_t)pos_off + n_piece > n) return fail(SPV_ERR_ARG, "%s: the piece [pos_off, pos_off + n_piece) must be non-empty and lie in [0, n)", who);
+  if (!c.rows && n_piece > n_rows) return fail(SPV_ERR_ARG, "%s: without a row list n_piece must not exceed n_rows", who);
+  if (c.col_off < 0 || c.ld < (int64_t)c.col_off + G) return fail(SPV_ERR_ARG, "%s: ld < col_off + G", who);
+  if (!genes && n_sel > G) return fail(SPV_ERR_ARG, "%s: without a gene list n_sel must not exceed G", who);
   return SPV_OK;
+}
+
+// the stage's launches: the reset of the head when asked for, then the tiles of the piece
+template <bool POS>
+static int rank_stage_launch(const char* who, const char* who_reset, const RankArgs& a, bool u16, bool reset, hipStream_t s) {
+  if (reset) {
+    hipLaunchKernelGGL(rank_reset_kernel, dim3((RANK_SLAB + RANK_MAX_SEG) / 256), dim3(256), 0, s, (int*)a.ws);
+    const int rc = launch_status(who_reset);
+    if (rc != SPV_OK) return rc;
+  }
+  const dim3 grid((unsigned)((a.n_piece + RANK_TP - 1) / RANK_TP), (unsigned)((a.n_sel + RANK_TG - 1) / RANK_TG));
+  if (u16) hipLaunchKernelGGL((rank_stage_kernel<true, POS>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((rank_stage_kernel<false, POS>), grid, dim3(256), 0, s, a);
+  return launch_status(who);
 }
 
 static RankArgs rank_args(const spv_rank_args* x) {
@@ -1418,25 +1449,10 @@ extern "C" int spv_rank_stage(const spv_rank_args* x, void* stream) {
   const char* const who = "spv_rank_stage";
   int rc = rank_check(x, who);
   if (rc != SPV_OK) return rc;
-  if (!x->x.X) return fail(SPV_ERR_ARG, "%s: null count matrix", who);
-  if (!x->seg) return fail(SPV_ERR_ARG, "%s: null seg", who);
-  if (x->x.dtype != SPV_COUNT_U16 && x->x.dtype != SPV_COUNT_F32) return fail(SPV_ERR_ARG, "%s: unknown count dtype", who);
-  if (x->G <= 0 || x->n_rows <= 0) return fail(SPV_ERR_ARG, "%s: G and n_rows must be positive", who);
-  if (x->n_piece <= 0 || x->pos_off < 0 || (int64_t)x->pos_off + x->n_piece > x->n) return fail(SPV_ERR_ARG, "%s: the piece [pos_off, pos_off + n_piece) must be non-empty and lie in [0, n)", who);
-  if (!x->x.rows && x->n_piece > x->n_rows) return fail(SPV_ERR_ARG, "%s: without a row list n_piece must not exceed n_rows", who);
-  if (x->x.col_off < 0 || x->x.ld < (int64_t)x->x.col_off + x->G) return fail(SPV_ERR_ARG, "%s: ld < col_off + G", who);
-  if (!x->genes && x->n_sel > x->G) return fail(SPV_ERR_ARG, "%s: without a gene list n_sel must not exceed G", who);
-  const RankArgs a = rank_args(x);
-  hipStream_t s = (hipStream_t)stream;
-  if (x->reset) {
-    hipLaunchKernelGGL(rank_reset_kernel, dim3((RANK_SLAB + RANK_MAX_SEG) / 256), dim3(256), 0, s, (int*)x->ws);
-    rc = launch_status("spv_rank_stage (reset)");
-    if (rc != SPV_OK) return rc;
-  }
-  const dim3 grid((unsigned)((x->n_piece + RANK_TP - 1) / RANK_TP), (unsigned)((x->n_sel + RANK_TG - 1) / RANK_TG));
-  if (x->x.dtype == SPV_COUNT_U16) hipLaunchKernelGGL(rank_stage_kernel<true>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(rank_stage_kernel<false>, grid, dim3(256), 0, s, a);
-  return launch_status(who);
+  if (!x->seg && x->x.X) return fail(SPV_ERR_ARG, "%s: null seg", who);   // (a null matrix is reported first, as before the checks were shared)
+  rc = rank_stage_check(who, x->x, x->G, x->n_rows, x->n_piece, x->pos_off, x->n, x->n_sel, x->genes);
+  if (rc != SPV_OK) return rc;
+  return rank_stage_launch<false>(who, "spv_rank_stage (reset)", rank_args(x), x->x.dtype == SPV_COUNT_U16, x->reset != 0, (hipStream_t)stream);
 }
 
 extern "C" int spv_rank_sums(const spv_rank_args* x, void* stream) {
@@ -1450,6 +1466,46 @@ extern "C" int spv_rank_sums(const spv_rank_args* x, void* stream) {
   if (reinterpret_cast<uintptr_t>(x->ties) & 7) return fail(SPV_ERR_ARG, "%s: ties must be 8-byte aligned", who);
   const RankArgs a = rank_args(x);
   hipLaunchKernelGGL(rank_sums_kernel, dim3((unsigned)x->n_sel), dim3(RANK_THREADS), 0, (hipStream_t)stream, a);
+  return launch_status(who);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the rank transform on the same column sort (spv_rank_values.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int64_t spv_rank_values_ws_bytes(int32_t n, int32_t n_sel) { return rank_values_ws_bytes(n, n_sel); }
+
+static int rank_values_check(const spv_rank_values_args* x, const char* who) {
+  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
+  if (x->n < 1 || x->n > RANK_MAX_N) return fail(SPV_ERR_ARG, "%s: n must lie in [1, 2^20]", who);
+  return rank_list_check(who, x->n, x->n_sel, x->ws, x->ws_bytes, rank_values_ws_bytes(x->n, x->n_sel), true);
+}
+
+extern "C" int spv_rank_values_stage(const spv_rank_values_args* x, void* stream) {
+  const char* const who = "spv_rank_values_stage";
+  int rc = rank_values_check(x, who);
+  if (rc != SPV_OK) return rc;
+  rc = rank_stage_check(who, x->x, x->G, x->n_rows, x->n_piece, x->pos_off, x->n, x->n_sel, x->genes);
+  if (rc != SPV_OK) return rc;
+  const RankArgs a{x->x.X, (long)x->x.ld, x->x.rows, x->x.col_off, x->G, x->n_rows, x->n_piece, x->pos_off, x->n, 0, x->n_sel,
+                   nullptr, x->w, x->genes, nullptr, 0, nullptr, (char*)x->ws};
+  return rank_stage_launch<true>(who, "spv_rank_values_stage (reset)", a, x->x.dtype == SPV_COUNT_U16, x->reset != 0, (hipStream_t)stream);
+}
+
+extern "C" int spv_rank_values(const spv_rank_values_args* x, void* stream) {
+  const char* const who = "spv_rank_values";
+  int rc = rank_values_check(x, who);
+  if (rc != SPV_OK) return rc;
+  if (!x->out) return fail(SPV_ERR_ARG, "%s: null out", who);
+  if (x->ld_out < x->n_sel) return fail(SPV_ERR_ARG, "%s: ld_out < n_sel", who);
+  if (reinterpret_cast<uintptr_t>(x->out) & 3) return fail(SPV_ERR_ARG, "%s: out must be 4-byte aligned", who);
+  if (reinterpret_cast<uintptr_t>(x->ties) & 7) return fail(SPV_ERR_ARG, "%s: ties must be 8-byte aligned", who);
+  if (reinterpret_cast<uintptr_t>(x->nonzero) & 3) return fail(SPV_ERR_ARG, "%s: nonzero must be 4-byte aligned", who);
+  const RankValuesArgs a{x->n, x->n_sel, x->out, (long)x->ld_out, (long long*)x->ties, x->nonzero, (char*)x->ws};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(rank_values_kernel, dim3((unsigned)x->n_sel), dim3(RANK_THREADS), 0, s, a);
+  rc = launch_status("spv_rank_values (walk)");
+  if (rc != SPV_OK) return rc;
+  hipLaunchKernelGGL(rank_values_store_kernel, dim3((unsigned)((x->n + RANKV_T - 1) / RANKV_T), (unsigned)((x->n_sel + RANKV_T - 1) / RANKV_T)), dim3(RANKV_THREADS), 0, s, a);
   return launch_status(who);
 }
 

@@ -81,6 +81,8 @@ __host__ __device__ __forceinline__ unsigned rank_key_bits(float c, float w, boo
 __host__ __device__ __forceinline__ rank_entry_t rank_entry(unsigned key, int code, int n_seg) {
   return ((rank_entry_t)key << 32) | (unsigned)(code >= 0 && code < n_seg ? code : n_seg);
 }
+// the rank transform's entry (spv_rank_values.h): the low word is the LIST POSITION itself (read back with rank_entry_seg)
+__host__ __device__ __forceinline__ rank_entry_t rank_pos_entry(unsigned key, int p) { return ((rank_entry_t)key << 32) | (unsigned)p; }
 __host__ __device__ __forceinline__ unsigned rank_entry_key(rank_entry_t e) { return (unsigned)(e >> 32); }
 __host__ __device__ __forceinline__ unsigned rank_entry_seg(rank_entry_t e) { return (unsigned)e; }
 
@@ -158,13 +160,15 @@ __global__ __launch_bounds__(256) void rank_reset_kernel(int* head) {
   head[blockIdx.x * 256 + threadIdx.x] = 0;   // (the grid covers exactly RANK_SLAB + RANK_MAX_SEG words, a multiple of 256)
 }
 
-template <bool U16>
+// POS (the rank transform, spv_rank_values.h): an entry's low word is the list position p, not a segment code -- seg is not read, no
+// histogram is built or flushed (count_segments is a constant false and the code behind it is dropped).  POS == false is the kernel above.
+template <bool U16, bool POS>
 __global__ __launch_bounds__(256) void rank_stage_kernel(RankArgs a) {
   __shared__ unsigned tile[RANK_TG][RANK_TP + 1];   // (+ 1: a wave writes one position of 64 genes, 129 words apart -> 64 banks)
-  __shared__ int hist[RANK_MAX_SEG];
+  __shared__ int hist[POS ? 1 : RANK_MAX_SEG];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int p0 = a.pos_off + (int)blockIdx.x * RANK_TP, p_end = a.pos_off + a.n_piece, j0 = (int)blockIdx.y * RANK_TG;
-  const bool count_segments = blockIdx.y == 0;
+  const bool count_segments = !POS && blockIdx.y == 0;
   if (count_segments) {
     for (int k = threadIdx.x; k < RANK_MAX_SEG; k += 256) hist[k] = 0;
   }
@@ -199,7 +203,8 @@ __global__ __launch_bounds__(256) void rank_stage_kernel(RankArgs a) {
   for (int c = 0; c < 2; ++c) {
     const int p = p0 + 64 * c + lane;
     live[c] = p < p_end;
-    code[c] = live[c] ? a.seg[p] : -1;
+    if constexpr (POS) code[c] = p;
+    else code[c] = live[c] ? a.seg[p] : -1;
   }
   __syncthreads();
   if (count_segments && wave == 0) {
@@ -224,11 +229,11 @@ __global__ __launch_bounds__(256) void rank_stage_kernel(RankArgs a) {
     rank_entry_t* const col = half_a + (long)jj * a.n;
     if (k0 != 0u) {
       const int slot = base + rank_popc(b0 & below);
-      if (slot >= 0 && slot < a.n) col[slot] = rank_entry(k0, code[0], a.n_seg);
+      if (slot >= 0 && slot < a.n) col[slot] = POS ? rank_pos_entry(k0, code[0]) : rank_entry(k0, code[0], a.n_seg);
     }
     if (k1 != 0u) {
       const int slot = base + c0 + rank_popc(b1 & below);
-      if (slot >= 0 && slot < a.n) col[slot] = rank_entry(k1, code[1], a.n_seg);
+      if (slot >= 0 && slot < a.n) col[slot] = POS ? rank_pos_entry(k1, code[1]) : rank_entry(k1, code[1], a.n_seg);
     }
   }
   if (count_segments) {
@@ -248,19 +253,12 @@ struct RankRadixLds {   // the radix path's view of the sort buffer
 };
 static_assert(sizeof(RankRadixLds) <= sizeof(rank_entry_t) * RANK_LDS_CAP, "the radix tables live in the LDS sort buffer");
 
-__global__ __launch_bounds__(RANK_THREADS) void rank_sums_kernel(RankArgs a) {
-  __shared__ rank_entry_t buf[RANK_LDS_CAP];
-  __shared__ unsigned long long acc[RANK_MAX_SEG];
-  __shared__ int stored[RANK_MAX_SEG];
-  __shared__ unsigned long long tie;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = blockIdx.x;
-  const int* const cursor = reinterpret_cast<const int*>(a.ws + rank_ws_cursor_off());
-  const int* const segcnt = reinterpret_cast<const int*>(a.ws + rank_ws_segcnt_off());
-  const int m = min(max(cursor[j], 0), a.n), n_zero = a.n - m;
-  rank_entry_t* src = reinterpret_cast<rank_entry_t*>(a.ws + rank_ws_half_off(0, a.n, a.n_sel)) + (long)j * a.n;
-  rank_entry_t* dst = reinterpret_cast<rank_entry_t*>(a.ws + rank_ws_half_off(1, a.n, a.n_sel)) + (long)j * a.n;
-  for (int k = tid; k < a.n_seg; k += RANK_THREADS) { acc[k] = 0ull; stored[k] = 0; }
-  if (tid == 0) tie = 0ull;
+// The sort both walks share (rank_sums_kernel here, rank_values_kernel of spv_rank_values.h): the whole workgroup of RANK_THREADS
+// threads sorts the m (<= n) entries of one column ascending -- in buf (LDS, RANK_LDS_CAP entries) up to RANK_LDS_CAP, else by the
+// radix passes between src and dst (n entries each) with buf as their tables -- and returns where the sorted column stands; a barrier
+// has made it visible to every thread.  Every thread must call it with the same arguments.
+__device__ __forceinline__ const rank_entry_t* rank_sort_column(rank_entry_t* buf, rank_entry_t* src, rank_entry_t* dst, const int m) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const rank_entry_t* sorted;
   if (m <= RANK_LDS_CAP) {
     const int P = rank_pow2(m);
@@ -345,6 +343,23 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_sums_kernel(RankArgs a) {
     sorted = src;
   }
   __syncthreads();
+  return sorted;
+}
+
+__global__ __launch_bounds__(RANK_THREADS) void rank_sums_kernel(RankArgs a) {
+  __shared__ rank_entry_t buf[RANK_LDS_CAP];
+  __shared__ unsigned long long acc[RANK_MAX_SEG];
+  __shared__ int stored[RANK_MAX_SEG];
+  __shared__ unsigned long long tie;
+  const int tid = threadIdx.x, j = blockIdx.x;
+  const int* const cursor = reinterpret_cast<const int*>(a.ws + rank_ws_cursor_off());
+  const int* const segcnt = reinterpret_cast<const int*>(a.ws + rank_ws_segcnt_off());
+  const int m = min(max(cursor[j], 0), a.n), n_zero = a.n - m;
+  rank_entry_t* src = reinterpret_cast<rank_entry_t*>(a.ws + rank_ws_half_off(0, a.n, a.n_sel)) + (long)j * a.n;
+  rank_entry_t* dst = reinterpret_cast<rank_entry_t*>(a.ws + rank_ws_half_off(1, a.n, a.n_sel)) + (long)j * a.n;
+  for (int k = tid; k < a.n_seg; k += RANK_THREADS) { acc[k] = 0ull; stored[k] = 0; }
+  if (tid == 0) tie = 0ull;
+  const rank_entry_t* const sorted = rank_sort_column(buf, src, dst, m);
   for (int i = tid; i < m; i += RANK_THREADS) {
     const int s = rank_run_begin(sorted, i), e = rank_run_end(sorted, i, m);
     const unsigned sg = rank_entry_seg(sorted[i]);

@@ -969,13 +969,15 @@ CORRELATION_MAX_GENES = 4096   # SPV_GRAM_MAX_N
 
 def check_correlation_args(correlation_type, n_sel: Optional[int] = None) -> None:
     """The refusals of ``get_feature_correlation_matrix`` that are its own, ahead of any device work: ``correlation_type`` "pearson";
-    "spearman" is a NotImplementedError (ranks need a gene's whole column, which the streaming reduction never holds), anything else a
-    ValueError; more than 4096 selected genes a ValueError naming the table they would need."""
+    "spearman" is a NotImplementedError that names ``get_feature_spearman_matrix`` (ranks need a gene's whole column, which this
+    streaming reduction never holds: Spearman is a method of its own), anything else a ValueError; more than 4096 selected genes a
+    ValueError naming the table they would need."""
     if isinstance(correlation_type, str) and correlation_type == "spearman":
-        raise NotImplementedError("correlation_type='spearman' is not implemented: ranks need every value of a gene at once, and the read-out "
-                                  "streams the cells through one Gram table; use 'pearson'")
+        raise NotImplementedError("correlation_type='spearman' is not implemented here: ranks need every value of a gene at once, and this read-out "
+                                  "streams the cells through one Gram table; call get_feature_spearman_matrix (same arguments), or "
+                                  "count_spearman_matrix for the observed counts")
     if not isinstance(correlation_type, str) or correlation_type != "pearson":
-        raise ValueError(f"correlation_type must be 'pearson' (or 'spearman', which is not implemented), got {correlation_type!r}")
+        raise ValueError(f"correlation_type must be 'pearson' (Spearman is get_feature_spearman_matrix, a method of its own), got {correlation_type!r}")
     if n_sel is not None and n_sel > CORRELATION_MAX_GENES:
         raise ValueError(f"{n_sel} genes selected: the fp64 table of their pairs would take n_sel^2 x 8 = {n_sel * n_sel * 8} bytes on the device; "
                          f"select at most {CORRELATION_MAX_GENES} genes (gene_list)")
@@ -1027,6 +1029,42 @@ def correlation_table(sums, gram, n) -> dict:
     live = np.nonzero(~dead)[0]
     corr[live, live] = 1.0
     return {"mean": mean, "cov": cov, "var": var, "corr": corr}
+
+
+# ---- Spearman correlation (model.get_feature_spearman_matrix / count_spearman_matrix): the table of the rank block's Gram ----------
+SPEARMAN_EXACT_ROWS = 208063   # the largest n with n^3 < 2^53 (208063^3 = 9 007 091 372 906 047 < 2^53 = 9 007 199 254 740 992 < 208064^3)
+SPEARMAN_MAX_ROWS = 1 << 20    # SPV_RANK_MAX_N
+SPEARMAN_GRAM_ROWS = 16384     # rows of the rank block one spv_gram_f64 call adds
+
+
+def spearman_table(gram, n) -> dict:
+    """Spearman's rho from the Gram of the rank block (``rank_ops.rank_transform`` then ``gram_ops.gram_accumulate``): ``gram`` C [p, p]
+    float64 with C_ij = sum over the n rows of c_i c_j, c = 2 * average rank - (n + 1).  Every column of the block sums to exactly 0,
+    so the sums are not read: -> ``correlation_table(zeros, C, n)`` ("mean" 0, "cov" C / (n - 1), "var", "corr" = rho: NaN in the row
+    and column of a constant gene -- its whole column is 0 --, exactly 1 on the rest of the diagonal, symmetric in bits for a symmetric
+    C) plus "tie_term" = n^3 - n - 3 diag(C), the sum of t^3 - t over every gene's runs of equal values (0 for a gene without ties).
+    Exactness (``SPEARMAN_EXACT_ROWS`` = 208 063): |c| <= n - 1, so every product and every partial sum of a Gram element is an
+    integer of magnitude at most n (n - 1)^2 < n^3, and n^3 < 2^53 holds up to n = 208 063 (208063^3 < 2^53 < 208064^3): up to there
+    C is the exact integer whatever the order of addition, and "tie_term" is exact as well (3 diag(C) <= n^3 - n).  Beyond it C carries
+    fp64 summation error like any Gram."""
+    Cm = np.asarray(gram)
+    if Cm.dtype != np.float64 or Cm.ndim != 2 or Cm.shape[0] != Cm.shape[1]:
+        raise ValueError(f"gram must be a square float64 matrix [p, p], got {Cm.dtype} {Cm.shape}")
+    table = correlation_table(np.zeros(Cm.shape[0], dtype=np.float64), Cm, n)
+    n = int(n)
+    table["tie_term"] = float(n) ** 3 - float(n) - 3.0 * np.diagonal(Cm)
+    return table
+
+
+def check_spearman_shape(n_rows: int, n_sel: int, who: str) -> None:
+    """The limits of the Spearman read-outs, ahead of any device work: at most 4096 genes (the fp64 table) and 2^20 ranked rows"""
+    if n_sel > CORRELATION_MAX_GENES:
+        raise ValueError(f"{who}: {n_sel} genes selected: the fp64 table of their pairs would take n_sel^2 x 8 = {n_sel * n_sel * 8} bytes on the "
+                         f"device; select at most {CORRELATION_MAX_GENES} genes (gene_list)")
+    if n_rows < 1:
+        raise ValueError(f"{who}: no cell to rank")
+    if n_rows > SPEARMAN_MAX_ROWS:
+        raise ValueError(f"{who}: {n_rows} rows (cells x n_samples) to rank; a column sort holds at most 2^20 = {SPEARMAN_MAX_ROWS}")
 
 
 # ---- neighbours in latent space (model.latent_neighbors / transfer_labels): host-side argument handling and the label vote ------

@@ -29,6 +29,7 @@ from .data import (check_tsne_args, check_tsne_rep, check_tsne_schedule, tsne_fr
                    SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table,
                    check_lisi_args, check_lisi_keys, lisi_frame, lisi_rep_frame,
                    check_correlation_args, correlation_cells, correlation_table)
+from .data import SPEARMAN_EXACT_ROWS, SPEARMAN_GRAM_ROWS, check_spearman_shape, spearman_table
 from .module import spVIPESmodule
 from .plan import SparsePlan
 from .train import Trainer, default_max_epochs
@@ -1030,6 +1031,109 @@ class spVIPES:
         frame = pd.DataFrame(table["corr"], index=index, columns=index)
         frame.attrs.update(mean=table["mean"], var=table["var"], n_cells=n_cells, n_samples=n_samples, sums=sums)
         return frame
+
+    def _spearman_frame(self, block: torch.Tensor, ties: torch.Tensor, index, n_cells: int, n_samples: int):
+        """The shared tail of the two Spearman read-outs.  ``block``: the fp32 device tensor [rows, n_sel] of rank-transformed values
+        (every column sums to 0), ``ties`` the transform's int64 [n_sel] -> the frame of ``data.spearman_table`` over the block's Gram,
+        added up ``SPEARMAN_GRAM_ROWS`` rows at a time."""
+        import pandas as pd
+
+        from .gram_ops import gram_accumulate, gram_workspace
+
+        n, n_sel = int(block.shape[0]), int(block.shape[1])
+        S = torch.zeros(n_sel, dtype=torch.float64, device=self.device)
+        Cm = torch.zeros((n_sel, n_sel), dtype=torch.float64, device=self.device)
+        ws = gram_workspace(n_sel, min(n, SPEARMAN_GRAM_ROWS), self.device)   # the largest a chunk can need: it grows with the counted rows
+        for r0 in range(0, n, SPEARMAN_GRAM_ROWS):
+            gram_accumulate(block[r0:r0 + SPEARMAN_GRAM_ROWS], sums=S, gram=Cm, ws=ws)
+        sums = {"S": S.cpu().numpy(), "C": Cm.cpu().numpy()}
+        table = spearman_table(sums["C"], n)
+        frame = pd.DataFrame(table["corr"], index=index, columns=index)
+        frame.attrs.update(n_cells=n_cells, n_samples=n_samples, exact=n <= SPEARMAN_EXACT_ROWS, ties=ties.cpu().numpy(), sums=sums)
+        return frame
+
+    @torch.no_grad()
+    def get_feature_spearman_matrix(self, group_indices_list: List[List[int]], group: int, gene_list=None, cells=None, component: str = "mixture",
+                                    library_size="latent", n_samples: int = 1, use_mean: bool = True, batch_size: Optional[int] = None, _noise=None):
+        """Spearman's rank correlation of the decoded expression of ONE group's genes over the cells (scvi-tools'
+        ``get_feature_correlation_matrix(correlation_type="spearman")``): a pandas DataFrame [n_sel, n_sel] labelled on both axes by the
+        selected genes, the Pearson correlation of the genes' average ranks.  Arguments, checks and errors are exactly those of
+        ``get_feature_correlation_matrix`` (without ``correlation_type``), and the ranked values are the very fp32 numbers
+        ``get_normalized_expression`` returns for the same arguments: same minibatch walk, same kernel.
+
+        How it is computed: every step's counted rows of the decoded [batch, n_sel] block are copied on the device into ONE fp32 block
+        [n_cells * n_samples, n_sel] (with sampled latents, draw ``sample`` of the counted cell at rank i among the counted cells is row
+        ``sample * n_cells + i``: the correlation runs over n_cells * n_samples rows, scvi-tools' flattening).  ``rank_ops.
+        rank_transform`` then replaces every column IN PLACE by 2 * average rank - (rows + 1) (spv_rank_values: the column sort of
+        ``rank_genes_groups``, exact integers), and spv_gram_f64 adds the block's Gram up in row chunks.
+        ``attrs``: ``n_cells``, ``n_samples``, ``exact`` (rows <= 208 063: every sum is then an exact integer whatever the order of
+        addition, ``data.spearman_table``), ``ties`` (int64 [n_sel]: the sum of t^3 - t over each gene's runs of equal values, 0 for
+        a gene without ties) and ``sums`` = {"S": [n_sel], "C": [n_sel, n_sel]} straight from the kernel -- S is exactly 0.  A gene
+        whose values are all equal has NaN in its row and column; the diagonal is exactly 1 elsewhere; the frame is symmetric in bits
+        and two calls agree bit for bit.
+        Limits, each a ValueError ahead of any device work: at most 4096 genes and at most 2^20 rows (cells * n_samples).
+        Device memory, in bytes: the block 4 * rows * n_sel; the sort's workspace at most 8192 + max(``rank_ops.WS_BUDGET_BYTES``,
+        20 * rows) (1 GiB by default: the genes are walked in slabs that fit); the table 8 * n_sel^2 (plus n_sel * 8 for S and one
+        decoded [batch, n_sel] block)."""
+        _what, _log_l, n_samples = check_expression_args(component, library_size, n_samples, use_mean)
+        g = check_group(group)
+        counted = correlation_cells(group_indices_list[g], cells, group=g)
+        n_g, n_cells = len(counted), int(counted.sum())
+        _sel, dev_sel, n_sel, index = self._genes(g, gene_list, own=True)
+        check_spearman_shape(n_cells * n_samples, n_sel, "get_feature_spearman_matrix")
+        from .ops import GroupCounts
+        from .rank_ops import rank_transform
+
+        place = np.cumsum(counted) - 1   # position in the group's read-out -> row among the counted cells
+        block = torch.empty((n_cells * n_samples, n_sel), dtype=torch.float32, device=self.device)
+        blk = None
+        for step, tensors, B, _off, pos in walk_positions(self._eval_minibatches(group_indices_list, batch_size, None), g, n_g):
+            use = np.nonzero((pos >= 0) & counted[np.maximum(pos, 0)])[0]   # a cut row (pos -1) is never counted
+            if not use.size:
+                continue   # eval mode: steps are independent of each other
+            src = torch.as_tensor(use, device=self.device)
+            dst = torch.as_tensor(place[pos[use]], device=self.device)
+            if blk is None or blk.shape[0] < B[g]:
+                blk = torch.empty((B[g], n_sel), dtype=torch.float32, device=self.device)
+            for smp, out in self._draws(step, tensors, B, n_samples, _noise):
+                x = self.module.expected_expression(out, g, genes=dev_sel, what=component, library_size=library_size, use_mean=use_mean, out=blk)
+                block.index_copy_(0, dst + smp * n_cells, x.index_select(0, src))
+        rows = torch.arange(block.shape[0], dtype=torch.int32, device=self.device)
+        _block, ties = rank_transform(GroupCounts(block, n_sel, 0), rows, out=block, ties=True)
+        return self._spearman_frame(block, ties, index, n_cells, n_samples)
+
+    @torch.no_grad()
+    def count_spearman_matrix(self, group_indices_list: List[List[int]], group: int, gene_list=None, cells=None, normalize: bool = True,
+                              target_sum: float = 1e4):
+        """Spearman's rank correlation of the OBSERVED counts of ONE group's genes over the cells: the frame of
+        ``get_feature_spearman_matrix`` -- same labels, same ``attrs`` (``n_samples`` is 1) -- for the data itself.  It needs no
+        trained model and decodes nothing: the companion of ``count_statistics`` and ``rank_genes_groups``.
+        The ranked keys are ``rank_genes_groups``': ``normalize=True`` ranks count * fp32(target_sum / the cell's total over ALL of the
+        group's genes) (a cell without counts gets the weight 0; log1p is monotone, so these are the ranks of log-normalised data),
+        ``normalize=False`` the raw counts (``target_sum`` is still checked).  ``gene_list``: this group's selection, as
+        ``rank_genes_groups`` takes it; ``cells``: None (all of ``group_indices_list[group]``) or adata row numbers of cells of it,
+        resolved like ``cells`` of ``get_feature_correlation_matrix`` with its errors; the rows are ranked in the group's order.
+        Single-cell counts are mostly zeros: all zero keys of a gene form one run at the bottom that is never stored or sorted
+        (spv_rank_values_stage), which is what this method is fast for.  Every device output is an integer, so dense and sparse
+        ``counts_storage`` give the same frame bit for bit and two calls agree bit for bit.
+        Limits, each a ValueError ahead of any device work: at most 4096 genes and 2^20 cells.  Device memory, in bytes: the rank
+        block 4 * cells * n_sel, the sort's workspace at most 8192 + max(``rank_ops.WS_BUDGET_BYTES``, 20 * cells), the table 8 * n_sel^2."""
+        from .count_ops import count_totals
+        from .rank_ops import rank_transform
+
+        target_sum = check_target_sum(target_sum)
+        g = check_group(group)
+        counted = correlation_cells(group_indices_list[g], cells, group=g)
+        listed = np.asarray(group_indices_list[g]).astype(np.int64).ravel()[counted]
+        _sel, dev_sel, n_sel, index = self._genes(g, gene_list, own=True)
+        check_spearman_shape(len(listed), n_sel, "count_spearman_matrix")
+        rows = torch.as_tensor(self._local_rows(g, listed).astype(np.int32), device=self.device)
+        w = None
+        if normalize:
+            total = count_totals(self.counts[g]).index_select(0, rows.long())
+            w = torch.where(total > 0, target_sum / total, torch.zeros_like(total)).to(torch.float32)
+        block, ties = rank_transform(self.counts[g], rows, w=w, genes=dev_sel, ties=True)
+        return self._spearman_frame(block, ties, index, len(listed), 1)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
