@@ -950,6 +950,55 @@ int spv_rank_values(const spv_rank_values_args* a, void* stream);
 /* the workspace in bytes (8-byte multiple; 0 for a non-positive or out-of-range argument, like spv_rank_ws_bytes) */
 int64_t spv_rank_values_ws_bytes(int32_t n, int32_t n_sel);
 
+/* PCA of the log-normalised OBSERVED counts (pca_ops.block_lanczos; spVIPES.count_pca / spVIPES.pca of the user API): the operand
+ * stage and the two skinny products of a block Krylov step against a matrix X [n][G] that is never stored.  The list, the piece and
+ * the addressing of x are spv_rank_stage's: position p of a list of n names the cell x.rows[p - pos_off] (x.rows == NULL: cell
+ * p - pos_off) of a dense matrix that holds the positions [pos_off, pos_off + n_piece); w is an optional fp32 weight per LIST POSITION.
+ * The operand, the same device function in all three kernels, for the count c (uint16, or a non-negative finite fp32) of gene j:
+ *     u = (float) c * w[p]          ONE fp32 multiply, never contracted (spv_rank_stage's key; (float) c without w)
+ *     a = pca_log1p(u)              one fixed sequence of fp32 operations (csrc/spv_pca.h), a == 0 exactly for u == 0
+ *     x(p, j) = (a - mu[j]) * scale[j]     an fp32 subtract, then an fp32 multiply, not fused; mu == NULL reads as 0, scale == NULL as 1
+ * A gene with scale[j] == 0 contributes exactly 0: a gene selection is a scale vector; every kernel walks all G genes and gathers no
+ * column.  A row number outside [0, n_rows) reads as a zero count and is never dereferenced.  l is 16, 32, 48 or 64.
+ *   spv_pca_stage    WRITES block[(p - pos_off) * ld_block + j] = x(p, j), fp32 [n_piece][ld_block >= G]; columns >= G are never touched.
+ *     It reads x, G, n_rows, n_piece, pos_off, n, w, mu, scale, block, ld_block.
+ *   spv_pca_project  WRITES Y[p * ld_y + t] = sum_j x(p, j) V[j * ld_v + t] for the piece's positions and t < l.  V fp32 [G][ld_v >= l],
+ *     Y fp32 [n][ld_y >= l].  One workgroup owns spv_pca_cell_tile() positions and walks the genes in ascending order into
+ *     v_mfma_f32_32x32x2_f32 accumulators: every product is exact, the sum of a row is ONE fp32 chain over the genes 0 .. G - 1.  A
+ *     row's result depends on that row alone: not on the piece, not on the other rows, not on dense or CSR storage.
+ *   spv_pca_back     ADDS sum_p x(p, j) Y[p * ld_y + t] over the piece's positions onto Z[j * ld_z + t], fp64 [G][ld_z >= l].  The list
+ *     is cut into slabs at ABSOLUTE positions, multiples of spv_pca_slab(); pos_off must be one.  One workgroup per (64 genes, slab)
+ *     sums its slab in ascending position order on the same MFMA and stores an fp32 partial tile to ws; a merge launch of the same
+ *     call adds the piece's slabs onto Z in ascending slab order, one fp64 addition per slab.  No floating-point atomics, every element
+ *     one writer, every order fixed: a list passed in one piece or in slab-aligned pieces (in list order) gives the same bits, two
+ *     calls agree bit for bit, and the calls of several groups collect in one Z.
+ *     ws: spv_pca_ws_bytes(G, n_piece, l) = 4 * ceil(n_piece / slab) * round_up(G, 64) * l bytes, 8-byte aligned, overwritten.
+ * Nothing is allocated.  Rejected ahead of any HIP call with SPV_ERR_ARG, all three: null arguments / x.X; unknown dtype; G, n_rows, n
+ * or n_piece < 1; pos_off < 0 or pos_off + n_piece > n; n_piece > n_rows without a row list; ld < col_off + G.  stage: null block;
+ * ld_block < G.  project and back: l not 16, 32, 48 or 64; null Y; ld_y < l.  project: null V; ld_v < l.  back: pos_off off a slab
+ * bound; null Z; Z not 8-byte aligned; ld_z < l; ws null, not 8-byte aligned, or ws_bytes short. */
+typedef struct spv_pca_args {
+  spv_counts x;                            /* the matrix that holds the piece */
+  int32_t G, n_rows, n_piece, pos_off;
+  int32_t n, l;                            /* the list; the columns of V / Y / Z */
+  const float* w;                          /* [n] or NULL */
+  const float* mu;                         /* [G] or NULL */
+  const float* scale;                      /* [G] or NULL */
+  float* block; int64_t ld_block;          /* stage: [n_piece][ld_block >= G] */
+  const float* V; int64_t ld_v;            /* project: [G][ld_v >= l] */
+  float* Y; int64_t ld_y;                  /* project writes, back reads: [n][ld_y >= l] */
+  double* Z; int64_t ld_z;                 /* back: [G][ld_z >= l] */
+  void* ws; int64_t ws_bytes;              /* back: spv_pca_ws_bytes(G, n_piece, l) bytes or more */
+} spv_pca_args;
+int spv_pca_stage(const spv_pca_args* a, void* stream);
+int spv_pca_project(const spv_pca_args* a, void* stream);
+int spv_pca_back(const spv_pca_args* a, void* stream);
+/* pure shape functions: the slab of back (it divides 4096); the cell tile of project; the workspace of back in bytes (0 for a
+ * non-positive G or n_piece or an l outside the four) */
+int32_t spv_pca_slab(void);
+int32_t spv_pca_cell_tile(void);
+int64_t spv_pca_ws_bytes(int32_t G, int32_t n_piece, int32_t l);
+
 /* Exact t-SNE of a layout of at most SPV_TSNE_DMAX dimensions (spVIPES.latent_tsne / spVIPES.tsne of the user API): three entry points.
  *
  * spv_tsne_repulsion: the all-pairs half of the gradient, nothing of size n_q x n_c stored.  For query row i of Q over the candidates C

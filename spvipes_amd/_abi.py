@@ -376,6 +376,17 @@ class SpvRankValuesArgs(C.Structure):
                 ("ties", C.c_void_p), ("nonzero", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+PCA_COLUMNS = (16, 32, 48, 64)   # the l of spv_pca_project / spv_pca_back
+
+
+class SpvPcaArgs(C.Structure):
+    """the arguments of spv_pca_stage / spv_pca_project / spv_pca_back (include/spvipes_hip.h: spv_pca_args)"""
+    _fields_ = [("x", SpvCounts), ("G", C.c_int32), ("n_rows", C.c_int32), ("n_piece", C.c_int32), ("pos_off", C.c_int32), ("n", C.c_int32),
+                ("l", C.c_int32), ("w", C.c_void_p), ("mu", C.c_void_p), ("scale", C.c_void_p), ("block", C.c_void_p), ("ld_block", C.c_int64),
+                ("V", C.c_void_p), ("ld_v", C.c_int64), ("Y", C.c_void_p), ("ld_y", C.c_int64), ("Z", C.c_void_p), ("ld_z", C.c_int64),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 TSNE_DMAX = 4   # SPV_TSNE_DMAX
 
 
@@ -508,6 +519,12 @@ _SIGNATURES = {
     "spv_rank_values_stage": (C.c_int, [C.POINTER(SpvRankValuesArgs), C.c_void_p]),
     "spv_rank_values": (C.c_int, [C.POINTER(SpvRankValuesArgs), C.c_void_p]),
     "spv_rank_values_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "spv_pca_stage": (C.c_int, [C.POINTER(SpvPcaArgs), C.c_void_p]),
+    "spv_pca_project": (C.c_int, [C.POINTER(SpvPcaArgs), C.c_void_p]),
+    "spv_pca_back": (C.c_int, [C.POINTER(SpvPcaArgs), C.c_void_p]),
+    "spv_pca_slab": (C.c_int32, []),
+    "spv_pca_cell_tile": (C.c_int32, []),
+    "spv_pca_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "spv_tsne_repulsion": (C.c_int, [C.POINTER(SpvTsneRepArgs), C.c_void_p]),
     "spv_tsne_splits": (C.c_int32, [C.c_int32, C.c_int32]),
     "spv_tsne_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "libspvipes_hip.so")
 SOURCES = ["spv_abi.hip"]
-HEADERS = ["spv_common.h", "spv_adam.h", "spv_gemm.h", "spv_fc1.h", "spv_dec_gemm.h", "spv_decoder.h", "spv_dec_expected.h", "spv_dec_sample.h", "spv_dec_sample_stats.h", "spv_dec_expected_stats.h", "spv_de.h", "spv_de_median.h", "spv_count_stats.h", "spv_knn.h", "spv_pair_scan.h", "spv_ot.h", "spv_ot_segments.h", "spv_ot_project.h", "spv_silhouette.h", "spv_gram.h", "spv_rank.h", "spv_rank_values.h", "spv_tsne.h", "spv_lisi.h", "spv_small.h", "spv_poe_n.h", os.path.join("..", "..", "include", "spvipes_hip.h")]
+HEADERS = ["spv_common.h", "spv_adam.h", "spv_gemm.h", "spv_fc1.h", "spv_dec_gemm.h", "spv_decoder.h", "spv_dec_expected.h", "spv_dec_sample.h", "spv_dec_sample_stats.h", "spv_dec_expected_stats.h", "spv_de.h", "spv_de_median.h", "spv_count_stats.h", "spv_knn.h", "spv_pair_scan.h", "spv_ot.h", "spv_ot_segments.h", "spv_ot_project.h", "spv_silhouette.h", "spv_gram.h", "spv_rank.h", "spv_rank_values.h", "spv_pca.h", "spv_tsne.h", "spv_lisi.h", "spv_small.h", "spv_poe_n.h", os.path.join("..", "..", "include", "spvipes_hip.h")]
 
 
 FLAGS = [

@@ -20,6 +20,7 @@
 #include "spv_gram.h"
 #include "spv_rank.h"
 #include "spv_rank_values.h"
+#include "spv_pca.h"
 #include "spv_tsne.h"
 #include "spv_lisi.h"
 #include "spv_small.h"
@@ -1507,6 +1508,88 @@ extern "C" int spv_rank_values(const spv_rank_values_args* x, void* stream) {
   if (rc != SPV_OK) return rc;
   hipLaunchKernelGGL(rank_values_store_kernel, dim3((unsigned)((x->n + RANKV_T - 1) / RANKV_T), (unsigned)((x->n_sel + RANKV_T - 1) / RANKV_T)), dim3(RANKV_THREADS), 0, s, a);
   return launch_status(who);
+}
+
+// ---------------------------------------------------------------------------------------------
+// PCA of the log-normalised counts: the operand stage and the two skinny products on the fp32 MFMA (spv_pca.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t spv_pca_slab(void) { return PCA_SLAB; }
+extern "C" int32_t spv_pca_cell_tile(void) { return PCA_CELL_TILE; }
+extern "C" int64_t spv_pca_ws_bytes(int32_t G, int32_t n_piece, int32_t l) { return pca_ws_bytes(G, n_piece, l); }
+
+// what the three entry points check of the matrix, the list and the piece
+static int pca_check(const spv_pca_args* x, const char* who) {
+  if (!x) return fail(SPV_ERR_ARG, "%s: null arguments", who);
+  if (!x->x.X) return fail(SPV_ERR_ARG, "%s: null count matrix", who);
+  if (x->x.dtype != SPV_COUNT_U16 && x->x.dtype != SPV_COUNT_F32) return fail(SPV_ERR_ARG, "%s: unknown count dtype", who);
+  if (x->G < 1 || x->n_rows < 1) return fail(SPV_ERR_ARG, "%s: G and n_rows must be positive", who);
+  if (x->n < 1) return fail(SPV_ERR_ARG, "%s: n < 1", who);
+  if (x->n_piece < 1 || x->pos_off < 0 || (int64_t)x->pos_off + x->n_piece > x->n) return fail(SPV_ERR_ARG, "%s: the piece [pos_off, pos_off + n_piece) must be non-empty and lie in [0, n)", who);
+  if (!x->x.rows && x->n_piece > x->n_rows) return fail(SPV_ERR_ARG, "%s: without a row list n_piece must not exceed n_rows", who);
+  if (x->x.col_off < 0 || x->x.ld < (int64_t)x->x.col_off + x->G) return fail(SPV_ERR_ARG, "%s: ld < col_off + G", who);
+  return SPV_OK;
+}
+// ... and of the l columns of the two products
+static int pca_check_y(const spv_pca_args* x, const char* who) {
+  if (!pca_l_ok(x->l)) return fail(SPV_ERR_ARG, "%s: l must be 16, 32, 48 or 64", who);
+  if (!x->Y) return fail(SPV_ERR_ARG, "%s: null Y", who);
+  if (x->ld_y < x->l) return fail(SPV_ERR_ARG, "%s: ld_y < l", who);
+  return SPV_OK;
+}
+
+static PcaArgs pca_args(const spv_pca_args* x) {
+  return PcaArgs{x->x.X, (long)x->x.ld, x->x.rows, x->x.col_off, x->G, x->n_rows, x->n_piece, x->pos_off, x->n, x->l, x->w, x->mu, x->scale,
+                 x->block, (long)x->ld_block, x->V, (long)x->ld_v, x->Y, (long)x->ld_y, x->Z, (long)x->ld_z, (float*)x->ws};
+}
+
+extern "C" int spv_pca_stage(const spv_pca_args* x, void* stream) {
+  const char* const who = "spv_pca_stage";
+  int rc = pca_check(x, who);
+  if (rc != SPV_OK) return rc;
+  if (!x->block) return fail(SPV_ERR_ARG, "%s: null block", who);
+  if (x->ld_block < x->G) return fail(SPV_ERR_ARG, "%s: ld_block < G", who);
+  const PcaArgs a = pca_args(x);
+  const dim3 grid((unsigned)((x->n_piece + PCA_ST_P - 1) / PCA_ST_P), (unsigned)((x->G + PCA_THREADS - 1) / PCA_THREADS));
+  if (x->x.dtype == SPV_COUNT_U16) hipLaunchKernelGGL(pca_stage_kernel<true>, grid, dim3(PCA_THREADS), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(pca_stage_kernel<false>, grid, dim3(PCA_THREADS), 0, (hipStream_t)stream, a);
+  return launch_status(who);
+}
+
+extern "C" int spv_pca_project(const spv_pca_args* x, void* stream) {
+  const char* const who = "spv_pca_project";
+  int rc = pca_check(x, who);
+  if (rc == SPV_OK) rc = pca_check_y(x, who);
+  if (rc != SPV_OK) return rc;
+  if (!x->V) return fail(SPV_ERR_ARG, "%s: null V", who);
+  if (x->ld_v < x->l) return fail(SPV_ERR_ARG, "%s: ld_v < l", who);
+  const PcaArgs a = pca_args(x);
+  const dim3 grid((unsigned)((x->n_piece + PCA_CELL_TILE - 1) / PCA_CELL_TILE));
+  if (x->x.dtype == SPV_COUNT_U16) hipLaunchKernelGGL(pca_project_kernel<true>, grid, dim3(PCA_THREADS), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(pca_project_kernel<false>, grid, dim3(PCA_THREADS), 0, (hipStream_t)stream, a);
+  return launch_status(who);
+}
+
+extern "C" int spv_pca_back(const spv_pca_args* x, void* stream) {
+  const char* const who = "spv_pca_back";
+  int rc = pca_check(x, who);
+  if (rc == SPV_OK) rc = pca_check_y(x, who);
+  if (rc != SPV_OK) return rc;
+  if (x->pos_off % PCA_SLAB) return fail(SPV_ERR_ARG, "%s: pos_off must be a multiple of spv_pca_slab()", who);
+  if (!x->Z) return fail(SPV_ERR_ARG, "%s: null Z", who);
+  if (reinterpret_cast<uintptr_t>(x->Z) & 7) return fail(SPV_ERR_ARG, "%s: Z must be 8-byte aligned", who);
+  if (x->ld_z < x->l) return fail(SPV_ERR_ARG, "%s: ld_z < l", who);
+  if (!x->ws) return fail(SPV_ERR_ARG, "%s: null ws", who);
+  if (reinterpret_cast<uintptr_t>(x->ws) & 7) return fail(SPV_ERR_ARG, "%s: ws must be 8-byte aligned", who);
+  if (x->ws_bytes < pca_ws_bytes(x->G, x->n_piece, x->l)) return fail(SPV_ERR_ARG, "%s: ws_bytes is less than spv_pca_ws_bytes(G, n_piece, l)", who);
+  const PcaArgs a = pca_args(x);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(pca_gene_pad(x->G) / PCA_GENE_TILE), (unsigned)pca_slabs(x->n_piece));
+  if (x->x.dtype == SPV_COUNT_U16) hipLaunchKernelGGL(pca_back_kernel<true>, grid, dim3(PCA_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(pca_back_kernel<false>, grid, dim3(PCA_THREADS), 0, s, a);
+  rc = launch_status("spv_pca_back (partial pass)");
+  if (rc != SPV_OK) return rc;
+  hipLaunchKernelGGL(pca_merge_kernel, dim3((unsigned)(((long)x->G * x->l + PCA_THREADS - 1) / PCA_THREADS)), dim3(PCA_THREADS), 0, s, a);
+  return launch_status("spv_pca_back (merge pass)");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1867,3 +1867,206 @@ def check_transport_project_args(adata, rep, plan, values, onto, key_added):
     if not np.isfinite(V).all():
         raise ValueError("values holds non-finite entries (after the conversion to float32)")
     return obs_idx, X0, X1, V, categories
+
+
+# ---- PCA of the log-normalised counts (model.count_pca / spVIPES.pca): the resident counts, the pairing, the argument checks, the sign rule ----
+PCA_MAX_COMPS = 56       # n_comps, at most: the block is min(64, round_up(n_comps + 8, 16)) columns and the kernels take 64
+PCA_MIN_GENES = 16       # paired genes, at least: the smallest block the kernels take
+
+
+def resident_group_counts(X, obs_idx, var_idx, device, counts_storage: str = "auto"):
+    """The per-group count matrices resident in HBM, as the model's constructor keeps them: rows = the group's cells (obs order),
+    columns = its own genes.  ``counts_storage``: "dense", "sparse" (CSR) or "auto" (CSR for a scipy.sparse ``X``, else dense); a
+    scipy.sparse input is never densified as a whole (csr_group_arrays works on its stored entries)."""
+    sparse_in = is_sparse(X)
+    if (counts_storage == "sparse") or (counts_storage == "auto" and sparse_in):
+        return [to_sparse_group_counts(X, obs_idx[g], var_idx[g], device) for g in range(2)]
+    if sparse_in:   # "dense" storage of a sparse input: one group's slice at a time
+        return [to_group_counts(csr_to_dense(*csr_group_arrays(X, obs_idx[g], var_idx[g])[:3], len(var_idx[g])), device) for g in range(2)]
+    X = np.asarray(X)
+    return [to_group_counts(X[obs_idx[g]][:, var_idx[g]], device) for g in range(2)]
+
+
+def check_pca_args(n_comps, tol=1e-4, seed=0, n_cells: Optional[int] = None, n_genes: Optional[int] = None):
+    """The argument checks of count_pca -> (n_comps, tol, seed) as plain numbers; every refusal is a ValueError with the limit in it"""
+    if isinstance(n_comps, bool) or not isinstance(n_comps, (int, np.integer)) or not 1 <= int(n_comps) <= PCA_MAX_COMPS:
+        raise ValueError(f"n_comps must be an integer between 1 and {PCA_MAX_COMPS}, got {n_comps!r}")
+    try:
+        t = float(tol)
+    except (TypeError, ValueError):
+        t = float("nan")
+    if isinstance(tol, (bool, str)) or not (math.isfinite(t) and 0.0 < t < 1.0):
+        raise ValueError(f"tol must be a number in (0, 1), got {tol!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= SAMPLE_MAX_SEED:
+        raise ValueError(f"seed must be an integer in [0, 2^32), got {seed!r}")
+    n_comps = int(n_comps)
+    if n_cells is not None and n_cells < 2:
+        raise ValueError(f"count_pca needs at least 2 cells, got {n_cells}")
+    if n_genes is not None and n_genes < PCA_MIN_GENES:
+        raise ValueError(f"count_pca needs at least {PCA_MIN_GENES} genes (the smallest block of the kernels), got {n_genes}")
+    for what, m in (("cells", n_cells), ("genes", n_genes)):
+        if m is not None and n_comps >= m:
+            raise ValueError(f"n_comps must be smaller than the number of {what} ({m}), got {n_comps}")
+    if n_genes is not None and (n_comps + 15) // 16 * 16 > n_genes:
+        raise ValueError(f"n_comps={n_comps} needs an iteration block of {(n_comps + 15) // 16 * 16} columns (a multiple of 16), and a block cannot "
+                         f"be wider than the number of genes ({n_genes}): at most n_comps={n_genes // 16 * 16} with these genes")
+    return n_comps, t, int(seed)
+
+
+def pca_block(n_comps: int, n_genes: Optional[int] = None) -> int:
+    """The block of block_lanczos: min(64, round_up(n_comps + 8, 16)) by default; with fewer genes than that, the largest multiple of
+    16 the genes allow (a block cannot be wider than the operator).  It is at least round_up(n_comps, 16) wherever ``check_pca_args``
+    has accepted (n_comps, n_genes)."""
+    b = min(64, (int(n_comps) + 8 + 15) // 16 * 16)
+    return b if n_genes is None else min(b, int(n_genes) // 16 * 16)
+
+
+def pca_group_keys(uns, n_groups: int = 2):
+    """the group keys of ``uns["groups_mapping"]`` (prepare_adatas: {position: key}; a list is taken as it is), or None"""
+    gm = uns.get("groups_mapping") if hasattr(uns, "get") else None
+    if gm is None:
+        return None
+    if isinstance(gm, dict):
+        keys = [gm[k] if k in gm else list(gm.values())[k] for k in range(n_groups)] if len(gm) >= n_groups else None
+    else:
+        keys = list(gm)[:n_groups] if len(gm) >= n_groups else None
+    return None if keys is None else [str(k) for k in keys]
+
+
+def pca_pair_genes(names, keys=None, gene_list=None, n_genes=None):
+    """The PAIRED genes of the joint PCA -> (pos0 int32 [p], pos1 int32 [p], labels [p]): column t of the joint matrix is gene pos0[t]
+    of group 0 and gene pos1[t] of group 1.
+    Default: every group's names (``group_var_names``) lose the prefix ``"<group key>_"`` that prepare_adatas adds (``keys``: the
+    group keys, None = nothing is stripped; a name without the prefix stays as it is); the pairing keeps the names BOTH groups have, in
+    group 0's order (the first occurrence of a repeated name).  ``gene_list=[names0, names1]`` (names or positions, as
+    ``resolve_gene_list`` takes them) pairs BY POSITION: equal lengths, no repeats.  Without names and without ``gene_list`` there is
+    nothing to pair by: a ValueError that says so -- nothing is guessed."""
+    if gene_list is not None:
+        sel = resolve_gene_list(gene_list, n_genes, names)
+        if sel[0] is None or sel[1] is None:
+            raise ValueError("gene_list of the joint PCA must name BOTH groups' genes: [names0, names1], paired by position")
+        if len(sel[0]) != len(sel[1]):
+            raise ValueError(f"gene_list pairs by position: the two lists must have equal length, got {len(sel[0])} and {len(sel[1])}")
+        for g in range(2):
+            if len(np.unique(sel[g])) != len(sel[g]):
+                raise ValueError(f"gene_list[{g}] repeats a gene: a paired gene is one column of the joint matrix")
+        labels = np.asarray(names[0])[sel[0]] if names is not None and names[0] is not None else np.asarray(sel[0])
+        return sel[0].astype(np.int32), sel[1].astype(np.int32), labels
+    if names is None or names[0] is None or names[1] is None:
+        raise ValueError("the joint PCA pairs the groups' genes by name, and this AnnData carries neither var_names nor uns['groups_var_names']: "
+                         "pass gene_list=[names0, names1] (positions paired by position), or group=g for one group's own PCA")
+    stripped = []
+    for g in range(2):
+        pre = None if keys is None else keys[g] + "_"
+        stripped.append([s[len(pre):] if pre and s.startswith(pre) else s for s in np.asarray(names[g]).astype(str)])
+    first1 = {}
+    for i, s in enumerate(stripped[1]):
+        first1.setdefault(s, i)
+    pos0, pos1, labels, seen = [], [], [], set()
+    for i, s in enumerate(stripped[0]):
+        if s in first1 and s not in seen:
+            seen.add(s)
+            pos0.append(i), pos1.append(first1[s]), labels.append(s)
+    if not pos0:
+        raise ValueError("the two groups share no gene name (after the '<group key>_' prefixes are stripped): pass gene_list=[names0, names1]")
+    return np.asarray(pos0, np.int32), np.asarray(pos1, np.int32), np.asarray(labels)
+
+
+def pca_sign_flip(components: np.ndarray) -> np.ndarray:
+    """The sign rule of count_pca: +1 / -1 per component (row of ``components`` [n_comps, p]) such that its largest |loading| becomes
+    positive; ties go to the smaller gene index; an all-zero row keeps +1"""
+    c = np.asarray(components, np.float64)
+    at = np.argmax(np.abs(c), axis=1)   # (the first of equal maxima)
+    lead = c[np.arange(c.shape[0]), at]
+    return np.where(lead < 0, -1.0, 1.0)
+
+
+@dataclass
+class PcaResult:
+    """What count_pca returns.  ``scores`` fp32 [cells, n_comps]; ``components`` fp64 [n_comps, p] (the fp32 vectors the scores were
+    made with); ``genes``: per group the paired names (positions without names), or the one group's; ``mean`` / ``var`` fp64 [p] of the
+    log-normalised values (ddof 1); ``variance`` = theta / (n - 1); ``variance_ratio`` against the total variance from the moments;
+    ``residuals``: || X^T X v - theta v || of the returned vectors; ``n_blocks`` / ``n_restarts`` / ``converged``: the iteration's
+    record; ``obs``: the adata rows of the scores' rows"""
+    scores: np.ndarray
+    components: np.ndarray
+    genes: list
+    mean: np.ndarray
+    var: np.ndarray
+    variance: np.ndarray
+    variance_ratio: np.ndarray
+    residuals: np.ndarray
+    n_blocks: int
+    n_restarts: int
+    converged: bool
+    obs: np.ndarray
+    theta: Optional[np.ndarray] = None
+    params: Optional[dict] = None
+
+
+def pca_plan(adata, n_genes, obs_idx, group_indices_list, n_comps=50, group=None, gene_list=None, normalize=True, target_sum=1e4, scale=False,
+             tol=1e-4, seed=0) -> dict:
+    """Everything count_pca decides on the host, every refusal included, ahead of any device work -> dict of ``groups`` (the group
+    numbers whose cells are stacked), ``cols`` (per such group the int32 positions of the joint columns among its genes), ``genes``
+    (per such group the columns' names, positions without names), ``rows`` (per such group the rows of its resident matrix),
+    ``obs`` (the adata rows of the stacked cells), ``params``.  ``n_genes``: the groups' gene counts; ``obs_idx``: their adata rows."""
+    target_sum = check_target_sum(target_sum)
+    for what, v in (("normalize", normalize), ("scale", scale)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{what} must be True or False, got {v!r}")
+    names = group_var_names(adata)
+    if group is None:
+        gs = [0, 1]
+        pos0, pos1, _labels = pca_pair_genes(names, pca_group_keys(adata.uns), gene_list, n_genes)
+        cols = [pos0, pos1]
+    else:
+        g = check_group(group)
+        gs = [g]
+        sel = resolve_gene_list(gene_list, n_genes, names)[g]
+        if sel is None:
+            sel = np.arange(n_genes[g], dtype=np.int32)
+        elif len(np.unique(sel)) != len(sel):
+            raise ValueError(f"gene_list[{g}] repeats a gene: a gene is one column of the PCA")
+        cols = [np.asarray(sel, np.int32)]
+    if not hasattr(group_indices_list, "__len__") or len(group_indices_list) != 2:
+        raise ValueError("group_indices_list must hold one list of adata row numbers per group (2)")
+    rows, obs = [], []
+    for g in gs:
+        listed = np.asarray(group_indices_list[g]).astype(np.int64).ravel()
+        if listed.size and (listed.min() < 0 or listed.max() >= adata.n_obs):
+            raise ValueError(f"group_indices_list[{g}] must hold adata row numbers in [0, {adata.n_obs})")
+        pos = np.full(adata.n_obs, -1, dtype=np.int64)
+        pos[np.asarray(obs_idx[g])] = np.arange(len(obs_idx[g]))
+        loc = pos[listed]
+        if (loc < 0).any():
+            raise ValueError(f"group_indices_list[{g}] contains cells that do not belong to group {g}")
+        rows.append(loc.astype(np.int32))
+        obs.append(listed)
+    if any(len(r) == 0 for r in rows):
+        raise ValueError("count_pca: every group that takes part needs at least one listed cell")
+    n_comps, tol, seed = check_pca_args(n_comps, tol, seed, n_cells=sum(len(r) for r in rows), n_genes=len(cols[0]))
+    genes = [np.asarray(c) if names[g] is None else np.asarray(names[g])[c] for g, c in zip(gs, cols)]
+    params = dict(n_comps=n_comps, group=group, normalize=bool(normalize), target_sum=target_sum, scale=bool(scale), tol=tol, seed=seed,
+                  block=pca_block(n_comps, len(cols[0])), n_genes=len(cols[0]))
+    return dict(groups=gs, cols=cols, genes=genes, rows=rows, obs=np.concatenate(obs), params=params)
+
+
+def check_pca_adata(adata, layer=None, counts_storage="auto", key_added="X_pca", kwargs=None):
+    """The refusals of spVIPES.pca that concern the AnnData and its own arguments -> the count matrix (``adata.X`` or the layer)"""
+    for k in ("groups_var_indices", "groups_obs_indices"):
+        if k not in adata.uns:
+            raise ValueError(f"adata.uns['{k}'] missing: build the AnnData with prepare_adatas (or the same schema)")
+    if counts_storage not in ("auto", "dense", "sparse"):
+        raise ValueError(f"counts_storage must be 'auto', 'dense' or 'sparse', got {counts_storage!r}")
+    if not isinstance(key_added, str) or not key_added:
+        raise ValueError(f"key_added must be a non-empty string, got {key_added!r}")
+    allowed = ("gene_list", "normalize", "target_sum", "scale", "tol", "seed")
+    for k in (kwargs or {}):
+        if k not in allowed:
+            raise ValueError(f"spVIPES.pca takes the keyword arguments {allowed} of count_pca (the joint PCA over every cell), got {k!r}")
+    if layer is not None:
+        layers = getattr(adata, "layers", None)
+        if layers is None or layer not in layers:
+            raise KeyError(f"layer '{layer}' not found in adata.layers")
+        return layers[layer]
+    return adata.X

@@ -21,14 +21,15 @@ import numpy as np
 import torch
 
 from . import _abi
-from .data import (check_tsne_args, check_tsne_rep, check_tsne_schedule, tsne_frame, MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, check_transport_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table, csr_group_arrays,
-                   csr_to_dense, de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
-                   latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, to_group_counts, to_sparse_group_counts, vs_rest_frames, walk_positions,
+from .data import (check_tsne_args, check_tsne_rep, check_tsne_schedule, tsne_frame, MinibatchSampler, RowBlocks, check_de_args, check_neighbor_args, check_transport_args, neighbor_self_positions, transfer_frame, vote_labels, check_expression_args, check_group, check_ppc_library, check_sample_args, check_target_sum, count_rest, count_table,
+                   de_bank_rows, de_label_populations, de_pair_rows, de_populations, de_subsample, de_table, expression_stats_frame, expression_stats_table, expression_tile_plan, format_latent_results, group_cell_labels, group_var_names, is_sparse,
+                   latent_loader_mode, latent_steps, ppc_frame, ppc_observed_columns, ppc_segments, ppc_table, resolve_gene_list, vs_rest_frames, walk_positions,
                    ClusterMatching, check_match_clusters_args, cluster_entropy_score, cluster_pair_scores, cluster_tables_from_matrix, match_cluster_labels,
                    check_transport_project_args, label_projection_frame,
                    SILHOUETTE_MAX_LABELS, check_silhouette_args, silhouette_frame, silhouette_query_blocks, silhouette_segments, silhouette_table,
                    check_lisi_args, check_lisi_keys, lisi_frame, lisi_rep_frame,
                    check_correlation_args, correlation_cells, correlation_table)
+from .data import PcaResult, check_pca_adata, pca_plan, resident_group_counts
 from .data import SPEARMAN_EXACT_ROWS, SPEARMAN_GRAM_ROWS, check_spearman_shape, spearman_table
 from .module import spVIPESmodule
 from .plan import SparsePlan
@@ -42,6 +43,18 @@ def _codes(column) -> np.ndarray:
     arr = np.asarray(column)
     _, inv = np.unique(arr, return_inverse=True)
     return inv.astype(np.float32)
+
+
+def _run_count_pca(counts, plan: dict, device) -> PcaResult:
+    """the device half of count_pca / pca: ``plan`` is ``data.pca_plan``'s"""
+    from .pca_ops import count_pca
+    q = plan["params"]
+    groups = [(counts[g], torch.as_tensor(r, dtype=torch.int32, device=device)) for g, r in zip(plan["groups"], plan["rows"])]
+    out = count_pca(groups, plan["cols"], q["n_comps"], normalize=q["normalize"], target_sum=q["target_sum"], scale=q["scale"], tol=q["tol"],
+                    seed=q["seed"], block=q["block"])
+    return PcaResult(scores=out["scores"].cpu().numpy(), components=out["components"], genes=plan["genes"], mean=out["mean"], var=out["var"],
+                     variance=out["variance"], variance_ratio=out["variance_ratio"], residuals=out["residuals"], n_blocks=out["n_blocks"],
+                     n_restarts=out["n_restarts"], converged=out["converged"], obs=plan["obs"], theta=out["theta"], params=q)
 
 
 class spVIPES:
@@ -93,18 +106,10 @@ class spVIPES:
             n_hidden=n_hidden, n_dimensions_shared=n_dimensions_shared, n_dimensions_private=n_dimensions_private,
             dropout_rate=dropout_rate, precision=precision, **model_kwargs,
         ).to(self.device)
-        # resident per-group count matrices: rows = the group's cells (obs order), columns = its own genes; a scipy.sparse input is
-        # never densified as a whole (csr_group_arrays works on its stored entries)
+        # resident per-group count matrices: rows = the group's cells (obs order), columns = its own genes (data.resident_group_counts,
+        # which spVIPES.pca shares)
         X = adata.X if setup.get("layer") is None else adata.layers[setup["layer"]]
-        sparse_in = is_sparse(X)
-        if (counts_storage == "sparse") or (counts_storage == "auto" and sparse_in):
-            self.counts = [to_sparse_group_counts(X, self.obs_idx[g], var_idx[g], self.device) for g in range(2)]
-        elif sparse_in:   # "dense" storage of a sparse input: one group's slice at a time
-            self.counts = [to_group_counts(csr_to_dense(*csr_group_arrays(X, self.obs_idx[g], var_idx[g])[:3], len(var_idx[g])), self.device)
-                           for g in range(2)]
-        else:
-            X = np.asarray(X)
-            self.counts = [to_group_counts(X[self.obs_idx[g]][:, var_idx[g]], self.device) for g in range(2)]
+        self.counts = resident_group_counts(X, self.obs_idx, var_idx, self.device, counts_storage)
         obs = adata.obs
         self._labels = [torch.tensor(_codes(obs[setup["label_key"]])[self.obs_idx[g]], device=self.device) for g in range(2)] if use_labels else None
         self._components = ([torch.tensor(_codes(obs["processed_transport_labels"])[self.obs_idx[g]], device=self.device) for g in range(2)]
@@ -242,6 +247,34 @@ class spVIPES:
         names = getattr(adata, "obs_names", None)
         return lisi_rep_frame(np.arange(n) if names is None else np.asarray(names), keyed, np.concatenate(parts), n_valid.cpu().numpy(),
                               converged.cpu().numpy(), perplexity, k)
+
+    @classmethod
+    def pca(cls, adata, n_comps: int = 50, key_added: str = "X_pca", layer: Optional[str] = None, counts_storage: str = "auto",
+            device: Optional[str] = None, **kwargs):
+        """The ``X_pca`` that ``compute_transport_plan``, ``match_transport_clusters``, ``transport_project``, ``tsne`` and ``lisi`` take
+        as ``use_rep``, made here from the raw counts: the joint PCA of ``count_pca`` (``group=None``: the paired genes of both groups,
+        log-normalised) over EVERY cell of ``adata``.  Needs no model and no training.  The count matrices become resident the way the
+        constructor keeps them (``layer``: a key of ``adata.layers``, None = ``adata.X``; ``counts_storage``: "auto" | "dense" |
+        "sparse").  ``kwargs``: ``gene_list``, ``normalize``, ``target_sum``, ``scale``, ``tol``, ``seed`` of ``count_pca``.
+        Writes the fp32 scores [n_obs, n_comps] to ``adata.obsm[key_added]``, rows in adata order (a cell of neither group gets NaN),
+        and ``adata.uns["pca"] = {"variance", "variance_ratio", "params"}``; returns the ``PcaResult``.  Every refusal comes ahead of
+        any device work, as a ValueError or KeyError with the limit in the message."""
+        X = check_pca_adata(adata, layer, counts_storage, key_added, kwargs)
+        var_idx = [np.asarray(v) for v in adata.uns["groups_var_indices"]]
+        obs_idx = [np.asarray(v) for v in adata.uns["groups_obs_indices"]]
+        plan = pca_plan(adata, [len(v) for v in var_idx], obs_idx, obs_idx, n_comps=n_comps, group=None, **kwargs)
+        if not torch.cuda.is_available():
+            raise _abi.SpvError("spvipes_amd needs an MI355X: there is no CPU fallback for the hot path")
+        dev = torch.device(device or "cuda:0")
+        counts = resident_group_counts(X, obs_idx, var_idx, dev, counts_storage)
+        result = _run_count_pca(counts, plan, dev)
+        out = np.full((adata.n_obs, result.scores.shape[1]), np.nan, dtype=np.float32)
+        out[result.obs] = result.scores
+        if getattr(adata, "obsm", None) is None:
+            adata.obsm = {}
+        adata.obsm[key_added] = out
+        adata.uns["pca"] = {"variance": result.variance, "variance_ratio": result.variance_ratio, "params": dict(result.params)}
+        return result
 
     @classmethod
     def match_transport_clusters(cls, adata, use_rep=None, plan=None, n_clusters=(4, 6, 8, 12, 16, 24, 32), cluster_key: Optional[str] = None,
@@ -1134,6 +1167,35 @@ class spVIPES:
             w = torch.where(total > 0, target_sum / total, torch.zeros_like(total)).to(torch.float32)
         block, ties = rank_transform(self.counts[g], rows, w=w, genes=dev_sel, ties=True)
         return self._spearman_frame(block, ties, index, len(listed), 1)
+
+    @torch.no_grad()
+    def count_pca(self, group_indices_list: List[List[int]], n_comps: int = 50, group: Optional[int] = None, gene_list=None, normalize: bool = True,
+                  target_sum: float = 1e4, scale: bool = False, tol: float = 1e-4, seed: int = 0) -> PcaResult:
+        """Principal components of the log-normalised OBSERVED counts: scanpy's normalize_total -> log1p -> pca on the resident count
+        matrices, which never leave the device and are never expanded -- the matrix of log-normalised values is made in registers
+        inside two fused fp32 MFMA kernels (``pca_ops``).  It needs no trained model and decodes nothing: the
+        companion of ``count_statistics``, ``rank_genes_groups`` and ``count_spearman_matrix``, with their weights -- count *
+        fp32(target_sum / the cell's total over ALL of its group's genes), a cell without counts gets the weight 0;
+        ``normalize=False`` takes log1p of the raw counts (``target_sum`` is still checked).
+        ``group=None``: the JOINT PCA both groups share, which is what ``compute_transport_plan`` wants.  Rows are group 0's listed cells,
+        then group 1's; columns are PAIRED genes.  By default the pairing strips the ``"<group key>_"`` prefix that prepare_adatas adds
+        (keys: ``uns["groups_mapping"]``, names: ``var_names`` / ``uns["groups_var_names"]``) and keeps the names both groups have, in
+        group 0's order; ``gene_list=[names0, names1]`` pairs by position (equal lengths, no repeats).  Without names and without
+        ``gene_list`` it is a ValueError -- nothing is guessed.  ``group=g``: one group's own PCA over its genes (or ``gene_list[g]``).
+        ``scale=True`` divides every gene by its standard deviation (ddof 1; a gene without variance gets the scale 0).  There is no
+        clipping: scanpy's ``max_value`` is not built.
+        The eigenpairs come from a block Lanczos iteration (``pca_ops.block_lanczos``) with the block min(64, round_up(n_comps + 8, 16), 16 * (genes // 16));
+        it stops when every residual || X^T X v - theta v || is at most ``tol`` * theta_1.  Not reaching that is reported
+        (``converged=False``), not raised.  The reported ``residuals`` are those of the fp32 vectors actually returned, whose largest
+        |loading| is positive (ties: the smaller gene index).  Deterministic in ``seed``.
+        Limits, each a ValueError ahead of any device work: 1 <= n_comps <= 56, n_comps below the number of cells and of genes, at
+        least 16 genes, at least 2 cells, and round_up(n_comps, 16) <= the number of genes (the iteration's block is a multiple of 16
+        and cannot be wider than the operator; with fewer genes than the default block it shrinks to the largest multiple that fits).  Device memory beyond the counts: the scores and one block of 4 * cells * 64 bytes each, the
+        basis of at most 2 * 12 * 64 * 8 * genes bytes, and a workspace of at most 16 * round_up(genes, 64) * 256 bytes."""
+        n_genes = [int(self.module.input_dims[k]) for k in range(2)]
+        plan = pca_plan(self.adata, n_genes, self.obs_idx, group_indices_list, n_comps=n_comps, group=group, gene_list=gene_list,
+                        normalize=normalize, target_sum=target_sum, scale=scale, tol=tol, seed=seed)
+        return _run_count_pca(self.counts, plan, self.device)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
